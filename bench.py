@@ -9,7 +9,13 @@ frozen reference model co-resident on its MI355X; every optimizer step consumes
 reference fwd, fused DPO loss, bucketed RCCL reduce-scatter overlapped with backward, clip,
 fused AdamW, all-gather. Data: synthetic token ids, random-init weights (no network).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline figure needs: set up, W warm-up steps, K timed steps, the
+result line (`ms_per_step` = the timed window / K). `--dump-outputs DIR` also writes what the last
+timed step computed as `DIR/<name>.npy` (same arguments, same inputs: two builds can be compared
+output for output). `--full` adds the measurements that take runs of their own (multi-rank: the
+RCCL bus-bandwidth probe recorded as `config.rccl`).
 
 Launch contract: under torchrun (WORLD_SIZE set) every process is one rank and the world size
 must equal --gpus. Invoked bare with --gpus N > 1, this process is only a launcher: it never
@@ -100,7 +106,20 @@ def parse(argv=None):
                          "RCCL's stream during backward, shard AdamW, overlapped all-gather)")
     ap.add_argument("--layers", type=int, default=None, help="debug only: override layer count "
                     "(a reduced model is NOT the benchmark config)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements the headline figure does not need (multi-rank: the "
+                         "RCCL bus-bandwidth probe before the timed window); a plain run only sets up, "
+                         "warms up, times --steps steps and prints the result line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, rank 0 writes what the last timed step computed as "
+                         "DIR/<name>.npy (float32): per-micro-batch loss and policy / reference "
+                         "log-probs, the step's gradient norm, and a fixed seeded sample of the updated "
+                         "policy parameters")
     a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be >= 1")
+    if a.warmup < 0:
+        ap.error("--warmup must be >= 0")
     if a.edp_shape > 1 and a.ep_shape <= 1:
         ap.error("--edp-shape needs --ep-shape")
     if a.ep_hot and a.ep_shape <= 1:
@@ -216,7 +235,7 @@ def preflight(st, dev) -> None:
 
 
 def collective_bandwidth(st, dev, mb: int = 256, iters: int = 5) -> dict:
-    """RCCL bus bandwidth over this run's ranks, measured before the timed window: a `mb` MB bf16
+    """(--full) RCCL bus bandwidth over this run's ranks, measured before the timed window: a `mb` MB bf16
     all-reduce and reduce-scatter (the collectives of the DDP / ZeRO-1 gradient sync), 2 warm-up +
     `iters` timed calls each, slowest rank's time (nccl-tests' busbw convention:
     all-reduce algbw x 2(n-1)/n, reduce-scatter algbw x (n-1)/n). Recorded in the result line so a
@@ -267,6 +286,39 @@ def _maybe_fail(step: int, rank: int) -> None:
         os._exit(17)
 
 
+PARAM_SAMPLE = 4096  # elements kept of each policy parameter in --dump-outputs
+
+
+def dump_outputs(out_dir: str, state: dict, policy) -> None:
+    """--dump-outputs: what the last timed step handed back, as float32 `.npy` files. Per
+    micro-batch (rows, in order): the DPO loss, the policy's and the frozen reference's sequence
+    log-probs ([chosen..., rejected...] for the reference); the step's gradient norm; and the
+    updated policy weights as a fixed sample (the same seeded PARAM_SAMPLE positions of every
+    parameter, in `named_parameters()` order: a few MB instead of the whole model)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+
+    def save(name, t):
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().to("cpu", torch.float32).numpy())
+
+    outs = state["outs"]
+    save("loss", torch.stack([o[0].reshape(()) for o in outs]))
+    save("policy_chosen_logps", torch.stack([o[1] for o in outs]))
+    save("policy_rejected_logps", torch.stack([o[2] for o in outs]))
+    save("ref_logps", torch.stack([o[3] for o in outs]))
+    save("grad_norm", torch.as_tensor(state["grad_norm"]).reshape(1))
+    gen = torch.Generator().manual_seed(20240229)
+    parts = []
+    for _, p in policy.named_parameters():
+        flat = p.detach().reshape(-1)
+        if flat.numel() == 0:  # a ZeRO-3 parameter whose shard lives in its unit's flat buffer
+            continue
+        idx = torch.randint(flat.numel(), (min(PARAM_SAMPLE, flat.numel()),), generator=gen)
+        parts.append(flat[idx.to(flat.device)].to("cpu", torch.float32))
+    save("policy_param_sample", torch.cat(parts))
+
+
 def main(argv=None) -> int:
     argv = list(sys.argv[1:] if argv is None else argv)
     args = parse(argv)
@@ -315,7 +367,8 @@ def main(argv=None) -> int:
     coll_bw = {}
     if st.world_size > 1 or st.forced or os.environ.get("DLA_BENCH_PREFLIGHT") == "1":
         preflight(st, dev)
-        if dev.type == "cuda" or os.environ.get("DLA_BENCH_COLLBW") == "1":
+        # a measurement of its own (14 large collectives): only with --full (or its own switch)
+        if args.full or os.environ.get("DLA_BENCH_COLLBW") == "1":
             coll_bw = collective_bandwidth(st, dev, mb=int(os.environ.get("DLA_BENCH_COLLBW_MB", "256")))
     world = st.world_size
     mesh = build_mesh(tp=args.tp, ep=args.ep, sp=args.sp)
@@ -420,17 +473,21 @@ def main(argv=None) -> int:
         _maybe_fail(state["step"], st.rank)
         state["step"] += 1
         pending = refs.submit(batches[state["i"] % n_batches])
+        outs = []  # what a caller of the step receives (references only: no copy, no sync)
         for a in range(args.accum):
             b = batches[state["i"] % n_batches]
             state["i"] += 1
             ctx = engine.no_sync() if a < args.accum - 1 else _null()
             with ctx:
-                loss, _ = dpo_step_loss(policy, ref, b, beta=args.beta, ref_logps=refs.result(pending))
+                ref_lp = refs.result(pending)
+                loss, metrics = dpo_step_loss(policy, ref, b, beta=args.beta, ref_logps=ref_lp)
                 if a + 1 < args.accum:
                     pending = refs.submit(batches[state["i"] % n_batches])
                 (loss / args.accum).backward()
             state["loss"] = loss
-        engine.step()
+            outs.append((loss.detach(), metrics["policy_chosen_logps"], metrics["policy_rejected_logps"], ref_lp))
+        state["grad_norm"] = engine.step()
+        state["outs"] = outs
 
     def sync():
         if dev.type == "cuda":
@@ -478,6 +535,12 @@ def main(argv=None) -> int:
             fh.write(prof.key_averages(group_by_input_shape=True).table(sort_by="cuda_time_total",
                                                                          row_limit=100, max_name_column_width=60,
                                                                          max_shapes_column_width=120))
+
+    if args.dump_outputs and st.rank == 0:
+        if hasattr(engine, "wait_params"):
+            engine.wait_params()  # the last step's overlapped all-gathers write the weights sampled here
+        sync()
+        dump_outputs(args.dump_outputs, state, policy)
 
     pairs_per_step = args.micro_pairs * args.accum * mesh.dp
     ms = elapsed / args.steps * 1000.0

@@ -109,8 +109,8 @@ def test_bench_records_collective_bandwidth():
     xGMI). Here on gloo: the all-reduce is measured; gloo's missing reduce-scatter is skipped
     without failing the run."""
     p = _run(["--gpus", "2", "--device", "cpu", "--model", "tiny-llama", "--steps", "1",
-              "--warmup", "0", "--seq-len", "64", "--micro-pairs", "2", "--accum", "1"],
-             {"DLA_BENCH_COLLBW": "1", "DLA_BENCH_COLLBW_MB": "2"})
+              "--warmup", "0", "--seq-len", "64", "--micro-pairs", "2", "--accum", "1", "--full"],
+             {"DLA_BENCH_COLLBW_MB": "2"})
     assert p.returncode == 0, p.stderr[-3000:]
     rec = _record(p.stdout)
     bw = rec["config"]["rccl"]
@@ -118,6 +118,35 @@ def test_bench_records_collective_bandwidth():
 
 
 import pytest  # noqa: E402
+
+
+def test_bench_dump_outputs_and_full(tmp_path):
+    """`--dump-outputs DIR` writes the last timed step's outputs as float32 .npy files, the same
+    arguments give the same inputs (two runs agree output for output), `--steps` is the number of
+    timed steps, and `--full` is accepted on a one-rank run."""
+    import numpy as np
+
+    args = ["--device", "cpu", "--model", "tiny-llama", "--steps", "2", "--warmup", "1",
+            "--seq-len", "64", "--micro-pairs", "2", "--accum", "3"]
+    dumps = []
+    for name, extra in (("a", []), ("b", ["--full"])):
+        p = _run(args + extra + ["--dump-outputs", str(tmp_path / name)])
+        assert p.returncode == 0, p.stderr[-3000:]
+        rec = _record(p.stdout)
+        assert rec["steps"] == 2 and rec["ms_per_step"] > 0
+        assert rec["value"] == pytest.approx(2 * 3 / (rec["ms_per_step"] / 1e3), rel=1e-2)
+        files = sorted(os.listdir(tmp_path / name))
+        assert files == ["grad_norm.npy", "loss.npy", "policy_chosen_logps.npy", "policy_param_sample.npy",
+                         "policy_rejected_logps.npy", "ref_logps.npy"]
+        d = {f[:-4]: np.load(tmp_path / name / f) for f in files}
+        assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in d.values())
+        assert sum(v.nbytes for v in d.values()) <= 64 * 2 ** 20
+        assert d["loss"].shape == (3,) and d["grad_norm"].shape == (1,)  # one row per micro-batch
+        assert d["policy_chosen_logps"].shape == (3, 2) and d["ref_logps"].shape == (3, 4)
+        assert d["loss"][-1] == pytest.approx(rec["config"]["final_loss"], abs=1e-5)
+        dumps.append(d)
+    for k, v in dumps[0].items():
+        assert np.allclose(v, dumps[1][k], rtol=1e-5, atol=1e-6), k
 
 
 @pytest.mark.parametrize("flags,mesh,gpus", [
