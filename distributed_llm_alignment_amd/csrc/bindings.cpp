@@ -63,6 +63,10 @@ void launch_ppo_policy_loss(const float*, const float*, const float*, const floa
                             float*, float*, float*, hipStream_t);
 void launch_ppo_value_loss(const float*, const float*, const float*, const float*, int64_t, float,
                            float*, float*, hipStream_t);
+void launch_group_advantages(const float*, int, int, bool, float, float*, float*, hipStream_t);
+void launch_grpo_loss(const float*, const float*, const float*, const float*, const float*,
+                      const float*, int, int, float, float, float, int, float, float*, float*,
+                      float*, float*, hipStream_t);
 void launch_adamw(bf16_t*, float*, const void*, bool, float*, float*, int64_t, float, float,
                   float, float, float, int, const float*, float, hipStream_t);
 void launch_grad_sumsq(const void*, bool, int64_t, float*, float*, bool, hipStream_t);
@@ -813,6 +817,64 @@ std::tuple<at::Tensor, at::Tensor> ppo_value_loss(const at::Tensor& values, cons
   return {loss, dval};
 }
 
+// ---- GRPO: group advantages + clipped surrogate with a k3 reference-KL term ----
+std::tuple<at::Tensor, at::Tensor> group_advantages(const at::Tensor& scores, int64_t G,
+                                                    bool scale_std, double eps) {
+  check_f32(scores, "scores");
+  TORCH_CHECK(scores.dim() == 1 && scores.is_contiguous(), "scores [P*G] contiguous");
+  TORCH_CHECK(G >= 1 && scores.numel() % G == 0, "scores must hold whole groups of G");
+  const int64_t P = scores.numel() / G;
+  TORCH_CHECK(P < (1ll << 31) && G < (1ll << 31), "group_advantages: too many groups");
+  c10::hip::HIPGuardMasqueradingAsCUDA g(scores.device());
+  auto adv = at::empty_like(scores);
+  auto sd = at::empty({P}, scores.options());
+  launch_group_advantages(scores.data_ptr<float>(), static_cast<int>(P), static_cast<int>(G),
+                          scale_std, static_cast<float>(eps), adv.data_ptr<float>(),
+                          sd.data_ptr<float>(), cur_stream(scores));
+  return {adv, sd};
+}
+
+// lp / old / ref / mask: [S, T] fp32 grids, adv [S] (one value per rollout), denom: optional
+// device [1] replacing the final divisor. mode: 0 sequence, 1 token, 2 constant (S * max_len).
+// Returns (loss, dloss/dlp, metrics[4]); no host read of any device value.
+std::tuple<at::Tensor, at::Tensor, at::Tensor> grpo_loss(
+    const at::Tensor& lp, const at::Tensor& old, const at::Tensor& ref, const at::Tensor& adv,
+    const at::Tensor& mask, const c10::optional<at::Tensor>& denom, double clip_low,
+    double clip_high, double beta, int64_t mode, double max_len) {
+  check_f32(lp, "lp");
+  TORCH_CHECK(lp.dim() == 2 && lp.is_contiguous(), "lp [S, T] contiguous");
+  check_grid(old, lp, "old");
+  check_grid(ref, lp, "ref");
+  check_grid(mask, lp, "mask");
+  check_f32(adv, "adv");
+  TORCH_CHECK(adv.is_contiguous() && adv.numel() == lp.size(0), "adv must be [S] contiguous");
+  TORCH_CHECK(mode >= 0 && mode <= 2, "grpo_loss mode must be 0 (sequence), 1 (token), 2 (constant)");
+  TORCH_CHECK(mode != 2 || max_len > 0 || denom.has_value(), "constant mode needs max_len > 0");
+  TORCH_CHECK(lp.size(0) > 0 && lp.size(0) < (1ll << 31) && lp.size(1) < (1ll << 31), "grpo_loss grid size");
+  same_device(lp, adv);
+  const float* dn = nullptr;
+  if (denom.has_value()) {
+    check_f32(*denom, "denom");
+    same_device(lp, *denom);
+    TORCH_CHECK(denom->numel() == 1, "denom must hold one value");
+    dn = denom->data_ptr<float>();
+  }
+  c10::hip::HIPGuardMasqueradingAsCUDA g(lp.device());
+  auto opt = lp.options();
+  const int S = static_cast<int>(lp.size(0)), T = static_cast<int>(lp.size(1));
+  auto loss = at::empty({}, opt);
+  auto dlp = at::empty_like(lp);
+  auto metrics = at::empty({4}, opt);
+  auto part = at::empty({5, S}, opt);
+  launch_grpo_loss(lp.data_ptr<float>(), old.data_ptr<float>(), ref.data_ptr<float>(),
+                   adv.data_ptr<float>(), mask.data_ptr<float>(), dn, S, T,
+                   static_cast<float>(1.0 - clip_low), static_cast<float>(1.0 + clip_high),
+                   static_cast<float>(beta), static_cast<int>(mode), static_cast<float>(max_len),
+                   part.data_ptr<float>(), loss.data_ptr<float>(), dlp.data_ptr<float>(),
+                   metrics.data_ptr<float>(), cur_stream(lp));
+  return {loss, dlp, metrics};
+}
+
 std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> kl_penalty_pg(const at::Tensor& lp,
                                                                          const at::Tensor& lr,
                                                                          const at::Tensor& reward,
@@ -938,6 +1000,8 @@ TORCH_LIBRARY(dla, m) {
   m.def("gae(Tensor rewards, Tensor values, Tensor mask, float gamma, float lam) -> (Tensor, Tensor)");
   m.def("ppo_policy_loss(Tensor lp, Tensor old, Tensor adv, Tensor mask, float eps) -> (Tensor, Tensor, Tensor)");
   m.def("ppo_value_loss(Tensor values, Tensor old, Tensor returns, Tensor mask, float clip) -> (Tensor, Tensor)");
+  m.def("group_advantages(Tensor scores, int G, bool scale_std, float eps) -> (Tensor, Tensor)");
+  m.def("grpo_loss(Tensor lp, Tensor old, Tensor ref, Tensor adv, Tensor mask, Tensor? denom, float clip_low, float clip_high, float beta, int mode, float max_len) -> (Tensor, Tensor, Tensor)");
   m.def("kl_penalty_pg(Tensor lp, Tensor lr, Tensor reward, float kl_coef) -> (Tensor, Tensor, Tensor, Tensor)");
   m.def("adamw_step(Tensor(a!)? param, Tensor(b!)? master, Tensor grad, Tensor(c!) m, Tensor(d!) v, float lr, float b1, float b2, float eps, float wd, int step, Tensor? clip, float grad_scale) -> ()");
   m.def("grad_sumsq(Tensor grad, Tensor(a!) out, bool accumulate) -> ()");
@@ -972,6 +1036,8 @@ TORCH_LIBRARY_IMPL(dla, CUDA, m) {
   m.impl("gae", &dla::gae);
   m.impl("ppo_policy_loss", &dla::ppo_policy_loss);
   m.impl("ppo_value_loss", &dla::ppo_value_loss);
+  m.impl("group_advantages", &dla::group_advantages);
+  m.impl("grpo_loss", &dla::grpo_loss);
   m.impl("adamw_step", &dla::adamw_step);
   m.impl("grad_sumsq", &dla::grad_sumsq);
   m.impl("clip_coef", &dla::clip_coef);

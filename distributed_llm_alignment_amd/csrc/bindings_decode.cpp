@@ -33,6 +33,9 @@ size_t sample_workspace_bytes(int64_t, int);
 void launch_sample_split(const void*, bool, int64_t, int64_t, int, int, float, int, float,
                          const int64_t*, int64_t*, void*, hipStream_t);
 
+void launch_kv_replicate(const bf16_t*, const bf16_t*, bf16_t*, bf16_t*, int, int, int, int, int,
+                         int, const int64_t*, const int64_t*, hipStream_t);
+
 int skinny_splits(int M, int N, int K);
 bool skinny_use_ksplit(int N, int K);
 void launch_skinny_ksplit(const bf16_t*, int64_t, const bf16_t*, int64_t, bf16_t*, int64_t, int,
@@ -724,9 +727,51 @@ at::Tensor sample_tokens(const at::Tensor& logits, double temperature, int64_t t
   return out;
 }
 
+// Shared-prefill replication: keys / values [0, Tp) of every layer of the P-row prefill cache
+// (src_k / src_v [L, P, Tp, Hkv, D]) go to rows p*G .. p*G+G-1 of the P*G-row decode cache
+// (dst_k / dst_v [L, P*G, Tmax >= Tp, Hkv, D]); any strides with D contiguous and 16-byte
+// aligned rows (head-major or token-major storage). Positions >= Tp of dst are not written.
+void kv_replicate(const at::Tensor& src_k, const at::Tensor& src_v, at::Tensor& dst_k,
+                  at::Tensor& dst_v, int64_t G) {
+  check_bf16(src_k, "src_k");
+  check_bf16(src_v, "src_v");
+  check_bf16(dst_k, "dst_k");
+  check_bf16(dst_v, "dst_v");
+  same_device(src_k, dst_k);
+  same_device(src_v, dst_k);
+  same_device(dst_v, dst_k);
+  TORCH_CHECK(src_k.dim() == 5 && dst_k.dim() == 5, "kv_replicate: caches are [L, rows, T, Hkv, D]");
+  TORCH_CHECK(src_v.sizes() == src_k.sizes() && src_v.strides() == src_k.strides(),
+              "kv_replicate: src_k / src_v must share shape and strides");
+  TORCH_CHECK(dst_v.sizes() == dst_k.sizes() && dst_v.strides() == dst_k.strides(),
+              "kv_replicate: dst_k / dst_v must share shape and strides");
+  const int64_t L = src_k.size(0), P = src_k.size(1), Tp = src_k.size(2), H = src_k.size(3),
+                D = src_k.size(4);
+  TORCH_CHECK(G >= 1 && G < (1 << 20), "kv_replicate: bad group size");
+  TORCH_CHECK(dst_k.size(0) == L && dst_k.size(1) == P * G && dst_k.size(2) >= Tp &&
+                  dst_k.size(3) == H && dst_k.size(4) == D,
+              "kv_replicate: destination must be [L, P*G, >= Tp, Hkv, D]");
+  TORCH_CHECK(D % 8 == 0, "kv_replicate: head_dim * 2 bytes must be a multiple of 16");
+  TORCH_CHECK(L * P <= 65535 && Tp < (1ll << 31) && H < (1ll << 31) && Tp * H * (D / 8) < (1ll << 40),
+              "kv_replicate: shape out of range");
+  for (const at::Tensor* t : std::initializer_list<const at::Tensor*>{&src_k, &src_v, &dst_k, &dst_v}) {
+    TORCH_CHECK(t->stride(4) == 1 || D == 1, "kv_replicate: head_dim must be contiguous");
+    for (int i = 0; i < 4; ++i)
+      TORCH_CHECK(t->stride(i) % 8 == 0 && t->stride(i) >= 0, "kv_replicate: strides must be multiples of 8 elements");
+    check_aligned16(*t, "kv_replicate operand");
+  }
+  const int64_t sstr[4] = {src_k.stride(0), src_k.stride(1), src_k.stride(2), src_k.stride(3)};
+  const int64_t dstr[4] = {dst_k.stride(0), dst_k.stride(1), dst_k.stride(2), dst_k.stride(3)};
+  c10::hip::HIPGuardMasqueradingAsCUDA g(dst_k.device());
+  launch_kv_replicate(cbp(src_k), cbp(src_v), bp(dst_k), bp(dst_v), static_cast<int>(L),
+                      static_cast<int>(P), static_cast<int>(G), static_cast<int>(Tp),
+                      static_cast<int>(H), static_cast<int>(D), sstr, dstr, cur_stream(dst_k));
+}
+
 }  // namespace dla
 
 TORCH_LIBRARY_FRAGMENT(dla, m) {
+  m.def("kv_replicate(Tensor src_k, Tensor src_v, Tensor(a!) dst_k, Tensor(b!) dst_v, int G) -> ()");
   m.def("decode_attn(Tensor q, Tensor k_cache, Tensor v_cache, Tensor kv_len, Tensor? kv_start, int window, float scale) -> Tensor");
   m.def("rope_cache_write(Tensor qkv, Tensor cos, Tensor sin, Tensor pos, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor slot, int Hq, int Hkv, int D, int rot) -> Tensor");
   m.def("decode_attn_rope(Tensor qkv, Tensor cos, Tensor sin, Tensor pos, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor slot, Tensor kv_len, Tensor? kv_start, int window, float scale, int Hq, int Hkv, int D, int rot) -> Tensor");
@@ -744,6 +789,7 @@ TORCH_LIBRARY_FRAGMENT(dla, m) {
 }
 
 TORCH_LIBRARY_IMPL(dla, CUDA, m) {
+  m.impl("kv_replicate", &dla::kv_replicate);
   m.impl("decode_attn", &dla::decode_attn);
   m.impl("sample_tokens", &dla::sample_tokens);
   m.impl("rope_cache_write", &dla::rope_cache_write);

@@ -9,6 +9,7 @@
 //   kl_penalty_pg   : kl = lp - lr; r' = r - c*kl; A = r' - mean(r'); loss = -mean(A*lp)
 //                                                                   train_rlhf.py:149-153
 //   gae / ppo_policy_loss / ppo_value_loss : token-level actor-critic PPO (below)
+//   group_advantages / grpo_loss : critic-free group-relative policy optimisation (below)
 // Batch dimensions here are small (pairs per micro-batch), so each loss is a single
 // 256-thread block; the point is fusing fwd+bwd+metrics into one launch with no host sync.
 #include "common.h"
@@ -276,7 +277,169 @@ __global__ __launch_bounds__(1024) void ppo_value_loss_kernel(
   if (threadIdx.x == 0) loss[0] = l * inv;
 }
 
+// ==============================================================================================
+// GRPO (critic-free, group-relative): group advantages + token-level clipped surrogate with a k3
+// reference-KL term and the GRPO / DAPO / Dr. GRPO normalisations.
+// ==============================================================================================
+
+// Advantage of a rollout = its reward standardised inside its group of G samples of one prompt.
+// One wave per group (G <= 64 lives in the wave, larger groups loop); a constant-reward group
+// gives exactly 0 (and sd = 0), never NaN.
+//   mu = mean, sd = population std;  adv = (r - mu) / (sd + eps)  or  r - mu  (scale_std = 0)
+__global__ __launch_bounds__(64) void group_advantages_kernel(const float* __restrict__ r, int G,
+                                                              int scale_std, float eps,
+                                                              float* __restrict__ adv,
+                                                              float* __restrict__ sd_out) {
+  const int lane = threadIdx.x;
+  const int64_t base = static_cast<int64_t>(blockIdx.x) * G;
+  float s = 0.f, hi = -INFINITY, lo = INFINITY;
+  for (int g = lane; g < G; g += 64) {
+    const float x = r[base + g];
+    s += x;
+    hi = fmaxf(hi, x);
+    lo = fminf(lo, x);
+  }
+  s = wave_sum(s);
+  hi = wave_max(hi);
+  lo = -wave_max(-lo);
+  const float mu = s / G;
+  float q = 0.f;
+  for (int g = lane; g < G; g += 64) {
+    const float c = r[base + g] - mu;
+    q += c * c;
+  }
+  q = wave_sum(q);
+  const bool constant = hi == lo;
+  const float sd = constant ? 0.f : sqrtf(q / G);
+  const float inv = scale_std ? 1.f / (sd + eps) : 1.f;
+  for (int g = lane; g < G; g += 64)
+    adv[base + g] = constant ? 0.f : (r[base + g] - mu) * inv;
+  if (lane == 0) sd_out[blockIdx.x] = sd;
+}
+
+// GRPO loss, launch 1 of 2: one workgroup per sequence reduces its row of the [S, T] grids to
+// five partials part[k * S + s]: token count, sum m*per, sum m*[rho outside the clip range],
+// sum m*((rho - 1) - d), sum m*k3.
+//   d = lp - old; rho = exp(d); pg = max(-A rho, -A clamp(rho, lo, hi)), lo = 1 - clip_low, hi = 1 + clip_high
+//   dr = ref - lp; k3 = exp(dr) - dr - 1; per = pg + beta * k3          (A = adv[s], per rollout)
+struct GrpoTok {
+  float per, l1, l2, rho, d, edr, k3;
+};
+__device__ __forceinline__ GrpoTok grpo_token(float lp, float old, float ref, float a, float lo,
+                                              float hi, float beta) {
+  GrpoTok t;
+  t.d = lp - old;
+  t.rho = expf(t.d);
+  t.l1 = -a * t.rho;
+  t.l2 = -a * fminf(fmaxf(t.rho, lo), hi);
+  const float dr = ref - lp;
+  t.edr = expf(dr);
+  t.k3 = t.edr - dr - 1.f;
+  t.per = fmaxf(t.l1, t.l2) + beta * t.k3;
+  return t;
+}
+
+constexpr int kGrpoThreads = 256;
+
+__global__ __launch_bounds__(kGrpoThreads) void grpo_partials_kernel(
+    const float* __restrict__ lp, const float* __restrict__ old, const float* __restrict__ ref,
+    const float* __restrict__ adv, const float* __restrict__ m, int S, int T, float lo, float hi,
+    float beta, float* __restrict__ part) {
+  __shared__ float scratch[kGrpoThreads / 64];
+  const int s = blockIdx.x;
+  const int64_t base = static_cast<int64_t>(s) * T;
+  const float a = adv[s];
+  float cnt = 0.f, l = 0.f, cf = 0.f, akl = 0.f, klr = 0.f;
+  for (int t = threadIdx.x; t < T; t += kGrpoThreads) {
+    const float mi = m[base + t];
+    const GrpoTok k = grpo_token(lp[base + t], old[base + t], ref[base + t], a, lo, hi, beta);
+    cnt += mi;
+    l += mi * k.per;
+    cf += mi * ((k.rho < lo || k.rho > hi) ? 1.f : 0.f);
+    akl += mi * ((k.rho - 1.f) - k.d);
+    klr += mi * k.k3;
+  }
+  cnt = block_sum<kGrpoThreads>(cnt, scratch);
+  l = block_sum<kGrpoThreads>(l, scratch);
+  cf = block_sum<kGrpoThreads>(cf, scratch);
+  akl = block_sum<kGrpoThreads>(akl, scratch);
+  klr = block_sum<kGrpoThreads>(klr, scratch);
+  if (threadIdx.x == 0) {
+    part[s] = cnt;
+    part[S + s] = l;
+    part[2 * S + s] = cf;
+    part[3 * S + s] = akl;
+    part[4 * S + s] = klr;
+  }
+}
+
+// Launch 2 of 2: every workgroup sums the S token counts in the same fixed order (the divisor of
+// the `token` mode), then writes its sequence's gradient row; workgroup 0 also finalises the loss
+// and the metrics from the partials. No float atomics: two runs are bitwise equal.
+//   mode 0 sequence (GRPO):  sum_s [l_s / max(c_s, 1)] / S
+//   mode 1 token (DAPO):     sum_s l_s / max(sum_s c_s, 1)
+//   mode 2 constant (Dr. GRPO): sum_s l_s / (S * max_len)
+//   denom (optional, device [1]) replaces the final divisor (micro-batches of one rollout batch)
+//   dlp = m * w_s * [(l1 >= l2 ? l1 : 0) - beta * (exp(dr) - 1)] / divisor, w_s = 1/max(c_s,1) in mode 0
+//   metrics: [0] clipfrac, [1] approx KL, [2] k3 KL to the reference (token means), [3] tokens
+__global__ __launch_bounds__(kGrpoThreads) void grpo_grad_kernel(
+    const float* __restrict__ lp, const float* __restrict__ old, const float* __restrict__ ref,
+    const float* __restrict__ adv, const float* __restrict__ m, const float* __restrict__ part,
+    const float* __restrict__ denom, int S, int T, float lo, float hi, float beta, int mode,
+    float max_len, float* __restrict__ loss, float* __restrict__ dlp, float* __restrict__ metrics) {
+  __shared__ float scratch[kGrpoThreads / 64];
+  const int s = blockIdx.x;
+  float cnt = 0.f;
+  for (int i = threadIdx.x; i < S; i += kGrpoThreads) cnt += part[i];
+  cnt = block_sum<kGrpoThreads>(cnt, scratch);
+  const float div = denom != nullptr ? denom[0]
+                    : mode == 0      ? static_cast<float>(S)
+                    : mode == 1      ? fmaxf(cnt, 1.f)
+                                     : static_cast<float>(S) * max_len;
+  if (s == 0) {
+    float l = 0.f, cf = 0.f, akl = 0.f, klr = 0.f;
+    for (int i = threadIdx.x; i < S; i += kGrpoThreads) {
+      l += mode == 0 ? part[S + i] / fmaxf(part[i], 1.f) : part[S + i];
+      cf += part[2 * S + i];
+      akl += part[3 * S + i];
+      klr += part[4 * S + i];
+    }
+    l = block_sum<kGrpoThreads>(l, scratch);
+    cf = block_sum<kGrpoThreads>(cf, scratch);
+    akl = block_sum<kGrpoThreads>(akl, scratch);
+    klr = block_sum<kGrpoThreads>(klr, scratch);
+    if (threadIdx.x == 0) {
+      const float inv = 1.f / fmaxf(cnt, 1.f);
+      loss[0] = l / div;
+      metrics[0] = cf * inv;
+      metrics[1] = akl * inv;
+      metrics[2] = klr * inv;
+      metrics[3] = cnt;
+    }
+  }
+  const int64_t base = static_cast<int64_t>(s) * T;
+  const float a = adv[s];
+  const float scale = (mode == 0 ? 1.f / fmaxf(part[s], 1.f) : 1.f) / div;
+  for (int t = threadIdx.x; t < T; t += kGrpoThreads) {
+    const GrpoTok k = grpo_token(lp[base + t], old[base + t], ref[base + t], a, lo, hi, beta);
+    dlp[base + t] = m[base + t] * scale * ((k.l1 >= k.l2 ? k.l1 : 0.f) - beta * (k.edr - 1.f));
+  }
+}
+
 // ----------------------------------------------------------------------------------------------
+void launch_group_advantages(const float* r, int P, int G, bool scale_std, float eps, float* adv,
+                             float* sd, hipStream_t st) {
+  if (P == 0 || G == 0) return;
+  group_advantages_kernel<<<P, 64, 0, st>>>(r, G, scale_std ? 1 : 0, eps, adv, sd);
+}
+void launch_grpo_loss(const float* lp, const float* old, const float* ref, const float* adv,
+                      const float* m, const float* denom, int S, int T, float lo, float hi,
+                      float beta, int mode, float max_len, float* part, float* loss, float* dlp,
+                      float* metrics, hipStream_t st) {
+  grpo_partials_kernel<<<S, kGrpoThreads, 0, st>>>(lp, old, ref, adv, m, S, T, lo, hi, beta, part);
+  grpo_grad_kernel<<<S, kGrpoThreads, 0, st>>>(lp, old, ref, adv, m, part, denom, S, T, lo, hi, beta,
+                                              mode, max_len, loss, dlp, metrics);
+}
 void launch_gae(const float* r, const float* v, const float* m, int S, int T, float gamma,
                 float lam, float* adv, float* ret, hipStream_t st) {
   if (S == 0 || T == 0) return;

@@ -307,13 +307,43 @@ PREFILL_FP8 = os.environ.get("DLA_PREFILL_FP8", "1") != "0"
 
 
 @torch.no_grad()
+def prefill_shared(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor],
+                   G: int, max_len: int, cache: Optional[KVCache] = None):
+    """Prefill P left-padded prompts ONCE for G samples each: the prompts run through a P-row
+    cache of length Tp, and their keys / values [0, Tp) of every layer are replicated into rows
+    p*G .. p*G+G-1 of a P*G-row cache of length `max_len` (`ops.decode.kv_replicate`, one HIP
+    launch on the GPU). `cache`: an emptied (`reset`) P*G-row cache to fill instead of a new one
+    (the decode-graph reuse slot). Returns (cache advanced to Tp, last hidden rows [P*G, H]) in
+    `repeat_interleave` order: what a prefill of the G-times repeated prompts leaves behind, for
+    1/G of the prompt forward."""
+    P, Tp = input_ids.shape
+    kv_start = attention_layout(attention_mask)[0] if attention_mask is not None else None
+    small = KVCache(model, P, Tp, kv_start)
+    h = model(input_ids, cache=small)
+    if cache is None:
+        cache = KVCache(model, P * G, max_len,
+                        kv_start.repeat_interleave(G) if kv_start is not None else None)
+    if cache.batch != P * G or cache.max_len < Tp or cache.len != 0:
+        raise ValueError("prefill_shared: cache must be an empty P*G-row cache of at least Tp keys")
+    ops.decode.kv_replicate(small.k, small.v, cache.k, cache.v, G)
+    cache.advance(Tp)
+    return cache, h[:, -1].repeat_interleave(G, 0)
+
+
+@torch.no_grad()
 def generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
              max_new_tokens: int = 256, do_sample: bool = True, temperature: float = 1.0,
              top_p: float = 1.0, top_k: int = 0, eos_token_id: Optional[int] = None,
              pad_token_id: Optional[int] = None, generator: Optional[torch.Generator] = None,
              return_mask: bool = False, use_graph: Optional[bool] = None, seed: Optional[int] = None,
-             weight_dtype: str = "bf16"):
+             weight_dtype: str = "bf16", num_return_sequences: int = 1, share_prefill: bool = True):
     """Left-padded prompts [B, Tp] -> sequences [B, Tp + n] (n <= max_new_tokens).
+
+    `num_return_sequences=G` (group rollouts, GRPO): G samples per prompt, output [B*G, Tp + n]
+    with row p*G + g = sample g of prompt p (`repeat_interleave` order). With `share_prefill` the
+    prompt is prefilled once per prompt and its K/V replicated to the G rows (`prefill_shared`);
+    `share_prefill=False` repeats the prompts and prefills every copy (the A/B arm). The G rows of
+    a group sample independently: the sampler's Philox stream is keyed by (seed, row, step).
 
     With `return_mask`, also returns the attention mask of the full sequence (prompt mask, then
     1 for every generated token up to and including EOS, 0 afterwards) — the correct mask for
@@ -330,17 +360,24 @@ def generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional[
     scales, hipBLASLt fp8). Attention, norms and the KV cache stay bf16."""
     if weight_dtype not in ("bf16", "fp8"):
         raise ValueError(f"weight_dtype must be 'bf16' or 'fp8', got {weight_dtype!r}")
+    G = int(num_return_sequences)
+    if G < 1:
+        raise ValueError(f"num_return_sequences must be >= 1, got {num_return_sequences!r}")
+    if G > 1 and not share_prefill:
+        input_ids = input_ids.repeat_interleave(G, 0)
+        attention_mask = attention_mask.repeat_interleave(G, 0) if attention_mask is not None else None
+        G = 1
     f8 = weight_dtype == "fp8" or ops.decode.fp8_enabled()
     with ops.decode.fp8_weights(f8), ops.fp8_inference_scope(model, f8 and PREFILL_FP8):
         return _generate(model, input_ids, attention_mask, max_new_tokens, do_sample, temperature, top_p,
-                         top_k, eos_token_id, pad_token_id, generator, return_mask, use_graph, seed)
+                         top_k, eos_token_id, pad_token_id, generator, return_mask, use_graph, seed, G)
 
 
 def _generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor],
               max_new_tokens: int, do_sample: bool, temperature: float, top_p: float, top_k: int,
               eos_token_id: Optional[int], pad_token_id: Optional[int],
               generator: Optional[torch.Generator], return_mask: bool, use_graph: Optional[bool],
-              seed: Optional[int]):
+              seed: Optional[int], G: int = 1):
     if DECODE_GATHER and model.layers_sharded():
         # ZeRO-3 policy: gather it once for the whole rollout (fused decode kernels + captured
         # graph) instead of an all-gather per layer per token
@@ -352,7 +389,7 @@ def _generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional
                     stack.enter_context(eng.gathered_for_inference())
                 return _generate(model, input_ids, attention_mask, max_new_tokens, do_sample, temperature,
                                  top_p, top_k, eos_token_id, pad_token_id, generator, return_mask, use_graph,
-                                 seed)
+                                 seed, G)
         finally:
             # the gathered units are freed on exit: the captured graph (it reads their addresses),
             # its KV cache and the derived decode weight copies (a second full set of layer
@@ -380,6 +417,9 @@ def _generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional
     kv_start = None
     if attention_mask is not None:
         kv_start, _, _ = attention_layout(attention_mask)
+    if G > 1:  # group rollouts: B counts the P*G decode rows from here on
+        B = B * G
+        kv_start = kv_start.repeat_interleave(G) if kv_start is not None else None
     greedy = not do_sample or temperature <= 0
     reuse_key, dg = None, None
     if GRAPH_REUSE and use_graph is not False and max_new_tokens > 2 and input_ids.is_cuda \
@@ -397,7 +437,13 @@ def _generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional
     # folded RMSNorm weights of the fused decode layer are refreshed in place (never inside the
     # captured step): a cached graph replays the same buffers with the current weights
     ops.decode.refresh_folded_weights(model)
-    h = model(input_ids, cache=cache)
+    if G > 1:
+        # one prompt forward per group; its K/V and last hidden row replicated to the G rows
+        cache, last = prefill_shared(model, input_ids, attention_mask, G, Tp + max_new_tokens, cache)
+        input_ids = input_ids.repeat_interleave(G, 0)
+        attention_mask = attention_mask.repeat_interleave(G, 0) if attention_mask is not None else None
+    else:
+        last = model(input_ids, cache=cache)[:, -1]
     if seed is None:
         seed = int(torch.randint(0, 2 ** 62, (1,), generator=generator).item()) if generator is not None \
             and generator.device.type == "cpu" else int(torch.randint(0, 2 ** 62, (1,)).item())
@@ -408,7 +454,7 @@ def _generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional
                               top_p, seed)
         else:
             dg.reset(seed)
-        dg.sample(model.logits(h[:, -1]))  # token 1 from the prefill, eager
+        dg.sample(model.logits(last))  # token 1 from the prefill, eager
         h = model(dg.tok, cache=cache)  # token 2 eagerly: warms every decode-shape kernel/GEMM
         dg.sample(model.logits(h[:, -1]))
         n = 2
@@ -429,7 +475,6 @@ def _generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional
         out, gen_mask = [input_ids], []
         finished = torch.zeros(B, dtype=torch.bool, device=input_ids.device)
         rng = torch.tensor([seed, 0], dtype=torch.long, device=input_ids.device)
-        last = h[:, -1]
         for step in range(max_new_tokens):
             logits = model.logits(last)
             if ops._ext.use_native(logits):

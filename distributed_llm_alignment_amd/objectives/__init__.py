@@ -7,6 +7,9 @@ benchmarks and tests share one implementation.
   rlhf_loss        reference train_rlhf.py:127-153 (REINFORCE with KL-shaped reward)
   ppo_rollout_stats / ppo_loss  token-level actor-critic PPO (GAE, clipped surrogate + value
                    loss) for `ppo.algorithm: ppo` (north-star config; not in the reference)
+  grpo_rollout_stats / grpo_loss  critic-free group-relative policy optimisation (group
+                   advantages, token-level clipped surrogate + k3 KL to the reference) for
+                   `ppo.algorithm: grpo` (not in the reference)
   distill_loss     reference train_distill.py:125-147 (CE on rollouts or ensemble forward KL)
 """
 from __future__ import annotations
@@ -211,6 +214,43 @@ def ppo_backward(loss: torch.Tensor) -> None:
     cs = ppo_critic_stream(loss.device)
     if cs is not None:
         torch.cuda.current_stream(loss.device).wait_stream(cs)
+
+
+@torch.no_grad()
+def grpo_rollout_stats(policy, ref, seqs, mask, prompt_len: int, scores, G: int, beta: float = 0.04,
+                       scale_std: bool = True, need_old: bool = False):
+    """GRPO targets for one batch of group rollouts (rows p*G .. p*G+G-1 sample prompt p). The
+    reward is the reward-model score alone (the KL lives in the loss); a rollout's advantage is its
+    score standardised inside its group. The reference's token log-probs are skipped entirely
+    when beta == 0, and the old policy's are computed only with `need_old` (more than one update
+    per rollout batch; a single on-policy update uses old = logp.detach())."""
+    act = action_mask(mask, prompt_len)
+    adv, gm = ops.group_advantages(scores, G, scale_std)
+    return {"act": act, "advantages": adv,
+            "ref_logp": ref.token_logprobs(seqs, mask) if beta != 0 else None,
+            "old_logp": policy.token_logprobs(seqs, mask) if need_old else None,
+            "scores": scores.float(), "reward_std": gm["reward_std"], "frac_zero_std": gm["frac_zero_std"]}
+
+
+def grpo_loss(policy, seqs, mask, stats: Dict[str, torch.Tensor], clip_low: float = 0.2,
+              clip_high: Optional[float] = None, beta: float = 0.04, loss_type: str = "sequence",
+              max_len: Optional[int] = None, denom: Optional[torch.Tensor] = None):
+    """Token-level clipped surrogate + beta * k3 KL to the reference (HIP fused fwd+bwd) on one
+    (micro-)batch of rollouts; `stats` from `grpo_rollout_stats`, sliced to the same rows."""
+    lp = policy.token_logprobs(seqs, mask)
+    loss, m = ops.grpo_loss(lp, stats.get("old_logp"), stats.get("ref_logp"), stats["advantages"],
+                            stats["act"], clip_low, clip_high, beta, loss_type, max_len, denom)
+    return loss, {"kl": m["kl_ref"], **m}
+
+
+def grpo_denominator(act: torch.Tensor, loss_type: str, max_len: Optional[int] = None) -> torch.Tensor:
+    """The whole rollout batch's divisor as a device tensor [1] (no host sync), shared by its
+    micro-batches: S (sequence), the action-token count (token), S * max_len (constant)."""
+    S = act.shape[0]
+    if loss_type == "token":
+        return act.sum().clamp(min=1).reshape(1)
+    return torch.full((1,), float(S if loss_type == "sequence" else S * int(max_len)),
+                      dtype=torch.float32, device=act.device)
 
 
 # Tokens per ensemble-KL chunk: (teachers + 1) x chunk x V bf16 logits exist at a time

@@ -1,4 +1,5 @@
-"""Decode-path ops: split-KV GQA decode attention and the fused top-k/top-p sampler.
+"""Decode-path ops: split-KV GQA decode attention, the fused top-k/top-p sampler and
+the shared-prefill KV replication of group rollouts (`kv_replicate`).
 
 GPU tensors run `torch.ops.dla.decode_attn` / `torch.ops.dla.sample_tokens` (csrc/decode.hip,
 csrc/sampling.hip); both take their lengths / RNG counter from device memory so a decode step can
@@ -60,6 +61,29 @@ def sample_tokens(logits: torch.Tensor, temperature: float, top_k: int, top_p: f
     from ..models.generation import sample_next
 
     return sample_next(logits.float(), not greedy, temperature, top_p, top_k, generator)
+
+
+def kv_replicate(src_k, src_v, dst_k, dst_v, G: int) -> None:
+    """Shared-prefill replication for group rollouts: keys / values [0, Tp) of every layer of the
+    P-row prefill cache (`src_*` [L, P, Tp, Hkv, D], or the layer-split list of [P, Tp, Hkv, D]) are
+    copied into rows p*G .. p*G+G-1 of the P*G-row decode cache (`dst_*`, T_max >= Tp; positions
+    >= Tp are left alone). bf16 GPU caches run `torch.ops.dla.kv_replicate` (csrc/kv_replicate.hip:
+    one launch for K and V of all layers, every 16-byte vector read once and stored G times, no
+    [P*G]-row temporary); CPU tensors, other dtypes and the layer-split list form use
+    `repeat_interleave` + a slice copy (per layer for the list form)."""
+    G = int(G)
+    if isinstance(src_k, (list, tuple)):
+        for sk, sv, dk, dv in zip(src_k, src_v, dst_k, dst_v):
+            Tp = sk.shape[1]
+            dk[:, :Tp] = sk.repeat_interleave(G, dim=0).to(dk.device)
+            dv[:, :Tp] = sv.repeat_interleave(G, dim=0).to(dv.device)
+        return
+    Tp = src_k.shape[2]
+    if _ext.use_native(dst_k) and dst_k.dtype == torch.bfloat16 and src_k.dtype == torch.bfloat16:
+        _ext.require().kv_replicate(src_k, src_v, dst_k, dst_v, G)
+        return
+    dst_k[:, :, :Tp] = src_k.repeat_interleave(G, dim=1)
+    dst_v[:, :, :Tp] = src_v.repeat_interleave(G, dim=1)
 
 
 # ------------------------------------------------------------------------- skinny GEMM (M <= 16)

@@ -8,10 +8,12 @@ host sync); CPU paths are the literal reference formulas:
   * ensemble_kl     src/training/train_distill.py:127-144
   * gae / ppo_policy_loss / ppo_value_loss: token-level actor-critic PPO (north-star config; the
     reference's REINFORCE above stays the default RLHF algorithm)
+  * group_advantages / grpo_loss: critic-free group-relative policy optimisation (GRPO and its
+    DAPO / Dr. GRPO normalisations; not in the reference)
 """
 from __future__ import annotations
 
-from typing import Dict, Tuple
+from typing import Dict, Optional, Tuple
 
 import torch
 import torch.nn.functional as F
@@ -238,3 +240,131 @@ def ppo_value_loss(values: torch.Tensor, old_values: torch.Tensor, returns: torc
     n = m.sum().clamp(min=1)
     vc = old + (v - old).clamp(-clip, clip)
     return 0.5 * (torch.maximum((v - R) ** 2, (vc - R) ** 2) * m).sum() / n
+
+
+# ------------------------------------------------------- GRPO (critic-free, group-relative)
+# Every prompt is sampled G times (rows p*G .. p*G+G-1 of the rollout batch); a rollout's advantage
+# is its reward standardised inside its group, and the update is a token-level clipped surrogate
+# plus a k3 KL term to the frozen reference. `loss_type` picks the normalisation: "sequence"
+# (GRPO), "token" (DAPO), "constant" (Dr. GRPO).
+GRPO_LOSS_TYPES = ("sequence", "token", "constant")
+
+
+def _ref_group_advantages(scores: torch.Tensor, G: int, scale_std: bool = True, eps: float = 1e-4):
+    """The torch formula of `group_advantages` (any device): (adv [P*G], in-group std [P])."""
+    r = scores.detach().float().reshape(-1, G)
+    mu = r.mean(1, keepdim=True)
+    sd = ((r - mu) ** 2).mean(1, keepdim=True).sqrt()
+    const = r.max(1, keepdim=True).values == r.min(1, keepdim=True).values
+    sd = torch.where(const, torch.zeros_like(sd), sd)
+    adv = (r - mu) / (sd + eps) if scale_std else r - mu
+    adv = torch.where(const, torch.zeros_like(adv), adv)  # a constant group is exactly 0
+    return adv.reshape(-1), sd.reshape(-1)
+
+
+def group_advantages(scores: torch.Tensor, G: int, scale_std: bool = True, eps: float = 1e-4
+                     ) -> Tuple[torch.Tensor, Dict[str, torch.Tensor]]:
+    """Group-relative advantages (no gradient): per group of G consecutive scores mu = mean,
+    sd = population std; adv = (r - mu) / (sd + eps), or r - mu with `scale_std=False`
+    (Dr. GRPO). A constant-reward group gives exactly 0. Returns (adv [P*G], metrics) with device
+    tensors `frac_zero_std` (groups with sd == 0) and `reward_std` (mean in-group sd)."""
+    G = int(G)
+    if G < 1 or scores.numel() % G:
+        raise ValueError(f"group_advantages: {scores.numel()} scores do not split into groups of {G}")
+    r = scores.detach().float().contiguous().view(-1)
+    if _ext.use_native(r):
+        adv, sd = _ext.require().group_advantages(r, G, bool(scale_std), float(eps))
+    else:
+        adv, sd = _ref_group_advantages(r, G, scale_std, eps)
+    return adv, {"frac_zero_std": (sd == 0).float().mean(), "reward_std": sd.mean()}
+
+
+def _ref_grpo_loss(logp, old_logp, ref_logp, adv, mask, clip_low: float = 0.2,
+                   clip_high: Optional[float] = None, beta: float = 0.04, loss_type: str = "sequence",
+                   max_len: Optional[int] = None, denom: Optional[torch.Tensor] = None):
+    """The torch formula of `grpo_loss` (any device, differentiable in `logp` through autograd)."""
+    clip_high = clip_low if clip_high is None else clip_high
+    lp = logp.float()
+    m = mask.detach().float()
+    a = adv.detach().float().view(-1, 1)
+    old = lp.detach() if old_logp is None else old_logp.detach().float()
+    d = lp - old
+    rho = torch.exp(d)
+    per = torch.maximum(-a * rho, -a * rho.clamp(1 - clip_low, 1 + clip_high))
+    kl = torch.zeros_like(per)
+    if ref_logp is not None:
+        dr = ref_logp.detach().float() - lp
+        kl = torch.exp(dr) - dr - 1
+        per = per + beta * kl
+    S = lp.shape[0]
+    c = m.sum(1)
+    if loss_type == "sequence":
+        num, div = ((per * m).sum(1) / c.clamp(min=1)).sum(), float(S)
+    elif loss_type == "token":
+        num, div = (per * m).sum(), m.sum().clamp(min=1)
+    else:
+        num, div = (per * m).sum(), float(S) * float(max_len if max_len is not None else 0)
+    if denom is not None:
+        div = denom.detach().float().reshape(())
+    loss = num / div
+    with torch.no_grad():
+        n = m.sum()
+        inv = 1.0 / n.clamp(min=1)
+        out = ((rho < 1 - clip_low) | (rho > 1 + clip_high)).float()
+        metrics = {"clipfrac": (out * m).sum() * inv, "approx_kl": (((rho - 1) - d) * m).sum() * inv,
+                   "kl_ref": (kl * m).sum() * inv, "tokens": n}
+    return loss, metrics
+
+
+class _GRPOFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, lp, old, ref, adv, mask, denom, clip_low, clip_high, beta, mode, max_len):
+        loss, dlp, metrics = _ext.require().grpo_loss(lp, old, ref, adv, mask, denom, clip_low, clip_high,
+                                                      beta, mode, max_len)
+        ctx.save_for_backward(dlp)
+        ctx.mark_non_differentiable(metrics)
+        return loss, metrics
+
+    @staticmethod
+    def backward(ctx, gloss, _gm):
+        (dlp,) = ctx.saved_tensors
+        return (dlp * gloss,) + (None,) * 10
+
+
+def grpo_loss(logp: torch.Tensor, old_logp: Optional[torch.Tensor], ref_logp: Optional[torch.Tensor],
+              adv: torch.Tensor, mask: torch.Tensor, clip_low: float = 0.2,
+              clip_high: Optional[float] = None, beta: float = 0.04, loss_type: str = "sequence",
+              max_len: Optional[int] = None, denom: Optional[torch.Tensor] = None
+              ) -> Tuple[torch.Tensor, Dict[str, torch.Tensor]]:
+    """GRPO objective on [S, T] fp32 grids (`mask`: action tokens), `adv` [S] one value per rollout.
+
+        d = logp - old; rho = exp(d); pg = max(-A rho, -A clamp(rho, 1 - clip_low, 1 + clip_high))
+        dr = ref - logp; kl = exp(dr) - dr - 1 (k3); per = pg + beta kl
+        sequence: sum_s [sum_t m per / max(c_s, 1)] / S     token: sum m per / max(sum m, 1)
+        constant: sum m per / (S max_len)
+
+    `old_logp=None`: on-policy (old = logp.detach()); `ref_logp=None` only with beta == 0;
+    `clip_high=None`: clip_low. `denom` (fp32 device tensor [1]) replaces the final divisor, so the
+    micro-batches of one rollout batch share the whole batch's normaliser without a host sync
+    (sequence mode: the full batch's S). Returns (loss, metrics) with device tensors `clipfrac`,
+    `approx_kl`, `kl_ref` (token means over the mask) and `tokens`."""
+    if loss_type not in GRPO_LOSS_TYPES:
+        raise ValueError(f"grpo_loss: loss_type must be one of {'|'.join(GRPO_LOSS_TYPES)}, got {loss_type!r}")
+    if loss_type == "constant" and max_len is None and denom is None:
+        raise ValueError("grpo_loss: loss_type='constant' needs max_len")
+    if ref_logp is None and beta != 0:
+        raise ValueError("grpo_loss: ref_logp=None is allowed only with beta == 0")
+    clip_high = clip_low if clip_high is None else clip_high
+    lp = logp.float().contiguous()
+    if not _ext.use_native(lp):
+        return _ref_grpo_loss(lp, old_logp, ref_logp, adv, mask, clip_low, clip_high,
+                              beta, loss_type, max_len, denom)
+    # absent operands alias logp: d = 0 (rho = 1) on-policy, dr = 0 (kl = 0) without a reference
+    old = lp.detach() if old_logp is None else old_logp.detach().float().contiguous()
+    ref = lp.detach() if ref_logp is None else ref_logp.detach().float().contiguous()
+    a = adv.detach().float().contiguous().view(-1)
+    m = mask.detach().float().contiguous()
+    dn = denom.detach().float().reshape(1) if denom is not None else None
+    loss, met = _GRPOFn.apply(lp, old, ref, a, m, dn, float(clip_low), float(clip_high), float(beta),
+                              GRPO_LOSS_TYPES.index(loss_type), float(max_len or 0))
+    return loss, {"clipfrac": met[0], "approx_kl": met[1], "kl_ref": met[2], "tokens": met[3]}

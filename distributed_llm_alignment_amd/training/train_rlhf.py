@@ -23,6 +23,17 @@ per-token values, the per-token reward is -kl_coef * (logp - logp_ref) plus the 
 score on the last generated token, advantages are GAE(gamma, lam) (HIP wave-scan kernel),
 whitened; `ppo_epochs` x `num_minibatches` updates of the clipped surrogate + `vf_coef` x the
 clipped value loss (fused HIP fwd+bwd kernels), policy and critic each on their own engine.
+
+`ppo.algorithm: grpo` is the critic-free, group-relative family (GRPO and its DAPO / Dr. GRPO
+normalisations): each step draws `ppo.batch_size / ppo.group_size` prompts and samples every one
+`group_size` times on ONE shared prompt prefill (`generate(num_return_sequences=G)`); the reward is
+the reward-model score alone, a rollout's advantage is its score standardised inside its group
+(`ppo.scale_rewards: false`: only centred), and the update is the token-level clipped surrogate
+(`ppo.clip_range` / `ppo.clip_range_high`) plus `ppo.kl_coef` x the k3 KL to the frozen reference,
+normalised per `ppo.loss_type: sequence|token|constant` (fused HIP fwd+bwd kernels). No critic:
+the memory plan is the REINFORCE one. `ppo_epochs`, `num_minibatches`, `update_micro_batch` and
+`async_rollouts` work as for the other algorithms; with one epoch and one minibatch the update is
+on-policy and the old-policy forward is skipped.
 """
 from __future__ import annotations
 
@@ -37,7 +48,9 @@ import torch
 from ..data import read_jsonl
 from ..models import (build_reward_model, build_value_model, generate, load_causal_lm,
                       load_reward_checkpoint)
-from ..objectives import ppo_backward, ppo_loss, ppo_rollout_stats, rlhf_loss
+from ..objectives import (grpo_denominator, grpo_loss, grpo_rollout_stats, ppo_backward, ppo_loss,
+                          ppo_rollout_stats, rlhf_loss)
+from ..ops.losses import GRPO_LOSS_TYPES
 from ..parallel.dist import barrier, split_for_rank
 from ..utils.checkpoint import save_state
 from ..utils.config import add_config_args, config_from_args
@@ -83,6 +96,15 @@ def main(argv=None) -> int:
     ctx = setup(config, "rlhf", default_seed=0)
     model_cfg: Dict = config["model"]
     ppo = config["ppo"]
+    group = 1
+    if str(ppo.get("algorithm", "reinforce")).lower() == "grpo":
+        # ppo.batch_size stays the number of rollouts per step: whole groups of one prompt each
+        group = int(ppo.get("group_size", 8))
+        if group < 1 or int(ppo.get("batch_size", 64)) % group:
+            raise ValueError(f"ppo.batch_size ({ppo.get('batch_size', 64)}) must be divisible by "
+                             f"ppo.group_size ({group})")
+        if str(ppo.get("loss_type", "sequence")).lower() not in GRPO_LOSS_TYPES:
+            raise ValueError(f"ppo.loss_type must be {'|'.join(GRPO_LOSS_TYPES)}, got {ppo.get('loss_type')!r}")
     policy = load_causal_lm(model_cfg["policy_model_name_or_path"],
                             gradient_checkpointing=model_cfg.get("gradient_checkpointing", True),
                             device=ctx.device, seed=ctx.seed)
@@ -123,8 +145,8 @@ def main(argv=None) -> int:
     running = RunningLoss()
     log_every = (config.get("logging", {}) or {}).get("log_every_steps", 10)
     algo = str(ppo.get("algorithm", "reinforce")).lower()
-    if algo not in ("reinforce", "ppo"):
-        raise ValueError(f"ppo.algorithm must be reinforce|ppo, got {algo!r}")
+    if algo not in ("reinforce", "ppo", "grpo"):
+        raise ValueError(f"ppo.algorithm must be reinforce|ppo|grpo, got {algo!r}")
 
     # reward inputs built on the device when the reward tokenizer equals the policy's (no
     # decode / re-tokenise round trip through the host; training/handoff.py), else the
@@ -137,7 +159,8 @@ def main(argv=None) -> int:
     ctx.log(f"reward hand-off: {'device ids' if handoff.device_path else 'decode + re-tokenise'}")
 
     def rollout():
-        batch_prompts = rng.sample(prompts, k=min(batch_size, len(prompts)))
+        # grpo: batch_size / group_size prompts, split by prompt (a group never straddles ranks)
+        batch_prompts = rng.sample(prompts, k=min(batch_size // group, len(prompts)))
         mine = split_for_rank(batch_prompts)
         ids, am = _tokenize_left(tok, mine, max_len, ctx.device)
         seqs, mask = generate(policy.model, ids, am, max_new_tokens=gen.get("max_new_tokens", 256),
@@ -145,7 +168,11 @@ def main(argv=None) -> int:
                               top_p=gen.get("top_p", 1.0), top_k=gen.get("top_k", 0),
                               pad_token_id=tok.pad_token_id, eos_token_id=getattr(tok, "eos_token_id", None),
                               generator=gen_g, return_mask=True,
-                              weight_dtype=ppo.get("rollout_weight_dtype", "bf16"))
+                              weight_dtype=ppo.get("rollout_weight_dtype", "bf16"),
+                              num_return_sequences=group, share_prefill=bool(ppo.get("share_prefill", True)))
+        if group > 1:  # the reward hand-off sees one prompt row per rollout
+            mine = [p for p in mine for _ in range(group)]
+            ids, am = ids.repeat_interleave(group, 0), am.repeat_interleave(group, 0)
         r_ids, r_mask = handoff(mine, ids, am, seqs, mask)
         with torch.no_grad():
             scores = rm(r_ids, r_mask)
@@ -154,6 +181,8 @@ def main(argv=None) -> int:
     policy.model.train()
     if algo == "ppo":
         return _ppo_loop(ctx, config, ppo, policy, ref, rm, rollout, engine, steps, kl_coef, log_every)
+    if algo == "grpo":
+        return _grpo_loop(ctx, config, ppo, policy, ref, rm, rollout, engine, steps, group, log_every)
     micro = int(ppo.get("update_micro_batch", 0) or 0)
     pending = rollout()
     for step in range(steps):
@@ -219,6 +248,89 @@ def reinforce_update(policy, ref, engine, seqs, mask, scores, kl_coef: float, mi
         tot = tot + loss.detach() * w
         kl = kl + m["kl"] * w
     return tot, {"kl": kl}
+
+
+def grpo_update(policy, engine, seqs, mask, stats, clip_low: float, clip_high, beta: float,
+                loss_type: str, max_len, micro: int = 0):
+    """Backward of the GRPO loss over one minibatch of rollouts. micro > 0
+    (`ppo.update_micro_batch`): gradient-accumulated micro-batches of `micro` rollouts that share
+    the whole minibatch's divisor (`denom`, a device tensor: no host sync), so their gradients sum
+    to the full minibatch's; every micro-batch but the last runs under `engine.no_sync()`.
+    Returns (loss, metrics) with token-weighted metric means."""
+    n = seqs.shape[0]
+    rows = ("act", "advantages", "ref_logp", "old_logp")
+    if micro <= 0 or micro >= n:
+        loss, m = grpo_loss(policy, seqs, mask, stats, clip_low, clip_high, beta, loss_type, max_len)
+        loss.backward()
+        return loss.detach(), m
+    denom = grpo_denominator(stats["act"], loss_type, max_len)
+    bounds = micro_bounds(n, micro)
+    tot, acc = 0.0, {"clipfrac": 0.0, "approx_kl": 0.0, "kl_ref": 0.0}
+    tokens = stats["act"].sum().clamp(min=1)
+    for i, (s0, s1) in enumerate(bounds):
+        mb = {k: (stats[k][s0:s1] if stats.get(k) is not None else None) for k in rows}
+        ctx = engine.no_sync() if i < len(bounds) - 1 else contextlib.nullcontext()
+        with ctx:
+            loss, m = grpo_loss(policy, seqs[s0:s1], mask[s0:s1], mb, clip_low, clip_high, beta, loss_type,
+                                max_len, denom)
+            loss.backward()
+        tot = tot + loss.detach()
+        for k in acc:
+            acc[k] = acc[k] + m[k] * m["tokens"] / tokens
+    return tot, {"kl": acc["kl_ref"], "tokens": tokens, **acc}
+
+
+def _grpo_loop(ctx, config, ppo, policy, ref, rm, rollout, engine, steps, group, log_every) -> int:
+    """Critic-free group-relative policy optimisation (`ppo.algorithm: grpo`)."""
+    clip_low = float(ppo.get("clip_range", 0.2))
+    clip_high = ppo.get("clip_range_high")
+    clip_high = float(clip_high) if clip_high is not None else None
+    beta = float(ppo.get("kl_coef", 0.04))
+    loss_type = str(ppo.get("loss_type", "sequence")).lower()
+    scale_std = bool(ppo.get("scale_rewards", True))
+    gen_len = int((ppo.get("generation_params", {}) or {}).get("max_new_tokens", 256))
+    epochs, nmb = int(ppo.get("ppo_epochs", 1)), max(1, int(ppo.get("num_minibatches", 1)))
+    micro = int(ppo.get("update_micro_batch", 0) or 0)
+    overlap = bool(ppo.get("async_rollouts", False))
+    need_old = epochs * nmb > 1  # a single update per rollout batch is on-policy: rho = 1
+    rows = ("act", "advantages", "ref_logp", "old_logp")
+    running = RunningLoss()
+    pending = rollout()
+    for step in range(steps):
+        seqs, mask, scores, tp = pending
+        stats = grpo_rollout_stats(policy.model, ref.model, seqs, mask, tp, scores, group, beta, scale_std,
+                                   need_old)
+        S = seqs.shape[0]
+        bounds = [(i * S // nmb, (i + 1) * S // nmb) for i in range(nmb)]
+        for ep in range(epochs):
+            for mi, (a, b) in enumerate(bounds):
+                if b <= a:
+                    continue
+                mb = {k: (stats[k][a:b] if stats.get(k) is not None else None) for k in rows}
+                loss, m = grpo_update(policy.model, engine, seqs[a:b], mask[a:b], mb, clip_low, clip_high,
+                                      beta, loss_type, gen_len, micro)
+                last = ep == epochs - 1 and mi == len(bounds) - 1
+                if last and overlap and step + 1 < steps:
+                    pending = rollout()  # overlaps the in-flight gradient collectives (see _ppo_loop)
+                engine.step()
+                running.update(loss)
+        if not overlap and step + 1 < steps:
+            pending = rollout()
+        if (step + 1) % log_every == 0:
+            ctx.logger.log({"train/loss": running.average, "train/kl": m["kl"],
+                            "train/reward_mean": stats["scores"].mean(),
+                            "train/reward_std": stats["reward_std"],
+                            "train/frac_zero_std": stats["frac_zero_std"],
+                            "train/clipfrac": m["clipfrac"], "train/approx_kl": m["approx_kl"],
+                            "train/grad_norm": engine.last_grad_norm,
+                            "train/comm_exposed_ms": engine.comm_timer.last_step_ms()}, step + 1)
+            running = RunningLoss()
+    barrier()
+    save_state(config["logging"]["output_dir"], [policy.model, ref.model, rm], engine, None, steps,
+               policy.tokenizer)
+    ctx.log("RLHF GRPO loop complete")
+    ctx.logger.close()
+    return 0
 
 
 def _ppo_loop(ctx, config, ppo, policy, ref, rm, rollout, engine, steps, kl_coef, log_every) -> int:

@@ -1,0 +1,136 @@
+#!/usr/bin/env python
+"""Micro-benchmarks of the GRPO kernels on one GPU (device events around repeated launches):
+
+  kv_replicate  the shared-prefill K/V replication at an RLHF shape (default Llama-3-8B: L 32,
+                P 8, G 8, Tp 512, Hkv 8, D 128, head-major cache) vs the torch
+                `repeat_interleave` + slice-copy fallback on the same tensors: time, effective
+                GB/s over the bytes the copy needs (read once + written G times) and the transient
+                memory each allocates.
+  grpo_loss     the fused loss launch pair (fwd + bwd + metrics) at S = 64, T = 768 vs the composed
+                torch formula + autograd backward on the GPU.
+
+Prints one JSON line per kernel."""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+
+def timed(fn, iters, warmup=3):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / iters  # ms
+
+
+def transient_bytes(fn):
+    torch.cuda.synchronize()
+    base = torch.cuda.memory_allocated()
+    torch.cuda.reset_peak_memory_stats()
+    fn()
+    torch.cuda.synchronize()
+    return torch.cuda.max_memory_allocated() - base
+
+
+def main() -> int:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--layers", type=int, default=32)
+    ap.add_argument("--prompts", type=int, default=8)
+    ap.add_argument("--group", type=int, default=8)
+    ap.add_argument("--prompt", type=int, default=512)
+    ap.add_argument("--new", type=int, default=256)
+    ap.add_argument("--kv-heads", type=int, default=8)
+    ap.add_argument("--head-dim", type=int, default=128)
+    ap.add_argument("--token-major", action="store_true")
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--rollouts", type=int, default=64)
+    ap.add_argument("--tokens", type=int, default=768)
+    a = ap.parse_args()
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    from distributed_llm_alignment_amd import ops
+    from distributed_llm_alignment_amd.ops import _ext
+    from distributed_llm_alignment_amd.ops.losses import _ref_grpo_loss
+
+    _ext.require()
+    dev = torch.device("cuda", 0)
+    L, P, G, Tp, H, D = a.layers, a.prompts, a.group, a.prompt, a.kv_heads, a.head_dim
+    T_max = Tp + a.new
+
+    def cache(rows, T):
+        if a.token_major:
+            return torch.zeros((L, rows, T, H, D), device=dev, dtype=torch.bfloat16)
+        return torch.zeros((L, rows, H, T, D), device=dev, dtype=torch.bfloat16).transpose(2, 3)
+
+    sk, sv = cache(P, Tp), cache(P, Tp)
+    sk.normal_()
+    sv.normal_()
+    dk, dv = cache(P * G, T_max), cache(P * G, T_max)
+
+    def hip():
+        ops.decode.kv_replicate(sk, sv, dk, dv, G)
+
+    def fallback():
+        dk[:, :, :Tp] = sk.repeat_interleave(G, dim=1)
+        dv[:, :, :Tp] = sv.repeat_interleave(G, dim=1)
+
+    fallback()
+    want_k, want_v = dk.clone(), dv.clone()
+    dk.zero_()
+    dv.zero_()
+    hip()
+    same = bool(torch.equal(dk, want_k) and torch.equal(dv, want_v))
+    del want_k, want_v
+    src_bytes = 2 * sk.numel() * 2
+    moved = src_bytes * (1 + G)  # read once, written G times
+    t_hip, t_fb = timed(hip, a.iters), timed(fallback, a.iters)
+    print(json.dumps({"bench": "kv_replicate", "layout": "token-major" if a.token_major else "head-major",
+                      "L": L, "P": P, "G": G, "Tp": Tp, "Hkv": H, "D": D, "bitwise_equal_fallback": same,
+                      "needed_gb": round(moved / 1e9, 3), "hip_ms": round(t_hip, 4),
+                      "hip_gb_s": round(moved / t_hip / 1e6, 1), "fallback_ms": round(t_fb, 4),
+                      "fallback_gb_s_same_bytes": round(moved / t_fb / 1e6, 1),
+                      "hip_transient_mib": round(transient_bytes(hip) / 2 ** 20, 1),
+                      "fallback_transient_mib": round(transient_bytes(fallback) / 2 ** 20, 1)}), flush=True)
+    del sk, sv, dk, dv
+
+    S, T = a.rollouts, a.tokens
+    g = torch.Generator(device=dev).manual_seed(0)
+    lp = -torch.rand(S, T, device=dev, generator=g) * 3
+    old = lp + 0.3 * torch.randn(S, T, device=dev, generator=g)
+    ref = lp + 0.2 * torch.randn(S, T, device=dev, generator=g)
+    mask = (torch.rand(S, T, device=dev, generator=g) > 0.3).float()
+    adv = torch.randn(S, device=dev, generator=g)
+    out = {"bench": "grpo_loss", "S": S, "T": T}
+    for lt in ("sequence", "token", "constant"):
+        def fused():
+            x = lp.detach().requires_grad_(True)
+            loss, _ = ops.grpo_loss(x, old, ref, adv, mask, 0.2, 0.28, 0.04, lt, T)
+            loss.backward()
+            return loss, x.grad
+
+        def composed():
+            x = lp.detach().requires_grad_(True)
+            loss, _ = _ref_grpo_loss(x, old, ref, adv, mask, 0.2, 0.28, 0.04, lt, T)
+            loss.backward()
+            return loss, x.grad
+
+        (l1, g1), (l2, g2) = fused(), composed()
+        out[f"{lt}_loss_diff"] = float((l1 - l2).detach().abs())
+        out[f"{lt}_grad_max_diff"] = float((g1 - g2).abs().max())
+        out[f"{lt}_fused_ms"] = round(timed(fused, 50), 4)
+        out[f"{lt}_composed_ms"] = round(timed(composed, 50), 4)
+    print(json.dumps(out), flush=True)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

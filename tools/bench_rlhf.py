@@ -18,7 +18,15 @@ and critic values, GAE) -> `--ppo-epochs` x `--minibatches` clipped-surrogate + 
 two engines. `--zero-shape N` lays both engines out as rank 0 of an N-rank ZeRO-1 job (fp32 master
 and moments for 1/N of each model, no collectives), so the memory and per-rank work are those of
 one GPU of the N-GPU node (reference: config/rlhf_config.yaml:13 batch 64 over 8 processes = 8
-rollouts per rank). Prints the phase split and a per-rank memory plan."""
+rollouts per rank). Prints the phase split and a per-rank memory plan.
+
+--algorithm grpo: critic-free group-relative policy optimisation (`ppo.algorithm: grpo`,
+config/rlhf_grpo_llama3_8b.yaml): `--batch` rollouts = batch / `--group` prompts sampled `--group`
+times each (`--share-prefill 1`: one prompt prefill per group, its K/V replicated by the
+kv_replicate kernel; `0`: the prompts repeated, every copy prefilled -- the A/B arm), generate ->
+score -> stats (group advantages, reference log-probs) -> one on-policy update of the clipped
+surrogate + k3 KL (`--loss-type`), optionally in `--micro` gradient-accumulated micro-batches that
+share the batch's divisor. Same phase split and per-phase peak memory as --algorithm ppo."""
 from __future__ import annotations
 
 import argparse
@@ -50,7 +58,12 @@ def main() -> int:
                          "micro-batches, each with its own advantage baseline -- one rank's share of "
                          "a batch/micro-rank DDP job (the reference splits the batch across processes "
                          "and takes rewards.mean() per process), so no activation recompute is needed")
-    ap.add_argument("--algorithm", choices=("reinforce", "ppo"), default="reinforce")
+    ap.add_argument("--algorithm", choices=("reinforce", "ppo", "grpo"), default="reinforce")
+    ap.add_argument("--group", type=int, default=8, help="grpo: samples per prompt (ppo.group_size)")
+    ap.add_argument("--share-prefill", type=int, choices=(0, 1), default=1,
+                    help="grpo: 1 = one prompt prefill per group, 0 = repeated prompts (A/B arm)")
+    ap.add_argument("--loss-type", choices=("sequence", "token", "constant"), default="sequence")
+    ap.add_argument("--kl-coef", type=float, default=0.04, help="grpo: beta of the k3 KL term")
     ap.add_argument("--rollout-dtype", choices=("bf16", "fp8"), default="bf16",
                     help="decode weight streams of the rollout generation (ppo.rollout_weight_dtype)")
     ap.add_argument("--frozen-fp8", action="store_true",
@@ -68,9 +81,15 @@ def main() -> int:
     if a.micro and a.batch % a.micro:
         ap.error("--batch must be a multiple of --micro")
     if a.micro and (a.overlap or a.algorithm == "ppo"):
-        ap.error("--micro applies to the synchronous reinforce update only")
+        ap.error("--micro applies to the synchronous reinforce and grpo updates only")
     if a.algorithm == "ppo":
         return ppo_main(a)
+    if a.algorithm == "grpo":
+        if a.batch % a.group:
+            ap.error("--batch must be a multiple of --group")
+        if a.overlap:
+            ap.error("--overlap is not implemented for grpo")
+        return grpo_main(a)
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from distributed_llm_alignment_amd.models import build_model, generate, get_config
     from distributed_llm_alignment_amd.models.reward import RewardModel
@@ -352,6 +371,117 @@ def ppo_main(a) -> int:
                       "rollout_dtype": a.rollout_dtype, "frozen_fp8": a.frozen_fp8,
                       "zero_shape": a.zero_shape, "ppo_epochs": a.ppo_epochs, "minibatches": a.minibatches,
                       "grad_ckpt": a.grad_ckpt or "none", "prompt": a.prompt, "new_tokens": a.new,
+                      "s_per_step": round(dt / a.steps, 3), "rollouts_per_s": round(a.batch * a.steps / dt, 3),
+                      **{f"{k}_s": round(v / a.steps, 3) for k, v in phases.items()},
+                      "mem_after_gib": mem, "peak_gib_by_phase": peaks,
+                      "device_total_gib": round(torch.cuda.get_device_properties(dev).total_memory / gib, 1),
+                      **health}), flush=True)
+    return 0
+
+
+def grpo_main(a) -> int:
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    from distributed_llm_alignment_amd.models import build_model, generate, get_config
+    from distributed_llm_alignment_amd.models.reward import RewardModel
+    from distributed_llm_alignment_amd.models.tokenizer import ByteTokenizer
+    from distributed_llm_alignment_amd.objectives import grpo_rollout_stats
+    from distributed_llm_alignment_amd.ops import _ext
+    from distributed_llm_alignment_amd.parallel.data_parallel import DataParallelEngine
+    from distributed_llm_alignment_amd.training.handoff import RewardHandoff
+    from distributed_llm_alignment_amd.training.train_rlhf import grpo_update
+    from distributed_llm_alignment_amd.utils.tuning import enable_gemm_tuning
+
+    dev = torch.device("cuda", 0)
+    _ext.require()
+    enable_gemm_tuning(0)
+    cfg = get_config(a.model)
+    gib = 2.0 ** 30
+    mem = {}
+
+    def note(k):
+        torch.cuda.synchronize()
+        mem[k] = round(torch.cuda.memory_allocated(dev) / gib, 2)
+
+    note("start")
+    pol = build_model(cfg, device=dev, dtype=torch.bfloat16, seed=1)
+    note("policy")
+    ref = build_model(cfg, device=dev, dtype=torch.bfloat16, seed=1).requires_grad_(False).eval()
+    note("reference")
+    rm = RewardModel(build_model(cfg, device=dev, dtype=torch.bfloat16, seed=2, headless=True)).to(dev, torch.bfloat16)
+    if a.frozen_fp8:
+        from distributed_llm_alignment_amd.ops import enable_fp8_inference
+
+        enable_fp8_inference(ref)
+        enable_fp8_inference(rm.backbone)
+    rm.eval().requires_grad_(False)
+    note("reward")
+    if a.grad_ckpt:
+        pol.gradient_checkpointing_enable(a.grad_ckpt)
+    eng = DataParallelEngine(pol, lr=1e-6, betas=(0.9, 0.95), weight_decay=0.01, max_grad_norm=1.0,
+                             shape_world=a.zero_shape)
+    note("policy_engine")
+    g = torch.Generator(device=dev).manual_seed(0)
+    tok = ByteTokenizer(vocab_size=cfg.vocab_size)
+    handoff = RewardHandoff(tok, tok, cfg.vocab_size, dev, a.prompt + a.new + 8, "device")
+    G, P = a.group, a.batch // a.group
+    prompts = ["synthetic prompt"] * a.batch
+    phases = {"generate": 0.0, "score": 0.0, "stats": 0.0, "update": 0.0}
+    peaks = {}
+
+    def sync():
+        torch.cuda.synchronize()
+        return time.perf_counter()
+
+    def phase_peak(name):
+        torch.cuda.synchronize()
+        peaks[name] = max(peaks.get(name, 0.0), round(torch.cuda.max_memory_allocated(dev) / gib, 2))
+        torch.cuda.reset_peak_memory_stats(dev)
+
+    def step(record):
+        ids = torch.randint(3, cfg.vocab_size, (P, a.prompt), device=dev, generator=g)
+        am = torch.ones_like(ids)
+        torch.cuda.reset_peak_memory_stats(dev)
+        t0 = sync()
+        seqs, mask = generate(pol, ids, am, max_new_tokens=a.new, do_sample=True, temperature=0.7,
+                              top_p=0.9, eos_token_id=-1, return_mask=True, seed=3,
+                              weight_dtype=a.rollout_dtype, num_return_sequences=G,
+                              share_prefill=bool(a.share_prefill))
+        t1 = sync()
+        phase_peak("generate")
+        with torch.no_grad():
+            r_ids, r_mask = handoff(prompts, ids.repeat_interleave(G, 0), am.repeat_interleave(G, 0), seqs, mask)
+            scores = rm(r_ids, r_mask)
+        t2 = sync()
+        phase_peak("score")
+        stats = grpo_rollout_stats(pol, ref, seqs, mask, a.prompt, scores, G, a.kl_coef, True, False)
+        t3 = sync()
+        phase_peak("stats")
+        pol.train()
+        loss, m = grpo_update(pol, eng, seqs, mask, stats, 0.2, None, a.kl_coef, a.loss_type, a.new, a.micro)
+        eng.step()
+        t4 = sync()
+        phase_peak("update")
+        if record:
+            phases["generate"] += t1 - t0
+            phases["score"] += t2 - t1
+            phases["stats"] += t3 - t2
+            phases["update"] += t4 - t3
+        return loss, m, stats
+
+    for _ in range(a.warmup):
+        step(False)
+    t = sync()
+    for _ in range(a.steps):
+        loss, m, stats = step(True)
+    dt = sync() - t
+    health = {"loss": round(float(loss), 6), "policy_grad_norm": round(float(eng.last_grad_norm), 5),
+              "kl_ref": round(float(m["kl"]), 6), "reward_std": round(float(stats["reward_std"]), 4),
+              "frac_zero_std": round(float(stats["frac_zero_std"]), 4)}
+    print(json.dumps({"bench": "grpo_step", "model": cfg.name, "rollouts_per_step": a.batch, "group": G,
+                      "share_prefill": bool(a.share_prefill), "loss_type": a.loss_type, "kl_coef": a.kl_coef,
+                      "rollout_dtype": a.rollout_dtype, "frozen_fp8": a.frozen_fp8, "zero_shape": a.zero_shape,
+                      "update_micro": a.micro or a.batch, "grad_ckpt": a.grad_ckpt or "none",
+                      "prompt": a.prompt, "new_tokens": a.new,
                       "s_per_step": round(dt / a.steps, 3), "rollouts_per_s": round(a.batch * a.steps / dt, 3),
                       **{f"{k}_s": round(v / a.steps, 3) for k, v in phases.items()},
                       "mem_after_gib": mem, "peak_gib_by_phase": peaks,
