@@ -11,6 +11,8 @@
 //   * partial (m, l, o) per split in fp32, merged by `decode_combine_kernel`.
 // Lengths are DEVICE values (kv_len scalar, per-row kv_start for left padding), so the same
 // launch replays inside a captured hipGraph while the cache grows; splits beyond kv_len exit.
+// Group rollouts whose rows share a prompt prefix have a two-launch form that reads the prefix once
+// per group (DecGroup, decode_prefix_kernel, launch_decode_attn_group below).
 #include <algorithm>
 #include <cstdlib>
 
@@ -295,17 +297,33 @@ __device__ __forceinline__ void dec_pub(float* p, float v, bool wt) {
 
 constexpr int kDecMaxFuse = 8;  // most splits the in-kernel combine merges
 
-template <int D, int G>
+// Group-structured decode step (GRPO rollouts: rows p * G .. p * G + G - 1 share prompt p's keys
+// [0, Tp), bitwise identical copies). The prefix part [lo, Tp) is attended once per (prompt, kv
+// head) for all of the group's queries (decode_prefix_kernel, K / V of row p * G only) and lands in
+// split slots [0, npre) of every (row, q head) partial; the loop kernel then runs per row over
+// chunks >= c0 with Tp as its lower bound, fills slots [npre, npre + nsuf) and merges all of them.
+// Everything here is a host constant of the captured graph; the lengths stay device values.
+struct DecGroup {
+  int G;     // rows per prompt
+  int Tp;    // shared prefix length (keys)
+  int npre;  // prefix split slots per (row, q head)
+  int nsuf;  // suffix splits = arrivals per (row, kv head) counter
+  int c0;    // first suffix chunk
+};
+
+// GRP: `nsplit` partial slots are merged, `narrive` of them (the suffix splits of this launch)
+// arrive at the counter; the others were complete before the launch (decode_prefix_kernel).
+template <int D, int G, bool GRP = false>
 __device__ __forceinline__ void dec_arrive_combine(int* __restrict__ cnt, const float* part_o,
                                                    const float* part_ml, int64_t pbase0, int nsplit,
                                                    bf16_t* __restrict__ out, int64_t o_base,
-                                                   int64_t o_sh) {
+                                                   int64_t o_sh, int narrive = 0) {
   __shared__ int last_s;
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   if (threadIdx.x == 0) {
     const int old = __hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const int last = old == nsplit - 1;
+    const int last = old == (GRP ? narrive : nsplit) - 1;
     if (last) {
       __hip_atomic_store(cnt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
@@ -375,7 +393,7 @@ __device__ __forceinline__ void dec_glds16(const void* src, void* lds_base) {
 
 // The loop kernel's body: a block streams chunks [cbeg, cend) of one (split, kv head, sequence)
 // through a 2-deep K / V ring.
-template <int D, int G, bool ROPE>
+template <int D, int G, bool ROPE, bool GRP = false>
 __device__ __forceinline__ void dec_loop_body(
     const int split, const int hk, const int b, const int Hkv_grid,
     const bf16_t* __restrict__ q, int64_t q_sb, int64_t q_sh,
@@ -383,7 +401,11 @@ __device__ __forceinline__ void dec_loop_body(
     int64_t c_sb, int64_t c_st, int64_t c_sh, const int* __restrict__ kv_len,
     const int* __restrict__ kv_start, int window, float scale_log2, int nsplit, int cpb,
     float* __restrict__ part_o, float* __restrict__ part_ml, int Hq, const DecRope& rp,
-    bf16_t* __restrict__ out, int64_t o_sb, int64_t o_sh, int* __restrict__ cnt, int Tcap) {
+    bf16_t* __restrict__ out, int64_t o_sb, int64_t o_sh, int* __restrict__ cnt, int Tcap,
+    const DecGroup& gp = DecGroup{}) {
+  // GRP (the suffix part of a group-structured step, see DecGroup): `split` counts from chunk
+  // gp.c0, keys below gp.Tp are masked, the partials go to slots gp.npre + split of `nsplit`, and
+  // the host always asks for partials (+ the in-kernel combine when `cnt` is given).
   // out != nullptr, cnt == nullptr (one split per sequence): the block writes the normalised bf16
   // output itself; out and cnt (nsplit > 1): partials + in-kernel combine (dec_arrive_combine).
   // Either way the combine launch is skipped.
@@ -404,7 +426,7 @@ __device__ __forceinline__ void dec_loop_body(
   // this block's q heads, k and v of the newest token: a row of the qkv projection
   const bf16_t *qh = nullptr, *kh = nullptr, *vh = nullptr;
   const float *cs = nullptr, *sn = nullptr;
-  const int cfirst = split * cpb;
+  const int cfirst = (GRP ? gp.c0 : 0) + split * cpb;
   auto cache_write = [&]() {  // the newest key's rotated K / raw V into its cache slot
     if constexpr (ROPE) {
       const int cn = newest / kDecChunk;
@@ -450,10 +472,11 @@ __device__ __forceinline__ void dec_loop_body(
   };
   loadK(std::integral_constant<int, 0>{}, cfirst);  // speculative: the split's first chunk
   if (window > 0) lo = max(lo, len - window);
+  if constexpr (GRP) lo = max(lo, gp.Tp);
   // chunks [cbeg, cend) of this split that hold visible keys
   const int cbeg = max(cfirst, lo / kDecChunk);
   const int cend = min(cfirst + cpb, (len + kDecChunk - 1) / kDecChunk);
-  const int64_t pbase = ((int64_t)b * Hq + (int64_t)hk * G) * nsplit + split;
+  const int64_t pbase = ((int64_t)b * Hq + (int64_t)hk * G) * nsplit + (GRP ? gp.npre : 0) + split;
   const bool fuse = cnt != nullptr;
   int* const cslot = fuse ? cnt + (int64_t)b * Hkv_grid + hk : nullptr;
   const int64_t pbase0 = ((int64_t)b * Hq + (int64_t)hk * G) * nsplit;
@@ -469,7 +492,7 @@ __device__ __forceinline__ void dec_loop_body(
       dec_pub(&part_ml[(pbase + (int64_t)tid * nsplit) * 2 + 0], -INFINITY, fuse);
       dec_pub(&part_ml[(pbase + (int64_t)tid * nsplit) * 2 + 1], 0.f, fuse);
     }
-    if (fuse) dec_arrive_combine<D, G>(cslot, part_o, part_ml, pbase0, nsplit, out, obase, o_sh);
+    if (fuse) dec_arrive_combine<D, G, GRP>(cslot, part_o, part_ml, pbase0, nsplit, out, obase, o_sh, gp.nsuf);
     return;
   }
   // q fragments first, the oldest loads: S of chunk 0 waits for them and K(0) only
@@ -652,7 +675,7 @@ __device__ __forceinline__ void dec_loop_body(
       dec_pub(&part_ml[(pbase + (int64_t)g * nsplit) * 2 + 1], ll, fuse);
     }
   }
-  if (fuse) dec_arrive_combine<D, G>(cslot, part_o, part_ml, pbase0, nsplit, out, obase, o_sh);
+  if (fuse) dec_arrive_combine<D, G, GRP>(cslot, part_o, part_ml, pbase0, nsplit, out, obase, o_sh, gp.nsuf);
 }
 
 template <int D, int G, bool ROPE>
@@ -666,6 +689,293 @@ __global__ __launch_bounds__(256, 2) void decode_attn_loop_kernel(
   dec_loop_body<D, G, ROPE>(blockIdx.x, blockIdx.y, blockIdx.z, gridDim.y, q, q_sb, q_sh, kc, vc, c_sb, c_st,
                             c_sh, kv_len, kv_start, window, scale_log2, nsplit, cpb, part_o, part_ml, Hq, rp,
                             out, o_sb, o_sh, cnt, Tcap);
+}
+
+// The suffix part of a group-structured step: the loop kernel with GRP set (see dec_loop_body).
+template <int D, int G, bool ROPE>
+__global__ __launch_bounds__(256, 2) void decode_attn_loop_group_kernel(
+    const bf16_t* __restrict__ q, int64_t q_sb, int64_t q_sh,
+    bf16_t* __restrict__ kc, bf16_t* __restrict__ vc,
+    int64_t c_sb, int64_t c_st, int64_t c_sh, const int* __restrict__ kv_len,
+    const int* __restrict__ kv_start, int window, float scale_log2, int nsplit, int cpb,
+    float* __restrict__ part_o, float* __restrict__ part_ml, int Hq, DecRope rp,
+    bf16_t* __restrict__ out, int64_t o_sb, int64_t o_sh, int* __restrict__ cnt, int Tcap, DecGroup gp) {
+  dec_loop_body<D, G, ROPE, true>(blockIdx.x, blockIdx.y, blockIdx.z, gridDim.y, q, q_sb, q_sh, kc, vc, c_sb,
+                                  c_st, c_sh, kv_len, kv_start, window, scale_log2, nsplit, cpb, part_o,
+                                  part_ml, Hq, rp, out, o_sb, o_sh, cnt, Tcap, gp);
+}
+
+// The prefix part of a group-structured step (see DecGroup): grid (npre, Hkv, P * ntile). A block
+// streams chunks [split * cpb, +cpb) of keys [lo, min(Tp, kv_len)) of ONE cache row, p * G, with the
+// loop kernel's machinery (K rows as MFMA A fragments in a 2-slot register ring, V by LDS-DMA into
+// the wave's swizzled image, read back transposed, exp2-domain online softmax per wave), but against
+// NT 16-column query tiles at once: column c of row tile `tg` is q head hk * GQ + c % GQ of group
+// row tg * rpt + c / GQ. Every K fragment and every V image read feeds NT MFMAs; each tile keeps
+// its own (m, l, o). Columns past rpt * GQ or rows past G are padding: zero queries, never stored.
+// The 4 waves merge in a fixed tree ((0 + 1) + (2 + 3)) through the dead V images, lane for lane
+// in the accumulator layout, and the block stores the fp32 partial of slot `split` for each of
+// its (row, q head) columns. An empty range stores m = -inf, l = 0 and no o row.
+template <int D, int NT, bool ROPE>
+__global__ __launch_bounds__(256, NT > 2 ? 1 : 2) void decode_prefix_kernel(
+    const bf16_t* __restrict__ q, int64_t q_sb, int64_t q_sh,
+    const bf16_t* __restrict__ kc, const bf16_t* __restrict__ vc,
+    int64_t c_sb, int64_t c_st, int64_t c_sh, const int* __restrict__ kv_len,
+    const int* __restrict__ kv_start, int window, float scale_log2, int ntot, int cpb,
+    float* __restrict__ part_o, float* __restrict__ part_ml, int Hq, int GQ, DecRope rp,
+    DecGroup gp, int rpt, int ntile, int Tcap) {
+  constexpr int LPK = D / 8, KPI = 64 / LPK, KPW = kDecChunk / 4, NIT = KPW / KPI;
+  constexpr int KST = D / 32, NDT = D / 16, RD = 2;
+  constexpr int WSZ = NT * 16 * D;  // floats of one wave's partial O
+  static_assert(NT >= 1 && NT <= 4 && KPW == 32, "prefix tile geometry");
+  static_assert(2 * WSZ * 4 <= 4 * RD * KPW * D * 2, "two waves' partial O alias the V images");
+  __shared__ __attribute__((aligned(16))) bf16_t vimg[4][RD][KPW * D];
+  __shared__ float mls[2][NT][2][64];
+  __shared__ float mlf[NT * 16][2];
+  const int split = blockIdx.x, hk = blockIdx.y;
+  const int p = blockIdx.z / ntile, tg = blockIdx.z % ntile;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int sub = lane / LPK, dl = (lane % LPK) * 8;
+  const int r16 = lane & 15, kg = lane >> 4;
+  const int b0 = p * gp.G;  // the row whose prefix K / V the whole group reads
+  const int len = kv_len[0];
+  int lo = kv_start ? kv_start[b0] : 0;
+  const bf16_t* kb0 = kc + (int64_t)b0 * c_sb + (int64_t)hk * c_sh;
+  const bf16_t* vb0 = vc + (int64_t)b0 * c_sb + (int64_t)hk * c_sh;
+  const int cfirst = split * cpb;
+  s16x8 kf[RD][2][KST];
+  auto loadK = [&](auto J, int c) {
+    constexpr int j = decltype(J)::value;
+    const int kw0 = c * kDecChunk + wv * KPW;
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      const int kcl = min(kw0 + 16 * t + r16, Tcap - 1);
+#pragma unroll
+      for (int s = 0; s < KST; ++s)
+        kf[j][t][s] = __builtin_bit_cast(s16x8, load_bf16x8(kb0 + (int64_t)kcl * c_st + 32 * s + 8 * kg));
+    }
+  };
+  loadK(std::integral_constant<int, 0>{}, cfirst);  // speculative, as in dec_loop_body
+  if (window > 0) lo = max(lo, len - window);
+  const int hi = min(gp.Tp, len);
+  const int cbeg = max(cfirst, lo / kDecChunk);
+  const int cend = min(cfirst + cpb, (hi + kDecChunk - 1) / kDecChunk);
+  // column c = 16 n + r16 of this row tile (S layout: the lane's own column of tile n)
+  const int ncol = rpt * GQ;
+  auto col_row = [&](int c) { return tg * rpt + c / GQ; };
+  auto col_ok = [&](int c) { return c < ncol && col_row(c) < gp.G; };
+  auto col_pbase = [&](int c) {  // partial slot `split` of the column's (row, q head)
+    return ((int64_t)(b0 + col_row(c)) * Hq + (int64_t)hk * GQ + c % GQ) * ntot + split;
+  };
+  if (cbeg >= cend || max(cbeg * kDecChunk, lo) >= hi) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the speculative K loads
+    if (tid < NT * 16 && col_ok(tid)) {
+      part_ml[col_pbase(tid) * 2 + 0] = -INFINITY;
+      part_ml[col_pbase(tid) * 2 + 1] = 0.f;
+    }
+    return;
+  }
+  s16x8 qf[NT][KST];
+  bool cok[NT];
+#pragma unroll
+  for (int n = 0; n < NT; ++n) {
+    const int c = 16 * n + r16;
+    cok[n] = col_ok(c);
+    const int b = b0 + col_row(c), h = hk * GQ + c % GQ;
+#pragma unroll
+    for (int s = 0; s < KST; ++s) {
+      qf[n][s] = s16x8{};
+      if (cok[n]) {
+        if constexpr (ROPE) {
+          const int half = rp.rot >> 1;
+          const float* cs = rp.cos_t + (int64_t)rp.pos[b] * half;
+          const float* sn = rp.sin_t + (int64_t)rp.pos[b] * half;
+          qf[n][s] = __builtin_bit_cast(s16x8, dec_rope8(rp.qkv + (int64_t)b * rp.ld + (int64_t)h * D, 32 * s + 8 * kg, rp.rot, cs, sn));
+        } else {
+          qf[n][s] = __builtin_bit_cast(s16x8, load_bf16x8(q + (int64_t)b * q_sb + (int64_t)h * q_sh + 32 * s + 8 * kg));
+        }
+      }
+    }
+  }
+  auto loadV = [&](auto J, int c) {
+    constexpr int j = decltype(J)::value;
+    const int base = c * kDecChunk, k0 = max(base, lo), k1 = min(base + kDecChunk, hi);
+    const int kw0 = base + wv * KPW;
+    bf16_t* img = &vimg[wv][j][0];
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+      const int row = it * KPI + sub;
+      const int key = min(max(kw0 + row, k0), k1 - 1);
+      const int ch = (dec_swz<D>(row, dl >> 3) - row * D) >> 3;  // position dl/8 <-> chunk ch
+      dec_glds16(vb0 + (int64_t)key * c_st + ch * 8, img + it * 512);
+    }
+  };
+  auto load = [&](auto J, int c) {  // issue order per chunk: K then V
+    loadK(J, c);
+    loadV(J, c);
+  };
+  float m_run[NT], l_run[NT];
+  f32x4 oacc[NT][NDT];
+#pragma unroll
+  for (int n = 0; n < NT; ++n) {
+    m_run[n] = -INFINITY;
+    l_run[n] = 0.f;
+#pragma unroll
+    for (int dt = 0; dt < NDT; ++dt) oacc[n][dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  auto step = [&](auto J, int c) {
+    constexpr int j = decltype(J)::value;
+    const int base = c * kDecChunk, k0 = max(base, lo), k1 = min(base + kDecChunk, hi);
+    const int kw0 = base + wv * KPW;
+    s16x8 pa[NT];
+    float ai[NT][4];
+#pragma unroll
+    for (int n = 0; n < NT; ++n) {
+      f32x4 sacc[2];
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        sacc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int s = 0; s < KST; ++s) sacc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[j][t][s], qf[n][s], sacc[t], 0, 0, 0);
+      }
+      float sc[2][4];
+      float mc = -INFINITY;
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int key = kw0 + 16 * t + 4 * kg + i;
+          sc[t][i] = (key >= k0 && key < k1) ? sacc[t][i] * scale_log2 : -INFINITY;
+          mc = fmaxf(mc, sc[t][i]);
+        }
+      mc = fmaxf(mc, __shfl_xor(mc, 16, 64));
+      mc = fmaxf(mc, __shfl_xor(mc, 32, 64));
+      const float mnew = fmaxf(m_run[n], mc);
+      const float alpha = m_run[n] == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(m_run[n] - mnew);
+      const float muse = mnew == -INFINITY ? 0.f : mnew;
+      float pv8[8], ls = 0.f;
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const float pe = __builtin_amdgcn_exp2f(sc[t][i] - muse);
+          ls += pe;
+          pv8[4 * t + i] = cok[n] ? pe : 0.f;
+        }
+      ls += __shfl_xor(ls, 16, 64);
+      ls += __shfl_xor(ls, 32, 64);
+      l_run[n] = l_run[n] * alpha + ls;
+      m_run[n] = mnew;
+      pa[n] = __builtin_bit_cast(s16x8, pack_bf16x8(pv8));
+#pragma unroll
+      for (int i = 0; i < 4; ++i) ai[n][i] = __shfl(alpha, 4 * kg + i, 64);
+    }
+    // V(c) has landed once every VMEM op but the next chunk's is done (see dec_loop_body)
+    constexpr int PER = 2 * KST + NIT;
+    const int nlater = min(RD - 1, cend - 1 - c);
+    if (nlater == 1) {
+      if constexpr (PER == 16) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
+      else if constexpr (PER == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    } else {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    bf16_t* vw = &vimg[wv][j][0];
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int dt = 0; dt < NDT; ++dt) {
+      const s16x4 v0 = dec_tr_read<D>(vw, 4 * kg, 16 * dt, lane);
+      const s16x4 v1 = dec_tr_read<D>(vw, 16 + 4 * kg, 16 * dt, lane);
+      const s16x8 vb = s16x8{v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
+#pragma unroll
+      for (int n = 0; n < NT; ++n) {
+        f32x4 o = oacc[n][dt];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) o[i] *= ai[n][i];
+        oacc[n][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pa[n], vb, o, 0, 0, 0);
+      }
+    }
+    if (c + RD < cend) {
+      // WAR: this slot's transposed reads are complete before the DMA refill is issued
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      load(J, c + RD);
+    }
+  };
+  if (cbeg != cfirst) loadK(std::integral_constant<int, 0>{}, cbeg);  // the guess was wrong
+  loadV(std::integral_constant<int, 0>{}, cbeg);
+  if (cbeg + 1 < cend) load(std::integral_constant<int, 1>{}, cbeg + 1);
+  for (int c = cbeg; c < cend; c += RD) {
+    step(std::integral_constant<int, 0>{}, c);
+    if (c + 1 < cend) step(std::integral_constant<int, 1>{}, c + 1);
+  }
+  // ---- merge the 4 waves: 1 -> 0 and 3 -> 2, then 2 -> 0, through the (dead) V images
+  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+  __syncthreads();
+  float* mb = reinterpret_cast<float*>(&vimg[0][0][0]);
+  auto put = [&](int slot) {
+#pragma unroll
+    for (int n = 0; n < NT; ++n) {
+      mls[slot][n][0][lane] = m_run[n];
+      mls[slot][n][1][lane] = l_run[n];
+#pragma unroll
+      for (int dt = 0; dt < NDT; ++dt)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) mb[slot * WSZ + ((n * NDT + dt) * 4 + i) * 64 + lane] = oacc[n][dt][i];
+    }
+  };
+  auto take = [&](int slot) {
+#pragma unroll
+    for (int n = 0; n < NT; ++n) {
+      const float m2 = mls[slot][n][0][lane], l2 = mls[slot][n][1][lane];
+      const float mm = fmaxf(m_run[n], m2);
+      const float c1 = m_run[n] == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(m_run[n] - mm);
+      const float c2 = m2 == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(m2 - mm);
+      l_run[n] = c1 * l_run[n] + c2 * l2;
+      m_run[n] = mm;
+      float a1[4], a2[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        a1[i] = __shfl(c1, 4 * kg + i, 64);
+        a2[i] = __shfl(c2, 4 * kg + i, 64);
+      }
+#pragma unroll
+      for (int dt = 0; dt < NDT; ++dt)
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          oacc[n][dt][i] = a1[i] * oacc[n][dt][i] + a2[i] * mb[slot * WSZ + ((n * NDT + dt) * 4 + i) * 64 + lane];
+    }
+  };
+  if (wv & 1) put(wv >> 1);
+  __syncthreads();
+  if (!(wv & 1)) take(wv >> 1);
+  __syncthreads();
+  if (wv == 2) put(0);
+  __syncthreads();
+  if (wv == 0) {
+    take(0);
+    // the block's partial as [column][d] in slot 1 (slot 0 is being read by this wave)
+#pragma unroll
+    for (int n = 0; n < NT; ++n) {
+#pragma unroll
+      for (int dt = 0; dt < NDT; ++dt)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) mb[WSZ + (16 * n + 4 * kg + i) * D + 16 * dt + r16] = oacc[n][dt][i];
+      if (kg == 0) {
+        mlf[16 * n + r16][0] = m_run[n];
+        mlf[16 * n + r16][1] = l_run[n];
+      }
+    }
+  }
+  __syncthreads();
+  for (int i = tid; i < NT * 16 * D; i += 256) {
+    const int c = i / D, d = i % D;
+    if (!col_ok(c)) continue;
+    const int64_t pb = col_pbase(c);
+    part_o[pb * D + d] = mb[WSZ + i];
+    if (d == 0) {
+      part_ml[pb * 2 + 0] = mlf[c][0];
+      part_ml[pb * 2 + 1] = mlf[c][1];
+    }
+  }
 }
 
 // Decode-step prologue: rotate q (-> q_out [B, Hq, D]) and k of the newest token and write k and
@@ -873,6 +1183,148 @@ int decode_num_splits(int Tmax, int B, int Hkv) {
   const int nch = (Tmax + kDecChunk - 1) / kDecChunk;
   const int cpb = decode_cpb(Tmax, B, Hkv);
   return cpb == 0 ? nch : (nch + cpb - 1) / cpb;
+}
+
+// ---- group-structured step (DecGroup): split geometry and launches
+// Row tiles of at most 64 query columns (rpt rows x GQ heads), prefix chunks [0, ceil(Tp / 128))
+// and suffix chunks [Tp / 128, ceil(Tmax / 128)) each cut so that the grid stays near
+// DLA_DECODE_BLOCKS (default 256) blocks, as decode_cpb does for the per-row kernel; the prefix
+// cut is coarsened until prefix + suffix slots fit the in-kernel combine when they can.
+// When the suffix alone takes kDecMaxFuse splits there is no slot left for the prefix: the step
+// then runs the separate combine launch (a third launch) where the per-row op at that shape still
+// fuses. DLA_DECODE_LOOP=0: one chunk per block on both sides and the separate combine launch.
+struct DecGroupGeom {
+  int rpt, ntile, nt, cpb_p, cpb_s, npre, nsuf, c0;
+  bool fuse;
+};
+
+static DecGroupGeom decode_group_geom(int Tmax, int B, int Hq, int Hkv, int G, int Tp) {
+  const char* e = getenv("DLA_DECODE_LOOP");
+  const char* tb = getenv("DLA_DECODE_BLOCKS");
+  const int target = (e != nullptr && atoi(e) == 0) ? 0 : (tb ? atoi(tb) : 256);
+  const int GQ = Hq / Hkv, P = B / G;
+  DecGroupGeom g{};
+  g.rpt = std::min(G, 64 / GQ);
+  g.ntile = (G + g.rpt - 1) / g.rpt;
+  g.nt = (g.rpt * GQ + 15) / 16;
+  const int nch = (Tmax + kDecChunk - 1) / kDecChunk;
+  const int nchp = (Tp + kDecChunk - 1) / kDecChunk;
+  g.c0 = std::min(Tp / kDecChunk, nch - 1);
+  const int nchs = nch - g.c0;
+  g.fuse = target > 0;
+  if (target <= 0) {
+    g.cpb_p = g.cpb_s = 1;
+  } else {
+    const int64_t bp = static_cast<int64_t>(P) * g.ntile * Hkv * nchp;
+    const int64_t bs = static_cast<int64_t>(B) * Hkv * nchs;
+    g.cpb_p = static_cast<int>(std::min<int64_t>(std::max<int64_t>((bp + target - 1) / target, 1), nchp));
+    g.cpb_s = static_cast<int>(std::min<int64_t>(std::max<int64_t>((bs + target - 1) / target, 1), nchs));
+  }
+  g.nsuf = (nchs + g.cpb_s - 1) / g.cpb_s;
+  g.npre = (nchp + g.cpb_p - 1) / g.cpb_p;
+  if (g.fuse && g.nsuf < kDecMaxFuse && g.npre + g.nsuf > kDecMaxFuse) {
+    g.cpb_p = (nchp + (kDecMaxFuse - g.nsuf) - 1) / (kDecMaxFuse - g.nsuf);
+    g.npre = (nchp + g.cpb_p - 1) / g.cpb_p;
+  }
+  g.fuse = g.fuse && g.npre + g.nsuf <= kDecMaxFuse;
+  return g;
+}
+
+// partial slots per (row, q head) of a group-structured step: prefix splits, then suffix splits
+int decode_group_splits(int Tmax, int B, int Hq, int Hkv, int G, int Tp) {
+  const DecGroupGeom g = decode_group_geom(Tmax, B, Hq, Hkv, G, Tp);
+  return g.npre + g.nsuf;
+}
+
+template <int D>
+static void launch_decode_group_d(const bf16_t* q, int64_t q_sb, int64_t q_sh, bf16_t* kc, bf16_t* vc,
+                                  int64_t c_sb, int64_t c_st, int64_t c_sh, const int* kv_len,
+                                  const int* kv_start, int window, float scale_log2, int B, int Hq,
+                                  int Hkv, int Tmax, int G, int Tp, float* part_o, float* part_ml,
+                                  bf16_t* out, int64_t o_sb, int64_t o_sh, const DecRope* rp, int* cnt,
+                                  hipStream_t st) {
+  const int GQ = Hq / Hkv, P = B / G;
+  const DecGroupGeom g = decode_group_geom(Tmax, B, Hq, Hkv, G, Tp);
+  const DecGroup gp{G, Tp, g.npre, g.nsuf, g.c0};
+  const int ntot = g.npre + g.nsuf;
+  const DecRope r0 = rp ? *rp : DecRope{};
+  // prefix launch first: its partials are complete at the kernel boundary, ahead of the suffix
+  // launch's merge (same stream)
+  dim3 pgrid(g.npre, Hkv, P * g.ntile);
+#define DLA_PRE(NN)                                                                                      \
+  if (rp)                                                                                                \
+    decode_prefix_kernel<D, NN, true><<<pgrid, 256, 0, st>>>(q, q_sb, q_sh, kc, vc, c_sb, c_st, c_sh,    \
+                                                             kv_len, kv_start, window, scale_log2, ntot, \
+                                                             g.cpb_p, part_o, part_ml, Hq, GQ, r0, gp,   \
+                                                             g.rpt, g.ntile, Tmax);                      \
+  else                                                                                                   \
+    decode_prefix_kernel<D, NN, false><<<pgrid, 256, 0, st>>>(q, q_sb, q_sh, kc, vc, c_sb, c_st, c_sh,   \
+                                                              kv_len, kv_start, window, scale_log2, ntot, \
+                                                              g.cpb_p, part_o, part_ml, Hq, GQ, r0, gp,  \
+                                                              g.rpt, g.ntile, Tmax)
+  switch (g.nt) {
+    case 1: DLA_PRE(1); break;
+    case 2: DLA_PRE(2); break;
+    default: DLA_PRE(4); break;  // 3 tiles run as 4, the last one padding
+  }
+#undef DLA_PRE
+  int* const cn = (g.fuse && cnt != nullptr) ? cnt : nullptr;
+  bf16_t* const fin = cn != nullptr ? out : nullptr;
+  dim3 sgrid(g.nsuf, Hkv, B);
+#define DLA_SUF(GG)                                                                                      \
+  if (rp)                                                                                                \
+    decode_attn_loop_group_kernel<D, GG, true><<<sgrid, 256, 0, st>>>(                                   \
+        q, q_sb, q_sh, kc, vc, c_sb, c_st, c_sh, kv_len, kv_start, window, scale_log2, ntot, g.cpb_s,    \
+        part_o, part_ml, Hq, r0, fin, o_sb, o_sh, cn, Tmax, gp);                                         \
+  else                                                                                                   \
+    decode_attn_loop_group_kernel<D, GG, false><<<sgrid, 256, 0, st>>>(                                  \
+        q, q_sb, q_sh, kc, vc, c_sb, c_st, c_sh, kv_len, kv_start, window, scale_log2, ntot, g.cpb_s,    \
+        part_o, part_ml, Hq, r0, fin, o_sb, o_sh, cn, Tmax, gp)
+  switch (GQ) {
+    case 1: DLA_SUF(1); break;
+    case 2: DLA_SUF(2); break;
+    case 4: DLA_SUF(4); break;
+    case 8: DLA_SUF(8); break;
+    default: break;  // validated on the host
+  }
+#undef DLA_SUF
+  if (fin == nullptr)
+    decode_combine_kernel<D><<<B * Hq, 64, 0, st>>>(part_o, part_ml, ntot, out, o_sb, o_sh, Hq);
+}
+
+// Group-structured decode step (DecGroup). rp == nullptr: q [B, Hq, D] given; else the fused form
+// (raw qkv rows, rope + cache write of the newest token in the suffix launch).
+static void launch_decode_group(const bf16_t* q, int64_t q_sb, int64_t q_sh, const DecRope* rp, bf16_t* kc,
+                                bf16_t* vc, int64_t c_sb, int64_t c_st, int64_t c_sh, const int* kv_len,
+                              const int* kv_start, int window, float scale_log2, int B, int Hq, int Hkv,
+                              int D, int Tmax, int G, int Tp, float* part_o, float* part_ml, bf16_t* out,
+                              int64_t o_sb, int64_t o_sh, int* cnt, hipStream_t st) {
+  if (D == 128)
+    launch_decode_group_d<128>(q, q_sb, q_sh, kc, vc, c_sb, c_st, c_sh, kv_len, kv_start, window, scale_log2,
+                               B, Hq, Hkv, Tmax, G, Tp, part_o, part_ml, out, o_sb, o_sh, rp, cnt, st);
+  else
+    launch_decode_group_d<64>(q, q_sb, q_sh, kc, vc, c_sb, c_st, c_sh, kv_len, kv_start, window, scale_log2,
+                              B, Hq, Hkv, Tmax, G, Tp, part_o, part_ml, out, o_sb, o_sh, rp, cnt, st);
+}
+
+void launch_decode_attn_group(const bf16_t* q, int64_t q_sb, int64_t q_sh, bf16_t* kc, bf16_t* vc,
+                              int64_t c_sb, int64_t c_st, int64_t c_sh, const int* kv_len,
+                              const int* kv_start, int window, float scale_log2, int B, int Hq, int Hkv,
+                              int D, int Tmax, int G, int Tp, float* part_o, float* part_ml, bf16_t* out,
+                              int64_t o_sb, int64_t o_sh, int* cnt, hipStream_t st) {
+  launch_decode_group(q, q_sb, q_sh, nullptr, kc, vc, c_sb, c_st, c_sh, kv_len, kv_start, window, scale_log2,
+                      B, Hq, Hkv, D, Tmax, G, Tp, part_o, part_ml, out, o_sb, o_sh, cnt, st);
+}
+
+void launch_decode_attn_rope_group(const bf16_t* qkv, int64_t ld, const float* cos_t, const float* sin_t,
+                                   const int* pos, const int64_t* slot, int rot, bf16_t* kc, bf16_t* vc,
+                                   int64_t c_sb, int64_t c_st, int64_t c_sh, const int* kv_len,
+                                   const int* kv_start, int window, float scale_log2, int B, int Hq,
+                                   int Hkv, int D, int Tmax, int G, int Tp, float* part_o, float* part_ml,
+                                   bf16_t* out, int64_t o_sb, int64_t o_sh, int* cnt, hipStream_t st) {
+  const DecRope rp{qkv, ld, cos_t, sin_t, pos, slot, rot, Hkv};
+  launch_decode_group(nullptr, 0, 0, &rp, kc, vc, c_sb, c_st, c_sh, kv_len, kv_start, window, scale_log2,
+                           B, Hq, Hkv, D, Tmax, G, Tp, part_o, part_ml, out, o_sb, o_sh, cnt, st);
 }
 
 void launch_decode_attn(const bf16_t* q, int64_t q_sb, int64_t q_sh, bf16_t* kc,

@@ -58,6 +58,10 @@ class KVCache:
         self.pos = torch.zeros((batch, 1), dtype=torch.int32, device=dev)
         self.fast_decode = (not self.split and dev.type == "cuda" and dt == torch.bfloat16
                             and ops.decode.decode_supported(self.h_local, Hkv, D))
+        # (G, Tp) while rows p*G .. p*G+G-1 hold identical keys / values [0, Tp) and share kv_start
+        # (set by `prefill_shared(group_attention=True)`): the fast-decode branch of `attend` then
+        # reads that prefix once per group (the grouped decode attention ops); None = per row
+        self.group = None
 
     def nbytes(self) -> int:
         ks = self.k if isinstance(self.k, list) else [self.k]
@@ -69,6 +73,7 @@ class KVCache:
         self.len = 0
         self._pos = None
         self.capturing = False
+        self.group = None
         if kv_start is not None:
             self.kv_start.copy_(kv_start.to(torch.int32))
 
@@ -90,9 +95,19 @@ class KVCache:
         if T == 1 and self.len > 0 and self.fast_decode:
             # device-indexed cache write + split-KV decode kernel (graph-capturable)
             D = cfg.head_dim
+            if self.group is not None and self.len < self.group[1]:
+                # the grouped ops need kv_len > Tp: a newest token below the prefix boundary would
+                # be neither written by the suffix launch nor valid for the prefix launch to read
+                raise RuntimeError(f"group-structured cache of prefix {self.group[1]} holds only {self.len} keys")
             if rope is not None and rope.rot_dim % 16 == 0 and FUSED_DECODE_ROPE:
                 # rope + cache write of the newest token fused into the attention launch
                 cos, sin = rope.tables(qkv.device)
+                if self.group is not None:
+                    o = ops._ext.require().decode_attn_rope_group(
+                        qkv, cos, sin, self.pos.view(-1), self.k[layer], self.v[layer], self.slot,
+                        self.kv_len, self.kv_start, window, 1.0 / math.sqrt(D), self.h_local, self.kv_local, D,
+                        rope.rot_dim, self.group[0], self.group[1])
+                    return o.reshape(B, 1, self.h_local * D)
                 o = ops._ext.require().decode_attn_rope(
                     qkv, cos, sin, self.pos.view(-1), self.k[layer], self.v[layer], self.slot,
                     self.kv_len, self.kv_start, window, 1.0 / math.sqrt(D), self.h_local, self.kv_local, D,
@@ -108,8 +123,13 @@ class KVCache:
                                                 positions=self._pos)
                 self.k[layer].index_copy_(1, self.slot, k)
                 self.v[layer].index_copy_(1, self.slot, v)
+                o = ops.decode.decode_attention(q.reshape(B, self.h_local, D), self.k[layer],
+                                                self.v[layer], self.kv_len, self.kv_start, window)
+                return o.reshape(B, 1, self.h_local * D)
+            G, Tp = self.group if self.group is not None else (1, 0)
             o = ops.decode.decode_attention(q.reshape(B, self.h_local, D), self.k[layer],
-                                            self.v[layer], self.kv_len, self.kv_start, window)
+                                            self.v[layer], self.kv_len, self.kv_start, window,
+                                            group_size=G, prefix_len=Tp)
             return o.reshape(B, 1, self.h_local * D)
         pos, kv_start = self._pos, self.kv_start
         if self.split:
@@ -308,14 +328,16 @@ PREFILL_FP8 = os.environ.get("DLA_PREFILL_FP8", "1") != "0"
 
 @torch.no_grad()
 def prefill_shared(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor],
-                   G: int, max_len: int, cache: Optional[KVCache] = None):
+                   G: int, max_len: int, cache: Optional[KVCache] = None, group_attention: bool = False):
     """Prefill P left-padded prompts ONCE for G samples each: the prompts run through a P-row
     cache of length Tp, and their keys / values [0, Tp) of every layer are replicated into rows
     p*G .. p*G+G-1 of a P*G-row cache of length `max_len` (`ops.decode.kv_replicate`, one HIP
     launch on the GPU). `cache`: an emptied (`reset`) P*G-row cache to fill instead of a new one
     (the decode-graph reuse slot). Returns (cache advanced to Tp, last hidden rows [P*G, H]) in
     `repeat_interleave` order: what a prefill of the G-times repeated prompts leaves behind, for
-    1/G of the prompt forward."""
+    1/G of the prompt forward. `group_attention`: mark the cache as group-structured
+    (`cache.group = (G, Tp)`), so its fast-decode steps read the prompt keys / values once per
+    group instead of once per row (ops.decode.decode_attention `group_size`)."""
     P, Tp = input_ids.shape
     kv_start = attention_layout(attention_mask)[0] if attention_mask is not None else None
     small = KVCache(model, P, Tp, kv_start)
@@ -327,6 +349,7 @@ def prefill_shared(model: CausalLM, input_ids: torch.Tensor, attention_mask: Opt
         raise ValueError("prefill_shared: cache must be an empty P*G-row cache of at least Tp keys")
     ops.decode.kv_replicate(small.k, small.v, cache.k, cache.v, G)
     cache.advance(Tp)
+    cache.group = (int(G), int(Tp)) if group_attention and G > 1 else None
     return cache, h[:, -1].repeat_interleave(G, 0)
 
 
@@ -336,7 +359,8 @@ def generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional[
              top_p: float = 1.0, top_k: int = 0, eos_token_id: Optional[int] = None,
              pad_token_id: Optional[int] = None, generator: Optional[torch.Generator] = None,
              return_mask: bool = False, use_graph: Optional[bool] = None, seed: Optional[int] = None,
-             weight_dtype: str = "bf16", num_return_sequences: int = 1, share_prefill: bool = True):
+             weight_dtype: str = "bf16", num_return_sequences: int = 1, share_prefill: bool = True,
+             group_attention: bool = False):
     """Left-padded prompts [B, Tp] -> sequences [B, Tp + n] (n <= max_new_tokens).
 
     `num_return_sequences=G` (group rollouts, GRPO): G samples per prompt, output [B*G, Tp + n]
@@ -344,6 +368,10 @@ def generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional[
     prompt is prefilled once per prompt and its K/V replicated to the G rows (`prefill_shared`);
     `share_prefill=False` repeats the prompts and prefills every copy (the A/B arm). The G rows of
     a group sample independently: the sampler's Philox stream is keyed by (seed, row, step).
+    `group_attention=True` (only with G > 1 and `share_prefill`): every decode step's attention
+    reads the prompt keys / values once per group instead of once per row (csrc/decode.hip
+    decode_prefix_kernel); same mathematics, different bf16 rounding, so sampled rollouts differ
+    from the default arm's.
 
     With `return_mask`, also returns the attention mask of the full sequence (prompt mask, then
     1 for every generated token up to and including EOS, 0 afterwards) — the correct mask for
@@ -370,14 +398,15 @@ def generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional[
     f8 = weight_dtype == "fp8" or ops.decode.fp8_enabled()
     with ops.decode.fp8_weights(f8), ops.fp8_inference_scope(model, f8 and PREFILL_FP8):
         return _generate(model, input_ids, attention_mask, max_new_tokens, do_sample, temperature, top_p,
-                         top_k, eos_token_id, pad_token_id, generator, return_mask, use_graph, seed, G)
+                         top_k, eos_token_id, pad_token_id, generator, return_mask, use_graph, seed, G,
+                         bool(group_attention) and G > 1)
 
 
 def _generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor],
               max_new_tokens: int, do_sample: bool, temperature: float, top_p: float, top_k: int,
               eos_token_id: Optional[int], pad_token_id: Optional[int],
               generator: Optional[torch.Generator], return_mask: bool, use_graph: Optional[bool],
-              seed: Optional[int], G: int = 1):
+              seed: Optional[int], G: int = 1, group_attention: bool = False):
     if DECODE_GATHER and model.layers_sharded():
         # ZeRO-3 policy: gather it once for the whole rollout (fused decode kernels + captured
         # graph) instead of an all-gather per layer per token
@@ -389,7 +418,7 @@ def _generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional
                     stack.enter_context(eng.gathered_for_inference())
                 return _generate(model, input_ids, attention_mask, max_new_tokens, do_sample, temperature,
                                  top_p, top_k, eos_token_id, pad_token_id, generator, return_mask, use_graph,
-                                 seed, G)
+                                 seed, G, group_attention)
         finally:
             # the gathered units are freed on exit: the captured graph (it reads their addresses),
             # its KV cache and the derived decode weight copies (a second full set of layer
@@ -425,7 +454,8 @@ def _generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional
     if GRAPH_REUSE and use_graph is not False and max_new_tokens > 2 and input_ids.is_cuda \
             and _graph_capable(model):
         reuse_key = (B, Tp, max_new_tokens, kv_start is None, greedy, float(temperature), int(top_k),
-                     float(top_p), eos, pad, input_ids.device, _weights_key(model), ops.decode.fp8_enabled())
+                     float(top_p), eos, pad, input_ids.device, _weights_key(model), ops.decode.fp8_enabled(),
+                     G if group_attention else 0)  # the grouped ops capture G (and Tp) as host constants
         hit = _GRAPH_SLOT.get(id(model))
         if hit is not None and hit[0]() is model and hit[1] == reuse_key:
             cache, dg = hit[2], hit[3]
@@ -439,7 +469,8 @@ def _generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional
     ops.decode.refresh_folded_weights(model)
     if G > 1:
         # one prompt forward per group; its K/V and last hidden row replicated to the G rows
-        cache, last = prefill_shared(model, input_ids, attention_mask, G, Tp + max_new_tokens, cache)
+        cache, last = prefill_shared(model, input_ids, attention_mask, G, Tp + max_new_tokens, cache,
+                                     group_attention=group_attention)
         input_ids = input_ids.repeat_interleave(G, 0)
         attention_mask = attention_mask.repeat_interleave(G, 0) if attention_mask is not None else None
     else:

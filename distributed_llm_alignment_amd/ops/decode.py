@@ -1,9 +1,10 @@
 """Decode-path ops: split-KV GQA decode attention, the fused top-k/top-p sampler and
 the shared-prefill KV replication of group rollouts (`kv_replicate`).
 
-GPU tensors run `torch.ops.dla.decode_attn` / `torch.ops.dla.sample_tokens` (csrc/decode.hip,
-csrc/sampling.hip); both take their lengths / RNG counter from device memory so a decode step can
-be captured once in a hipGraph and replayed per token. CPU tensors use PyTorch references.
+GPU tensors run `torch.ops.dla.decode_attn` (`decode_attn_group` for group rollouts that share a
+prompt prefix) / `torch.ops.dla.sample_tokens` (csrc/decode.hip, csrc/sampling.hip); both take
+their lengths / RNG counter from device memory so a decode step can be captured once in a
+hipGraph and replayed per token. CPU tensors use PyTorch references.
 """
 from __future__ import annotations
 
@@ -20,18 +21,55 @@ def decode_supported(q_heads: int, kv_heads: int, head_dim: int) -> bool:
     return head_dim in (64, 128) and q_heads % kv_heads == 0 and (q_heads // kv_heads) in (1, 2, 4, 8)
 
 
+def _check_group(B: int, Tmax: int, group_size: int, prefix_len: int) -> None:
+    if group_size < 1 or B % group_size != 0:
+        raise ValueError(f"group_size {group_size!r} must be >= 1 and divide the batch ({B} rows)")
+    if group_size > 1 and not 1 <= prefix_len <= Tmax:
+        raise ValueError(f"prefix_len {prefix_len!r} must be in [1, {Tmax}] (the cache length)")
+
+
 def decode_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
                      kv_len: torch.Tensor, kv_start: Optional[torch.Tensor] = None, window: int = 0,
-                     scale: Optional[float] = None) -> torch.Tensor:
+                     scale: Optional[float] = None, group_size: int = 1, prefix_len: int = 0) -> torch.Tensor:
     """q [B, Hq, D] (the newest token), caches [B, Tmax, Hkv, D]; keys [kv_start, kv_len) are
-    attended (kv_len: int32 [1] on device). Returns [B, Hq, D]."""
+    attended (kv_len: int32 [1] on device). Returns [B, Hq, D].
+
+    `group_size=G > 1` (group rollouts): rows p*G .. p*G+G-1 share prompt p, whose keys / values
+    [0, prefix_len) are bitwise identical in the G rows, with one kv_start < prefix_len per group
+    and kv_len > prefix_len (preconditions, not checked on the device). The GPU op then reads
+    that prefix from row p*G only, once per (prompt, kv head) for all G rows
+    (`torch.ops.dla.decode_attn_group`), and merges it with the per-row attention over
+    [prefix_len, kv_len). Same mathematics as the per-row op; the bf16 rounding differs."""
     D = q.shape[-1]
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
+    group_size, prefix_len = int(group_size), int(prefix_len)
+    _check_group(q.shape[0], k_cache.shape[1], group_size, prefix_len)
     if _ext.use_native(q):
-        return _ext.require().decode_attn(q, k_cache, v_cache, kv_len.to(torch.int32),
-                                          kv_start.to(torch.int32) if kv_start is not None else None,
+        ks = kv_start.to(torch.int32) if kv_start is not None else None
+        if group_size > 1:
+            return _ext.require().decode_attn_group(q, k_cache, v_cache, kv_len.to(torch.int32), ks,
+                                                    int(window), float(scale), group_size, prefix_len)
+        return _ext.require().decode_attn(q, k_cache, v_cache, kv_len.to(torch.int32), ks,
                                           int(window), float(scale))
     return ref_decode_attention(q, k_cache, v_cache, int(kv_len.reshape(-1)[0]), kv_start, window, scale)
+
+
+def ref_decode_attention_grouped(q, k_cache, v_cache, L: int, group_size: int, prefix_len: int,
+                                 kv_start=None, window: int = 0, scale=None):
+    """`ref_decode_attention` of a group-structured batch that takes keys / values
+    [0, prefix_len) of EVERY row of group p from row p*G (what the grouped GPU op reads): equal to
+    the plain reference exactly when the group's rows share that prefix."""
+    B = q.shape[0]
+    G, Tp = int(group_size), int(prefix_len)
+    _check_group(B, k_cache.shape[1], G, Tp)
+    first = (torch.arange(B, device=q.device) // G) * G
+    n = max(0, min(Tp, L))
+    k = k_cache[:, :L].clone()
+    v = v_cache[:, :L].clone()
+    k[:, :n] = k_cache[first, :n]
+    v[:, :n] = v_cache[first, :n]
+    ks = kv_start[first] if kv_start is not None else None
+    return ref_decode_attention(q, k, v, L, ks, window, scale)
 
 
 def ref_decode_attention(q, k_cache, v_cache, L: int, kv_start=None, window: int = 0, scale=None):

@@ -26,7 +26,8 @@ clipped value loss (fused HIP fwd+bwd kernels), policy and critic each on their 
 
 `ppo.algorithm: grpo` is the critic-free, group-relative family (GRPO and its DAPO / Dr. GRPO
 normalisations): each step draws `ppo.batch_size / ppo.group_size` prompts and samples every one
-`group_size` times on ONE shared prompt prefill (`generate(num_return_sequences=G)`); the reward is
+`group_size` times on ONE shared prompt prefill (`generate(num_return_sequences=G)`;
+`ppo.group_attention: true` also reads the prompt K/V once per group in every decode step); the reward is
 the reward-model score alone, a rollout's advantage is its score standardised inside its group
 (`ppo.scale_rewards: false`: only centred), and the update is the token-level clipped surrogate
 (`ppo.clip_range` / `ppo.clip_range_high`) plus `ppo.kl_coef` x the k3 KL to the frozen reference,
@@ -169,7 +170,8 @@ def main(argv=None) -> int:
                               pad_token_id=tok.pad_token_id, eos_token_id=getattr(tok, "eos_token_id", None),
                               generator=gen_g, return_mask=True,
                               weight_dtype=ppo.get("rollout_weight_dtype", "bf16"),
-                              num_return_sequences=group, share_prefill=bool(ppo.get("share_prefill", True)))
+                              num_return_sequences=group, share_prefill=bool(ppo.get("share_prefill", True)),
+                              group_attention=bool(ppo.get("group_attention", False)))
         if group > 1:  # the reward hand-off sees one prompt row per rollout
             mine = [p for p in mine for _ in range(group)]
             ids, am = ids.repeat_interleave(group, 0), am.repeat_interleave(group, 0)

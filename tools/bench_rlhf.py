@@ -62,6 +62,9 @@ def main() -> int:
     ap.add_argument("--group", type=int, default=8, help="grpo: samples per prompt (ppo.group_size)")
     ap.add_argument("--share-prefill", type=int, choices=(0, 1), default=1,
                     help="grpo: 1 = one prompt prefill per group, 0 = repeated prompts (A/B arm)")
+    ap.add_argument("--group-attention", type=int, choices=(0, 1), default=0,
+                    help="grpo: 1 = decode attention reads a group's prompt K/V once for its G rows "
+                         "(ppo.group_attention)")
     ap.add_argument("--loss-type", choices=("sequence", "token", "constant"), default="sequence")
     ap.add_argument("--kl-coef", type=float, default=0.04, help="grpo: beta of the k3 KL term")
     ap.add_argument("--rollout-dtype", choices=("bf16", "fp8"), default="bf16",
@@ -445,7 +448,8 @@ def grpo_main(a) -> int:
         seqs, mask = generate(pol, ids, am, max_new_tokens=a.new, do_sample=True, temperature=0.7,
                               top_p=0.9, eos_token_id=-1, return_mask=True, seed=3,
                               weight_dtype=a.rollout_dtype, num_return_sequences=G,
-                              share_prefill=bool(a.share_prefill))
+                              share_prefill=bool(a.share_prefill),
+                              group_attention=bool(a.group_attention))
         t1 = sync()
         phase_peak("generate")
         with torch.no_grad():
@@ -478,7 +482,8 @@ def grpo_main(a) -> int:
               "kl_ref": round(float(m["kl"]), 6), "reward_std": round(float(stats["reward_std"]), 4),
               "frac_zero_std": round(float(stats["frac_zero_std"]), 4)}
     print(json.dumps({"bench": "grpo_step", "model": cfg.name, "rollouts_per_step": a.batch, "group": G,
-                      "share_prefill": bool(a.share_prefill), "loss_type": a.loss_type, "kl_coef": a.kl_coef,
+                      "share_prefill": bool(a.share_prefill), "group_attention": bool(a.group_attention),
+                      "loss_type": a.loss_type, "kl_coef": a.kl_coef,
                       "rollout_dtype": a.rollout_dtype, "frozen_fp8": a.frozen_fp8, "zero_shape": a.zero_shape,
                       "update_micro": a.micro or a.batch, "grad_ckpt": a.grad_ckpt or "none",
                       "prompt": a.prompt, "new_tokens": a.new,
