@@ -46,6 +46,12 @@ void launch_logprob_bwd(bf16_t*, int64_t, int, int64_t, int64_t, const int64_t*,
 void launch_row_lse(const bf16_t*, int64_t, int, int64_t, float*, hipStream_t);
 bool launch_logprob_bwd_t(bf16_t*, int64_t, int, int64_t, int64_t, const int64_t*, const float*,
                           const float*, bf16_t*, hipStream_t);
+void launch_logprob_entropy_fwd(const bf16_t*, int64_t, int, int64_t, int64_t, const int64_t*, float*,
+                                float*, float*, hipStream_t);
+void launch_logprob_entropy_bwd(bf16_t*, int64_t, int, int64_t, int64_t, const int64_t*, const float*,
+                                const float*, const float*, const float*, hipStream_t);
+bool launch_logprob_entropy_bwd_t(bf16_t*, int64_t, int, int64_t, int64_t, const int64_t*, const float*,
+                                  const float*, const float*, const float*, bf16_t*, hipStream_t);
 void launch_ensemble_kl(bf16_t*, const bf16_t*, int64_t, int64_t, int, int, const float*,
                         const float*, int64_t, const float*, float*, bool, hipStream_t);
 void launch_seq_reduce(const float*, const float*, int, int, float*, float*, hipStream_t);
@@ -646,6 +652,76 @@ at::Tensor logprob_bwd_t(at::Tensor& logits, const at::Tensor& tgt, const at::Te
   return outT;
 }
 
+// The entropy twins: the forward also emits the local shard's softmax entropy per row (every row,
+// whatever its target) from the same read; the backwards add grad_ent's term given the GLOBAL lse
+// and entropy. logp and lse are bitwise logprob_fwd's.
+std::tuple<at::Tensor, at::Tensor, at::Tensor> logprob_entropy_fwd(const at::Tensor& logits,
+                                                                   const at::Tensor& tgt,
+                                                                   int64_t vocab_offset) {
+  check_logits(logits);
+  TORCH_CHECK(tgt.scalar_type() == at::kLong && tgt.is_contiguous() && tgt.numel() == logits.size(0),
+              "targets int64 [N]");
+  same_device(logits, tgt);
+  c10::hip::HIPGuardMasqueradingAsCUDA g(logits.device());
+  auto opt = logits.options().dtype(at::kFloat);
+  auto logp = at::empty({logits.size(0)}, opt);
+  auto lse = at::empty({logits.size(0)}, opt);
+  auto ent = at::empty({logits.size(0)}, opt);
+  launch_logprob_entropy_fwd(cbp(logits), logits.stride(0), static_cast<int>(logits.size(1)),
+                             vocab_offset, logits.size(0), tgt.data_ptr<int64_t>(),
+                             logp.data_ptr<float>(), lse.data_ptr<float>(), ent.data_ptr<float>(),
+                             cur_stream(logits));
+  return {logp, lse, ent};
+}
+
+static void check_entropy_bwd(const at::Tensor& logits, const at::Tensor& tgt, const at::Tensor& lse,
+                              const at::Tensor& ent, const at::Tensor& grad_logp,
+                              const at::Tensor& grad_ent) {
+  check_logits(logits);
+  check_f32(lse, "lse");
+  check_f32(ent, "ent");
+  check_f32(grad_logp, "grad_logp");
+  check_f32(grad_ent, "grad_ent");
+  const int64_t N = logits.size(0);
+  TORCH_CHECK(tgt.scalar_type() == at::kLong && tgt.numel() == N && tgt.is_contiguous(), "targets");
+  TORCH_CHECK(lse.numel() == N && ent.numel() == N && grad_logp.numel() == N && grad_ent.numel() == N &&
+                  lse.is_contiguous() && ent.is_contiguous() && grad_logp.is_contiguous() &&
+                  grad_ent.is_contiguous(),
+              "lse/ent/grad shape");
+  same_device(logits, tgt);
+  same_device(logits, lse);
+  same_device(logits, ent);
+  same_device(logits, grad_logp);
+  same_device(logits, grad_ent);
+}
+
+void logprob_entropy_bwd(at::Tensor& logits, const at::Tensor& tgt, const at::Tensor& lse,
+                         const at::Tensor& ent, const at::Tensor& grad_logp, const at::Tensor& grad_ent,
+                         int64_t vocab_offset) {
+  check_entropy_bwd(logits, tgt, lse, ent, grad_logp, grad_ent);
+  c10::hip::HIPGuardMasqueradingAsCUDA g(logits.device());
+  launch_logprob_entropy_bwd(bp(logits), logits.stride(0), static_cast<int>(logits.size(1)), vocab_offset,
+                             logits.size(0), tgt.data_ptr<int64_t>(), lse.data_ptr<float>(),
+                             ent.data_ptr<float>(), grad_logp.data_ptr<float>(),
+                             grad_ent.data_ptr<float>(), cur_stream(logits));
+}
+
+at::Tensor logprob_entropy_bwd_t(at::Tensor& logits, const at::Tensor& tgt, const at::Tensor& lse,
+                                 const at::Tensor& ent, const at::Tensor& grad_logp,
+                                 const at::Tensor& grad_ent, int64_t vocab_offset) {
+  check_entropy_bwd(logits, tgt, lse, ent, grad_logp, grad_ent);
+  const int64_t N = logits.size(0), V = logits.size(1);
+  if (N == 0 || N % 8 != 0 || V % 8 != 0 || logits.stride(0) % 8 != 0) return at::empty({0}, logits.options());
+  c10::hip::HIPGuardMasqueradingAsCUDA g(logits.device());
+  auto outT = at::empty({V, N}, logits.options());
+  const bool ok = launch_logprob_entropy_bwd_t(bp(logits), logits.stride(0), static_cast<int>(V), N,
+                                               vocab_offset, tgt.data_ptr<int64_t>(), lse.data_ptr<float>(),
+                                               ent.data_ptr<float>(), grad_logp.data_ptr<float>(),
+                                               grad_ent.data_ptr<float>(), bp(outT), cur_stream(logits));
+  TORCH_CHECK(ok, "logprob_entropy_bwd_t: shape");
+  return outT;
+}
+
 at::Tensor row_lse(const at::Tensor& logits) {
   check_logits(logits);
   c10::hip::HIPGuardMasqueradingAsCUDA g(logits.device());
@@ -991,6 +1067,9 @@ TORCH_LIBRARY(dla, m) {
   m.def("logprob_fwd(Tensor logits, Tensor targets, int vocab_offset=0) -> (Tensor, Tensor)");
   m.def("logprob_bwd(Tensor(a!) logits, Tensor targets, Tensor lse, Tensor grad, int vocab_offset=0) -> ()");
   m.def("logprob_bwd_t(Tensor(a!) logits, Tensor targets, Tensor lse, Tensor grad, int vocab_offset=0) -> Tensor");
+  m.def("logprob_entropy_fwd(Tensor logits, Tensor targets, int vocab_offset=0) -> (Tensor, Tensor, Tensor)");
+  m.def("logprob_entropy_bwd(Tensor(a!) logits, Tensor targets, Tensor lse, Tensor ent, Tensor grad_logp, Tensor grad_ent, int vocab_offset=0) -> ()");
+  m.def("logprob_entropy_bwd_t(Tensor(a!) logits, Tensor targets, Tensor lse, Tensor ent, Tensor grad_logp, Tensor grad_ent, int vocab_offset=0) -> Tensor");
   m.def("row_lse(Tensor logits) -> Tensor");
   m.def("ensemble_kl(Tensor(a!) s_logits, Tensor t_logits, Tensor s_lse, Tensor t_lse, Tensor? grad, bool write_grad) -> Tensor");
   m.def("seq_reduce(Tensor lp, Tensor mask) -> (Tensor, Tensor)");
@@ -1026,6 +1105,9 @@ TORCH_LIBRARY_IMPL(dla, CUDA, m) {
   m.impl("logprob_fwd", &dla::logprob_fwd);
   m.impl("logprob_bwd", &dla::logprob_bwd);
   m.impl("logprob_bwd_t", &dla::logprob_bwd_t);
+  m.impl("logprob_entropy_fwd", &dla::logprob_entropy_fwd);
+  m.impl("logprob_entropy_bwd", &dla::logprob_entropy_bwd);
+  m.impl("logprob_entropy_bwd_t", &dla::logprob_entropy_bwd_t);
   m.impl("row_lse", &dla::row_lse);
   m.impl("ensemble_kl", &dla::ensemble_kl);
   m.impl("seq_reduce", &dla::seq_reduce);

@@ -21,11 +21,43 @@ __device__ __forceinline__ void lse_merge(float& m, float& s, float m2, float s2
   m = mn;
 }
 
-template <bool VEC>
+// The entropy twin carries u = sum_v exp(z_v - m) (z_v - m) next to (m, s): H = log s - u / s.
+// Moving the reference point of (s, u) from m to mn >= m: s' = e s, u' = e (u + (m - mn) s) with
+// e = exp(m - mn); an empty side (m = -inf, s = u = 0) stays 0 (the product would be 0 * inf).
+__device__ __forceinline__ float ent_shift(float u, float s, float m, float mn, float e) {
+  return m == -INFINITY ? 0.f : e * (u + (m - mn) * s);
+}
+
+// exp(d) is exactly 0 in fp32 below d = -104, so clamping the FACTOR d of a term exp(d) * d here
+// changes no term and turns the 0 * inf of a -inf logit into 0.
+#define ENT_DMIN (-128.f)
+
+// (max, sum-exp, u) triple merge. logprob_entropy_fwd promises logprob_fwd's lse bit for bit, and
+// lse_merge's `s * e1 + s2 * e2` leaves the rounding to the compiler's contraction: in
+// logprob_fwd_kernel it is fma(s2, e2, round(s * e1)) at every merge but the last wave level
+// (o == 1, sunk into the lane-0 branch as a packed multiply and an add: both products rounded).
+// Next to the u arithmetic the same expression contracts differently, so here it is spelled out
+// with contraction off (`fused` = every merge but o == 1); tests/test_entropy_gpu.py holds the
+// two kernels' lse equal.
+__device__ __forceinline__ void lse_merge_u(float& m, float& s, float& u, float m2, float s2, float u2,
+                                            bool fused) {
+#pragma clang fp contract(off)
+  const float mn = fmaxf(m, m2);
+  if (mn == -INFINITY) return;
+  const float e1 = __expf(m - mn), e2 = __expf(m2 - mn);
+  u = ent_shift(u, s, m, mn, e1) + ent_shift(u2, s2, m2, mn, e2);
+  const float a = s * e1;
+  s = fused ? __builtin_fmaf(s2, e2, a) : a + s2 * e2;
+  m = mn;
+}
+
+// ENT: also accumulate u (u_out). The (m, s) arithmetic rounds as with the flag off (contraction
+// is switched off wherever s is updated next to u); a -inf logit adds exactly 0 to s and u.
+template <bool VEC, bool ENT = false>
 __device__ __forceinline__ void row_lse(const bf16_t* __restrict__ row, int V, float& m_out,
-                                        float& s_out) {
-  __shared__ float sm[4], ss[4];
-  float m = -INFINITY, s = 0.f;
+                                        float& s_out, float* u_out = nullptr) {
+  __shared__ float sm[4], ss[4], su[ENT ? 4 : 1];
+  float m = -INFINITY, s = 0.f, u = 0.f;
   if constexpr (VEC) {
     const int nv = V >> 3;
     for (int i = threadIdx.x; i < nv; i += 256) {
@@ -37,59 +69,109 @@ __device__ __forceinline__ void row_lse(const bf16_t* __restrict__ row, int V, f
         x[j] = bf2f(a[j]);
         lm = fmaxf(lm, x[j]);
       }
+      if constexpr (ENT) {
+        if (lm == -INFINITY) continue;  // eight -inf logits add 0; m is finite below
+      }
       if (lm > m) {
-        s *= __expf(m - lm);
+        if constexpr (ENT) {
+#pragma clang fp contract(off)
+          const float e = __expf(m - lm);
+          u = ent_shift(u, s, m, lm, e);
+          s *= e;
+        } else {
+          s *= __expf(m - lm);
+        }
         m = lm;
       }
+      if constexpr (ENT) {
 #pragma unroll
-      for (int j = 0; j < 8; ++j) s += __expf(x[j] - m);
+        for (int j = 0; j < 8; ++j) {
+#pragma clang fp contract(off)
+          const float d = x[j] - m;
+          const float e = __expf(d);
+          s += e;
+          u = __builtin_fmaf(e, fmaxf(d, ENT_DMIN), u);
+        }
+      } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) s += __expf(x[j] - m);
+      }
     }
   } else {
     for (int i = threadIdx.x; i < V; i += 256) {
       const float x = bf2f(row[i]);
-      if (x > m) {
-        s *= __expf(m - x);
-        m = x;
+      if constexpr (ENT) {
+#pragma clang fp contract(off)
+        if (x > m) {
+          const float e = __expf(m - x);
+          u = ent_shift(u, s, m, x, e);
+          s *= e;
+          m = x;
+        }
+        const float d = x - m;
+        const float e = x == -INFINITY ? 0.f : __expf(d);  // (d is NaN while m is still -inf)
+        s += e;
+        u = __builtin_fmaf(e, fmaxf(d, ENT_DMIN), u);
+      } else {
+        if (x > m) {
+          s *= __expf(m - x);
+          m = x;
+        }
+        s += __expf(x - m);
       }
-      s += __expf(x - m);
     }
   }
   // wave merge
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
-    lse_merge(m, s, m2, s2);
+    if constexpr (ENT) {
+      const float u2 = __shfl_xor(u, o, 64);
+      lse_merge_u(m, s, u, m2, s2, u2, o != 1);
+    } else {
+      lse_merge(m, s, m2, s2);
+    }
   }
   const int w = threadIdx.x >> 6;
   if ((threadIdx.x & 63) == 0) {
     sm[w] = m;
     ss[w] = s;
+    if constexpr (ENT) su[w] = u;
   }
   __syncthreads();
   m = sm[0];
   s = ss[0];
+  if constexpr (ENT) u = su[0];
 #pragma unroll
-  for (int i = 1; i < 4; ++i) lse_merge(m, s, sm[i], ss[i]);
+  for (int i = 1; i < 4; ++i) {
+    if constexpr (ENT) lse_merge_u(m, s, u, sm[i], ss[i], su[i], true);
+    else lse_merge(m, s, sm[i], ss[i]);
+  }
   m_out = m;
   s_out = s;
+  if constexpr (ENT) *u_out = u;
 }
 
 // logp[r] = logits[r, tgt[r] - off] - lse[r] when this vocab shard [off, off+V) owns the
 // target; rows with tgt < 0 (ignored) or a target owned by another shard -> logp 0. lse (of the
 // local shard) is always written. off = 0, V = full vocab for the unsharded LM head.
-template <bool VEC>
+// ENT: ent_out[r] = entropy of the local shard's softmax, from the same read of the row, for
+// every row whatever its target.
+template <bool VEC, bool ENT = false>
 __global__ __launch_bounds__(256) void logprob_fwd_kernel(const bf16_t* __restrict__ logits,
                                                            int64_t ld, int V, int64_t off,
                                                            const int64_t* __restrict__ tgt,
                                                            float* __restrict__ logp,
-                                                           float* __restrict__ lse_out) {
+                                                           float* __restrict__ lse_out,
+                                                           float* __restrict__ ent_out = nullptr) {
   const int64_t r = blockIdx.x;
   const bf16_t* row = logits + r * ld;
-  float m, s;
-  row_lse<VEC>(row, V, m, s);
+  float m, s, u = 0.f;
+  row_lse<VEC, ENT>(row, V, m, s, &u);
   if (threadIdx.x == 0) {
     const float lse = m + __logf(s);
     lse_out[r] = lse;
+    if constexpr (ENT) ent_out[r] = __logf(s) - u / s;
     const int64_t t = tgt[r] - off;
     logp[r] = (tgt[r] >= 0 && t >= 0 && t < V) ? bf2f(row[t]) - lse : 0.f;
   }
@@ -97,17 +179,35 @@ __global__ __launch_bounds__(256) void logprob_fwd_kernel(const bf16_t* __restri
 
 // In place: logits[r, v] <- g[r] * (1[v == tgt - off] - exp(logits - lse)), g = dL/dlogp[r];
 // lse is the GLOBAL (all-shard) log-sum-exp. Ignored rows (tgt < 0) -> 0.
-template <bool VEC>
+// ENT adds the entropy gradient, e = dL/dent[r] and H = the GLOBAL entropy ent_in[r]:
+//   logits[r, v] <- g (1[v == t] - p) - e p (z - lse + H),  p = exp(z - lse);  z = -inf -> 0.
+template <bool ENT>
+__device__ __forceinline__ float dlogit(float z, bool hit, float gr, float lse, float er, float H) {
+#pragma clang fp contract(off)  // one rounding per operation in every kernel that inlines this
+  const float p = __expf(z - lse);
+  const float d = gr * ((hit ? 1.f : 0.f) - p);
+  if constexpr (!ENT) return d;
+  return z == -INFINITY ? 0.f : d - er * p * (z - lse + H);
+}
+
+template <bool VEC, bool ENT = false>
 __global__ __launch_bounds__(256) void logprob_bwd_kernel(bf16_t* __restrict__ logits, int64_t ld,
                                                            int V, int64_t off,
                                                            const int64_t* __restrict__ tgt,
                                                            const float* __restrict__ lse_in,
-                                                           const float* __restrict__ g) {
+                                                           const float* __restrict__ g,
+                                                           const float* __restrict__ ent_in = nullptr,
+                                                           const float* __restrict__ ge = nullptr) {
   const int64_t r = blockIdx.x;
   bf16_t* row = logits + r * ld;
   const int64_t t = tgt[r] - off;
   const float gr = tgt[r] >= 0 ? g[r] : 0.f;
   const float lse = lse_in[r];
+  float er = 0.f, H = 0.f;
+  if constexpr (ENT) {
+    er = tgt[r] >= 0 ? ge[r] : 0.f;
+    H = ent_in[r];
+  }
   if constexpr (VEC) {
     const int nv = V >> 3;
     for (int i = threadIdx.x; i < nv; i += 256) {
@@ -115,16 +215,13 @@ __global__ __launch_bounds__(256) void logprob_bwd_kernel(bf16_t* __restrict__ l
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const int v = i * 8 + j;
-        const float p = __expf(bf2f(a[j]) - lse);
-        o[j] = f2bf(gr * ((v == t ? 1.f : 0.f) - p));
+        o[j] = f2bf(dlogit<ENT>(bf2f(a[j]), v == t, gr, lse, er, H));
       }
       store_bf16x8(row + i * 8, o);
     }
   } else {
-    for (int v = threadIdx.x; v < V; v += 256) {
-      const float p = __expf(bf2f(row[v]) - lse);
-      row[v] = f2bf(gr * ((v == t ? 1.f : 0.f) - p));
-    }
+    for (int v = threadIdx.x; v < V; v += 256)
+      row[v] = f2bf(dlogit<ENT>(bf2f(row[v]), v == t, gr, lse, er, H));
   }
 }
 
@@ -134,11 +231,16 @@ __global__ __launch_bounds__(256) void logprob_bwd_kernel(bf16_t* __restrict__ l
 // gradient once more: 815 us per Llama-3-8B DPO micro-batch, profiles/r6_*). Each lane owns an
 // 8 x 8 block (8 rows x 8 vocab columns) and transposes it in registers (tr8_bf16); a wave covers
 // 64 rows x 64 columns; grid (ceil(V / 256), rows / 64); rows % 8 == 0, V % 8 == 0, ld % 8 == 0.
+// ENT: the entropy gradient too (dlogit<true>); two more per-row scalars live inside the unrolled
+// row loop, the 16 bf16x8 vectors per lane are unchanged.
+template <bool ENT = false>
 __global__ __launch_bounds__(256) void logprob_bwd_t_kernel(bf16_t* __restrict__ logits, int64_t ld, int V,
                                                              int64_t off, const int64_t* __restrict__ tgt,
                                                              const float* __restrict__ lse_in,
                                                              const float* __restrict__ g,
-                                                             bf16_t* __restrict__ outT, int64_t rows) {
+                                                             bf16_t* __restrict__ outT, int64_t rows,
+                                                             const float* __restrict__ ent_in = nullptr,
+                                                             const float* __restrict__ ge = nullptr) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int64_t r = static_cast<int64_t>(blockIdx.y) * 64 + (lane >> 3) * 8;
   const int c = blockIdx.x * 256 + w * 64 + (lane & 7) * 8;
@@ -151,11 +253,13 @@ __global__ __launch_bounds__(256) void logprob_bwd_t_kernel(bf16_t* __restrict__
     const int64_t t = tgt[r + i] - off;
     const float gr = tgt[r + i] >= 0 ? g[r + i] : 0.f;
     const float lse = lse_in[r + i];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float p = __expf(bf2f(a[i][j]) - lse);
-      o[i][j] = f2bf(gr * ((c + j == t ? 1.f : 0.f) - p));
+    float er = 0.f, H = 0.f;
+    if constexpr (ENT) {
+      er = tgt[r + i] >= 0 ? ge[r + i] : 0.f;
+      H = ent_in[r + i];
     }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) o[i][j] = f2bf(dlogit<ENT>(bf2f(a[i][j]), c + j == t, gr, lse, er, H));
     store_bf16x8(logits + (r + i) * ld + c, o[i]);
   }
   bf16x8 tt[8];
@@ -223,12 +327,39 @@ void launch_logprob_bwd(bf16_t* logits, int64_t ld, int V, int64_t off, int64_t 
   else logprob_bwd_kernel<false><<<rows, 256, 0, st>>>(logits, ld, V, off, tgt, lse, g);
 }
 
+void launch_logprob_entropy_fwd(const bf16_t* logits, int64_t ld, int V, int64_t off, int64_t rows,
+                                const int64_t* tgt, float* logp, float* lse, float* ent, hipStream_t st) {
+  if (rows == 0) return;
+  const bool vec = (V % 8 == 0) && (ld % 8 == 0);
+  if (vec) logprob_fwd_kernel<true, true><<<rows, 256, 0, st>>>(logits, ld, V, off, tgt, logp, lse, ent);
+  else logprob_fwd_kernel<false, true><<<rows, 256, 0, st>>>(logits, ld, V, off, tgt, logp, lse, ent);
+}
+
+void launch_logprob_entropy_bwd(bf16_t* logits, int64_t ld, int V, int64_t off, int64_t rows,
+                                const int64_t* tgt, const float* lse, const float* ent, const float* g,
+                                const float* ge, hipStream_t st) {
+  if (rows == 0) return;
+  const bool vec = (V % 8 == 0) && (ld % 8 == 0);
+  if (vec) logprob_bwd_kernel<true, true><<<rows, 256, 0, st>>>(logits, ld, V, off, tgt, lse, g, ent, ge);
+  else logprob_bwd_kernel<false, true><<<rows, 256, 0, st>>>(logits, ld, V, off, tgt, lse, g, ent, ge);
+}
+
+bool launch_logprob_entropy_bwd_t(bf16_t* logits, int64_t ld, int V, int64_t rows, int64_t off,
+                                  const int64_t* tgt, const float* lse, const float* ent, const float* g,
+                                  const float* ge, bf16_t* outT, hipStream_t st) {
+  if (rows % 8 != 0 || V % 8 != 0 || ld % 8 != 0) return false;
+  if (rows == 0) return true;
+  const dim3 grid((V + 255) / 256, static_cast<unsigned>((rows + 63) / 64));
+  logprob_bwd_t_kernel<true><<<grid, 256, 0, st>>>(logits, ld, V, off, tgt, lse, g, outT, rows, ent, ge);
+  return true;
+}
+
 bool launch_logprob_bwd_t(bf16_t* logits, int64_t ld, int V, int64_t rows, int64_t off, const int64_t* tgt,
                           const float* lse, const float* g, bf16_t* outT, hipStream_t st) {
   if (rows % 8 != 0 || V % 8 != 0 || ld % 8 != 0) return false;
   if (rows == 0) return true;
   const dim3 grid((V + 255) / 256, static_cast<unsigned>((rows + 63) / 64));
-  logprob_bwd_t_kernel<<<grid, 256, 0, st>>>(logits, ld, V, off, tgt, lse, g, outT, rows);
+  logprob_bwd_t_kernel<false><<<grid, 256, 0, st>>>(logits, ld, V, off, tgt, lse, g, outT, rows);
   return true;
 }
 

@@ -591,6 +591,14 @@ class CausalLM(nn.Module):
             return vocab_parallel_logprob(h2, self.head_weight, targets, self.vocab_parallel[0], self.tp)
         return ops.linear_logprob(h2, self.head_weight, targets)
 
+    def _token_logprob_entropy(self, h2: torch.Tensor, targets: torch.Tensor):
+        """`_token_logprob` plus the per-row policy entropy from the same vocabulary pass."""
+        if self.vocab_parallel is not None:
+            from ..parallel.tensor_parallel import vocab_parallel_logprob_entropy
+
+            return vocab_parallel_logprob_entropy(h2, self.head_weight, targets, self.vocab_parallel[0], self.tp)
+        return ops.linear_logprob_entropy(h2, self.head_weight, targets)
+
     def aux_loss(self):
         if not self.cfg.is_moe:
             return None
@@ -605,14 +613,23 @@ class CausalLM(nn.Module):
             return tgt, mask
         return sp.local(sp.pad(tgt, -100)), (None if mask is None else sp.local(sp.pad(mask, 0)))
 
-    def _masked_token_logprob(self, h: torch.Tensor, tgt: torch.Tensor) -> torch.Tensor:
+    def _masked_token_logprob(self, h: torch.Tensor, tgt: torch.Tensor, with_entropy: bool = False):
         """[S, T', H] hidden + [S, T'] targets (-100 = ignore) -> [S, T'] fp32 log-probs (0 where
-        ignored); the LM-head bias models (phi-2) go through full logits."""
+        ignored); the LM-head bias models (phi-2) go through full logits. `with_entropy`: also the
+        entropy of each position's next-token distribution (0 where ignored)."""
         S, T, H = h.shape
         if self.lm_head_bias is not None:
             lg = self.logits(h).float()
-            lp = torch.log_softmax(lg, -1).gather(-1, tgt.clamp(min=0).unsqueeze(-1)).squeeze(-1)
-            return torch.where(tgt >= 0, lp, torch.zeros_like(lp))
+            lsm = torch.log_softmax(lg, -1)
+            lp = lsm.gather(-1, tgt.clamp(min=0).unsqueeze(-1)).squeeze(-1)
+            lp = torch.where(tgt >= 0, lp, torch.zeros_like(lp))
+            if not with_entropy:
+                return lp
+            ent = -(lsm.exp() * lsm.masked_fill(lsm == float("-inf"), 0.0)).sum(-1)
+            return lp, torch.where(tgt >= 0, ent, torch.zeros_like(ent))
+        if with_entropy:
+            lp, ent = self._token_logprob_entropy(h.reshape(S * T, H), tgt.reshape(-1))
+            return lp.view(S, T), ent.view(S, T)
         return self._token_logprob(h.reshape(S * T, H), tgt.reshape(-1)).view(S, T)
 
     def sequence_logprob(self, input_ids, attention_mask=None, reduction: str = "mean"):
@@ -622,11 +639,18 @@ class CausalLM(nn.Module):
         lp = self._masked_token_logprob(h, tgt)
         return sp_seq_reduce(self.sp, lp, mask, reduction == "mean")
 
-    def token_logprobs(self, input_ids, attention_mask=None):
+    def token_logprobs(self, input_ids, attention_mask=None, with_entropy: bool = False):
         """[S, T] log p(x_{t+1} | x_<=t) at every scored position (0 elsewhere): the per-action
-        grid of token-level RL objectives (PPO)."""
+        grid of token-level RL objectives (PPO). `with_entropy`: returns (lp, ent), ent [S, T] the
+        entropy of p(. | x_<=t) at the same positions, from the same LM-head pass."""
         h = self(input_ids, attention_mask)
         tgt, _ = self._sp_targets(ops.shifted_targets(input_ids, attention_mask)[0])
+        if with_entropy:
+            lp, ent = self._masked_token_logprob(h, tgt, True)
+            if self.sp is not None:
+                lp = self.sp.gather(lp, dim=1)[:, :input_ids.shape[1]]
+                ent = self.sp.gather(ent, dim=1)[:, :input_ids.shape[1]]
+            return lp, ent
         lp = self._masked_token_logprob(h, tgt)
         if self.sp is not None:
             lp = self.sp.gather(lp, dim=1)[:, :input_ids.shape[1]]

@@ -183,10 +183,35 @@ def ppo_critic_stream(device: torch.device):
     return _CRITIC_STREAMS[i]
 
 
+def token_logprobs_entropy(policy, seqs, mask, act, entropy_coef: float = 0.0, log_entropy: bool = False,
+                           n_act: Optional[torch.Tensor] = None):
+    """Token log-probs of a PPO / GRPO (micro-)batch and, when `entropy_coef != 0` or
+    `log_entropy`, the policy entropy from the same LM-head pass: returns (lp, bonus, entropy).
+    `bonus` = entropy_coef * sum(ent * act) / n_act (None when the coefficient is 0: the entropy is
+    then detached and the plain backward kernels run); `n_act`, a device tensor (no host sync), is
+    the action-token count the bonus is normalised by -- the whole minibatch's for micro-batches,
+    this batch's own by default. `entropy` is this batch's detached mean over action tokens (None
+    when off)."""
+    if entropy_coef == 0 and not log_entropy:
+        return policy.token_logprobs(seqs, mask), None, None
+    lp, ent = policy.token_logprobs(seqs, mask, with_entropy=True)
+    if entropy_coef == 0:
+        ent = ent.detach()
+    tot = (ent * act).sum()
+    own = act.sum().clamp(min=1)
+    bonus = None
+    if entropy_coef != 0:
+        bonus = entropy_coef * tot / (own if n_act is None else n_act.reshape(()))
+    return lp, bonus, tot.detach() / own
+
+
 def ppo_loss(policy, critic, seqs, mask, stats: Dict[str, torch.Tensor], clip_eps: float = 0.2,
-             value_clip: float = 0.2, vf_coef: float = 0.1):
-    """Clipped surrogate (HIP fused fwd+bwd) + vf_coef * clipped value loss on one minibatch.
-    Run its backward through `ppo_backward` (joins the critic's stream afterwards)."""
+             value_clip: float = 0.2, vf_coef: float = 0.1, entropy_coef: float = 0.0,
+             log_entropy: bool = False):
+    """Clipped surrogate (HIP fused fwd+bwd) + vf_coef * clipped value loss on one minibatch,
+    minus entropy_coef * the mean policy entropy over action tokens (`metrics["entropy"]`, also
+    with `log_entropy` alone). Run its backward through `ppo_backward` (joins the critic's stream
+    afterwards)."""
     cs = ppo_critic_stream(seqs.device)
     main = torch.cuda.current_stream(seqs.device) if cs is not None else None
     if cs is not None:
@@ -194,7 +219,7 @@ def ppo_loss(policy, critic, seqs, mask, stats: Dict[str, torch.Tensor], clip_ep
         with torch.cuda.stream(cs):
             v = critic(seqs, mask)
             vl = ops.ppo_value_loss(v, stats["values"], stats["returns"], stats["act"], value_clip)
-    lp = policy.token_logprobs(seqs, mask)
+    lp, bonus, entropy = token_logprobs_entropy(policy, seqs, mask, stats["act"], entropy_coef, log_entropy)
     pl, pm = ops.ppo_policy_loss(lp, stats["old_logp"], stats["advantages"], stats["act"], clip_eps)
     if cs is None:
         v = critic(seqs, mask)
@@ -202,7 +227,12 @@ def ppo_loss(policy, critic, seqs, mask, stats: Dict[str, torch.Tensor], clip_ep
     else:
         main.wait_stream(cs)
         vl.record_stream(main)
-    return pl + vf_coef * vl, {"policy_loss": pl.detach(), "value_loss": vl.detach(), **pm}
+    loss, m = pl + vf_coef * vl, {"policy_loss": pl.detach(), "value_loss": vl.detach(), **pm}
+    if bonus is not None:
+        loss = loss - bonus
+    if entropy is not None:
+        m["entropy"] = entropy
+    return loss, m
 
 
 def ppo_backward(loss: torch.Tensor) -> None:
@@ -234,12 +264,20 @@ def grpo_rollout_stats(policy, ref, seqs, mask, prompt_len: int, scores, G: int,
 
 def grpo_loss(policy, seqs, mask, stats: Dict[str, torch.Tensor], clip_low: float = 0.2,
               clip_high: Optional[float] = None, beta: float = 0.04, loss_type: str = "sequence",
-              max_len: Optional[int] = None, denom: Optional[torch.Tensor] = None):
+              max_len: Optional[int] = None, denom: Optional[torch.Tensor] = None,
+              entropy_coef: float = 0.0, log_entropy: bool = False, n_act: Optional[torch.Tensor] = None):
     """Token-level clipped surrogate + beta * k3 KL to the reference (HIP fused fwd+bwd) on one
-    (micro-)batch of rollouts; `stats` from `grpo_rollout_stats`, sliced to the same rows."""
-    lp = policy.token_logprobs(seqs, mask)
+    (micro-)batch of rollouts; `stats` from `grpo_rollout_stats`, sliced to the same rows.
+    `entropy_coef` / `log_entropy` / `n_act`: the entropy bonus and metric of
+    `token_logprobs_entropy`."""
+    lp, bonus, entropy = token_logprobs_entropy(policy, seqs, mask, stats["act"], entropy_coef, log_entropy,
+                                                n_act)
     loss, m = ops.grpo_loss(lp, stats.get("old_logp"), stats.get("ref_logp"), stats["advantages"],
                             stats["act"], clip_low, clip_high, beta, loss_type, max_len, denom)
+    if bonus is not None:
+        loss = loss - bonus
+    if entropy is not None:
+        m = {**m, "entropy": entropy}
     return loss, {"kl": m["kl_ref"], **m}
 
 

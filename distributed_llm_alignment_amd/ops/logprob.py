@@ -13,6 +13,11 @@ ever materialising fp32 [N, V] tensors:
 Semantics mirror the reference `compute_logprobs` (src/training/train_dpo.py:31-39): logits in
 the model dtype (bf16), log-softmax in fp32, targets < 0 ignored (logp 0, no gradient).
 
+`linear_logprob_entropy(hidden, weight, targets)` also returns the entropy of each row's softmax,
+from the same vocabulary pass (a third online accumulator in the row kernel) and with its
+gradient written by the same in-place dlogits pass: the policy entropy of PPO / GRPO without an
+fp32 [N, V] softmax.
+
 `sequence_logprob(...)` adds the masked per-sequence reduction (length-normalised mean by default,
 exactly the reference's `/ mask.sum(1).clamp(min=1)`, or sum) as a HIP kernel pair.
 """
@@ -97,6 +102,90 @@ def linear_logprob(hidden: torch.Tensor, weight: torch.Tensor, targets: torch.Te
     if _ext.use_native(hidden):
         return _LinearLogprobFn.apply(hidden.contiguous(), weight, targets.contiguous())
     return _ref_linear_logprob(hidden, weight, targets)
+
+
+def _ref_linear_logprob_entropy(hidden, weight, targets):
+    """The formula of record: logp as `_ref_linear_logprob`, ent = -sum_v p_v (z_v - lse) (fp32),
+    both 0 on ignored rows; a -inf logit has p = 0 and adds exactly 0."""
+    logits = F.linear(hidden, weight).float()
+    lse = torch.logsumexp(logits, dim=-1)
+    safe = targets.clamp(min=0)
+    lp = logits.gather(-1, safe.unsqueeze(-1)).squeeze(-1) - lse
+    lsm = logits - lse.unsqueeze(-1)
+    ent = -(torch.exp(lsm) * lsm.masked_fill(logits == float("-inf"), 0.0)).sum(-1)
+    zero = torch.zeros_like(lp)
+    return torch.where(targets >= 0, lp, zero), torch.where(targets >= 0, ent, zero)
+
+
+class _LinearLogprobEntropyFn(torch.autograd.Function):
+    """`_LinearLogprobFn` with the row entropy as a second output of the same vocabulary pass; its
+    gradient goes into the same in-place dlogits pass. With no gradient arriving for the entropy
+    (logging only) the backward runs the plain log-prob kernels."""
+
+    @staticmethod
+    def forward(ctx, hidden, weight, targets):
+        ops = _ext.require()
+        ctx.set_materialize_grads(False)
+        need_grad = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        N = hidden.shape[0]
+        if need_grad:
+            logits = F.linear(hidden, weight)
+            logp, lse, ent = ops.logprob_entropy_fwd(logits, targets)
+            ent = ent.masked_fill_(targets < 0, 0.0)
+            ctx.save_for_backward(hidden, targets, lse, ent, logits)
+            ctx.weight = weight  # (on ctx: see ops.linear._LinearMainGradFn)
+            return logp, ent
+        logp = torch.empty(N, dtype=torch.float32, device=hidden.device)
+        ent = torch.empty(N, dtype=torch.float32, device=hidden.device)
+        for s in range(0, N, _NO_GRAD_CHUNK):
+            e = min(N, s + _NO_GRAD_CHUNK)
+            lg = F.linear(hidden[s:e], weight)
+            lp, _, en = ops.logprob_entropy_fwd(lg, targets[s:e])
+            logp[s:e] = lp
+            ent[s:e] = en
+        return logp, ent.masked_fill_(targets < 0, 0.0)
+
+    @staticmethod
+    def backward(ctx, g, ge):
+        ops = _ext.require()
+        hidden, targets, lse, ent, logits = ctx.saved_tensors
+        weight = ctx.weight
+        if g is None and ge is None:
+            return None, None, None
+        from .linear import _tn_ok, accumulate_weight_grad
+
+        g = torch.zeros_like(lse) if g is None else g.float().contiguous()
+        ge = None if ge is None else ge.float().contiguous()
+        dlt = None
+        mg = getattr(weight, "main_grad", None)
+        if (LOGPROB_T and ctx.needs_input_grad[1] and mg is not None and not getattr(weight, "_dla_shared", False)
+                and _tn_ok(mg, logits.shape[0])):
+            # as in _LinearLogprobFn: dlogits^T from the same pass (empty outside the kernel's shapes)
+            dlt = (ops.logprob_bwd_t(logits, targets, lse, g) if ge is None
+                   else ops.logprob_entropy_bwd_t(logits, targets, lse, ent, g, ge))
+            if not dlt.numel():
+                dlt = None
+        if dlt is None:
+            if ge is None:
+                ops.logprob_bwd(logits, targets, lse, g)
+            else:
+                ops.logprob_entropy_bwd(logits, targets, lse, ent, g, ge)
+        dlogits = logits  # rewritten in place
+        dh = input_grad(dlogits, weight) if ctx.needs_input_grad[0] else None
+        dw = None
+        if ctx.needs_input_grad[1]:
+            if not accumulate_weight_grad(weight, dlogits, hidden, dyt=dlt):
+                dw = dlogits.t() @ hidden
+        return dh, dw, None
+
+
+def linear_logprob_entropy(hidden: torch.Tensor, weight: torch.Tensor, targets: torch.Tensor):
+    """hidden [N, H], weight [V, H], targets [N] (int64, <0 = ignore) -> (logp, ent), fp32 [N]:
+    `linear_logprob` plus the entropy of softmax(hidden @ W^T) per row (0 where ignored),
+    differentiable through both."""
+    if _ext.use_native(hidden):
+        return _LinearLogprobEntropyFn.apply(hidden.contiguous(), weight, targets.contiguous())
+    return _ref_linear_logprob_entropy(hidden, weight, targets)
 
 
 class _SeqReduceFn(torch.autograd.Function):

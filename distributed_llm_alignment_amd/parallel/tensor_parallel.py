@@ -555,6 +555,100 @@ def vocab_parallel_logprob(hidden, weight_l, targets, off: int, group) -> torch.
     return _VPLogprobFn.apply(hidden.contiguous(), weight_l, targets.contiguous(), off, group)
 
 
+# The entropy twins. Shard l emits its local lse_l and the entropy H_l of its OWN softmax; with
+# w_l = exp(lse_l - lse) the global entropy is H = lse - sum_l w_l (lse_l - H_l) (each shard's
+# sum_v p_v z_v is w_l (lse_l - H_l)). The backward formula holds per shard given the global lse
+# and H, so no extra kernel: dz_j = g (1[j == t] - p_j) - e p_j (z_j - lse + H).
+def _local_fwd_entropy(logits_l, targets, off):
+    if _ext.use_native(logits_l):
+        return _ext.require().logprob_entropy_fwd(logits_l, targets, int(off))
+    logp, lse = _local_fwd(logits_l, targets, off)
+    lf = logits_l.float()
+    lsm = lf - lse.unsqueeze(-1)
+    ent = -(torch.exp(lsm) * lsm.masked_fill(lf == float("-inf"), 0.0)).sum(-1)
+    return logp, lse, ent
+
+
+def _local_bwd_entropy(logits_l, targets, lse, ent, g, ge, off):
+    if _ext.use_native(logits_l):
+        _ext.require().logprob_entropy_bwd(logits_l, targets, lse, ent, g.float().contiguous(),
+                                           ge.float().contiguous(), int(off))
+        return logits_l
+    lf = logits_l.float()
+    p = torch.exp(lf - lse.unsqueeze(-1))
+    t = targets - off
+    own = (targets >= 0) & (t >= 0) & (t < lf.shape[-1])
+    onehot = torch.zeros_like(p)
+    onehot.scatter_(-1, t.clamp(0, lf.shape[-1] - 1).unsqueeze(-1), own.unsqueeze(-1).float())
+    zero = torch.zeros_like(g.float())
+    gr = torch.where(targets >= 0, g.float(), zero).unsqueeze(-1)
+    er = torch.where(targets >= 0, ge.float(), zero).unsqueeze(-1)
+    d = gr * (onehot - p) - er * p * (lf - lse.unsqueeze(-1) + ent.unsqueeze(-1))
+    return torch.where(lf == float("-inf"), torch.zeros_like(d), d).to(logits_l.dtype)
+
+
+class _VPLogprobEntropyFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, hidden, weight_l, targets, off, group):
+        ctx.set_materialize_grads(False)
+        logits_l = F.linear(hidden, weight_l)
+        logp_l, lse_l, ent_l = _local_fwd_entropy(logits_l, targets, off)
+        V_l = weight_l.shape[0]
+        t = targets - off
+        own = (targets >= 0) & (t >= 0) & (t < V_l)
+        tl_l = torch.where(own, logp_l + lse_l, torch.zeros_like(logp_l))
+        # the ONE all-gather of _VPLogprobFn, a triple per row instead of the pair:
+        # (lse_r, target logit_r, lse_r - H_r), composed in fixed rank order on every rank
+        tp = coll.world_size(group)
+        tri = torch.stack([lse_l.float(), tl_l.float(), lse_l.float() - ent_l.float()])
+        allt = tri.new_empty((tp * 3,) + tuple(tri.shape[1:]))
+        coll.all_gather_into_tensor(allt, tri.contiguous(), group=group)
+        allt = allt.view((tp,) + tuple(tri.shape))
+        lse = torch.logsumexp(allt[:, 0], dim=0)
+        tl = allt[:, 1].sum(0)
+        ent = lse
+        for r in range(tp):
+            ent = ent - torch.exp(allt[r, 0] - lse) * allt[r, 2]
+        zero = torch.zeros_like(tl)
+        logp = torch.where(targets >= 0, tl - lse, zero)
+        ent = torch.where(targets >= 0, ent, zero)
+        ctx.save_for_backward(hidden, targets, lse, ent, logits_l)
+        ctx.weight_l = weight_l  # (on ctx: see ops.linear._LinearMainGradFn)
+        ctx.off, ctx.group = off, group
+        return logp, ent
+
+    @staticmethod
+    def backward(ctx, g, ge):
+        hidden, targets, lse, ent, logits_l = ctx.saved_tensors
+        weight_l = ctx.weight_l
+        g = torch.zeros_like(lse) if g is None else g
+        if ge is None:  # entropy only logged: the plain backward
+            dlog = _local_bwd(logits_l, targets, lse, g, ctx.off)
+        else:
+            dlog = _local_bwd_entropy(logits_l, targets, lse, ent, g, ge, ctx.off)
+        dh, work = None, None
+        if ctx.needs_input_grad[0]:
+            from ..ops.linear import input_grad
+
+            dh = input_grad(dlog, weight_l).contiguous()
+            # in flight on RCCL's stream while the (vocab-shard) weight-gradient GEMM runs
+            work = coll.all_reduce(dh, group=ctx.group, async_op=True)
+        dw = None
+        if ctx.needs_input_grad[1]:
+            from ..ops.linear import accumulate_weight_grad
+
+            if not accumulate_weight_grad(weight_l, dlog, hidden):
+                dw = dlog.t() @ hidden
+        if work is not None:
+            work.wait()
+        return dh, dw, None, None, None
+
+
+def vocab_parallel_logprob_entropy(hidden, weight_l, targets, off: int, group):
+    """(logp, ent) [N] fp32 over the vocabulary-parallel head, both 0 on ignored rows."""
+    return _VPLogprobEntropyFn.apply(hidden.contiguous(), weight_l, targets.contiguous(), off, group)
+
+
 # ------------------------------------------------------------------------- model sharding
 # A sharded parameter carries `_dla_tp_spec = (dim, segments)`: along `dim` the full tensor is the
 # concatenation of `segments` (e.g. [q, k, v] rows of the fused qkv projection); rank r keeps the

@@ -35,6 +35,12 @@ normalised per `ppo.loss_type: sequence|token|constant` (fused HIP fwd+bwd kerne
 the memory plan is the REINFORCE one. `ppo_epochs`, `num_minibatches`, `update_micro_batch` and
 `async_rollouts` work as for the other algorithms; with one epoch and one minibatch the update is
 on-policy and the old-policy forward is skipped.
+
+`ppo.entropy_coef` (default 0) and `ppo.log_entropy` (default false), for `ppo` and `grpo`: the
+per-token policy entropy comes out of the LM-head log-prob kernels' own vocabulary pass
+(`token_logprobs(with_entropy=True)`); the loss gains -entropy_coef x its mean over the
+minibatch's action tokens and `train/entropy` is logged. With both off a run launches exactly the
+kernels it launched before. The REINFORCE loop works on sequence log-probs and has no entropy term.
 """
 from __future__ import annotations
 
@@ -253,28 +259,33 @@ def reinforce_update(policy, ref, engine, seqs, mask, scores, kl_coef: float, mi
 
 
 def grpo_update(policy, engine, seqs, mask, stats, clip_low: float, clip_high, beta: float,
-                loss_type: str, max_len, micro: int = 0):
+                loss_type: str, max_len, micro: int = 0, entropy_coef: float = 0.0,
+                log_entropy: bool = False):
     """Backward of the GRPO loss over one minibatch of rollouts. micro > 0
     (`ppo.update_micro_batch`): gradient-accumulated micro-batches of `micro` rollouts that share
     the whole minibatch's divisor (`denom`, a device tensor: no host sync), so their gradients sum
-    to the full minibatch's; every micro-batch but the last runs under `engine.no_sync()`.
-    Returns (loss, metrics) with token-weighted metric means."""
+    to the full minibatch's; every micro-batch but the last runs under `engine.no_sync()`. The
+    entropy bonus (`ppo.entropy_coef`) is likewise normalised by the whole minibatch's
+    action-token count. Returns (loss, metrics) with token-weighted metric means."""
     n = seqs.shape[0]
     rows = ("act", "advantages", "ref_logp", "old_logp")
     if micro <= 0 or micro >= n:
-        loss, m = grpo_loss(policy, seqs, mask, stats, clip_low, clip_high, beta, loss_type, max_len)
+        loss, m = grpo_loss(policy, seqs, mask, stats, clip_low, clip_high, beta, loss_type, max_len,
+                            entropy_coef=entropy_coef, log_entropy=log_entropy)
         loss.backward()
         return loss.detach(), m
     denom = grpo_denominator(stats["act"], loss_type, max_len)
     bounds = micro_bounds(n, micro)
     tot, acc = 0.0, {"clipfrac": 0.0, "approx_kl": 0.0, "kl_ref": 0.0}
+    if entropy_coef != 0 or log_entropy:
+        acc["entropy"] = 0.0
     tokens = stats["act"].sum().clamp(min=1)
     for i, (s0, s1) in enumerate(bounds):
         mb = {k: (stats[k][s0:s1] if stats.get(k) is not None else None) for k in rows}
         ctx = engine.no_sync() if i < len(bounds) - 1 else contextlib.nullcontext()
         with ctx:
             loss, m = grpo_loss(policy, seqs[s0:s1], mask[s0:s1], mb, clip_low, clip_high, beta, loss_type,
-                                max_len, denom)
+                                max_len, denom, entropy_coef, log_entropy, tokens)
             loss.backward()
         tot = tot + loss.detach()
         for k in acc:
@@ -294,6 +305,7 @@ def _grpo_loop(ctx, config, ppo, policy, ref, rm, rollout, engine, steps, group,
     epochs, nmb = int(ppo.get("ppo_epochs", 1)), max(1, int(ppo.get("num_minibatches", 1)))
     micro = int(ppo.get("update_micro_batch", 0) or 0)
     overlap = bool(ppo.get("async_rollouts", False))
+    entropy_coef, log_entropy = float(ppo.get("entropy_coef", 0.0) or 0.0), bool(ppo.get("log_entropy", False))
     need_old = epochs * nmb > 1  # a single update per rollout batch is on-policy: rho = 1
     rows = ("act", "advantages", "ref_logp", "old_logp")
     running = RunningLoss()
@@ -310,7 +322,7 @@ def _grpo_loop(ctx, config, ppo, policy, ref, rm, rollout, engine, steps, group,
                     continue
                 mb = {k: (stats[k][a:b] if stats.get(k) is not None else None) for k in rows}
                 loss, m = grpo_update(policy.model, engine, seqs[a:b], mask[a:b], mb, clip_low, clip_high,
-                                      beta, loss_type, gen_len, micro)
+                                      beta, loss_type, gen_len, micro, entropy_coef, log_entropy)
                 last = ep == epochs - 1 and mi == len(bounds) - 1
                 if last and overlap and step + 1 < steps:
                     pending = rollout()  # overlaps the in-flight gradient collectives (see _ppo_loop)
@@ -324,6 +336,7 @@ def _grpo_loop(ctx, config, ppo, policy, ref, rm, rollout, engine, steps, group,
                             "train/reward_std": stats["reward_std"],
                             "train/frac_zero_std": stats["frac_zero_std"],
                             "train/clipfrac": m["clipfrac"], "train/approx_kl": m["approx_kl"],
+                            **({"train/entropy": m["entropy"]} if "entropy" in m else {}),
                             "train/grad_norm": engine.last_grad_norm,
                             "train/comm_exposed_ms": engine.comm_timer.last_step_ms()}, step + 1)
             running = RunningLoss()
@@ -355,6 +368,7 @@ def _ppo_loop(ctx, config, ppo, policy, ref, rm, rollout, engine, steps, kl_coef
     vf_coef = float(ppo.get("vf_coef", 0.1))
     epochs, nmb = int(ppo.get("ppo_epochs", 1)), max(1, int(ppo.get("num_minibatches", 1)))
     overlap = bool(ppo.get("async_rollouts", False))
+    entropy_coef, log_entropy = float(ppo.get("entropy_coef", 0.0) or 0.0), bool(ppo.get("log_entropy", False))
     running = RunningLoss()
     pending = rollout()
     for step in range(steps):
@@ -368,7 +382,8 @@ def _ppo_loop(ctx, config, ppo, policy, ref, rm, rollout, engine, steps, kl_coef
                 if b <= a:
                     continue
                 mb = {k: v[a:b] for k, v in stats.items() if k in ("old_logp", "values", "advantages", "returns", "act")}
-                loss, m = ppo_loss(policy.model, critic, seqs[a:b], mask[a:b], mb, clip, vclip, vf_coef)
+                loss, m = ppo_loss(policy.model, critic, seqs[a:b], mask[a:b], mb, clip, vclip, vf_coef,
+                                   entropy_coef, log_entropy)
                 ppo_backward(loss)
                 last = ep == epochs - 1 and mi == len(bounds) - 1
                 if last and overlap and step + 1 < steps:
@@ -386,6 +401,7 @@ def _ppo_loop(ctx, config, ppo, policy, ref, rm, rollout, engine, steps, kl_coef
                             "train/reward_mean": stats["scores"].mean(),
                             "train/policy_loss": m["policy_loss"], "train/value_loss": m["value_loss"],
                             "train/clipfrac": m["clipfrac"], "train/approx_kl": m["approx_kl"],
+                            **({"train/entropy": m["entropy"]} if "entropy" in m else {}),
                             "train/grad_norm": engine.last_grad_norm,
                             "train/comm_exposed_ms": engine.comm_timer.last_step_ms()}, step + 1)
             running = RunningLoss()

@@ -67,6 +67,10 @@ def main() -> int:
                          "(ppo.group_attention)")
     ap.add_argument("--loss-type", choices=("sequence", "token", "constant"), default="sequence")
     ap.add_argument("--kl-coef", type=float, default=0.04, help="grpo: beta of the k3 KL term")
+    ap.add_argument("--entropy-coef", type=float, default=0.0,
+                    help="ppo / grpo: entropy bonus (ppo.entropy_coef); the entropy comes out of the LM-head kernels")
+    ap.add_argument("--log-entropy", action="store_true",
+                    help="ppo / grpo: compute and report the policy entropy without a bonus (ppo.log_entropy)")
     ap.add_argument("--rollout-dtype", choices=("bf16", "fp8"), default="bf16",
                     help="decode weight streams of the rollout generation (ppo.rollout_weight_dtype)")
     ap.add_argument("--frozen-fp8", action="store_true",
@@ -347,7 +351,8 @@ def ppo_main(a) -> int:
         for _ in range(a.ppo_epochs):
             for lo, hi in bounds:
                 mb = {k: v[lo:hi] for k, v in stats.items() if k in ("old_logp", "values", "advantages", "returns", "act")}
-                loss, m = ppo_loss(pol, critic, seqs[lo:hi], mask[lo:hi], mb, 0.2, 0.2, 0.1)
+                loss, m = ppo_loss(pol, critic, seqs[lo:hi], mask[lo:hi], mb, 0.2, 0.2, 0.1, a.entropy_coef,
+                                   a.log_entropy)
                 ppo_backward(loss)
                 eng.step()
                 ceng.step()
@@ -370,7 +375,10 @@ def ppo_main(a) -> int:
     health = {"loss": round(float(loss), 5), "policy_grad_norm": round(float(eng.last_grad_norm), 5),
               "critic_grad_norm": round(float(ceng.last_grad_norm), 5),
               "clipfrac": round(float(m["clipfrac"]), 4)}
+    if "entropy" in m:
+        health["entropy"] = round(float(m["entropy"]), 5)
     print(json.dumps({"bench": "ppo_step", "model": cfg.name, "rollouts_per_step": a.batch,
+                      "entropy_coef": a.entropy_coef, "log_entropy": a.log_entropy,
                       "rollout_dtype": a.rollout_dtype, "frozen_fp8": a.frozen_fp8,
                       "zero_shape": a.zero_shape, "ppo_epochs": a.ppo_epochs, "minibatches": a.minibatches,
                       "grad_ckpt": a.grad_ckpt or "none", "prompt": a.prompt, "new_tokens": a.new,
@@ -461,7 +469,8 @@ def grpo_main(a) -> int:
         t3 = sync()
         phase_peak("stats")
         pol.train()
-        loss, m = grpo_update(pol, eng, seqs, mask, stats, 0.2, None, a.kl_coef, a.loss_type, a.new, a.micro)
+        loss, m = grpo_update(pol, eng, seqs, mask, stats, 0.2, None, a.kl_coef, a.loss_type, a.new, a.micro,
+                              a.entropy_coef, a.log_entropy)
         eng.step()
         t4 = sync()
         phase_peak("update")
@@ -481,9 +490,12 @@ def grpo_main(a) -> int:
     health = {"loss": round(float(loss), 6), "policy_grad_norm": round(float(eng.last_grad_norm), 5),
               "kl_ref": round(float(m["kl"]), 6), "reward_std": round(float(stats["reward_std"]), 4),
               "frac_zero_std": round(float(stats["frac_zero_std"]), 4)}
+    if "entropy" in m:
+        health["entropy"] = round(float(m["entropy"]), 5)
     print(json.dumps({"bench": "grpo_step", "model": cfg.name, "rollouts_per_step": a.batch, "group": G,
                       "share_prefill": bool(a.share_prefill), "group_attention": bool(a.group_attention),
                       "loss_type": a.loss_type, "kl_coef": a.kl_coef,
+                      "entropy_coef": a.entropy_coef, "log_entropy": a.log_entropy,
                       "rollout_dtype": a.rollout_dtype, "frozen_fp8": a.frozen_fp8, "zero_shape": a.zero_shape,
                       "update_micro": a.micro or a.batch, "grad_ckpt": a.grad_ckpt or "none",
                       "prompt": a.prompt, "new_tokens": a.new,
