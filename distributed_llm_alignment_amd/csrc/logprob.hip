@@ -52,7 +52,9 @@ __device__ __forceinline__ void lse_merge_u(float& m, float& s, float& u, float 
 }
 
 // ENT: also accumulate u (u_out). The (m, s) arithmetic rounds as with the flag off (contraction
-// is switched off wherever s is updated next to u); a -inf logit adds exactly 0 to s and u.
+// is switched off wherever s is updated next to u). With the flag on or off a -inf logit (a masked
+// vocabulary entry) adds exactly 0, also while the lane's running max is still -inf; only a row
+// of nothing but -inf has no lse.
 template <bool VEC, bool ENT = false>
 __device__ __forceinline__ void row_lse(const bf16_t* __restrict__ row, int V, float& m_out,
                                         float& s_out, float* u_out = nullptr) {
@@ -69,9 +71,8 @@ __device__ __forceinline__ void row_lse(const bf16_t* __restrict__ row, int V, f
         x[j] = bf2f(a[j]);
         lm = fmaxf(lm, x[j]);
       }
-      if constexpr (ENT) {
-        if (lm == -INFINITY) continue;  // eight -inf logits add 0; m is finite below
-      }
+      // eight -inf logits add 0 (with m still -inf, x - m below would be NaN); m is finite below
+      if (lm == -INFINITY) continue;
       if (lm > m) {
         if constexpr (ENT) {
 #pragma clang fp contract(off)
@@ -117,7 +118,7 @@ __device__ __forceinline__ void row_lse(const bf16_t* __restrict__ row, int V, f
           s *= __expf(m - x);
           m = x;
         }
-        s += __expf(x - m);
+        s += x == -INFINITY ? 0.f : __expf(x - m);  // (x - m is NaN while m is still -inf)
       }
     }
   }
@@ -178,7 +179,7 @@ __global__ __launch_bounds__(256) void logprob_fwd_kernel(const bf16_t* __restri
 }
 
 // In place: logits[r, v] <- g[r] * (1[v == tgt - off] - exp(logits - lse)), g = dL/dlogp[r];
-// lse is the GLOBAL (all-shard) log-sum-exp. Ignored rows (tgt < 0) -> 0.
+// lse is the GLOBAL (all-shard) log-sum-exp. Ignored rows (tgt < 0) -> 0; z = -inf -> 0.
 // ENT adds the entropy gradient, e = dL/dent[r] and H = the GLOBAL entropy ent_in[r]:
 //   logits[r, v] <- g (1[v == t] - p) - e p (z - lse + H),  p = exp(z - lse);  z = -inf -> 0.
 template <bool ENT>
@@ -186,7 +187,7 @@ __device__ __forceinline__ float dlogit(float z, bool hit, float gr, float lse, 
 #pragma clang fp contract(off)  // one rounding per operation in every kernel that inlines this
   const float p = __expf(z - lse);
   const float d = gr * ((hit ? 1.f : 0.f) - p);
-  if constexpr (!ENT) return d;
+  if constexpr (!ENT) return z == -INFINITY ? 0.f : d;  // (also when the target is the -inf logit)
   return z == -INFINITY ? 0.f : d - er * p * (z - lse + H);
 }
 
