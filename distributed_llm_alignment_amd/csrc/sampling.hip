@@ -127,6 +127,19 @@ __device__ void suffix_scan(int* c, float* m, int* tc, float* tm) {
 // in which the lanes' atomics land (a float LDS atomicAdd sum does, in its last bits).
 constexpr float kHistFix = 1099511627776.0f;  // 2^40
 
+// Bin of z in [lo, lo + w). The fp32 rounding of z - lo can carry a z just below a bin edge
+// onto it, while the window tests of the next pass (z >= lo, z < hi) and the final z >= tau
+// compare z itself against that edge, which lo + b * bw gives exactly (edges are multiples of
+// 2^-16 below 64). A token binned above the edge was counted once in the coarse suffix above its
+// bin and again in that bin's fine pass, and the top-k / nucleus edge came out one token short.
+// So the bin is made to agree with the comparisons.
+__device__ __forceinline__ int hist_bin(float z, float lo, float sc, float bw) {
+  int b = min(kBins - 1, (int)((z - lo) * sc));
+  if (z < lo + b * bw) --b;
+  else if (b < kBins - 1 && z >= lo + (b + 1) * bw) ++b;
+  return b;
+}
+
 template <bool VEC, typename T>
 __device__ void histogram(const T* row, int V, float gmax, float inv_t, float lo, float w,
                           float floor_z, int* c, float* m) {
@@ -136,13 +149,13 @@ __device__ void histogram(const T* row, int V, float gmax, float inv_t, float lo
     mfix[i] = 0ull;
   }
   __syncthreads();
-  const float sc = kBins / w;
+  const float sc = kBins / w, bw = w / kBins;
   const float hi = lo + w;
   const bool top = hi >= 0.f;  // the top bin also holds z == 0 (the max itself)
   for_each_logit<VEC>(row, V, [&](int, float xv) {
     const float z = (xv - gmax) * inv_t;
     if (z >= lo && (z < hi || (top && z <= 0.f)) && z >= floor_z) {
-      const int b = min(kBins - 1, (int)((z - lo) * sc));
+      const int b = hist_bin(z, lo, sc, bw);
       atomicAdd(&c[b], 1);
       atomicAdd(&mfix[b], static_cast<unsigned long long>(__expf(z) * kHistFix));
     }
@@ -205,6 +218,7 @@ __global__ __launch_bounds__(kSampNT) void sample_kernel(const T* __restrict__ l
   __syncthreads();
   int argmax = amin[0];
   for (int i = 1; i < kSampNT / 64; ++i) argmax = min(argmax, amin[i]);
+  if (argmax == 0x7fffffff) argmax = 0;  // no finite logit in the row (all -inf / NaN): token 0
   if (greedy || inv_temp <= 0.f) {
     if (tid == 0) out[r] = argmax;
     return;
@@ -381,7 +395,8 @@ __device__ __forceinline__ void chunk_range(int V, int G, int g, int& v0, int& v
   v1 = min(nv, v0 + cv);
 }
 
-// row max (first index on ties) from the G chunk partials; every lane gets the result
+// row max (first index on ties, 0 for a row without a finite logit) from the G chunk partials;
+// every lane gets the result
 __device__ __forceinline__ void row_max(const float* pmax, const int* parg, int G, float& gmax,
                                         int& argmax) {
   float m[kSplitG];
@@ -399,6 +414,7 @@ __device__ __forceinline__ void row_max(const float* pmax, const int* parg, int 
       gmax = m[g];
       argmax = a[g];
     }
+  if (argmax == 0x7fffffff) argmax = 0;  // no finite logit in the row (all -inf / NaN): token 0
 }
 
 template <typename T>
@@ -477,7 +493,7 @@ __global__ __launch_bounds__(kSplitNT) void split_hist_kernel(const T* __restric
   const T* row = logits + int64_t(r) * ld_;
   int v0, v1;
   chunk_range(V, G, g, v0, v1);
-  const float sc = kBins / w, hi = lo + w;
+  const float sc = kBins / w, bw = w / kBins, hi = lo + w;
   const bool top = hi >= 0.f;
   for (int i = v0 + tid; i < v1; i += kSplitNT) {
     float x[8];
@@ -486,7 +502,7 @@ __global__ __launch_bounds__(kSplitNT) void split_hist_kernel(const T* __restric
     for (int j = 0; j < 8; ++j) {
       const float z = (x[j] - gmax) * inv_t;
       if (z >= lo && (z < hi || (top && z <= 0.f)) && z >= floor_z) {
-        const int b = min(kBins - 1, (int)((z - lo) * sc));
+        const int b = hist_bin(z, lo, sc, bw);
         atomicAdd(&c[b], 1);
         atomicAdd(&m[b], static_cast<unsigned long long>(__expf(z) * kHistFix));
       }
