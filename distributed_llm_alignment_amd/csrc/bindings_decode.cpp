@@ -11,29 +11,11 @@
 #include <tuple>
 
 #include "bind_util.h"
+#include "decode_params.h"
 #include "skinny_params.h"
 
 namespace dla {
 
-void launch_decode_attn(const bf16_t*, int64_t, int64_t, bf16_t*, bf16_t*, int64_t,
-                        int64_t, int64_t, const int*, const int*, int, float, int, int, int, int,
-                        int, float*, float*, bf16_t*, int64_t, int64_t, int*, hipStream_t);
-void launch_decode_attn_rope(const bf16_t*, int64_t, const float*, const float*, const int*,
-                             const int64_t*, int, bf16_t*, bf16_t*, int64_t, int64_t, int64_t,
-                             const int*, const int*, int, float, int, int, int, int, int, float*,
-                             float*, bf16_t*, int64_t, int64_t, int*, hipStream_t);
-int decode_num_splits(int Tmax, int B, int Hkv);
-void launch_decode_attn_group(const bf16_t*, int64_t, int64_t, bf16_t*, bf16_t*, int64_t, int64_t,
-                              int64_t, const int*, const int*, int, float, int, int, int, int, int, int,
-                              int, float*, float*, bf16_t*, int64_t, int64_t, int*, hipStream_t);
-void launch_decode_attn_rope_group(const bf16_t*, int64_t, const float*, const float*, const int*,
-                                   const int64_t*, int, bf16_t*, bf16_t*, int64_t, int64_t, int64_t,
-                                   const int*, const int*, int, float, int, int, int, int, int, int, int,
-                                   float*, float*, bf16_t*, int64_t, int64_t, int*, hipStream_t);
-int decode_group_splits(int Tmax, int B, int Hq, int Hkv, int G, int Tp);
-void launch_rope_cache(const bf16_t*, int64_t, bf16_t*, bf16_t*, bf16_t*, int64_t, int64_t,
-                       int64_t, const int64_t*, const float*, const float*, const int*, int, int,
-                       int, int, int, hipStream_t);
 void launch_sample(const void*, bool, int64_t, int64_t, int, float, int, float, bool,
                    const int64_t*, int64_t*, hipStream_t);
 int sample_split_chunks(const void*, int64_t, int64_t, int, float, int, float, bool);
@@ -562,147 +544,148 @@ static int* decode_counters(const at::Tensor& like, int64_t n) {
   return t.data_ptr<int>();
 }
 
-at::Tensor decode_attn(const at::Tensor& q, const at::Tensor& k_cache, const at::Tensor& v_cache,
-                       const at::Tensor& kv_len, const c10::optional<at::Tensor>& kv_start,
-                       int64_t window, double scale) {
-  check_bf16(q, "q");
+// ---- decode attention ops: argument checks shared by the forms, one fill-and-launch routine
+
+// k / v caches [B, Tmax, Hkv, D] sharing strides, head dim contiguous
+static void check_kv_caches(const at::Tensor& k_cache, const at::Tensor& v_cache, int64_t B, int64_t Hkv,
+                            int64_t D) {
   check_bf16(k_cache, "k_cache");
   check_bf16(v_cache, "v_cache");
-  check_i32(kv_len, "kv_len");
-  TORCH_CHECK(q.dim() == 3 && k_cache.dim() == 4 && v_cache.sizes() == k_cache.sizes(),
-              "q [B, Hq, D], caches [B, Tmax, Hkv, D]");
-  const int64_t B = q.size(0), Hq = q.size(1), D = q.size(2);
-  const int64_t Tmax = k_cache.size(1), Hkv = k_cache.size(2);
-  TORCH_CHECK(k_cache.size(0) == B && k_cache.size(3) == D, "cache batch / head dim");
-  TORCH_CHECK(D == 64 || D == 128, "decode attention supports head_dim 64 or 128");
-  TORCH_CHECK(Hq % Hkv == 0, "Hq % Hkv");
-  const int64_t G = Hq / Hkv;
-  TORCH_CHECK(G == 1 || G == 2 || G == 4 || G == 8, "GQA group size must be 1, 2, 4 or 8");
-  TORCH_CHECK(q.stride(2) == 1 && k_cache.stride(3) == 1 && v_cache.stride(3) == 1,
-              "head dim must be contiguous");
-  TORCH_CHECK(k_cache.strides() == v_cache.strides(), "k/v caches must share strides");
-  TORCH_CHECK(q.stride(1) % 8 == 0 && k_cache.stride(1) % 8 == 0 && k_cache.stride(2) % 8 == 0 &&
-                  k_cache.stride(0) % 8 == 0,
-              "16-byte aligned rows");
+  TORCH_CHECK(k_cache.dim() == 4 && k_cache.size(0) == B && k_cache.size(2) == Hkv &&
+                  k_cache.size(3) == D && k_cache.sizes() == v_cache.sizes() &&
+                  k_cache.strides() == v_cache.strides() && k_cache.stride(3) == 1,
+              "caches [B, Tmax, Hkv, D]: cache batch / head dim, k/v caches must share strides");
   check_aligned16(k_cache, "k_cache");
   check_aligned16(v_cache, "v_cache");
-  TORCH_CHECK(kv_len.numel() >= 1, "kv_len");
-  const int* ks = nullptr;
-  if (kv_start && kv_start->defined()) {
-    check_i32(*kv_start, "kv_start");
-    TORCH_CHECK(kv_start->numel() == B && kv_start->is_contiguous(), "kv_start [B]");
-    ks = kv_start->data_ptr<int>();
-  }
-  c10::hip::HIPGuardMasqueradingAsCUDA g(q.device());
-  const int nsplit = decode_num_splits(static_cast<int>(Tmax), static_cast<int>(B), static_cast<int>(Hkv));
-  auto fopt = q.options().dtype(at::kFloat);
-  auto part_o = at::empty({B, Hq, nsplit, D}, fopt);
-  auto part_ml = at::empty({B, Hq, nsplit, 2}, fopt);
-  auto out = at::empty({B, Hq, D}, q.options());
-  launch_decode_attn(cbp(q), q.stride(0), q.stride(1), bp(k_cache), bp(v_cache),
-                     k_cache.stride(0), k_cache.stride(1), k_cache.stride(2),
-                     kv_len.data_ptr<int>(), ks, static_cast<int>(window),
-                     static_cast<float>(scale * 1.4426950408889634), (int)B, (int)Hq, (int)Hkv,
-                     (int)D, (int)Tmax, part_o.data_ptr<float>(), part_ml.data_ptr<float>(),
-                     bp(out), out.stride(0), out.stride(1), decode_counters(q, B * Hkv), cur_stream(q));
-  return out;
 }
 
-// qkv [B, 1, (Hq + 2 Hkv) D] of the newest token -> rotated q [B, Hq, D]; k/v written into
-// k_cache/v_cache [B, Tmax, Hkv, D] at row `slot` (int64 [1] on device).
-at::Tensor rope_cache_write(const at::Tensor& qkv, const at::Tensor& cos, const at::Tensor& sin,
-                            const at::Tensor& pos, at::Tensor& k_cache, at::Tensor& v_cache,
-                            const at::Tensor& slot, int64_t Hq, int64_t Hkv, int64_t D, int64_t rot) {
+// The raw-qkv rope step: qkv [B, 1, (Hq + 2 Hkv) D] rows of the newest token, fp32 tables
+// [max_pos, rot / 2], pos int32 [B], slot int64 [1] on the device
+static void check_rope_step(const at::Tensor& qkv, const at::Tensor& cos, const at::Tensor& sin,
+                            const at::Tensor& pos, const at::Tensor& slot, int64_t Hq, int64_t Hkv,
+                            int64_t D, int64_t rot) {
   check_bf16(qkv, "qkv");
-  check_bf16(k_cache, "k_cache");
-  check_bf16(v_cache, "v_cache");
   check_f32(cos, "cos");
   check_f32(sin, "sin");
   check_i32(pos, "pos");
   check_cuda(slot, "slot");
   TORCH_CHECK(slot.scalar_type() == at::kLong && slot.numel() >= 1, "slot int64");
-  const int64_t B = qkv.size(0);
   TORCH_CHECK(qkv.dim() == 3 && qkv.size(1) == 1 && qkv.size(2) == (Hq + 2 * Hkv) * D &&
                   qkv.stride(2) == 1 && qkv.stride(0) % 8 == 0,
               "qkv [B, 1, (Hq+2Hkv)D] with 16-byte aligned rows");
-  TORCH_CHECK(k_cache.dim() == 4 && k_cache.size(0) == B && k_cache.size(2) == Hkv &&
-                  k_cache.size(3) == D && k_cache.sizes() == v_cache.sizes() &&
-                  k_cache.strides() == v_cache.strides() && k_cache.stride(3) == 1,
-              "caches [B, Tmax, Hkv, D]");
-  TORCH_CHECK(D % 8 == 0 && rot % 16 == 0 && rot <= D, "D % 8, rot % 16");
+  TORCH_CHECK(rot % 16 == 0 && rot <= D, "rot % 16 == 0, rot <= D");
   TORCH_CHECK(cos.is_contiguous() && sin.is_contiguous() && cos.size(-1) == rot / 2, "rope tables");
-  TORCH_CHECK(pos.numel() == B && pos.is_contiguous(), "pos [B]");
+  TORCH_CHECK(pos.numel() == qkv.size(0) && pos.is_contiguous(), "pos [B]");
   check_aligned16(qkv, "qkv");
-  check_aligned16(k_cache, "k_cache");
-  check_aligned16(v_cache, "v_cache");
-  c10::hip::HIPGuardMasqueradingAsCUDA g(qkv.device());
-  auto q = at::empty({B, Hq, D}, qkv.options());
-  launch_rope_cache(cbp(qkv), qkv.stride(0), bp(q), bp(k_cache), bp(v_cache), k_cache.stride(0),
-                    k_cache.stride(1), k_cache.stride(2), slot.data_ptr<int64_t>(),
-                    cos.data_ptr<float>(), sin.data_ptr<float>(), pos.data_ptr<int>(), (int)B,
-                    (int)Hq, (int)Hkv, (int)D, (int)rot, cur_stream(qkv));
-  return q;
+}
+
+// What the four decode attention ops share: cache / kv_len / kv_start / GQA / head-dim checks,
+// the group arguments, then partials + output, the rest of `p` and the launch. `x` is q or qkv;
+// `p` arrives with q (or rope) set.
+static at::Tensor decode_step(const at::Tensor& x, DecodeParams& p, const at::Tensor& k_cache,
+                              const at::Tensor& v_cache, const at::Tensor& kv_len,
+                              const c10::optional<at::Tensor>& kv_start, int64_t window, double scale,
+                              int64_t B, int64_t Hq, int64_t Hkv, int64_t D, bool grouped,
+                              int64_t group_size, int64_t prefix_len) {
+  check_kv_caches(k_cache, v_cache, B, Hkv, D);
+  check_i32(kv_len, "kv_len");
+  TORCH_CHECK(D == 64 || D == 128, "decode attention supports head_dim 64 or 128");
+  TORCH_CHECK(Hq % Hkv == 0, "Hq % Hkv");
+  const int64_t GQ = Hq / Hkv;
+  TORCH_CHECK(GQ == 1 || GQ == 2 || GQ == 4 || GQ == 8, "GQA group size must be 1, 2, 4 or 8");
+  TORCH_CHECK(k_cache.stride(1) % 8 == 0 && k_cache.stride(2) % 8 == 0 && k_cache.stride(0) % 8 == 0,
+              "16-byte aligned cache rows");
+  if (kv_start && kv_start->defined()) {
+    check_i32(*kv_start, "kv_start");
+    TORCH_CHECK(kv_start->numel() == B && kv_start->is_contiguous(), "kv_start [B]");
+    p.kv_start = kv_start->data_ptr<int>();
+  }
+  const int64_t Tmax = k_cache.size(1);
+  if (grouped) {
+    TORCH_CHECK(group_size >= 1 && B % group_size == 0, "group_size must divide the batch");
+    TORCH_CHECK(prefix_len >= 1 && prefix_len <= Tmax, "1 <= prefix_len <= Tmax");
+    p.G = static_cast<int>(group_size);
+    p.Tp = static_cast<int>(prefix_len);
+  }
+  c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
+  p.kc = bp(k_cache);
+  p.vc = bp(v_cache);
+  p.c_sb = k_cache.stride(0);
+  p.c_st = k_cache.stride(1);
+  p.c_sh = k_cache.stride(2);
+  p.kv_len = kv_len.data_ptr<int>();
+  p.window = static_cast<int>(window);
+  p.scale_log2 = static_cast<float>(scale * 1.4426950408889634);
+  p.B = static_cast<int>(B);
+  p.Hq = static_cast<int>(Hq);
+  p.Hkv = static_cast<int>(Hkv);
+  p.D = static_cast<int>(D);
+  p.Tmax = static_cast<int>(Tmax);
+  const int nsplit = decode_splits(p);
+  auto fopt = x.options().dtype(at::kFloat);
+  auto part_o = at::empty({B, Hq, nsplit, D}, fopt);
+  auto part_ml = at::empty({B, Hq, nsplit, 2}, fopt);
+  auto out = at::empty({B, Hq, D}, x.options());
+  p.part_o = part_o.data_ptr<float>();
+  p.part_ml = part_ml.data_ptr<float>();
+  p.out = bp(out);
+  p.o_sb = out.stride(0);
+  p.o_sh = out.stride(1);
+  p.cnt = decode_counters(x, B * Hkv);
+  launch_decode(p, cur_stream(x));
+  return out;
+}
+
+// q [B, Hq, D] already rotated, the newest token already in the caches
+static at::Tensor decode_q(const at::Tensor& q, const at::Tensor& k_cache, const at::Tensor& v_cache,
+                           const at::Tensor& kv_len, const c10::optional<at::Tensor>& kv_start,
+                           int64_t window, double scale, bool grouped, int64_t group_size,
+                           int64_t prefix_len) {
+  check_bf16(q, "q");
+  TORCH_CHECK(q.dim() == 3 && k_cache.dim() == 4, "q [B, Hq, D], caches [B, Tmax, Hkv, D]");
+  TORCH_CHECK(q.stride(2) == 1, "head dim must be contiguous");
+  TORCH_CHECK(q.stride(1) % 8 == 0, "16-byte aligned rows");
+  TORCH_CHECK(kv_len.numel() >= 1, "kv_len");
+  DecodeParams p{};
+  p.q = cbp(q);
+  p.q_sb = q.stride(0);
+  p.q_sh = q.stride(1);
+  return decode_step(q, p, k_cache, v_cache, kv_len, kv_start, window, scale, q.size(0), q.size(1),
+                     k_cache.size(2), q.size(2), grouped, group_size, prefix_len);
 }
 
 // One decode step's attention with the rope + cache write of the newest token fused in (one
 // launch pair instead of rope_cache_write + decode_attn): qkv [B, 1, (Hq + 2 Hkv) D] raw row,
 // caches [B, Tmax, Hkv, D] (row `slot` is written), kv_len = slot + 1 (device).
+static at::Tensor decode_qkv(const at::Tensor& qkv, const at::Tensor& cos, const at::Tensor& sin,
+                             const at::Tensor& pos, const at::Tensor& k_cache, const at::Tensor& v_cache,
+                             const at::Tensor& slot, const at::Tensor& kv_len,
+                             const c10::optional<at::Tensor>& kv_start, int64_t window, double scale,
+                             int64_t Hq, int64_t Hkv, int64_t D, int64_t rot, bool grouped,
+                             int64_t group_size, int64_t prefix_len) {
+  check_rope_step(qkv, cos, sin, pos, slot, Hq, Hkv, D, rot);
+  TORCH_CHECK(rot > 0, "rot % 16 == 0, 0 < rot <= D");
+  DecodeParams p{};
+  p.rope = DecRope{cbp(qkv), qkv.stride(0), cos.data_ptr<float>(), sin.data_ptr<float>(),
+                   pos.data_ptr<int>(), slot.data_ptr<int64_t>(), static_cast<int>(rot),
+                   static_cast<int>(Hkv)};
+  return decode_step(qkv, p, k_cache, v_cache, kv_len, kv_start, window, scale, qkv.size(0), Hq, Hkv, D,
+                     grouped, group_size, prefix_len);
+}
+
+at::Tensor decode_attn(const at::Tensor& q, const at::Tensor& k_cache, const at::Tensor& v_cache,
+                       const at::Tensor& kv_len, const c10::optional<at::Tensor>& kv_start,
+                       int64_t window, double scale) {
+  return decode_q(q, k_cache, v_cache, kv_len, kv_start, window, scale, false, 0, 0);
+}
+
 at::Tensor decode_attn_rope(const at::Tensor& qkv, const at::Tensor& cos, const at::Tensor& sin,
                             const at::Tensor& pos, at::Tensor& k_cache, at::Tensor& v_cache,
                             const at::Tensor& slot, const at::Tensor& kv_len,
                             const c10::optional<at::Tensor>& kv_start, int64_t window, double scale,
                             int64_t Hq, int64_t Hkv, int64_t D, int64_t rot) {
-  check_bf16(qkv, "qkv");
-  check_bf16(k_cache, "k_cache");
-  check_bf16(v_cache, "v_cache");
-  check_f32(cos, "cos");
-  check_f32(sin, "sin");
-  check_i32(pos, "pos");
-  check_i32(kv_len, "kv_len");
-  check_cuda(slot, "slot");
-  TORCH_CHECK(slot.scalar_type() == at::kLong && slot.numel() >= 1, "slot int64");
-  const int64_t B = qkv.size(0);
-  TORCH_CHECK(qkv.dim() == 3 && qkv.size(1) == 1 && qkv.size(2) == (Hq + 2 * Hkv) * D &&
-                  qkv.stride(2) == 1 && qkv.stride(0) % 8 == 0,
-              "qkv [B, 1, (Hq+2Hkv)D] with 16-byte aligned rows");
-  TORCH_CHECK(k_cache.dim() == 4 && k_cache.size(0) == B && k_cache.size(2) == Hkv &&
-                  k_cache.size(3) == D && k_cache.sizes() == v_cache.sizes() &&
-                  k_cache.strides() == v_cache.strides() && k_cache.stride(3) == 1,
-              "caches [B, Tmax, Hkv, D]");
-  TORCH_CHECK(D == 64 || D == 128, "decode attention supports head_dim 64 or 128");
-  TORCH_CHECK(Hq % Hkv == 0, "Hq % Hkv");
-  const int64_t G = Hq / Hkv;
-  TORCH_CHECK(G == 1 || G == 2 || G == 4 || G == 8, "GQA group size must be 1, 2, 4 or 8");
-  TORCH_CHECK(rot % 16 == 0 && rot <= D && rot > 0, "rot % 16 == 0, 0 < rot <= D");
-  TORCH_CHECK(cos.is_contiguous() && sin.is_contiguous() && cos.size(-1) == rot / 2, "rope tables");
-  TORCH_CHECK(pos.numel() == B && pos.is_contiguous(), "pos [B]");
-  TORCH_CHECK(k_cache.stride(1) % 8 == 0 && k_cache.stride(2) % 8 == 0 && k_cache.stride(0) % 8 == 0,
-              "16-byte aligned cache rows");
-  check_aligned16(qkv, "qkv");
-  check_aligned16(k_cache, "k_cache");
-  check_aligned16(v_cache, "v_cache");
-  const int* ks = nullptr;
-  if (kv_start && kv_start->defined()) {
-    check_i32(*kv_start, "kv_start");
-    TORCH_CHECK(kv_start->numel() == B && kv_start->is_contiguous(), "kv_start [B]");
-    ks = kv_start->data_ptr<int>();
-  }
-  c10::hip::HIPGuardMasqueradingAsCUDA g(qkv.device());
-  const int64_t Tmax = k_cache.size(1);
-  const int nsplit = decode_num_splits(static_cast<int>(Tmax), static_cast<int>(B), static_cast<int>(Hkv));
-  auto fopt = qkv.options().dtype(at::kFloat);
-  auto part_o = at::empty({B, Hq, nsplit, D}, fopt);
-  auto part_ml = at::empty({B, Hq, nsplit, 2}, fopt);
-  auto out = at::empty({B, Hq, D}, qkv.options());
-  launch_decode_attn_rope(cbp(qkv), qkv.stride(0), cos.data_ptr<float>(), sin.data_ptr<float>(),
-                          pos.data_ptr<int>(), slot.data_ptr<int64_t>(), (int)rot, bp(k_cache),
-                          bp(v_cache), k_cache.stride(0), k_cache.stride(1), k_cache.stride(2),
-                          kv_len.data_ptr<int>(), ks, static_cast<int>(window),
-                          static_cast<float>(scale * 1.4426950408889634), (int)B, (int)Hq, (int)Hkv,
-                          (int)D, (int)Tmax, part_o.data_ptr<float>(), part_ml.data_ptr<float>(),
-                          bp(out), out.stride(0), out.stride(1), decode_counters(qkv, B * Hkv),
-                          cur_stream(qkv));
-  return out;
+  return decode_qkv(qkv, cos, sin, pos, k_cache, v_cache, slot, kv_len, kv_start, window, scale, Hq, Hkv,
+                    D, rot, false, 0, 0);
 }
 
 // Group-structured forms of decode_attn / decode_attn_rope (decode.hip DecGroup): rows
@@ -714,116 +697,38 @@ at::Tensor decode_attn_rope(const at::Tensor& qkv, const at::Tensor& cos, const 
 // prefix_len / 128 on, so a slot below them is never written, and the prefix launch reads whatever
 // that slot held before. KVCache.attend refuses that state on the host.
 at::Tensor decode_attn_group(const at::Tensor& q, const at::Tensor& k_cache, const at::Tensor& v_cache,
-                       const at::Tensor& kv_len, const c10::optional<at::Tensor>& kv_start,
-                       int64_t window, double scale, int64_t group_size, int64_t prefix_len) {
-  check_bf16(q, "q");
-  check_bf16(k_cache, "k_cache");
-  check_bf16(v_cache, "v_cache");
-  check_i32(kv_len, "kv_len");
-  TORCH_CHECK(q.dim() == 3 && k_cache.dim() == 4 && v_cache.sizes() == k_cache.sizes(),
-              "q [B, Hq, D], caches [B, Tmax, Hkv, D]");
-  const int64_t B = q.size(0), Hq = q.size(1), D = q.size(2);
-  const int64_t Tmax = k_cache.size(1), Hkv = k_cache.size(2);
-  TORCH_CHECK(k_cache.size(0) == B && k_cache.size(3) == D, "cache batch / head dim");
-  TORCH_CHECK(D == 64 || D == 128, "decode attention supports head_dim 64 or 128");
-  TORCH_CHECK(Hq % Hkv == 0, "Hq % Hkv");
-  const int64_t G = Hq / Hkv;
-  TORCH_CHECK(G == 1 || G == 2 || G == 4 || G == 8, "GQA group size must be 1, 2, 4 or 8");
-  TORCH_CHECK(q.stride(2) == 1 && k_cache.stride(3) == 1 && v_cache.stride(3) == 1,
-              "head dim must be contiguous");
-  TORCH_CHECK(k_cache.strides() == v_cache.strides(), "k/v caches must share strides");
-  TORCH_CHECK(q.stride(1) % 8 == 0 && k_cache.stride(1) % 8 == 0 && k_cache.stride(2) % 8 == 0 &&
-                  k_cache.stride(0) % 8 == 0,
-              "16-byte aligned rows");
-  check_aligned16(k_cache, "k_cache");
-  check_aligned16(v_cache, "v_cache");
-  TORCH_CHECK(kv_len.numel() >= 1, "kv_len");
-  const int* ks = nullptr;
-  if (kv_start && kv_start->defined()) {
-    check_i32(*kv_start, "kv_start");
-    TORCH_CHECK(kv_start->numel() == B && kv_start->is_contiguous(), "kv_start [B]");
-    ks = kv_start->data_ptr<int>();
-  }
-  TORCH_CHECK(group_size >= 1 && B % group_size == 0, "group_size must divide the batch");
-  TORCH_CHECK(prefix_len >= 1 && prefix_len <= Tmax, "1 <= prefix_len <= Tmax");
-  c10::hip::HIPGuardMasqueradingAsCUDA g(q.device());
-  const int nsplit =
-      decode_group_splits((int)Tmax, (int)B, (int)Hq, (int)Hkv, (int)group_size, (int)prefix_len);
-  auto fopt = q.options().dtype(at::kFloat);
-  auto part_o = at::empty({B, Hq, nsplit, D}, fopt);
-  auto part_ml = at::empty({B, Hq, nsplit, 2}, fopt);
-  auto out = at::empty({B, Hq, D}, q.options());
-  launch_decode_attn_group(cbp(q), q.stride(0), q.stride(1), bp(k_cache), bp(v_cache),
-                     k_cache.stride(0), k_cache.stride(1), k_cache.stride(2),
-                     kv_len.data_ptr<int>(), ks, static_cast<int>(window),
-                     static_cast<float>(scale * 1.4426950408889634), (int)B, (int)Hq, (int)Hkv,
-                     (int)D, (int)Tmax, (int)group_size, (int)prefix_len, part_o.data_ptr<float>(),
-                     part_ml.data_ptr<float>(),
-                     bp(out), out.stride(0), out.stride(1), decode_counters(q, B * Hkv), cur_stream(q));
-  return out;
+                             const at::Tensor& kv_len, const c10::optional<at::Tensor>& kv_start,
+                             int64_t window, double scale, int64_t group_size, int64_t prefix_len) {
+  return decode_q(q, k_cache, v_cache, kv_len, kv_start, window, scale, true, group_size, prefix_len);
 }
 
 at::Tensor decode_attn_rope_group(const at::Tensor& qkv, const at::Tensor& cos, const at::Tensor& sin,
+                                  const at::Tensor& pos, at::Tensor& k_cache, at::Tensor& v_cache,
+                                  const at::Tensor& slot, const at::Tensor& kv_len,
+                                  const c10::optional<at::Tensor>& kv_start, int64_t window, double scale,
+                                  int64_t Hq, int64_t Hkv, int64_t D, int64_t rot, int64_t group_size,
+                                  int64_t prefix_len) {
+  return decode_qkv(qkv, cos, sin, pos, k_cache, v_cache, slot, kv_len, kv_start, window, scale, Hq, Hkv,
+                    D, rot, true, group_size, prefix_len);
+}
+
+// qkv [B, 1, (Hq + 2 Hkv) D] of the newest token -> rotated q [B, Hq, D]; k/v written into
+// k_cache/v_cache [B, Tmax, Hkv, D] at row `slot` (int64 [1] on device). Any D % 8 == 0 (phi-2's
+// D = 80), rot = 0 allowed.
+at::Tensor rope_cache_write(const at::Tensor& qkv, const at::Tensor& cos, const at::Tensor& sin,
                             const at::Tensor& pos, at::Tensor& k_cache, at::Tensor& v_cache,
-                            const at::Tensor& slot, const at::Tensor& kv_len,
-                            const c10::optional<at::Tensor>& kv_start, int64_t window, double scale,
-                            int64_t Hq, int64_t Hkv, int64_t D, int64_t rot, int64_t group_size,
-                            int64_t prefix_len) {
-  check_bf16(qkv, "qkv");
-  check_bf16(k_cache, "k_cache");
-  check_bf16(v_cache, "v_cache");
-  check_f32(cos, "cos");
-  check_f32(sin, "sin");
-  check_i32(pos, "pos");
-  check_i32(kv_len, "kv_len");
-  check_cuda(slot, "slot");
-  TORCH_CHECK(slot.scalar_type() == at::kLong && slot.numel() >= 1, "slot int64");
+                            const at::Tensor& slot, int64_t Hq, int64_t Hkv, int64_t D, int64_t rot) {
+  TORCH_CHECK(D % 8 == 0, "D % 8");
+  check_rope_step(qkv, cos, sin, pos, slot, Hq, Hkv, D, rot);
   const int64_t B = qkv.size(0);
-  TORCH_CHECK(qkv.dim() == 3 && qkv.size(1) == 1 && qkv.size(2) == (Hq + 2 * Hkv) * D &&
-                  qkv.stride(2) == 1 && qkv.stride(0) % 8 == 0,
-              "qkv [B, 1, (Hq+2Hkv)D] with 16-byte aligned rows");
-  TORCH_CHECK(k_cache.dim() == 4 && k_cache.size(0) == B && k_cache.size(2) == Hkv &&
-                  k_cache.size(3) == D && k_cache.sizes() == v_cache.sizes() &&
-                  k_cache.strides() == v_cache.strides() && k_cache.stride(3) == 1,
-              "caches [B, Tmax, Hkv, D]");
-  TORCH_CHECK(D == 64 || D == 128, "decode attention supports head_dim 64 or 128");
-  TORCH_CHECK(Hq % Hkv == 0, "Hq % Hkv");
-  const int64_t G = Hq / Hkv;
-  TORCH_CHECK(G == 1 || G == 2 || G == 4 || G == 8, "GQA group size must be 1, 2, 4 or 8");
-  TORCH_CHECK(rot % 16 == 0 && rot <= D && rot > 0, "rot % 16 == 0, 0 < rot <= D");
-  TORCH_CHECK(cos.is_contiguous() && sin.is_contiguous() && cos.size(-1) == rot / 2, "rope tables");
-  TORCH_CHECK(pos.numel() == B && pos.is_contiguous(), "pos [B]");
-  TORCH_CHECK(k_cache.stride(1) % 8 == 0 && k_cache.stride(2) % 8 == 0 && k_cache.stride(0) % 8 == 0,
-              "16-byte aligned cache rows");
-  check_aligned16(qkv, "qkv");
-  check_aligned16(k_cache, "k_cache");
-  check_aligned16(v_cache, "v_cache");
-  const int* ks = nullptr;
-  if (kv_start && kv_start->defined()) {
-    check_i32(*kv_start, "kv_start");
-    TORCH_CHECK(kv_start->numel() == B && kv_start->is_contiguous(), "kv_start [B]");
-    ks = kv_start->data_ptr<int>();
-  }
+  check_kv_caches(k_cache, v_cache, B, Hkv, D);
   c10::hip::HIPGuardMasqueradingAsCUDA g(qkv.device());
-  const int64_t Tmax = k_cache.size(1);
-  TORCH_CHECK(group_size >= 1 && B % group_size == 0, "group_size must divide the batch");
-  TORCH_CHECK(prefix_len >= 1 && prefix_len <= Tmax, "1 <= prefix_len <= Tmax");
-  const int nsplit =
-      decode_group_splits((int)Tmax, (int)B, (int)Hq, (int)Hkv, (int)group_size, (int)prefix_len);
-  auto fopt = qkv.options().dtype(at::kFloat);
-  auto part_o = at::empty({B, Hq, nsplit, D}, fopt);
-  auto part_ml = at::empty({B, Hq, nsplit, 2}, fopt);
-  auto out = at::empty({B, Hq, D}, qkv.options());
-  launch_decode_attn_rope_group(cbp(qkv), qkv.stride(0), cos.data_ptr<float>(), sin.data_ptr<float>(),
-                          pos.data_ptr<int>(), slot.data_ptr<int64_t>(), (int)rot, bp(k_cache),
-                          bp(v_cache), k_cache.stride(0), k_cache.stride(1), k_cache.stride(2),
-                          kv_len.data_ptr<int>(), ks, static_cast<int>(window),
-                          static_cast<float>(scale * 1.4426950408889634), (int)B, (int)Hq, (int)Hkv,
-                          (int)D, (int)Tmax, (int)group_size, (int)prefix_len, part_o.data_ptr<float>(),
-                     part_ml.data_ptr<float>(),
-                          bp(out), out.stride(0), out.stride(1), decode_counters(qkv, B * Hkv),
-                          cur_stream(qkv));
-  return out;
+  auto q = at::empty({B, Hq, D}, qkv.options());
+  launch_rope_cache(cbp(qkv), qkv.stride(0), bp(q), bp(k_cache), bp(v_cache), k_cache.stride(0),
+                    k_cache.stride(1), k_cache.stride(2), slot.data_ptr<int64_t>(),
+                    cos.data_ptr<float>(), sin.data_ptr<float>(), pos.data_ptr<int>(), (int)B,
+                    (int)Hq, (int)Hkv, (int)D, (int)rot, cur_stream(qkv));
+  return q;
 }
 
 at::Tensor sample_tokens(const at::Tensor& logits, double temperature, int64_t top_k,

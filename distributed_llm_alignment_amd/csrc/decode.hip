@@ -12,35 +12,19 @@
 // Lengths are DEVICE values (kv_len scalar, per-row kv_start for left padding), so the same
 // launch replays inside a captured hipGraph while the cache grows; splits beyond kv_len exit.
 // Group rollouts whose rows share a prompt prefix have a two-launch form that reads the prefix once
-// per group (DecGroup, decode_prefix_kernel, launch_decode_attn_group below).
+// per group (DecGroup, decode_prefix_kernel, launch_decode below).
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 #include "common.h"
-
+#include "decode_geom.h"
+#include "decode_params.h"
 
 namespace dla {
 
-constexpr int kDecChunk = 128;  // keys per block (4 waves x 32)
-
 // Lanes cooperate on rows: LPK = D/8 lanes x 16 B cover one K/V row (coalesced 256-byte rows
 // for D = 128), KPI = 64/LPK rows per wave instruction.
-// Fused decode-step prologue (ROPE = true): instead of a separate rope + cache-write launch, the
-// kernel reads the raw qkv row of the newest token: every block rotates its G query heads while
-// filling `qs`; the newest key's K/V (rotated k, plain v) come from registers rather than the
-// cache, and the block whose split holds that key writes them into the cache slot for the next
-// steps. Rounding matches rope_cache_kernel + the unfused kernel (q and k rounded to bf16 after
-// the rotation), so fused and unfused decode agree bitwise.
-struct DecRope {
-  const bf16_t* qkv;  // [B, (Hq + 2 Hkv) * D] rows of the newest token
-  int64_t ld;
-  const float* cos_t;  // [P, rot/2]
-  const float* sin_t;
-  const int* pos;      // [B] rope position of the newest token
-  const int64_t* slot; // cache slot of the newest token (== kv_len - 1)
-  int rot;
-  int Hkv;
-};
 
 // 8 rotated dims [d0, d0 + 8) of one head (rotate-half over the first `rot` dims), rounded to bf16
 __device__ __forceinline__ bf16x8 dec_rope8(const bf16_t* src, int d0, int rot, const float* cs,
@@ -294,8 +278,6 @@ __device__ __forceinline__ void dec_pub(float* p, float v, bool wt) {
   if (wt) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   else *p = v;
 }
-
-constexpr int kDecMaxFuse = 8;  // most splits the in-kernel combine merges
 
 // Group-structured decode step (GRPO rollouts: rows p * G .. p * G + G - 1 share prompt p's keys
 // [0, Tp), bitwise identical copies). The prefix part [lo, Tp) is attended once per (prompt, kv
@@ -1091,269 +1073,102 @@ __global__ __launch_bounds__(64) void decode_combine_kernel(const float* __restr
     out[(int64_t)b * o_sb + (int64_t)h * o_sh + lane * DPT + j] = f2bf(acc[j] * inv);
 }
 
-static int decode_cpb(int Tmax, int B, int Hkv);
-int decode_num_splits(int Tmax, int B, int Hkv);
+// ---- host side: one launch path for the four forms (per-row / group-structured step, rotated q /
+// fused rope + cache write); split geometry in decode_geom.h
+template <int N>
+using dec_int = std::integral_constant<int, N>;
 
-template <int D>
-static void launch_decode_d(const bf16_t* q, int64_t q_sb, int64_t q_sh, bf16_t* kc,
-                            bf16_t* vc, int64_t c_sb, int64_t c_st, int64_t c_sh,
-                            const int* kv_len, const int* kv_start, int window, float scale_log2,
-                            int B, int Hq, int Hkv, int Tmax, float* part_o, float* part_ml,
-                            bf16_t* out, int64_t o_sb, int64_t o_sh, const DecRope* rp,
-                            int* cnt, hipStream_t st) {
-  const int G = Hq / Hkv;
-  const int cpb = decode_cpb(Tmax, B, Hkv);
-  const int nsplit = decode_num_splits(Tmax, B, Hkv);
-  dim3 grid(nsplit, Hkv, B);
-  const DecRope r0 = rp ? *rp : DecRope{};
-  if (cpb > 0) {
-    // one split per sequence, or the in-kernel combine (arrival counters given): no combine launch
-    int* const cn = (nsplit > 1 && nsplit <= kDecMaxFuse) ? cnt : nullptr;
-    bf16_t* fin = (nsplit == 1 || cn != nullptr) ? out : nullptr;
-#define DLA_DECL(GG)                                                                                    \
-  if (rp)                                                                                               \
-    decode_attn_loop_kernel<D, GG, true><<<grid, 256, 0, st>>>(q, q_sb, q_sh, kc, vc, c_sb, c_st, c_sh, \
-                                                               kv_len, kv_start, window, scale_log2,    \
-                                                               nsplit, cpb, part_o, part_ml, Hq, r0,    \
-                                                               fin, o_sb, o_sh, cn, Tmax);              \
-  else                                                                                                  \
-    decode_attn_loop_kernel<D, GG, false><<<grid, 256, 0, st>>>(q, q_sb, q_sh, kc, vc, c_sb, c_st, c_sh, \
-                                                                kv_len, kv_start, window, scale_log2,   \
-                                                                nsplit, cpb, part_o, part_ml, Hq, r0,   \
-                                                                fin, o_sb, o_sh, cn, Tmax)
-    switch (G) {
-      case 1: DLA_DECL(1); break;
-      case 2: DLA_DECL(2); break;
-      case 4: DLA_DECL(4); break;
-      case 8: DLA_DECL(8); break;
+// f(D, GQ, ROPE) with the launch's head dim, q heads per kv head and form as integral constants
+// (head dim and GQA ratio validated on the host)
+template <class F>
+static void decode_dispatch(const DecodeParams& p, F f) {
+  auto form = [&](auto d, auto gq) {
+    if (p.rope.qkv != nullptr) f(d, gq, std::true_type{});
+    else f(d, gq, std::false_type{});
+  };
+  auto heads = [&](auto d) {
+    switch (p.Hq / p.Hkv) {
+      case 1: form(d, dec_int<1>{}); break;
+      case 2: form(d, dec_int<2>{}); break;
+      case 4: form(d, dec_int<4>{}); break;
+      case 8: form(d, dec_int<8>{}); break;
       default: break;
     }
-#undef DLA_DECL
-    if (fin == nullptr)
-      decode_combine_kernel<D><<<B * Hq, 64, 0, st>>>(part_o, part_ml, nsplit, out, o_sb, o_sh, Hq);
+  };
+  if (p.D == 128) heads(dec_int<128>{});
+  else heads(dec_int<64>{});
+}
+
+template <int D>
+static void launch_decode_combine(const DecodeParams& p, int nsplit, hipStream_t st) {
+  decode_combine_kernel<D><<<p.B * p.Hq, 64, 0, st>>>(p.part_o, p.part_ml, nsplit, p.out, p.o_sb, p.o_sh, p.Hq);
+}
+
+template <int D, int GQ, bool ROPE>
+static void launch_decode_rows(const DecodeParams& p, hipStream_t st) {
+  const int cpb = decode_cpb(p.Tmax, p.B, p.Hkv);
+  const int nsplit = decode_num_splits(p.Tmax, p.B, p.Hkv);
+  dim3 grid(nsplit, p.Hkv, p.B);
+  if (cpb > 0) {
+    // one split per sequence, or the in-kernel combine (arrival counters given): no combine launch
+    int* const cn = (nsplit > 1 && nsplit <= kDecMaxFuse) ? p.cnt : nullptr;
+    bf16_t* fin = (nsplit == 1 || cn != nullptr) ? p.out : nullptr;
+    decode_attn_loop_kernel<D, GQ, ROPE><<<grid, 256, 0, st>>>(
+        p.q, p.q_sb, p.q_sh, p.kc, p.vc, p.c_sb, p.c_st, p.c_sh, p.kv_len, p.kv_start, p.window,
+        p.scale_log2, nsplit, cpb, p.part_o, p.part_ml, p.Hq, p.rope, fin, p.o_sb, p.o_sh, cn, p.Tmax);
+    if (fin == nullptr) launch_decode_combine<D>(p, nsplit, st);
     return;
   }
-#define DLA_DEC(GG)                                                                              \
-  if (rp)                                                                                        \
-    decode_attn_kernel<D, GG, true><<<grid, 256, 0, st>>>(q, q_sb, q_sh, kc, vc, c_sb, c_st,     \
-                                                              c_sh, kv_len, kv_start, window,    \
-                                                              scale_log2, nsplit, part_o,        \
-                                                              part_ml, Hq, r0, Tmax);            \
-  else                                                                                           \
-    decode_attn_kernel<D, GG, false><<<grid, 256, 0, st>>>(q, q_sb, q_sh, kc, vc, c_sb,          \
-                                                               c_st, c_sh, kv_len, kv_start,     \
-                                                               window, scale_log2, nsplit,       \
-                                                               part_o, part_ml, Hq, r0, Tmax)
-  switch (G) {
-    case 1: DLA_DEC(1); break;
-    case 2: DLA_DEC(2); break;
-    case 4: DLA_DEC(4); break;
-    case 8: DLA_DEC(8); break;
-    default: break;  // validated on the host
+  decode_attn_kernel<D, GQ, ROPE><<<grid, 256, 0, st>>>(
+      p.q, p.q_sb, p.q_sh, p.kc, p.vc, p.c_sb, p.c_st, p.c_sh, p.kv_len, p.kv_start, p.window,
+      p.scale_log2, nsplit, p.part_o, p.part_ml, p.Hq, p.rope, p.Tmax);
+  launch_decode_combine<D>(p, nsplit, st);
+}
+
+// Group-structured decode step (DecGroup); ROPE: rope + cache write of the newest token in the
+// suffix launch
+template <int D, int GQ, bool ROPE>
+static void launch_decode_group(const DecodeParams& p, hipStream_t st) {
+  const int P = p.B / p.G;
+  const DecGroupGeom g = decode_group_geom(p.Tmax, p.B, p.Hq, p.Hkv, p.G, p.Tp);
+  const DecGroup gp{p.G, p.Tp, g.npre, g.nsuf, g.c0};
+  const int ntot = g.npre + g.nsuf;
+  // prefix launch first: its partials are complete at the kernel boundary, ahead of the suffix
+  // launch's merge (same stream)
+  dim3 pgrid(g.npre, p.Hkv, P * g.ntile);
+  auto prefix = [&](auto nt) {
+    decode_prefix_kernel<D, decltype(nt)::value, ROPE><<<pgrid, 256, 0, st>>>(
+        p.q, p.q_sb, p.q_sh, p.kc, p.vc, p.c_sb, p.c_st, p.c_sh, p.kv_len, p.kv_start, p.window,
+        p.scale_log2, ntot, g.cpb_p, p.part_o, p.part_ml, p.Hq, GQ, p.rope, gp, g.rpt, g.ntile, p.Tmax);
+  };
+  switch (g.nt) {
+    case 1: prefix(dec_int<1>{}); break;
+    case 2: prefix(dec_int<2>{}); break;
+    default: prefix(dec_int<4>{}); break;  // 3 tiles run as 4, the last one padding
   }
-#undef DLA_DEC
-  decode_combine_kernel<D><<<B * Hq, 64, 0, st>>>(part_o, part_ml, nsplit, out, o_sb, o_sh, Hq);
+  int* const cn = (g.fuse && p.cnt != nullptr) ? p.cnt : nullptr;
+  bf16_t* const fin = cn != nullptr ? p.out : nullptr;
+  dim3 sgrid(g.nsuf, p.Hkv, p.B);
+  decode_attn_loop_group_kernel<D, GQ, ROPE><<<sgrid, 256, 0, st>>>(
+      p.q, p.q_sb, p.q_sh, p.kc, p.vc, p.c_sb, p.c_st, p.c_sh, p.kv_len, p.kv_start, p.window,
+      p.scale_log2, ntot, g.cpb_s, p.part_o, p.part_ml, p.Hq, p.rope, fin, p.o_sb, p.o_sh, cn, p.Tmax, gp);
+  if (fin == nullptr) launch_decode_combine<D>(p, ntot, st);
 }
 
-// DLA_DECODE_LOOP=0: one 128-key chunk per block (decode_attn_kernel); otherwise blocks loop over
-// chunks so that B x Hkv x splits stays near DLA_DECODE_BLOCKS (default 256; same-box graph decode:
-// B = 8 / 1152 keys 3 chunks per block 3.98-4.00 vs 4.02 ms/token one-chunk, 2 chunks 4.03-4.06,
-// 9 chunks (no combine) 4.25; B = 64 / ~576 keys: one split per sequence)
-static int decode_cpb(int Tmax, int B, int Hkv) {
-  // read per call (cheap next to a launch) so a test can force the loop kernel at small shapes
-  const char* e = getenv("DLA_DECODE_LOOP");
-  const char* tb = getenv("DLA_DECODE_BLOCKS");
-  const int target = (e != nullptr && atoi(e) == 0) ? 0 : (tb ? atoi(tb) : 256);
-  const int nch = (Tmax + kDecChunk - 1) / kDecChunk;
-  if (target <= 0) return 0;
-  const int64_t blocks = static_cast<int64_t>(B) * Hkv * nch;
-  const int cpb = static_cast<int>((blocks + target - 1) / target);
-  // Below DLA_DECODE_LOOP_MIN chunks per block the one-chunk kernel (3 blocks per CU) + the combine
-  // launch. Round 3 measured that faster under 3 chunks (B = 8, 1152 keys: 4.05 vs 4.12 ms/token);
-  // with the in-kernel combine the loop kernel now wins at 2 chunks and at 1 chunk whenever the
-  // splits fit the fused combine (B = 8, 512 + 256 tokens: 3.466-3.473 at 2, 3.485-3.497 at 1 vs
-  // 3.542-3.548 ms/token, same box, tools/gpu_passes.py r6-decode-combine)
-  const char* mn = getenv("DLA_DECODE_LOOP_MIN");
-  const int min_cpb = mn ? atoi(mn) : 2;
-  if (cpb < min_cpb) return (mn == nullptr && cpb == 1 && nch <= kDecMaxFuse) ? 1 : 0;
-  return std::min(cpb, nch);
-}
-
-int decode_num_splits(int Tmax, int B, int Hkv) {
-  const int nch = (Tmax + kDecChunk - 1) / kDecChunk;
-  const int cpb = decode_cpb(Tmax, B, Hkv);
-  return cpb == 0 ? nch : (nch + cpb - 1) / cpb;
-}
-
-// ---- group-structured step (DecGroup): split geometry and launches
-// Row tiles of at most 64 query columns (rpt rows x GQ heads), prefix chunks [0, ceil(Tp / 128))
-// and suffix chunks [Tp / 128, ceil(Tmax / 128)) each cut so that the grid stays near
-// DLA_DECODE_BLOCKS (default 256) blocks, as decode_cpb does for the per-row kernel; the prefix
-// cut is coarsened until prefix + suffix slots fit the in-kernel combine when they can.
-// When the suffix alone takes kDecMaxFuse splits there is no slot left for the prefix: the step
-// then runs the separate combine launch (a third launch) where the per-row op at that shape still
-// fuses. DLA_DECODE_LOOP=0: one chunk per block on both sides and the separate combine launch.
-struct DecGroupGeom {
-  int rpt, ntile, nt, cpb_p, cpb_s, npre, nsuf, c0;
-  bool fuse;
-};
-
-static DecGroupGeom decode_group_geom(int Tmax, int B, int Hq, int Hkv, int G, int Tp) {
-  const char* e = getenv("DLA_DECODE_LOOP");
-  const char* tb = getenv("DLA_DECODE_BLOCKS");
-  const int target = (e != nullptr && atoi(e) == 0) ? 0 : (tb ? atoi(tb) : 256);
-  const int GQ = Hq / Hkv, P = B / G;
-  DecGroupGeom g{};
-  g.rpt = std::min(G, 64 / GQ);
-  g.ntile = (G + g.rpt - 1) / g.rpt;
-  g.nt = (g.rpt * GQ + 15) / 16;
-  const int nch = (Tmax + kDecChunk - 1) / kDecChunk;
-  const int nchp = (Tp + kDecChunk - 1) / kDecChunk;
-  g.c0 = std::min(Tp / kDecChunk, nch - 1);
-  const int nchs = nch - g.c0;
-  g.fuse = target > 0;
-  if (target <= 0) {
-    g.cpb_p = g.cpb_s = 1;
-  } else {
-    const int64_t bp = static_cast<int64_t>(P) * g.ntile * Hkv * nchp;
-    const int64_t bs = static_cast<int64_t>(B) * Hkv * nchs;
-    g.cpb_p = static_cast<int>(std::min<int64_t>(std::max<int64_t>((bp + target - 1) / target, 1), nchp));
-    g.cpb_s = static_cast<int>(std::min<int64_t>(std::max<int64_t>((bs + target - 1) / target, 1), nchs));
-  }
-  g.nsuf = (nchs + g.cpb_s - 1) / g.cpb_s;
-  g.npre = (nchp + g.cpb_p - 1) / g.cpb_p;
-  if (g.fuse && g.nsuf < kDecMaxFuse && g.npre + g.nsuf > kDecMaxFuse) {
-    g.cpb_p = (nchp + (kDecMaxFuse - g.nsuf) - 1) / (kDecMaxFuse - g.nsuf);
-    g.npre = (nchp + g.cpb_p - 1) / g.cpb_p;
-  }
-  g.fuse = g.fuse && g.npre + g.nsuf <= kDecMaxFuse;
-  return g;
-}
-
-// partial slots per (row, q head) of a group-structured step: prefix splits, then suffix splits
-int decode_group_splits(int Tmax, int B, int Hq, int Hkv, int G, int Tp) {
-  const DecGroupGeom g = decode_group_geom(Tmax, B, Hq, Hkv, G, Tp);
+// partial slots per (row, q head); a group-structured step: prefix splits, then suffix splits
+int decode_splits(const DecodeParams& p) {
+  if (p.G == 0) return decode_num_splits(p.Tmax, p.B, p.Hkv);
+  const DecGroupGeom g = decode_group_geom(p.Tmax, p.B, p.Hq, p.Hkv, p.G, p.Tp);
   return g.npre + g.nsuf;
 }
 
-template <int D>
-static void launch_decode_group_d(const bf16_t* q, int64_t q_sb, int64_t q_sh, bf16_t* kc, bf16_t* vc,
-                                  int64_t c_sb, int64_t c_st, int64_t c_sh, const int* kv_len,
-                                  const int* kv_start, int window, float scale_log2, int B, int Hq,
-                                  int Hkv, int Tmax, int G, int Tp, float* part_o, float* part_ml,
-                                  bf16_t* out, int64_t o_sb, int64_t o_sh, const DecRope* rp, int* cnt,
-                                  hipStream_t st) {
-  const int GQ = Hq / Hkv, P = B / G;
-  const DecGroupGeom g = decode_group_geom(Tmax, B, Hq, Hkv, G, Tp);
-  const DecGroup gp{G, Tp, g.npre, g.nsuf, g.c0};
-  const int ntot = g.npre + g.nsuf;
-  const DecRope r0 = rp ? *rp : DecRope{};
-  // prefix launch first: its partials are complete at the kernel boundary, ahead of the suffix
-  // launch's merge (same stream)
-  dim3 pgrid(g.npre, Hkv, P * g.ntile);
-#define DLA_PRE(NN)                                                                                      \
-  if (rp)                                                                                                \
-    decode_prefix_kernel<D, NN, true><<<pgrid, 256, 0, st>>>(q, q_sb, q_sh, kc, vc, c_sb, c_st, c_sh,    \
-                                                             kv_len, kv_start, window, scale_log2, ntot, \
-                                                             g.cpb_p, part_o, part_ml, Hq, GQ, r0, gp,   \
-                                                             g.rpt, g.ntile, Tmax);                      \
-  else                                                                                                   \
-    decode_prefix_kernel<D, NN, false><<<pgrid, 256, 0, st>>>(q, q_sb, q_sh, kc, vc, c_sb, c_st, c_sh,   \
-                                                              kv_len, kv_start, window, scale_log2, ntot, \
-                                                              g.cpb_p, part_o, part_ml, Hq, GQ, r0, gp,  \
-                                                              g.rpt, g.ntile, Tmax)
-  switch (g.nt) {
-    case 1: DLA_PRE(1); break;
-    case 2: DLA_PRE(2); break;
-    default: DLA_PRE(4); break;  // 3 tiles run as 4, the last one padding
-  }
-#undef DLA_PRE
-  int* const cn = (g.fuse && cnt != nullptr) ? cnt : nullptr;
-  bf16_t* const fin = cn != nullptr ? out : nullptr;
-  dim3 sgrid(g.nsuf, Hkv, B);
-#define DLA_SUF(GG)                                                                                      \
-  if (rp)                                                                                                \
-    decode_attn_loop_group_kernel<D, GG, true><<<sgrid, 256, 0, st>>>(                                   \
-        q, q_sb, q_sh, kc, vc, c_sb, c_st, c_sh, kv_len, kv_start, window, scale_log2, ntot, g.cpb_s,    \
-        part_o, part_ml, Hq, r0, fin, o_sb, o_sh, cn, Tmax, gp);                                         \
-  else                                                                                                   \
-    decode_attn_loop_group_kernel<D, GG, false><<<sgrid, 256, 0, st>>>(                                  \
-        q, q_sb, q_sh, kc, vc, c_sb, c_st, c_sh, kv_len, kv_start, window, scale_log2, ntot, g.cpb_s,    \
-        part_o, part_ml, Hq, r0, fin, o_sb, o_sh, cn, Tmax, gp)
-  switch (GQ) {
-    case 1: DLA_SUF(1); break;
-    case 2: DLA_SUF(2); break;
-    case 4: DLA_SUF(4); break;
-    case 8: DLA_SUF(8); break;
-    default: break;  // validated on the host
-  }
-#undef DLA_SUF
-  if (fin == nullptr)
-    decode_combine_kernel<D><<<B * Hq, 64, 0, st>>>(part_o, part_ml, ntot, out, o_sb, o_sh, Hq);
-}
-
-// Group-structured decode step (DecGroup). rp == nullptr: q [B, Hq, D] given; else the fused form
-// (raw qkv rows, rope + cache write of the newest token in the suffix launch).
-static void launch_decode_group(const bf16_t* q, int64_t q_sb, int64_t q_sh, const DecRope* rp, bf16_t* kc,
-                                bf16_t* vc, int64_t c_sb, int64_t c_st, int64_t c_sh, const int* kv_len,
-                              const int* kv_start, int window, float scale_log2, int B, int Hq, int Hkv,
-                              int D, int Tmax, int G, int Tp, float* part_o, float* part_ml, bf16_t* out,
-                              int64_t o_sb, int64_t o_sh, int* cnt, hipStream_t st) {
-  if (D == 128)
-    launch_decode_group_d<128>(q, q_sb, q_sh, kc, vc, c_sb, c_st, c_sh, kv_len, kv_start, window, scale_log2,
-                               B, Hq, Hkv, Tmax, G, Tp, part_o, part_ml, out, o_sb, o_sh, rp, cnt, st);
-  else
-    launch_decode_group_d<64>(q, q_sb, q_sh, kc, vc, c_sb, c_st, c_sh, kv_len, kv_start, window, scale_log2,
-                              B, Hq, Hkv, Tmax, G, Tp, part_o, part_ml, out, o_sb, o_sh, rp, cnt, st);
-}
-
-void launch_decode_attn_group(const bf16_t* q, int64_t q_sb, int64_t q_sh, bf16_t* kc, bf16_t* vc,
-                              int64_t c_sb, int64_t c_st, int64_t c_sh, const int* kv_len,
-                              const int* kv_start, int window, float scale_log2, int B, int Hq, int Hkv,
-                              int D, int Tmax, int G, int Tp, float* part_o, float* part_ml, bf16_t* out,
-                              int64_t o_sb, int64_t o_sh, int* cnt, hipStream_t st) {
-  launch_decode_group(q, q_sb, q_sh, nullptr, kc, vc, c_sb, c_st, c_sh, kv_len, kv_start, window, scale_log2,
-                      B, Hq, Hkv, D, Tmax, G, Tp, part_o, part_ml, out, o_sb, o_sh, cnt, st);
-}
-
-void launch_decode_attn_rope_group(const bf16_t* qkv, int64_t ld, const float* cos_t, const float* sin_t,
-                                   const int* pos, const int64_t* slot, int rot, bf16_t* kc, bf16_t* vc,
-                                   int64_t c_sb, int64_t c_st, int64_t c_sh, const int* kv_len,
-                                   const int* kv_start, int window, float scale_log2, int B, int Hq,
-                                   int Hkv, int D, int Tmax, int G, int Tp, float* part_o, float* part_ml,
-                                   bf16_t* out, int64_t o_sb, int64_t o_sh, int* cnt, hipStream_t st) {
-  const DecRope rp{qkv, ld, cos_t, sin_t, pos, slot, rot, Hkv};
-  launch_decode_group(nullptr, 0, 0, &rp, kc, vc, c_sb, c_st, c_sh, kv_len, kv_start, window, scale_log2,
-                           B, Hq, Hkv, D, Tmax, G, Tp, part_o, part_ml, out, o_sb, o_sh, cnt, st);
-}
-
-void launch_decode_attn(const bf16_t* q, int64_t q_sb, int64_t q_sh, bf16_t* kc,
-                        bf16_t* vc, int64_t c_sb, int64_t c_st, int64_t c_sh,
-                        const int* kv_len, const int* kv_start, int window, float scale_log2, int B,
-                        int Hq, int Hkv, int D, int Tmax, float* part_o, float* part_ml,
-                        bf16_t* out, int64_t o_sb, int64_t o_sh, int* cnt, hipStream_t st) {
-  if (D == 128)
-    launch_decode_d<128>(q, q_sb, q_sh, kc, vc, c_sb, c_st, c_sh, kv_len, kv_start, window,
-                         scale_log2, B, Hq, Hkv, Tmax, part_o, part_ml, out, o_sb, o_sh, nullptr, cnt, st);
-  else
-    launch_decode_d<64>(q, q_sb, q_sh, kc, vc, c_sb, c_st, c_sh, kv_len, kv_start, window,
-                        scale_log2, B, Hq, Hkv, Tmax, part_o, part_ml, out, o_sb, o_sh, nullptr, cnt, st);
-}
-
-// rope + cache write of the newest token fused into the decode attention (see DecRope)
-void launch_decode_attn_rope(const bf16_t* qkv, int64_t ld, const float* cos_t, const float* sin_t,
-                             const int* pos, const int64_t* slot, int rot, bf16_t* kc, bf16_t* vc,
-                             int64_t c_sb, int64_t c_st, int64_t c_sh, const int* kv_len,
-                             const int* kv_start, int window, float scale_log2, int B, int Hq,
-                             int Hkv, int D, int Tmax, float* part_o, float* part_ml, bf16_t* out,
-                             int64_t o_sb, int64_t o_sh, int* cnt, hipStream_t st) {
-  const DecRope rp{qkv, ld, cos_t, sin_t, pos, slot, rot, Hkv};
-  if (D == 128)
-    launch_decode_d<128>(nullptr, 0, 0, kc, vc, c_sb, c_st, c_sh, kv_len, kv_start, window,
-                         scale_log2, B, Hq, Hkv, Tmax, part_o, part_ml, out, o_sb, o_sh, &rp, cnt, st);
-  else
-    launch_decode_d<64>(nullptr, 0, 0, kc, vc, c_sb, c_st, c_sh, kv_len, kv_start, window,
-                        scale_log2, B, Hq, Hkv, Tmax, part_o, part_ml, out, o_sb, o_sh, &rp, cnt, st);
+void launch_decode(const DecodeParams& p, hipStream_t st) {
+  decode_dispatch(p, [&](auto d, auto gq, auto rope) {
+    constexpr int D = decltype(d)::value, GQ = decltype(gq)::value;
+    constexpr bool ROPE = decltype(rope)::value;
+    if (p.G > 0) launch_decode_group<D, GQ, ROPE>(p, st);
+    else launch_decode_rows<D, GQ, ROPE>(p, st);
+  });
 }
 
 }  // namespace dla
