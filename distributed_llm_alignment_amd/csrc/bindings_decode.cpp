@@ -22,6 +22,11 @@ int sample_split_chunks(const void*, int64_t, int64_t, int, float, int, float, b
 size_t sample_workspace_bytes(int64_t, int);
 void launch_sample_split(const void*, bool, int64_t, int64_t, int, int, float, int, float,
                          const int64_t*, int64_t*, void*, hipStream_t);
+void launch_sample_logp(const void*, bool, int64_t, int64_t, int, float, int, float, bool,
+                        const int64_t*, int64_t*, float*, hipStream_t);
+size_t sample_workspace_bytes_logp(int64_t, int);
+void launch_sample_split_logp(const void*, bool, int64_t, int64_t, int, int, float, int, float,
+                              const int64_t*, int64_t*, float*, void*, hipStream_t);
 
 void launch_kv_replicate(const bf16_t*, const bf16_t*, bf16_t*, bf16_t*, int, int, int, int, int,
                          int, const int64_t*, const int64_t*, hipStream_t);
@@ -731,8 +736,7 @@ at::Tensor rope_cache_write(const at::Tensor& qkv, const at::Tensor& cos, const 
   return q;
 }
 
-at::Tensor sample_tokens(const at::Tensor& logits, double temperature, int64_t top_k,
-                         double top_p, bool greedy, const at::Tensor& rng) {
+static void check_sample_args(const at::Tensor& logits, double top_p, const at::Tensor& rng) {
   check_cuda(logits, "logits");
   TORCH_CHECK(logits.scalar_type() == at::kBFloat16 || logits.scalar_type() == at::kFloat,
               "logits must be bf16 or fp32");
@@ -740,8 +744,13 @@ at::Tensor sample_tokens(const at::Tensor& logits, double temperature, int64_t t
   check_cuda(rng, "rng");
   TORCH_CHECK(rng.scalar_type() == at::kLong && rng.numel() >= 2, "rng int64 [seed, counter]");
   TORCH_CHECK(top_p > 0.0 && top_p <= 1.0, "top_p in (0, 1]");
+  TORCH_CHECK(logits.size(1) < (1ll << 31), "vocab too large");
+}
+
+at::Tensor sample_tokens(const at::Tensor& logits, double temperature, int64_t top_k,
+                         double top_p, bool greedy, const at::Tensor& rng) {
+  check_sample_args(logits, top_p, rng);
   const int64_t B = logits.size(0), V = logits.size(1);
-  TORCH_CHECK(V < (1ll << 31), "vocab too large");
   c10::hip::HIPGuardMasqueradingAsCUDA g(logits.device());
   auto out = at::empty({B}, logits.options().dtype(at::kLong));
   const float inv_t = temperature > 0.0 ? static_cast<float>(1.0 / temperature) : 0.f;
@@ -759,6 +768,36 @@ at::Tensor sample_tokens(const at::Tensor& logits, double temperature, int64_t t
                 static_cast<float>(top_p), greedy, rng.data_ptr<int64_t>(),
                 out.data_ptr<int64_t>(), cur_stream(logits));
   return out;
+}
+
+// sample_tokens plus logp [B] fp32: log softmax(logits)[token] at temperature 1 over the full
+// vocabulary (the engine's model log-prob of the draw). Same checks and the same path choice; the
+// LOGP kernel instantiations return the tokens of the plain op bit for bit.
+std::tuple<at::Tensor, at::Tensor> sample_tokens_logp(const at::Tensor& logits, double temperature,
+                                                      int64_t top_k, double top_p, bool greedy,
+                                                      const at::Tensor& rng) {
+  check_sample_args(logits, top_p, rng);
+  const int64_t B = logits.size(0), V = logits.size(1);
+  c10::hip::HIPGuardMasqueradingAsCUDA g(logits.device());
+  auto out = at::empty({B}, logits.options().dtype(at::kLong));
+  auto logp = at::empty({B}, logits.options().dtype(at::kFloat));
+  const float inv_t = temperature > 0.0 ? static_cast<float>(1.0 / temperature) : 0.f;
+  const bool is_bf16 = logits.scalar_type() == at::kBFloat16;
+  const int G = sample_split_chunks(logits.data_ptr(), logits.stride(0), B, (int)V, inv_t,
+                                    (int)top_k, static_cast<float>(top_p), greedy);
+  if (G > 0) {
+    auto ws = at::empty({(int64_t)sample_workspace_bytes_logp(B, G)},
+                        logits.options().dtype(at::kByte));
+    launch_sample_split_logp(logits.data_ptr(), is_bf16, logits.stride(0), B, (int)V, G, inv_t,
+                             (int)top_k, static_cast<float>(top_p), rng.data_ptr<int64_t>(),
+                             out.data_ptr<int64_t>(), logp.data_ptr<float>(), ws.data_ptr(),
+                             cur_stream(logits));
+    return {out, logp};
+  }
+  launch_sample_logp(logits.data_ptr(), is_bf16, logits.stride(0), B, (int)V, inv_t, (int)top_k,
+                     static_cast<float>(top_p), greedy, rng.data_ptr<int64_t>(),
+                     out.data_ptr<int64_t>(), logp.data_ptr<float>(), cur_stream(logits));
+  return {out, logp};
 }
 
 // Shared-prefill replication: keys / values [0, Tp) of every layer of the P-row prefill cache
@@ -812,6 +851,7 @@ TORCH_LIBRARY_FRAGMENT(dla, m) {
   m.def("decode_attn_group(Tensor q, Tensor k_cache, Tensor v_cache, Tensor kv_len, Tensor? kv_start, int window, float scale, int group_size, int prefix_len) -> Tensor");
   m.def("decode_attn_rope_group(Tensor qkv, Tensor cos, Tensor sin, Tensor pos, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor slot, Tensor kv_len, Tensor? kv_start, int window, float scale, int Hq, int Hkv, int D, int rot, int group_size, int prefix_len) -> Tensor");
   m.def("sample_tokens(Tensor logits, float temperature, int top_k, float top_p, bool greedy, Tensor rng) -> Tensor");
+  m.def("sample_tokens_logp(Tensor logits, float temperature, int top_k, float top_p, bool greedy, Tensor rng) -> (Tensor, Tensor)");
   m.def("skinny_gemm(Tensor x, Tensor w, Tensor(a!) counters, bool swiglu, bool glu_out=False) -> Tensor");
   m.def("skinny_glu_ks(Tensor x, Tensor w) -> Tensor");
   m.def("skinny_fused(Tensor x, Tensor w, Tensor? res, Tensor? ssq_in, float eps, bool glu) -> (Tensor, Tensor)");
@@ -830,6 +870,7 @@ TORCH_LIBRARY_IMPL(dla, CUDA, m) {
   m.impl("decode_attn_group", &dla::decode_attn_group);
   m.impl("decode_attn_rope_group", &dla::decode_attn_rope_group);
   m.impl("sample_tokens", &dla::sample_tokens);
+  m.impl("sample_tokens_logp", &dla::sample_tokens_logp);
   m.impl("rope_cache_write", &dla::rope_cache_write);
   m.impl("decode_attn_rope", &dla::decode_attn_rope);
   m.impl("skinny_gemm", &dla::skinny_gemm);

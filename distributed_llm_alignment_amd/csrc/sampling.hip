@@ -184,12 +184,29 @@ __device__ int find_bin_mass(const float* sm, float need, int* out) {
   return *out;
 }
 
-template <typename T, bool VEC>
+// exp(x - gmax) as a term of the temperature-1 full-vocabulary mass S1 behind the `logp` output:
+// NaN logits count as -inf (never drawn, no mass); no -64 window and no tau.
+__device__ __forceinline__ float logp_term(float x, float gmax) {
+  const float d = x - gmax;
+  return d == d ? __expf(d) : 0.f;
+}
+// log softmax(x)[token] = (x_t - gmax) - log(S1); a row whose max is not finite (+inf present, or
+// no finite logit) has no defined value and gets exactly 0
+__device__ __forceinline__ float logp_value(float d, float s1, float gmax) {
+  return (gmax - gmax == 0.f) ? d - logf(s1) : 0.f;
+}
+
+// LOGP: also write logp[r], the row's temperature-1 log-softmax at the returned token (the
+// engine's model log-prob of the draw). Its mass sum S1 rides the draw pass (step 4) as a second
+// per-thread accumulator over the same contiguous segments, reduced by block_sum: shuffles and a
+// fixed LDS order, so two launches give the same bits. !LOGP compiles to the kernel without it.
+template <typename T, bool VEC, bool LOGP>
 __global__ __launch_bounds__(kSampNT) void sample_kernel(const T* __restrict__ logits, int64_t ld_,
                                                           int V, float inv_temp, int top_k,
                                                           float top_p, bool greedy,
                                                           const int64_t* __restrict__ rng,
-                                                          int64_t* __restrict__ out) {
+                                                          int64_t* __restrict__ out,
+                                                          float* __restrict__ logp) {
   __shared__ float sc[kSampNT / 64];
   __shared__ int amin[kSampNT / 64];
   __shared__ int hc[kBins];
@@ -220,6 +237,12 @@ __global__ __launch_bounds__(kSampNT) void sample_kernel(const T* __restrict__ l
   for (int i = 1; i < kSampNT / 64; ++i) argmax = min(argmax, amin[i]);
   if (argmax == 0x7fffffff) argmax = 0;  // no finite logit in the row (all -inf / NaN): token 0
   if (greedy || inv_temp <= 0.f) {
+    if constexpr (LOGP) {  // one more pass for S1; the token is the max, so x_t - gmax = 0
+      float s1 = 0.f;
+      for_each_logit<VEC>(row, V, [&](int, float x) { s1 += logp_term(x, gmax); });
+      s1 = block_sum<kSampNT>(s1, sc);
+      if (tid == 0) logp[r] = logp_value(0.f, s1, gmax);
+    }
     if (tid == 0) out[r] = argmax;
     return;
   }
@@ -288,6 +311,7 @@ __global__ __launch_bounds__(kSampNT) void sample_kernel(const T* __restrict__ l
   const int per = VEC ? ((V / 8 + kSampNT - 1) / kSampNT) * 8 : (V + kSampNT - 1) / kSampNT;
   const int s0 = min(V, tid * per), s1 = min(V, s0 + per);
   float mine = 0.f;
+  [[maybe_unused]] float mine1 = 0.f;  // LOGP: this segment's share of S1
   if constexpr (VEC) {
     for (int v = s0; v < s1; v += 8) {
       float x[8];
@@ -296,13 +320,22 @@ __global__ __launch_bounds__(kSampNT) void sample_kernel(const T* __restrict__ l
       for (int j = 0; j < 8; ++j) {
         const float z = (x[j] - gmax) * inv_temp;
         mine += z >= tau ? __expf(z) : 0.f;
+        if constexpr (LOGP) mine1 += logp_term(x[j], gmax);
       }
     }
   } else {
     for (int v = s0; v < s1; ++v) {
-      const float z = (ld(row, v) - gmax) * inv_temp;
+      const float xv = ld(row, v);
+      const float z = (xv - gmax) * inv_temp;
       mine += z >= tau ? __expf(z) : 0.f;
+      if constexpr (LOGP) mine1 += logp_term(xv, gmax);
     }
+  }
+  [[maybe_unused]] __shared__ float dsel;  // LOGP: x_t - gmax of the picked token
+  [[maybe_unused]] float mass1 = 0.f;  // LOGP: S1
+  if constexpr (LOGP) {
+    mass1 = block_sum<kSampNT>(mine1, sc);
+    if (tid == 0) dsel = 0.f;  // the argmax fallback below: x_t = gmax
   }
   tm[tid] = mine;
   if (tid == 0) ans = -1;
@@ -328,9 +361,15 @@ __global__ __launch_bounds__(kSampNT) void sample_kernel(const T* __restrict__ l
       }
     }
     ans = pick;
+    if constexpr (LOGP) {
+      if (pick >= 0) dsel = ld(row, pick) - gmax;
+    }
   }
   __syncthreads();
   if (tid == 0) out[r] = ans >= 0 ? ans : argmax;  // u on a rounding gap at the top: argmax
+  if constexpr (LOGP) {
+    if (tid == 0) logp[r] = logp_value(dsel, mass1, gmax);
+  }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -593,11 +632,15 @@ __global__ __launch_bounds__(kSampNT) void split_resolve_kernel(int G, int top_k
   if (tid == 0) ws.state[r] = s;
 }
 
-template <typename T>
+// LOGP: the chunk's share of the temperature-1 full-vocabulary mass S1 goes to csum [B, G] (a
+// workspace region of its own behind the SplitWs ones); split_pick_kernel adds the G partials in
+// index order.
+template <typename T, bool LOGP>
 __global__ __launch_bounds__(kSplitNT) void split_mass_kernel(const T* __restrict__ logits,
                                                               int64_t ld_, int V, int G,
                                                               float inv_t, bool has_tau,
-                                                              SplitWs ws) {
+                                                              SplitWs ws,
+                                                              float* __restrict__ csum) {
   __shared__ float red[kSplitNT / 64];
   const int r = blockIdx.y, g = blockIdx.x, tid = threadIdx.x;
   float gmax;
@@ -608,6 +651,7 @@ __global__ __launch_bounds__(kSplitNT) void split_mass_kernel(const T* __restric
   int v0, v1;
   chunk_range(V, G, g, v0, v1);
   float acc = 0.f;
+  [[maybe_unused]] float acc1 = 0.f;
   for (int i = v0 + tid; i < v1; i += kSplitNT) {
     float x[8];
     ld8(row, i, x);
@@ -615,21 +659,29 @@ __global__ __launch_bounds__(kSplitNT) void split_mass_kernel(const T* __restric
     for (int j = 0; j < 8; ++j) {
       const float z = (x[j] - gmax) * inv_t;
       acc += z >= tau ? __expf(z) : 0.f;
+      if constexpr (LOGP) acc1 += logp_term(x[j], gmax);
     }
   }
   const float tot = block_sum<kSplitNT>(acc, red);
   if (tid == 0) ws.cmass[r * G + g] = tot;
+  if constexpr (LOGP) {
+    const float tot1 = block_sum<kSplitNT>(acc1, red);
+    if (tid == 0) csum[r * G + g] = tot1;
+  }
 }
 
-template <typename T>
+template <typename T, bool LOGP>
 __global__ __launch_bounds__(kSplitNT) void split_pick_kernel(const T* __restrict__ logits,
                                                               int64_t ld_, int V, int G,
                                                               float inv_t, bool has_tau,
                                                               const int64_t* __restrict__ rng,
                                                               SplitWs ws,
-                                                              int64_t* __restrict__ out) {
+                                                              int64_t* __restrict__ out,
+                                                              const float* __restrict__ csum,
+                                                              float* __restrict__ logp) {
   __shared__ float tm[kSplitNT];
   __shared__ int ans;
+  [[maybe_unused]] __shared__ float dsel;  // LOGP: x_t - gmax of the picked token
   const int r = blockIdx.x, tid = threadIdx.x;
   float gmax;
   int argmax;
@@ -661,6 +713,9 @@ __global__ __launch_bounds__(kSplitNT) void split_pick_kernel(const T* __restric
     acc += cm;
   }
   if (tid == 0) ans = -1;
+  if constexpr (LOGP) {
+    if (tid == 0) dsel = 0.f;  // the argmax fallback below: x_t = gmax
+  }
   const T* row = logits + int64_t(r) * ld_;
   float mine = 0.f;
   int s0 = 0, s1 = 0;
@@ -696,9 +751,20 @@ __global__ __launch_bounds__(kSplitNT) void split_pick_kernel(const T* __restric
       }
     }
     ans = pick;
+    if constexpr (LOGP) {
+      if (pick >= 0) dsel = ld(row, pick) - gmax;
+    }
   }
   __syncthreads();
   if (tid == 0) out[r] = ans >= 0 ? ans : argmax;  // u on a rounding gap: argmax
+  if constexpr (LOGP) {
+    if (tid == 0) {
+      float s1sum = 0.f;
+#pragma unroll
+      for (int g = 0; g < kSplitG; ++g) s1sum += csum[r * kSplitG + g];  // index order
+      logp[r] = logp_value(dsel, s1sum, gmax);
+    }
+  }
 }
 
 static bool split_enabled() {
@@ -718,12 +784,19 @@ int sample_split_chunks(const void* logits, int64_t ld_, int64_t rows, int V, fl
   return kSplitG;
 }
 size_t sample_workspace_bytes(int64_t rows, int G) { return G > 0 ? split_ws_bytes(rows, G) : 0; }
+// with the [B, G] chunk sums of S1 behind the regions above (split_ws_bytes is a sum of
+// 256-byte multiples, so the new region starts 256-byte aligned too)
+size_t sample_workspace_bytes_logp(int64_t rows, int G) {
+  return G > 0 ? split_ws_bytes(rows, G) + align256(size_t(rows) * G * 4) : 0;
+}
 
-template <typename T>
+template <typename T, bool LOGP>
 static void launch_split(const T* lg, int64_t ld_, int64_t rows, int V, int G, float inv_t,
-                         int top_k, float top_p, const int64_t* rng, int64_t* out, void* wsp,
-                         hipStream_t st) {
+                         int top_k, float top_p, const int64_t* rng, int64_t* out, float* logp,
+                         void* wsp, hipStream_t st) {
   const SplitWs ws = split_ws(wsp, rows, G);
+  float* csum = LOGP ? reinterpret_cast<float*>(static_cast<char*>(wsp) + split_ws_bytes(rows, G))
+                     : nullptr;
   const dim3 grid(G, rows);
   const bool need_k = top_k > 0 && top_k < V, need_p = top_p < 1.f;
   split_max_kernel<T><<<grid, kSplitNT, 0, st>>>(lg, ld_, V, G, ws);
@@ -733,31 +806,50 @@ static void launch_split(const T* lg, int64_t ld_, int64_t rows, int V, int G, f
     const int first_phase = p == 0 ? (need_k ? kKCoarse : kPCoarse) : kDone;
     split_resolve_kernel<<<rows, kSampNT, 0, st>>>(G, top_k, top_p, need_p, first_phase, ws);
   }
-  split_mass_kernel<T><<<grid, kSplitNT, 0, st>>>(lg, ld_, V, G, inv_t, passes > 0, ws);
-  split_pick_kernel<T><<<rows, kSplitNT, 0, st>>>(lg, ld_, V, G, inv_t, passes > 0, rng, ws, out);
+  split_mass_kernel<T, LOGP><<<grid, kSplitNT, 0, st>>>(lg, ld_, V, G, inv_t, passes > 0, ws, csum);
+  split_pick_kernel<T, LOGP><<<rows, kSplitNT, 0, st>>>(lg, ld_, V, G, inv_t, passes > 0, rng, ws,
+                                                        out, csum, logp);
+}
+
+template <bool LOGP>
+static void sample_split_any(const void* logits, bool is_bf16, int64_t ld_, int64_t rows, int V,
+                             int G, float inv_temp, int top_k, float top_p, const int64_t* rng,
+                             int64_t* out, float* logp, void* ws, hipStream_t st) {
+  if (rows == 0) return;
+  if (is_bf16)
+    launch_split<bf16_t, LOGP>(static_cast<const bf16_t*>(logits), ld_, rows, V, G, inv_temp,
+                               top_k, top_p, rng, out, logp, ws, st);
+  else
+    launch_split<float, LOGP>(static_cast<const float*>(logits), ld_, rows, V, G, inv_temp, top_k,
+                              top_p, rng, out, logp, ws, st);
 }
 
 void launch_sample_split(const void* logits, bool is_bf16, int64_t ld_, int64_t rows, int V,
                          int G, float inv_temp, int top_k, float top_p, const int64_t* rng,
                          int64_t* out, void* ws, hipStream_t st) {
-  if (rows == 0) return;
-  if (is_bf16)
-    launch_split(static_cast<const bf16_t*>(logits), ld_, rows, V, G, inv_temp, top_k, top_p, rng,
-                 out, ws, st);
-  else
-    launch_split(static_cast<const float*>(logits), ld_, rows, V, G, inv_temp, top_k, top_p, rng,
-                 out, ws, st);
+  sample_split_any<false>(logits, is_bf16, ld_, rows, V, G, inv_temp, top_k, top_p, rng, out,
+                          nullptr, ws, st);
 }
 
-void launch_sample(const void* logits, bool is_bf16, int64_t ld_, int64_t rows, int V,
-                   float inv_temp, int top_k, float top_p, bool greedy, const int64_t* rng,
-                   int64_t* out, hipStream_t st) {
+// ws: sample_workspace_bytes_logp(rows, G) bytes
+void launch_sample_split_logp(const void* logits, bool is_bf16, int64_t ld_, int64_t rows, int V,
+                              int G, float inv_temp, int top_k, float top_p, const int64_t* rng,
+                              int64_t* out, float* logp, void* ws, hipStream_t st) {
+  sample_split_any<true>(logits, is_bf16, ld_, rows, V, G, inv_temp, top_k, top_p, rng, out, logp,
+                         ws, st);
+}
+
+template <bool LOGP>
+static void sample_any(const void* logits, bool is_bf16, int64_t ld_, int64_t rows, int V,
+                       float inv_temp, int top_k, float top_p, bool greedy, const int64_t* rng,
+                       int64_t* out, float* logp, hipStream_t st) {
   if (rows == 0) return;
   const bool vec = V % 8 == 0 && ld_ % 8 == 0 &&
                    reinterpret_cast<uintptr_t>(logits) % 16 == 0;
-#define DLA_SAMPLE(T, VV)                                                                         \
-  sample_kernel<T, VV><<<rows, kSampNT, 0, st>>>(static_cast<const T*>(logits), ld_, V, inv_temp, \
-                                                 top_k, top_p, greedy, rng, out)
+#define DLA_SAMPLE(T, VV)                                                                  \
+  sample_kernel<T, VV, LOGP><<<rows, kSampNT, 0, st>>>(static_cast<const T*>(logits), ld_, V, \
+                                                       inv_temp, top_k, top_p, greedy, rng, out, \
+                                                       logp)
   if (is_bf16) {
     if (vec) DLA_SAMPLE(bf16_t, true);
     else DLA_SAMPLE(bf16_t, false);
@@ -766,6 +858,20 @@ void launch_sample(const void* logits, bool is_bf16, int64_t ld_, int64_t rows, 
     else DLA_SAMPLE(float, false);
   }
 #undef DLA_SAMPLE
+}
+
+void launch_sample(const void* logits, bool is_bf16, int64_t ld_, int64_t rows, int V,
+                   float inv_temp, int top_k, float top_p, bool greedy, const int64_t* rng,
+                   int64_t* out, hipStream_t st) {
+  sample_any<false>(logits, is_bf16, ld_, rows, V, inv_temp, top_k, top_p, greedy, rng, out,
+                    nullptr, st);
+}
+
+void launch_sample_logp(const void* logits, bool is_bf16, int64_t ld_, int64_t rows, int V,
+                        float inv_temp, int top_k, float top_p, bool greedy, const int64_t* rng,
+                        int64_t* out, float* logp, hipStream_t st) {
+  sample_any<true>(logits, is_bf16, ld_, rows, V, inv_temp, top_k, top_p, greedy, rng, out, logp,
+                   st);
 }
 
 }  // namespace dla

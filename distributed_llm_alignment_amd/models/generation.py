@@ -218,13 +218,17 @@ class _DecodeGraph:
     """One captured decode step: embed -> layers (device-indexed cache writes, decode kernel)
     -> norm -> LM head -> fused sampler -> finished/pad bookkeeping, all on device."""
 
-    def __init__(self, model, cache, B, max_new, eos, pad, greedy, temperature, top_k, top_p, seed):
+    def __init__(self, model, cache, B, max_new, eos, pad, greedy, temperature, top_k, top_p, seed,
+                 logprobs: bool = False):
         dev = cache.k.device
         self.model, self.cache = model, cache
         self.tok = torch.zeros((B, 1), dtype=torch.long, device=dev)
         self.finished = torch.zeros(B, dtype=torch.bool, device=dev)
         self.out = torch.full((B, max_new), pad, dtype=torch.long, device=dev)
         self.gen_mask = torch.zeros((B, max_new), dtype=torch.long, device=dev)
+        # the sampling engine's log-prob of every emitted token (0 for finished rows); only with
+        # `logprobs`, which also selects the sampler op that produces them
+        self.logp = torch.zeros((B, max_new), dtype=torch.float32, device=dev) if logprobs else None
         self.col = torch.zeros(1, dtype=torch.long, device=dev)
         self.rng = torch.tensor([seed, 0], dtype=torch.long, device=dev)
         self.eos, self.pad = eos, pad
@@ -238,7 +242,11 @@ class _DecodeGraph:
 
     def sample(self, logits):
         t, k, p, g = self.args
-        nxt = ops.decode.sample_tokens(logits, t, k, p, g, self.rng)
+        if self.logp is not None:
+            nxt, lp = ops.decode.sample_tokens_logp(logits, t, k, p, g, self.rng)
+            self.logp.index_copy_(1, self.col, torch.where(self.finished, torch.zeros_like(lp), lp).unsqueeze(1))
+        else:
+            nxt = ops.decode.sample_tokens(logits, t, k, p, g, self.rng)
         nxt = torch.where(self.finished, torch.full_like(nxt, self.pad), nxt)
         self.gen_mask.index_copy_(1, self.col, (~self.finished).long().unsqueeze(1))
         self.out.index_copy_(1, self.col, nxt.unsqueeze(1))
@@ -252,6 +260,8 @@ class _DecodeGraph:
         self.finished.zero_()
         self.out.fill_(self.pad)
         self.gen_mask.zero_()
+        if self.logp is not None:
+            self.logp.zero_()
         self.col.zero_()
         self.rng[0].fill_(seed)
         self.rng[1].fill_(0)
@@ -360,7 +370,7 @@ def generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional[
              pad_token_id: Optional[int] = None, generator: Optional[torch.Generator] = None,
              return_mask: bool = False, use_graph: Optional[bool] = None, seed: Optional[int] = None,
              weight_dtype: str = "bf16", num_return_sequences: int = 1, share_prefill: bool = True,
-             group_attention: bool = False):
+             group_attention: bool = False, return_logprobs: bool = False):
     """Left-padded prompts [B, Tp] -> sequences [B, Tp + n] (n <= max_new_tokens).
 
     `num_return_sequences=G` (group rollouts, GRPO): G samples per prompt, output [B*G, Tp + n]
@@ -376,6 +386,13 @@ def generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional[
     With `return_mask`, also returns the attention mask of the full sequence (prompt mask, then
     1 for every generated token up to and including EOS, 0 afterwards) — the correct mask for
     the RLHF log-prob pass (fixes Appendix A #10's `generated != pad` which drops real EOS).
+
+    With `return_logprobs`, also returns `logp` [B, n] fp32: `logp[s, j]` is the log-prob of the
+    token at sequence position Tp + j under the engine that sampled it, log softmax(logits)[token]
+    at temperature 1 over the full vocabulary (comparable with `CausalLM.token_logprobs` whatever
+    `temperature` / `top_k` / `top_p` shaped the draw; on the GPU it comes out of the fused
+    sampler's own passes, `ops.decode.sample_tokens_logp`), and exactly 0 where the generation
+    mask is 0. Return order: `seqs[, mask][, logp]`.
 
     On MI355X the prompt is prefilled with the flash-attention kernel, then every new token is
     ONE replay of a captured hipGraph (decode kernel + fused sampler, no host sync except an
@@ -399,14 +416,15 @@ def generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional[
     with ops.decode.fp8_weights(f8), ops.fp8_inference_scope(model, f8 and PREFILL_FP8):
         return _generate(model, input_ids, attention_mask, max_new_tokens, do_sample, temperature, top_p,
                          top_k, eos_token_id, pad_token_id, generator, return_mask, use_graph, seed, G,
-                         bool(group_attention) and G > 1)
+                         bool(group_attention) and G > 1, bool(return_logprobs))
 
 
 def _generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor],
               max_new_tokens: int, do_sample: bool, temperature: float, top_p: float, top_k: int,
               eos_token_id: Optional[int], pad_token_id: Optional[int],
               generator: Optional[torch.Generator], return_mask: bool, use_graph: Optional[bool],
-              seed: Optional[int], G: int = 1, group_attention: bool = False):
+              seed: Optional[int], G: int = 1, group_attention: bool = False,
+              return_logprobs: bool = False):
     if DECODE_GATHER and model.layers_sharded():
         # ZeRO-3 policy: gather it once for the whole rollout (fused decode kernels + captured
         # graph) instead of an all-gather per layer per token
@@ -418,7 +436,7 @@ def _generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional
                     stack.enter_context(eng.gathered_for_inference())
                 return _generate(model, input_ids, attention_mask, max_new_tokens, do_sample, temperature,
                                  top_p, top_k, eos_token_id, pad_token_id, generator, return_mask, use_graph,
-                                 seed, G, group_attention)
+                                 seed, G, group_attention, return_logprobs)
         finally:
             # the gathered units are freed on exit: the captured graph (it reads their addresses),
             # its KV cache and the derived decode weight copies (a second full set of layer
@@ -455,7 +473,8 @@ def _generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional
             and _graph_capable(model):
         reuse_key = (B, Tp, max_new_tokens, kv_start is None, greedy, float(temperature), int(top_k),
                      float(top_p), eos, pad, input_ids.device, _weights_key(model), ops.decode.fp8_enabled(),
-                     G if group_attention else 0)  # the grouped ops capture G (and Tp) as host constants
+                     G if group_attention else 0,  # the grouped ops capture G (and Tp) as host constants
+                     return_logprobs)  # the captured step holds one sampler op or the other
         hit = _GRAPH_SLOT.get(id(model))
         if hit is not None and hit[0]() is model and hit[1] == reuse_key:
             cache, dg = hit[2], hit[3]
@@ -482,7 +501,7 @@ def _generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional
     if graph_ok and max_new_tokens > 2:
         if dg is None:
             dg = _DecodeGraph(model, cache, B, max_new_tokens, eos, pad, greedy, temperature, top_k,
-                              top_p, seed)
+                              top_p, seed, return_logprobs)
         else:
             dg.reset(seed)
         dg.sample(model.logits(last))  # token 1 from the prefill, eager
@@ -502,13 +521,20 @@ def _generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional
         cache.capturing = False
         seqs = torch.cat([input_ids, dg.out[:, :n]], dim=1)
         gm = dg.gen_mask[:, :n]
+        glp = dg.logp[:, :n].clone() if return_logprobs else None
     else:
-        out, gen_mask = [input_ids], []
+        out, gen_mask, logps = [input_ids], [], []
         finished = torch.zeros(B, dtype=torch.bool, device=input_ids.device)
         rng = torch.tensor([seed, 0], dtype=torch.long, device=input_ids.device)
         for step in range(max_new_tokens):
             logits = model.logits(last)
-            if ops._ext.use_native(logits):
+            lp = None
+            if return_logprobs:  # native on the GPU; sample_next + log_softmax off it
+                nxt, lp = ops.decode.sample_tokens_logp(logits, temperature, top_k, top_p, greedy, rng,
+                                                        generator)
+                if ops._ext.use_native(logits):
+                    rng[1:].add_(1)
+            elif ops._ext.use_native(logits):
                 nxt = ops.decode.sample_tokens(logits, temperature, top_k, top_p, greedy, rng)
                 rng[1:].add_(1)
             else:
@@ -517,7 +543,11 @@ def _generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional
                 import torch.distributed as dist
 
                 dist.broadcast(nxt, src=dist.get_global_rank(model.tp, 0), group=model.tp)
+                if lp is not None:
+                    dist.broadcast(lp, src=dist.get_global_rank(model.tp, 0), group=model.tp)
             nxt = torch.where(finished, torch.full_like(nxt, pad), nxt)
+            if lp is not None:
+                logps.append(torch.where(finished, torch.zeros_like(lp), lp))
             gen_mask.append((~finished).long())
             out.append(nxt.unsqueeze(1))
             finished = finished | (nxt == eos)
@@ -527,11 +557,15 @@ def _generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional
                 last = model(nxt.unsqueeze(1), cache=cache)[:, -1]
         seqs = torch.cat(out, dim=1)
         gm = torch.stack(gen_mask, 1)
+        glp = torch.stack(logps, 1) if return_logprobs else None
     if was_training:
         model.train()
     pm = attention_mask if attention_mask is not None else torch.ones_like(input_ids)
     if extra:
         seqs, pm = seqs[:, extra:].contiguous(), pm[:, extra:]
-    if not return_mask:
-        return seqs
-    return seqs, torch.cat([pm.long(), gm], dim=1)
+    ret = (seqs,)
+    if return_mask:
+        ret += (torch.cat([pm.long(), gm], dim=1),)
+    if return_logprobs:
+        ret += (glp,)
+    return ret[0] if len(ret) == 1 else ret

@@ -137,14 +137,39 @@ def action_mask(mask: torch.Tensor, prompt_len: int) -> torch.Tensor:
     return act
 
 
+def rollout_logp_grid(logp: torch.Tensor, prompt_len: int, T: int) -> torch.Tensor:
+    """The rollout engine's log-probs (`generate(return_logprobs=True)`, [S, n]: column j belongs
+    to the token at sequence position prompt_len + j) placed into the [S, T] action grid of
+    `token_logprobs` / `action_mask`, where position t holds the log-prob of token t + 1: column
+    j goes to prompt_len + j - 1, everything else is 0."""
+    S, n = logp.shape
+    if prompt_len < 1 or prompt_len + n > T:
+        raise ValueError(f"rollout_logp_grid: prompt_len {prompt_len} + {n} generated columns do not fit T = {T}")
+    grid = torch.zeros((S, T), dtype=torch.float32, device=logp.device)
+    grid[:, prompt_len - 1:prompt_len - 1 + n] = logp.float()
+    return grid
+
+
+def rollout_mismatch(rollout_lp: torch.Tensor, trainer_lp: torch.Tensor, act: torch.Tensor):
+    """How far the engine that sampled the rollouts is from the trainer's own forward, on the
+    sampled tokens (both [S, T] action grids): `rollout_kl`, the mean over action tokens of
+    logp_rollout - logp_trainer (the k1 estimate of KL(rollout engine || trainer)), and
+    `rollout_logp_absdiff_max`. Device tensors: no host sync."""
+    d = (rollout_lp.float() - trainer_lp.float()) * act
+    return {"rollout_kl": d.sum() / act.sum().clamp(min=1), "rollout_logp_absdiff_max": d.abs().max()}
+
+
 @torch.no_grad()
 def ppo_rollout_stats(policy, ref, critic, seqs, mask, prompt_len: int, scores, kl_coef: float = 0.1,
-                      gamma: float = 1.0, lam: float = 0.95, whiten: bool = True):
+                      gamma: float = 1.0, lam: float = 0.95, whiten: bool = True,
+                      old_logp: Optional[torch.Tensor] = None):
     """Token-level PPO targets for one batch of rollouts (actor-critic; the north-star
     "PPO RLHF (actor + critic + reward)" config). Per-token reward = -kl_coef * (logp - logp_ref)
     on every action, plus the reward-model score on the last action; GAE(gamma, lam) over the
-    critic's values; advantages whitened over the action tokens."""
-    old_lp = policy.token_logprobs(seqs, mask)
+    critic's values; advantages whitened over the action tokens. `old_logp` ([S, T] action grid,
+    e.g. `rollout_logp_grid` of the rollout engine's log-probs): used as the old-policy log-probs,
+    in the KL reward too, instead of a policy forward over the rollouts."""
+    old_lp = old_logp.float() if old_logp is not None else policy.token_logprobs(seqs, mask)
     ref_lp = ref.token_logprobs(seqs, mask)
     values = critic(seqs, mask)
     act = action_mask(mask, prompt_len)
@@ -248,17 +273,23 @@ def ppo_backward(loss: torch.Tensor) -> None:
 
 @torch.no_grad()
 def grpo_rollout_stats(policy, ref, seqs, mask, prompt_len: int, scores, G: int, beta: float = 0.04,
-                       scale_std: bool = True, need_old: bool = False):
+                       scale_std: bool = True, need_old: bool = False,
+                       old_logp: Optional[torch.Tensor] = None):
     """GRPO targets for one batch of group rollouts (rows p*G .. p*G+G-1 sample prompt p). The
     reward is the reward-model score alone (the KL lives in the loss); a rollout's advantage is its
     score standardised inside its group. The reference's token log-probs are skipped entirely
     when beta == 0, and the old policy's are computed only with `need_old` (more than one update
-    per rollout batch; a single on-policy update uses old = logp.detach())."""
+    per rollout batch; a single on-policy update uses old = logp.detach()). `old_logp` ([S, T]
+    action grid, e.g. `rollout_logp_grid` of the rollout engine's log-probs): returned as the
+    old-policy log-probs, whatever `need_old`, with no policy forward."""
     act = action_mask(mask, prompt_len)
     adv, gm = ops.group_advantages(scores, G, scale_std)
-    return {"act": act, "advantages": adv,
-            "ref_logp": ref.token_logprobs(seqs, mask) if beta != 0 else None,
-            "old_logp": policy.token_logprobs(seqs, mask) if need_old else None,
+    ref_lp = ref.token_logprobs(seqs, mask) if beta != 0 else None
+    if old_logp is not None:
+        old_logp = old_logp.float()
+    elif need_old:
+        old_logp = policy.token_logprobs(seqs, mask)
+    return {"act": act, "advantages": adv, "ref_logp": ref_lp, "old_logp": old_logp,
             "scores": scores.float(), "reward_std": gm["reward_std"], "frac_zero_std": gm["frac_zero_std"]}
 
 

@@ -101,6 +101,25 @@ def sample_tokens(logits: torch.Tensor, temperature: float, top_k: int, top_p: f
     return sample_next(logits.float(), not greedy, temperature, top_p, top_k, generator)
 
 
+def sample_tokens_logp(logits: torch.Tensor, temperature: float, top_k: int, top_p: float, greedy: bool,
+                       rng: torch.Tensor, generator: Optional[torch.Generator] = None):
+    """`sample_tokens` that also returns the engine's model log-prob of every drawn token:
+    (token ids [B] int64, logp [B] fp32) with logp = log_softmax(logits, -1)[token] at temperature
+    1 over the full vocabulary, whatever `temperature` / `top_k` / `top_p` shaped the draw (the
+    quantity `CausalLM.token_logprobs` returns, not the log-prob under the tempered / filtered draw
+    distribution). On the GPU it comes out of the fused sampler's own passes
+    (`torch.ops.dla.sample_tokens_logp`); the tokens are bitwise those of `sample_tokens`."""
+    if _ext.use_native(logits):
+        tok, lp = _ext.require().sample_tokens_logp(logits, float(temperature), int(top_k), float(top_p),
+                                                    bool(greedy), rng)
+        return tok, lp
+    from ..models.generation import sample_next
+
+    x = logits.float()
+    tok = sample_next(x, not greedy, temperature, top_p, top_k, generator)
+    return tok, torch.log_softmax(x, dim=-1).gather(-1, tok.unsqueeze(-1)).squeeze(-1)
+
+
 def kv_replicate(src_k, src_v, dst_k, dst_v, G: int) -> None:
     """Shared-prefill replication for group rollouts: keys / values [0, Tp) of every layer of the
     P-row prefill cache (`src_*` [L, P, Tp, Hkv, D], or the layer-split list of [P, Tp, Hkv, D]) are

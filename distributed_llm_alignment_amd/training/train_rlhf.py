@@ -41,6 +41,15 @@ per-token policy entropy comes out of the LM-head log-prob kernels' own vocabula
 (`token_logprobs(with_entropy=True)`); the loss gains -entropy_coef x its mean over the
 minibatch's action tokens and `train/entropy` is logged. With both off a run launches exactly the
 kernels it launched before. The REINFORCE loop works on sequence log-probs and has no entropy term.
+
+`ppo.rollout_logprobs: off|monitor|old` (default off), for `ppo` and `grpo`: the fused sampler also
+returns the log-prob of every sampled token under the engine that sampled it
+(`generate(return_logprobs=True)`; temperature 1, full vocabulary, like `token_logprobs`). `monitor`
+leaves the update alone and logs `train/rollout_kl` (mean over action tokens of logp_rollout -
+logp_trainer) and `train/rollout_logp_absdiff_max`: how far fp8 / stale / differently rounded
+rollouts are from the trainer's policy. `old` uses them AS the old-policy log-probs (in PPO's KL
+reward too) and skips the trainer's old-policy forward over the rollouts. With `off` the rollouts
+do not request them and a run launches exactly the kernels it launched before.
 """
 from __future__ import annotations
 
@@ -56,7 +65,7 @@ from ..data import read_jsonl
 from ..models import (build_reward_model, build_value_model, generate, load_causal_lm,
                       load_reward_checkpoint)
 from ..objectives import (grpo_denominator, grpo_loss, grpo_rollout_stats, ppo_backward, ppo_loss,
-                          ppo_rollout_stats, rlhf_loss)
+                          ppo_rollout_stats, rlhf_loss, rollout_logp_grid, rollout_mismatch)
 from ..ops.losses import GRPO_LOSS_TYPES
 from ..parallel.dist import barrier, split_for_rank
 from ..utils.checkpoint import save_state
@@ -87,6 +96,21 @@ def load_prompts(cfg: Dict[str, str]) -> List[str]:
         return [r["prompt"] for r in synthetic_prompt_records(int(cfg.get("num_samples", 256)))]
     path = cfg.get("prompt_path") or cfg.get("path")
     return [r["prompt"] for r in read_jsonl(path) if r.get("prompt")]
+
+
+ROLLOUT_LOGPROBS = ("off", "monitor", "old")
+
+
+def rollout_logprobs_mode(ppo: Dict, algo: str) -> str:
+    """`ppo.rollout_logprobs` (a bare YAML `off` arrives as False)."""
+    v = ppo.get("rollout_logprobs", "off")
+    mode = "off" if v is None or v is False else str(v).lower()
+    if mode not in ROLLOUT_LOGPROBS:
+        raise ValueError(f"ppo.rollout_logprobs must be {'|'.join(ROLLOUT_LOGPROBS)}, got {v!r}")
+    if mode != "off" and algo == "reinforce":
+        raise ValueError("ppo.rollout_logprobs needs token-level log-probs (ppo.algorithm: ppo|grpo); "
+                         "the reinforce loop works on sequence log-probs")
+    return mode
 
 
 def _tokenize_left(tok, texts, max_len, device):
@@ -154,6 +178,7 @@ def main(argv=None) -> int:
     algo = str(ppo.get("algorithm", "reinforce")).lower()
     if algo not in ("reinforce", "ppo", "grpo"):
         raise ValueError(f"ppo.algorithm must be reinforce|ppo|grpo, got {algo!r}")
+    want_logp = rollout_logprobs_mode(ppo, algo) != "off"
 
     # reward inputs built on the device when the reward tokenizer equals the policy's (no
     # decode / re-tokenise round trip through the host; training/handoff.py), else the
@@ -170,21 +195,24 @@ def main(argv=None) -> int:
         batch_prompts = rng.sample(prompts, k=min(batch_size // group, len(prompts)))
         mine = split_for_rank(batch_prompts)
         ids, am = _tokenize_left(tok, mine, max_len, ctx.device)
-        seqs, mask = generate(policy.model, ids, am, max_new_tokens=gen.get("max_new_tokens", 256),
-                              do_sample=gen["do_sample"], temperature=gen.get("temperature", 1.0),
-                              top_p=gen.get("top_p", 1.0), top_k=gen.get("top_k", 0),
-                              pad_token_id=tok.pad_token_id, eos_token_id=getattr(tok, "eos_token_id", None),
-                              generator=gen_g, return_mask=True,
-                              weight_dtype=ppo.get("rollout_weight_dtype", "bf16"),
-                              num_return_sequences=group, share_prefill=bool(ppo.get("share_prefill", True)),
-                              group_attention=bool(ppo.get("group_attention", False)))
+        seqs, mask, *rlp = generate(policy.model, ids, am, max_new_tokens=gen.get("max_new_tokens", 256),
+                                    do_sample=gen["do_sample"], temperature=gen.get("temperature", 1.0),
+                                    top_p=gen.get("top_p", 1.0), top_k=gen.get("top_k", 0),
+                                    pad_token_id=tok.pad_token_id, eos_token_id=getattr(tok, "eos_token_id", None),
+                                    generator=gen_g, return_mask=True,
+                                    weight_dtype=ppo.get("rollout_weight_dtype", "bf16"),
+                                    num_return_sequences=group, share_prefill=bool(ppo.get("share_prefill", True)),
+                                    group_attention=bool(ppo.get("group_attention", False)),
+                                    return_logprobs=want_logp)
         if group > 1:  # the reward hand-off sees one prompt row per rollout
             mine = [p for p in mine for _ in range(group)]
             ids, am = ids.repeat_interleave(group, 0), am.repeat_interleave(group, 0)
         r_ids, r_mask = handoff(mine, ids, am, seqs, mask)
         with torch.no_grad():
             scores = rm(r_ids, r_mask)
-        return seqs, mask, scores, ids.shape[1]
+        # the sampling engine's token log-probs in the trainer's [S, T] action grid, or None
+        rlp = rollout_logp_grid(rlp[0], ids.shape[1], seqs.shape[1]) if want_logp else None
+        return seqs, mask, scores, ids.shape[1], rlp
 
     policy.model.train()
     if algo == "ppo":
@@ -194,7 +222,7 @@ def main(argv=None) -> int:
     micro = int(ppo.get("update_micro_batch", 0) or 0)
     pending = rollout()
     for step in range(steps):
-        seqs, mask, scores, _ = pending
+        seqs, mask, scores, _, _ = pending
         loss, m = reinforce_update(policy.model, ref.model, engine, seqs, mask, scores, kl_coef, micro)
         if ppo.get("async_rollouts", False) and step + 1 < steps:
             # the bucketed reduce-scatter launched by the backward hooks is in flight on RCCL's
@@ -307,13 +335,21 @@ def _grpo_loop(ctx, config, ppo, policy, ref, rm, rollout, engine, steps, group,
     overlap = bool(ppo.get("async_rollouts", False))
     entropy_coef, log_entropy = float(ppo.get("entropy_coef", 0.0) or 0.0), bool(ppo.get("log_entropy", False))
     need_old = epochs * nmb > 1  # a single update per rollout batch is on-policy: rho = 1
+    lp_mode = rollout_logprobs_mode(ppo, "grpo")
     rows = ("act", "advantages", "ref_logp", "old_logp")
     running = RunningLoss()
     pending = rollout()
     for step in range(steps):
-        seqs, mask, scores, tp = pending
+        seqs, mask, scores, tp, rlp = pending
+        # monitor: the trainer's own old-policy log-probs are computed even on-policy, to compare;
+        # old: the rollout engine's ARE the old-policy log-probs (rho reflects fp8 / stale /
+        # rounding mismatch, which the clip handles) and the policy forward is skipped
         stats = grpo_rollout_stats(policy.model, ref.model, seqs, mask, tp, scores, group, beta, scale_std,
-                                   need_old)
+                                   need_old or lp_mode == "monitor",
+                                   old_logp=rlp if lp_mode == "old" else None)
+        mism = rollout_mismatch(rlp, stats["old_logp"], stats["act"]) if lp_mode == "monitor" else {}
+        if lp_mode == "monitor" and not need_old:
+            stats["old_logp"] = None  # the update itself stays the on-policy one
         S = seqs.shape[0]
         bounds = [(i * S // nmb, (i + 1) * S // nmb) for i in range(nmb)]
         for ep in range(epochs):
@@ -337,6 +373,7 @@ def _grpo_loop(ctx, config, ppo, policy, ref, rm, rollout, engine, steps, group,
                             "train/frac_zero_std": stats["frac_zero_std"],
                             "train/clipfrac": m["clipfrac"], "train/approx_kl": m["approx_kl"],
                             **({"train/entropy": m["entropy"]} if "entropy" in m else {}),
+                            **{f"train/{k}": v for k, v in mism.items()},
                             "train/grad_norm": engine.last_grad_norm,
                             "train/comm_exposed_ms": engine.comm_timer.last_step_ms()}, step + 1)
             running = RunningLoss()
@@ -369,12 +406,14 @@ def _ppo_loop(ctx, config, ppo, policy, ref, rm, rollout, engine, steps, kl_coef
     epochs, nmb = int(ppo.get("ppo_epochs", 1)), max(1, int(ppo.get("num_minibatches", 1)))
     overlap = bool(ppo.get("async_rollouts", False))
     entropy_coef, log_entropy = float(ppo.get("entropy_coef", 0.0) or 0.0), bool(ppo.get("log_entropy", False))
+    lp_mode = rollout_logprobs_mode(ppo, "ppo")
     running = RunningLoss()
     pending = rollout()
     for step in range(steps):
-        seqs, mask, scores, tp = pending
+        seqs, mask, scores, tp, rlp = pending
         stats = ppo_rollout_stats(policy.model, ref.model, critic, seqs, mask, tp, scores, kl_coef,
-                                  gamma, lam)
+                                  gamma, lam, old_logp=rlp if lp_mode == "old" else None)
+        mism = rollout_mismatch(rlp, stats["old_logp"], stats["act"]) if lp_mode == "monitor" else {}
         S = seqs.shape[0]
         bounds = [(i * S // nmb, (i + 1) * S // nmb) for i in range(nmb)]
         for ep in range(epochs):
@@ -402,6 +441,7 @@ def _ppo_loop(ctx, config, ppo, policy, ref, rm, rollout, engine, steps, kl_coef
                             "train/policy_loss": m["policy_loss"], "train/value_loss": m["value_loss"],
                             "train/clipfrac": m["clipfrac"], "train/approx_kl": m["approx_kl"],
                             **({"train/entropy": m["entropy"]} if "entropy" in m else {}),
+                            **{f"train/{k}": v for k, v in mism.items()},
                             "train/grad_norm": engine.last_grad_norm,
                             "train/comm_exposed_ms": engine.comm_timer.last_step_ms()}, step + 1)
             running = RunningLoss()

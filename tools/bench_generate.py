@@ -29,10 +29,12 @@ def main() -> int:
                     help="samples per prompt (generate(num_return_sequences=G)); --batch counts prompts")
     ap.add_argument("--group-attention", type=int, choices=(0, 1), default=0,
                     help="decode attention reads a group's prompt K/V once (generate(group_attention=...))")
+    ap.add_argument("--logprobs", type=int, choices=(0, 1), default=0,
+                    help="also return the sampler's token log-probs (generate(return_logprobs=...))")
     a = ap.parse_args()
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from distributed_llm_alignment_amd.models import build_model, generate, get_config
-    from distributed_llm_alignment_amd.ops import _ext
+    from distributed_llm_alignment_amd.ops import _ext, decode
     from distributed_llm_alignment_amd.utils.tuning import enable_gemm_tuning
 
     dev = torch.device("cuda", 0)
@@ -43,10 +45,25 @@ def main() -> int:
     g = torch.Generator(device=dev).manual_seed(0)
     ids = torch.randint(3, cfg.vocab_size, (a.batch, a.prompt), device=dev, generator=g)
     am = torch.ones_like(ids)
+    # the sampler op alone at the decode step's shape, for its share of a token
+    lg = torch.randn((a.batch * a.group, cfg.vocab_size), device=dev, generator=g).mul_(3).to(torch.bfloat16)
+    rng = torch.tensor([1, 0], dtype=torch.long, device=dev)
+    op = decode.sample_tokens_logp if a.logprobs else decode.sample_tokens
+    for _ in range(5):
+        op(lg, 0.7, 0, 0.9, False, rng)
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    ev[0].record()
+    for _ in range(50):
+        op(lg, 0.7, 0, 0.9, False, rng)
+    ev[1].record()
+    torch.cuda.synchronize()
+    sampler_ms = ev[0].elapsed_time(ev[1]) / 50
     for mode in a.modes.split(","):
         kw = dict(max_new_tokens=a.new, do_sample=True, temperature=0.7, top_p=0.9, eos_token_id=-1,
                   use_graph=(mode == "graph"), seed=1, weight_dtype=a.weight_dtype,
                   num_return_sequences=a.group, group_attention=bool(a.group_attention))
+        if a.logprobs:  # (left out otherwise: the call an older build of the package takes)
+            kw["return_logprobs"] = True
         generate(m, ids[:, :64], am[:, :64], **{**kw, "max_new_tokens": 8})  # warm
         generate(m, ids, am, **kw)  # warm at the timed shapes (graph mode: the capture is reused)
         torch.cuda.synchronize()
@@ -54,6 +71,7 @@ def main() -> int:
         out = generate(m, ids, am, **kw)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
+        out = out[0] if a.logprobs else out
         n = out.shape[1] - a.prompt
         # prefill alone, for the per-token decode latency
         t1 = time.perf_counter()
@@ -62,7 +80,8 @@ def main() -> int:
         tp = time.perf_counter() - t1
         print(json.dumps({"mode": mode, "model": cfg.name, "batch": a.batch, "prompt": a.prompt,
                           "weight_dtype": a.weight_dtype, "group": a.group,
-                          "group_attention": bool(a.group_attention),
+                          "group_attention": bool(a.group_attention), "logprobs": bool(a.logprobs),
+                          "sampler_ms": round(sampler_ms, 4),
                           "new_tokens": n, "total_s": round(dt, 3), "prefill_s": round(tp, 3),
                           "decode_ms_per_token": round((dt - tp) / max(n - 1, 1) * 1e3, 3),
                           "decode_tokens_per_s": round(a.batch * a.group * (n - 1) / max(dt - tp, 1e-9), 1)}),

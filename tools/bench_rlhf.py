@@ -73,6 +73,9 @@ def main() -> int:
                     help="ppo / grpo: compute and report the policy entropy without a bonus (ppo.log_entropy)")
     ap.add_argument("--rollout-dtype", choices=("bf16", "fp8"), default="bf16",
                     help="decode weight streams of the rollout generation (ppo.rollout_weight_dtype)")
+    ap.add_argument("--rollout-logprobs", choices=("off", "monitor", "old"), default="off",
+                    help="ppo / grpo: ppo.rollout_logprobs (the sampler's token log-probs: monitor = log "
+                         "rollout_kl / rollout_logp_absdiff_max against the trainer's, old = use them as old_logp)")
     ap.add_argument("--frozen-fp8", action="store_true",
                     help="reference + reward model layer GEMMs on fp8 (ppo.frozen_fp8, ops.enable_fp8_inference)")
     ap.add_argument("--force-pg", action="store_true",
@@ -97,6 +100,8 @@ def main() -> int:
         if a.overlap:
             ap.error("--overlap is not implemented for grpo")
         return grpo_main(a)
+    if a.rollout_logprobs != "off":
+        ap.error("--rollout-logprobs needs token-level log-probs: --algorithm ppo or grpo")
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from distributed_llm_alignment_amd.models import build_model, generate, get_config
     from distributed_llm_alignment_amd.models.reward import RewardModel
@@ -267,7 +272,9 @@ def ppo_main(a) -> int:
     from distributed_llm_alignment_amd.models import build_model, generate, get_config
     from distributed_llm_alignment_amd.models.reward import RewardModel, ValueModel
     from distributed_llm_alignment_amd.models.tokenizer import ByteTokenizer
-    from distributed_llm_alignment_amd.objectives import ppo_backward, ppo_loss, ppo_rollout_stats
+    from distributed_llm_alignment_amd.objectives import (ppo_backward, ppo_loss, ppo_rollout_stats,
+                                                          rollout_logp_grid, rollout_mismatch)
+    from distributed_llm_alignment_amd.training.train_rlhf import rollout_logprobs_mode
     from distributed_llm_alignment_amd.ops import _ext
     from distributed_llm_alignment_amd.parallel.data_parallel import DataParallelEngine
     from distributed_llm_alignment_amd.training.handoff import RewardHandoff
@@ -324,15 +331,17 @@ def ppo_main(a) -> int:
         torch.cuda.reset_peak_memory_stats(dev)
 
     exposed = []  # the update's gradient-collective wait nothing overlapped, ms per step
+    lp_mode, mism = rollout_logprobs_mode({"rollout_logprobs": a.rollout_logprobs}, "ppo"), {}
 
     def step(record):
         ids = torch.randint(3, cfg.vocab_size, (a.batch, a.prompt), device=dev, generator=g)
         am = torch.ones_like(ids)
         torch.cuda.reset_peak_memory_stats(dev)
         t0 = sync()
-        seqs, mask = generate(pol, ids, am, max_new_tokens=a.new, do_sample=True, temperature=0.7,
-                              top_p=0.9, eos_token_id=-1, return_mask=True, seed=3,
-                              weight_dtype=a.rollout_dtype)
+        seqs, mask, *rlp = generate(pol, ids, am, max_new_tokens=a.new, do_sample=True, temperature=0.7,
+                                    top_p=0.9, eos_token_id=-1, return_mask=True, seed=3,
+                                    weight_dtype=a.rollout_dtype, return_logprobs=lp_mode != "off")
+        rlp = rollout_logp_grid(rlp[0], a.prompt, seqs.shape[1]) if rlp else None
         t1 = sync()
         phase_peak("generate")
         with torch.no_grad():
@@ -340,7 +349,10 @@ def ppo_main(a) -> int:
             scores = rm(r_ids, r_mask)
         t2 = sync()
         phase_peak("score")
-        stats = ppo_rollout_stats(pol, ref, critic, seqs, mask, a.prompt, scores, 0.05, 1.0, 0.95)
+        stats = ppo_rollout_stats(pol, ref, critic, seqs, mask, a.prompt, scores, 0.05, 1.0, 0.95,
+                                  old_logp=rlp if lp_mode == "old" else None)
+        if lp_mode == "monitor":
+            mism.update(rollout_mismatch(rlp, stats["old_logp"], stats["act"]))
         t3 = sync()
         phase_peak("stats")
         S = seqs.shape[0]
@@ -377,7 +389,9 @@ def ppo_main(a) -> int:
               "clipfrac": round(float(m["clipfrac"]), 4)}
     if "entropy" in m:
         health["entropy"] = round(float(m["entropy"]), 5)
+    health.update({k: float(v) for k, v in mism.items()})  # the last step's
     print(json.dumps({"bench": "ppo_step", "model": cfg.name, "rollouts_per_step": a.batch,
+                      "rollout_logprobs": lp_mode,
                       "entropy_coef": a.entropy_coef, "log_entropy": a.log_entropy,
                       "rollout_dtype": a.rollout_dtype, "frozen_fp8": a.frozen_fp8,
                       "zero_shape": a.zero_shape, "ppo_epochs": a.ppo_epochs, "minibatches": a.minibatches,
@@ -395,11 +409,11 @@ def grpo_main(a) -> int:
     from distributed_llm_alignment_amd.models import build_model, generate, get_config
     from distributed_llm_alignment_amd.models.reward import RewardModel
     from distributed_llm_alignment_amd.models.tokenizer import ByteTokenizer
-    from distributed_llm_alignment_amd.objectives import grpo_rollout_stats
+    from distributed_llm_alignment_amd.objectives import grpo_rollout_stats, rollout_logp_grid, rollout_mismatch
     from distributed_llm_alignment_amd.ops import _ext
     from distributed_llm_alignment_amd.parallel.data_parallel import DataParallelEngine
     from distributed_llm_alignment_amd.training.handoff import RewardHandoff
-    from distributed_llm_alignment_amd.training.train_rlhf import grpo_update
+    from distributed_llm_alignment_amd.training.train_rlhf import grpo_update, rollout_logprobs_mode
     from distributed_llm_alignment_amd.utils.tuning import enable_gemm_tuning
 
     dev = torch.device("cuda", 0)
@@ -438,6 +452,7 @@ def grpo_main(a) -> int:
     prompts = ["synthetic prompt"] * a.batch
     phases = {"generate": 0.0, "score": 0.0, "stats": 0.0, "update": 0.0}
     peaks = {}
+    lp_mode, mism = rollout_logprobs_mode({"rollout_logprobs": a.rollout_logprobs}, "grpo"), {}
 
     def sync():
         torch.cuda.synchronize()
@@ -453,11 +468,12 @@ def grpo_main(a) -> int:
         am = torch.ones_like(ids)
         torch.cuda.reset_peak_memory_stats(dev)
         t0 = sync()
-        seqs, mask = generate(pol, ids, am, max_new_tokens=a.new, do_sample=True, temperature=0.7,
-                              top_p=0.9, eos_token_id=-1, return_mask=True, seed=3,
-                              weight_dtype=a.rollout_dtype, num_return_sequences=G,
-                              share_prefill=bool(a.share_prefill),
-                              group_attention=bool(a.group_attention))
+        seqs, mask, *rlp = generate(pol, ids, am, max_new_tokens=a.new, do_sample=True, temperature=0.7,
+                                    top_p=0.9, eos_token_id=-1, return_mask=True, seed=3,
+                                    weight_dtype=a.rollout_dtype, num_return_sequences=G,
+                                    share_prefill=bool(a.share_prefill),
+                                    group_attention=bool(a.group_attention), return_logprobs=lp_mode != "off")
+        rlp = rollout_logp_grid(rlp[0], a.prompt, seqs.shape[1]) if rlp else None
         t1 = sync()
         phase_peak("generate")
         with torch.no_grad():
@@ -465,7 +481,12 @@ def grpo_main(a) -> int:
             scores = rm(r_ids, r_mask)
         t2 = sync()
         phase_peak("score")
-        stats = grpo_rollout_stats(pol, ref, seqs, mask, a.prompt, scores, G, a.kl_coef, True, False)
+        # one update per rollout batch, as train_rlhf's loop at ppo_epochs = num_minibatches = 1
+        stats = grpo_rollout_stats(pol, ref, seqs, mask, a.prompt, scores, G, a.kl_coef, True,
+                                   lp_mode == "monitor", old_logp=rlp if lp_mode == "old" else None)
+        if lp_mode == "monitor":
+            mism.update(rollout_mismatch(rlp, stats["old_logp"], stats["act"]))
+            stats["old_logp"] = None  # the update stays the on-policy one
         t3 = sync()
         phase_peak("stats")
         pol.train()
@@ -492,7 +513,9 @@ def grpo_main(a) -> int:
               "frac_zero_std": round(float(stats["frac_zero_std"]), 4)}
     if "entropy" in m:
         health["entropy"] = round(float(m["entropy"]), 5)
+    health.update({k: float(v) for k, v in mism.items()})  # the last step's
     print(json.dumps({"bench": "grpo_step", "model": cfg.name, "rollouts_per_step": a.batch, "group": G,
+                      "rollout_logprobs": lp_mode,
                       "share_prefill": bool(a.share_prefill), "group_attention": bool(a.group_attention),
                       "loss_type": a.loss_type, "kl_coef": a.kl_coef,
                       "entropy_coef": a.entropy_coef, "log_entropy": a.log_entropy,
