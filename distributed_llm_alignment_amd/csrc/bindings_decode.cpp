@@ -1,6 +1,7 @@
-// torch.ops.dla decode-path ops: split-KV decode attention (decode.hip) and the fused sampler
-// (sampling.hip). Host-side validation only; both are graph-capture safe (device-side lengths
-// and RNG counter, outputs from the caching allocator, no host sync).
+// torch.ops.dla decode-path ops: split-KV decode attention (decode.hip), the decode projection
+// GEMMs with their weight re-layout passes (skinny.hip, skinny64.hip) and the fused sampler
+// (sampling.hip). Host-side validation only; all are graph-capture safe (device-side lengths
+// and RNG counter, outputs and workspaces from the caching allocator, no host sync).
 #include <ATen/ATen.h>
 #include <torch/library.h>
 
@@ -12,6 +13,7 @@
 
 #include "bind_util.h"
 #include "decode_params.h"
+#include "skinny_geom.h"
 #include "skinny_params.h"
 
 namespace dla {
@@ -31,112 +33,152 @@ void launch_sample_split_logp(const void*, bool, int64_t, int64_t, int, int, flo
 void launch_kv_replicate(const bf16_t*, const bf16_t*, bf16_t*, bf16_t*, int, int, int, int, int,
                          int, const int64_t*, const int64_t*, hipStream_t);
 
-int skinny_splits(int M, int N, int K);
-bool skinny_use_ksplit(int N, int K);
-void launch_skinny_ksplit(const bf16_t*, int64_t, const bf16_t*, int64_t, bf16_t*, int64_t, int,
-                          int, int, hipStream_t);
-void launch_skinny_gemm(const bf16_t*, int64_t, const bf16_t*, int64_t, bf16_t*, int64_t, float*,
-                        unsigned*, int, int, int, int, bool, bool, hipStream_t);
-bool skinny_glu_ks_ok(int N, int K);
-void launch_skinny_glu_ks(const bf16_t*, int64_t, const bf16_t*, int64_t, bf16_t*, int64_t, int,
-                          int, int, hipStream_t);
+// ---- decode projection ops (skinny.hip at M <= 16, skinny64.hip at 17..64 rows): argument
+// checks shared by the ops, one fill-and-launch routine per bf16 / fp8 pair
 
-void launch_skinny_ks_fused(const bf16_t*, int64_t, const bf16_t*, int64_t, bf16_t*, int64_t, int,
-                            int, int, const KsFuse&, bool, bool, bool, hipStream_t);
-void launch_skinny_glu_normin(const bf16_t*, int64_t, const bf16_t*, int64_t, bf16_t*, int64_t, int,
-                              int, int, const KsFuse&, bool, hipStream_t);
+// x [M, K] bf16 with 1 <= M <= max_rows
+static void fill_x(SkinnyParams& p, const at::Tensor& x, int64_t max_rows, int64_t width) {
+  check_bf16(x, "x");
+  TORCH_CHECK(x.dim() == 2 && x.stride(1) == 1 && x.stride(0) % 8 == 0,
+              "x [M, K]: unit inner stride, 16-byte aligned rows");
+  TORCH_CHECK(x.size(0) >= 1 && x.size(0) <= max_rows && x.size(1) == width, "x [M, K]: 1 <= M <= ", max_rows,
+              ", width K (2K with swiglu)");
+  check_aligned16(x, "x");
+  p.x = cbp(x);
+  p.ldx = x.stride(0);
+  p.M = static_cast<int>(x.size(0));
+}
 
-int m64_splits(int N, int K);
-void launch_tile_weight(const bf16_t*, int64_t, const bf16_t*, bf16_t*, int, int, bool, hipStream_t);
-void launch_quant_tile_f8(const bf16_t*, int64_t, const bf16_t*, uint8_t*, float*, int, int, bool, hipStream_t);
-void launch_skinny_glu_il(const bf16_t*, int64_t, const bf16_t*, bf16_t*, int64_t, int, int, int,
-                          const KsFuse&, hipStream_t);
-void launch_skinny_ks_fused_f8(const bf16_t*, int64_t, const uint8_t*, bf16_t*, int64_t, int, int, int,
-                               const KsFuse&, bool, bool, hipStream_t);
-void launch_skinny_glu_il_f8(const bf16_t*, int64_t, const uint8_t*, bf16_t*, int64_t, int, int, int,
-                             const KsFuse&, hipStream_t);
-bool m64_shape_ok(int N, int K, bool glu);
-void launch_m64_gemm(const bf16_t*, int64_t, const bf16_t*, int64_t, bf16_t*, int64_t, float*, int,
-                     int, int, int, bool, const float*, int, float, bool, hipStream_t);
-void launch_m64_reduce(const float*, int, int, int, bf16_t*, int64_t, const bf16_t*, int64_t,
-                       const float*, int, int, float, float*, hipStream_t);
-void launch_m64_gemm_f8(const bf16_t*, int64_t, const uint8_t*, bf16_t*, int64_t, float*, int, int, int, int,
-                        bool, const float*, int, float, const float*, hipStream_t);
+// bf16 weight: [N, K] row-major (unit inner stride, 16-byte aligned rows) and / or the tiled
+// layout [N/16, K/32, 4, 16, 8] (skinny64.hip TW), as the op takes
+static void fill_w(SkinnyParams& p, const at::Tensor& x, const at::Tensor& w, bool row_major, bool tiled) {
+  check_bf16(w, "w");
+  const bool tw = w.dim() == 5;
+  TORCH_CHECK(tw ? (tiled && w.size(2) == 4 && w.size(3) == 16 && w.size(4) == 8 && w.is_contiguous())
+                 : (row_major && w.dim() == 2 && w.stride(1) == 1 && w.stride(0) % 8 == 0),
+              "w [N, K] (unit inner stride, 16-byte aligned rows) or tiled [N/16, K/32, 4, 16, 8] contiguous");
+  const int64_t N = tw ? w.size(0) * 16 : w.size(0), K = tw ? w.size(1) * 32 : w.size(1);
+  TORCH_CHECK(N < (1ll << 30) && K < (1ll << 30), "shape too large");
+  check_aligned16(w, "w");
+  same_device(x, w);
+  p.w = w.data_ptr();
+  p.layout = tw ? SkinnyW::kTiled : SkinnyW::kRowMajor;
+  p.ldw = tw ? K : w.stride(0);
+  p.N = static_cast<int>(N);
+  p.K = static_cast<int>(K);
+}
 
-// Decode projection at 17..64 rows (skinny64.hip), the same fused-layer contract as
-// skinny_fused below with row-norm partials per (row, 1024 columns):
+// fp8 weight-only decode projections (ops/decode.py fp8_tiled_weight): w8 = e4m3 tiled copy
+// [N/16, K/64, 64, 16] (uint8 storage), wscale [N] fp32 per weight row
+static void check_w8(const at::Tensor& w8, const at::Tensor& wscale, const at::Tensor& x, int64_t* N,
+                     int64_t* K) {
+  check_cuda(w8, "w8");
+  TORCH_CHECK(w8.scalar_type() == at::kByte && w8.dim() == 4 && w8.size(2) == 64 && w8.size(3) == 16 &&
+                  w8.is_contiguous(),
+              "w8 uint8 [N/16, K/64, 64, 16] contiguous");
+  *N = w8.size(0) * 16;
+  *K = w8.size(1) * 64;
+  check_cuda(wscale, "wscale");
+  TORCH_CHECK(wscale.scalar_type() == at::kFloat && wscale.dim() == 1 && wscale.size(0) == *N &&
+                  wscale.is_contiguous(),
+              "wscale fp32 [N] contiguous");
+  check_aligned16(w8, "w8");
+  same_device(x, w8);
+  same_device(x, wscale);
+}
+
+static void fill_w8(SkinnyParams& p, const at::Tensor& x, const at::Tensor& w8, const at::Tensor& wscale) {
+  int64_t N = 0, K = 0;
+  check_w8(w8, wscale, x, &N, &K);
+  TORCH_CHECK(N < (1ll << 30) && K < (1ll << 30), "shape too large");
+  p.w = w8.data_ptr();
+  p.layout = SkinnyW::kTiledF8;
+  p.ldw = K;
+  p.wscale = wscale.data_ptr<float>();
+  p.N = static_cast<int>(N);
+  p.K = static_cast<int>(K);
+}
+
+// the producer's row-norm partials: fp32 [rows, nbp <= max_nbp], rows = 16 (skinny.hip) or M
+static void fill_ssq_in(SkinnyParams& p, const at::Tensor& x, const at::Tensor& sq, int64_t rows, int64_t max_nbp,
+                        double eps) {
+  check_cuda(sq, "ssq_in");
+  TORCH_CHECK(sq.scalar_type() == at::kFloat && sq.dim() == 2 && sq.size(0) == rows && sq.is_contiguous() &&
+                  sq.size(1) >= 1 && sq.size(1) <= max_nbp,
+              "ssq_in fp32 [", rows, ", nbp <= ", max_nbp, "] contiguous");
+  same_device(x, sq);
+  p.ssq_in = sq.data_ptr<float>();
+  p.nbp = static_cast<int>(sq.size(1));
+  p.eps = static_cast<float>(eps);
+}
+
+// res [M, N]; returns the row partials of the new residual stream, fp32 [rows, cols]
+static at::Tensor fill_res(SkinnyParams& p, const at::Tensor& x, const at::Tensor& r, int64_t rows, int64_t cols) {
+  check_bf16(r, "res");
+  TORCH_CHECK(r.dim() == 2 && r.size(0) == p.M && r.size(1) == p.N && r.stride(1) == 1, "res [M, N]");
+  same_device(x, r);
+  p.res = cbp(r);
+  p.ldr = r.stride(0);
+  auto ssq = at::empty({rows, cols}, x.options().dtype(at::kFloat));
+  p.ssq_out = ssq.data_ptr<float>();
+  return ssq;
+}
+
+static at::Tensor alloc_y(SkinnyParams& p, const at::Tensor& x) {
+  auto y = at::empty({p.M, p.glu_out ? p.N / 2 : p.N}, x.options());
+  p.y = bp(y);
+  p.ldy = y.stride(0);
+  return y;
+}
+
+// skinny64 / skinny64_f8 (`p` arrives with the weight set): decode projection at 17..64 rows
+// (skinny64.hip), the same fused-layer contract as skinny_fused below with row-norm partials per
+// (row, 1024 columns):
 //   * plain: y = x w^T;
 //   * res given: (s = bf16(bf16(x w^T) + res), ssq [M, ceil(N / 1024)]);
-//   * ssq_in given ([M, nbp], nbp <= 8): y = rstd[m] * (x w^T), w with the norm weight folded in;
+//   * ssq_in given ([M, nbp], nbp <= 64): y = rstd[m] * (x w^T), w with the norm weight folded in;
 //     with `glu` the gate|up projection + SwiGLU epilogue (w = [gate; up], output [M, F]).
+static std::tuple<at::Tensor, at::Tensor> m64_step(SkinnyParams& p, const at::Tensor& x,
+                                                   const c10::optional<at::Tensor>& res,
+                                                   const c10::optional<at::Tensor>& ssq_in, double eps, bool glu) {
+  fill_x(p, x, 64, p.K);
+  TORCH_CHECK(m64_shape_ok(p.N, p.K), "skinny64: K % 256 == 0 and N % 128 == 0");
+  if (ssq_in.has_value()) fill_ssq_in(p, x, *ssq_in, p.M, 64, eps);
+  TORCH_CHECK(!(res.has_value() && (ssq_in.has_value() || glu)), "skinny64: residual output takes a plain input");
+  c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
+  p.glu_out = glu;
+  const int S = m64_num_splits(p);
+  TORCH_CHECK(glu || S > 1 || !(ssq_in.has_value() || res.has_value()),
+              "skinny64: the residual / normalised-input epilogue needs a split-K shape");
+  auto y = alloc_y(p, x);
+  at::Tensor ws, ssq;
+  if (S > 1) {
+    ws = at::empty({S, p.M, p.N}, x.options().dtype(at::kFloat));
+    p.ws = ws.data_ptr<float>();
+  }
+  // row partials per 1024 columns (written by the reduce launch)
+  if (res.has_value()) ssq = fill_res(p, x, *res, p.M, (p.N + 1023) / 1024);
+  launch_m64(p, cur_stream(x));
+  return {y, ssq};
+}
+
 std::tuple<at::Tensor, at::Tensor> skinny64(const at::Tensor& x, const at::Tensor& w,
                                             const c10::optional<at::Tensor>& res,
                                             const c10::optional<at::Tensor>& ssq_in, double eps,
                                             bool glu) {
-  check_bf16(x, "x");
-  check_bf16(w, "w");
-  // w: [N, K] row-major, or the tiled layout [N / 16, K / 32, 4, 16, 8] (skinny64.hip TW)
-  const bool tiled = w.dim() == 5;
-  TORCH_CHECK(x.dim() == 2 && x.stride(1) == 1 && x.stride(0) % 8 == 0 &&
-                  (tiled ? (w.size(2) == 4 && w.size(3) == 16 && w.size(4) == 8 && w.is_contiguous())
-                         : (w.dim() == 2 && w.stride(1) == 1 && w.stride(0) % 8 == 0)),
-              "x [M, K] / w [N, K] (unit inner stride, 16-byte aligned rows) or tiled [N/16, K/32, 4, 16, 8]");
-  const int64_t M = x.size(0), N = tiled ? w.size(0) * 16 : w.size(0), K = tiled ? w.size(1) * 32 : w.size(1);
-  TORCH_CHECK(M >= 1 && M <= 64 && x.size(1) == K, "skinny64: 1 <= M <= 64, x [M, K]");
-  TORCH_CHECK(N < (1ll << 30) && K < (1ll << 30), "shape too large");
-  TORCH_CHECK(m64_shape_ok((int)N, (int)K, glu),
-              "skinny64: K % 256 == 0 and N % 128 == 0");
-  check_aligned16(x, "x");
-  check_aligned16(w, "w");
-  same_device(x, w);
-  const float* sq = nullptr;
-  int nbp = 0;
-  if (ssq_in.has_value()) {
-    const at::Tensor& t = *ssq_in;
-    check_cuda(t, "ssq_in");
-    TORCH_CHECK(t.scalar_type() == at::kFloat && t.dim() == 2 && t.size(0) == M && t.is_contiguous() &&
-                    t.size(1) >= 1 && t.size(1) <= 64,
-                "ssq_in fp32 [M, nbp <= 64] contiguous");
-    same_device(x, t);
-    sq = t.data_ptr<float>();
-    nbp = static_cast<int>(t.size(1));
-  }
-  TORCH_CHECK(!(res.has_value() && (sq || glu)), "skinny64: residual output takes a plain input");
-  c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
-  auto st = cur_stream(x);
-  if (glu) {
-    auto m = at::empty({M, N / 2}, x.options());
-    launch_m64_gemm(cbp(x), x.stride(0), cbp(w), tiled ? K : w.stride(0), bp(m), m.stride(0), nullptr,
-                    (int)M, (int)N, (int)K, 1, true, sq, nbp, static_cast<float>(eps), tiled, st);
-    return {m, at::Tensor()};
-  }
-  const int S = m64_splits((int)N, (int)K);
-  TORCH_CHECK(S > 1 || !(sq || res.has_value()),
-              "skinny64: the residual / normalised-input epilogue needs a split-K shape");
-  auto y = at::empty({M, N}, x.options());
-  at::Tensor ws;
-  if (S > 1) ws = at::empty({S, M, N}, x.options().dtype(at::kFloat));
-  const bf16_t* rp = nullptr;
-  int64_t ldr = 0;
-  at::Tensor ssq;
-  if (res.has_value()) {
-    const at::Tensor& r = *res;
-    check_bf16(r, "res");
-    TORCH_CHECK(r.dim() == 2 && r.size(0) == M && r.size(1) == N && r.stride(1) == 1, "res [M, N]");
-    same_device(x, r);
-    rp = cbp(r);
-    ldr = r.stride(0);
-    // row partials per 1024 columns (written by the reduce launch)
-    ssq = at::empty({M, (N + 1023) / 1024}, x.options().dtype(at::kFloat));
-  }
-  float* sqo = ssq.defined() ? ssq.data_ptr<float>() : nullptr;
-  launch_m64_gemm(cbp(x), x.stride(0), cbp(w), tiled ? K : w.stride(0), bp(y), y.stride(0),
-                  S > 1 ? ws.data_ptr<float>() : nullptr, (int)M, (int)N, (int)K, S, false, sq, nbp,
-                  static_cast<float>(eps), tiled, st);
-  if (S > 1)
-    launch_m64_reduce(ws.data_ptr<float>(), S, (int)M, (int)N, bp(y), y.stride(0), rp, ldr, sq, nbp,
-                      (int)K, static_cast<float>(eps), sqo, st);
-  return {y, ssq};
+  SkinnyParams p{};
+  fill_w(p, x, w, true, true);
+  return m64_step(p, x, res, ssq_in, eps, glu);
+}
+
+// fp8 form of skinny64: w8 the e4m3 tiled copy with per-row scales `wscale` (gate|up: the plain
+// [gate; up] row order, norm weight folded in)
+std::tuple<at::Tensor, at::Tensor> skinny64_f8(const at::Tensor& x, const at::Tensor& w8, const at::Tensor& wscale,
+                                               const c10::optional<at::Tensor>& res,
+                                               const c10::optional<at::Tensor>& ssq_in, double eps, bool glu) {
+  SkinnyParams p{};
+  fill_w8(p, x, w8, wscale);
+  return m64_step(p, x, res, ssq_in, eps, glu);
 }
 
 // out <- w [N, K] in the tiled decode layout [N/16, K/32, 4, 16, 8] (nw given: bf16(w * nw), the
@@ -195,331 +237,137 @@ void quant_tile_f8(const at::Tensor& w, const c10::optional<at::Tensor>& nw, at:
                        glu_il, cur_stream(w));
 }
 
-// Decode gate|up + SwiGLU at M <= 16 over the interleaved tiled weight (tile_weight glu_il, norm
-// folded) from the producer's row-norm partials: [M, F] = silu(rstd * g) * (rstd * u)
-at::Tensor skinny_glu_il(const at::Tensor& x, const at::Tensor& wt, const at::Tensor& ssq_in, double eps) {
-  check_bf16(x, "x");
-  check_bf16(wt, "wt");
-  TORCH_CHECK(x.dim() == 2 && x.stride(1) == 1 && x.stride(0) % 8 == 0, "x [M, K]");
-  TORCH_CHECK(wt.dim() == 5 && wt.size(2) == 4 && wt.size(3) == 16 && wt.size(4) == 8 && wt.is_contiguous(),
-              "wt [2F/16, K/32, 4, 16, 8] contiguous");
-  const int64_t M = x.size(0), N = wt.size(0) * 16, K = wt.size(1) * 32;
-  TORCH_CHECK(M >= 1 && M <= 16 && x.size(1) == K, "skinny_glu_il: 1 <= M <= 16, x [M, K]");
-  TORCH_CHECK(K % 512 == 0 && N < (1ll << 30) && K < (1ll << 30) && M * (K + 8) * 2 <= 148 * 1024,
-              "K % 512 == 0, x fits LDS");
-  check_cuda(ssq_in, "ssq_in");
-  TORCH_CHECK(ssq_in.scalar_type() == at::kFloat && ssq_in.dim() == 2 && ssq_in.size(0) == 16 &&
-                  ssq_in.is_contiguous() && ssq_in.size(1) >= 1 && ssq_in.size(1) <= 512,
-              "ssq_in fp32 [16, nbp <= 512] contiguous");
-  check_aligned16(x, "x");
-  check_aligned16(wt, "wt");
-  same_device(x, wt);
-  same_device(x, ssq_in);
-  KsFuse fz{};
-  fz.ssq_in = ssq_in.data_ptr<float>();
-  fz.nbp = static_cast<int>(ssq_in.size(1));
-  fz.eps = static_cast<float>(eps);
+// skinny_glu_il / skinny_glu_il_f8 (`p` arrives with the weight set): decode gate|up + SwiGLU at
+// M <= 16 over the interleaved tiled weight (tile_weight / quant_tile_f8 glu_il, norm folded) from
+// the producer's row-norm partials: [M, F] = silu(rstd * g) * (rstd * u)
+static at::Tensor glu_il_step(SkinnyParams& p, const at::Tensor& x, const at::Tensor& ssq_in, double eps) {
+  fill_x(p, x, 16, p.K);
+  TORCH_CHECK(p.K % 512 == 0 && (p.layout != SkinnyW::kTiledF8 || p.N % 32 == 0) &&
+                  skinny_lds_bytes(p.M, p.K) <= kSkLdsNormX,
+              "skinny_glu_il: K % 512 == 0 (fp8: 2F % 32 == 0), x fits LDS");
+  fill_ssq_in(p, x, ssq_in, 16, 512, eps);
   c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
-  auto m = at::empty({M, N / 2}, x.options());
-  launch_skinny_glu_il(cbp(x), x.stride(0), cbp(wt), bp(m), m.stride(0), (int)M, (int)N, (int)K, fz,
-                       cur_stream(x));
+  p.glu_out = true;
+  auto m = alloc_y(p, x);
+  launch_skinny_glu_il(p, cur_stream(x));
   return m;
 }
 
-// fp8 weight-only decode projections (ops/decode.py fp8_tiled_weight): w8 = e4m3 tiled copy
-// [N/16, K/64, 64, 16] (uint8 storage), wscale [N] fp32 per weight row; otherwise skinny_fused /
-// skinny_glu_il (res: o / down producing the residual; ssq_in: qkv / gate|up on a normalised input).
-static void check_w8(const at::Tensor& w8, const at::Tensor& wscale, const at::Tensor& x, int64_t* N,
-                     int64_t* K) {
-  check_cuda(w8, "w8");
-  TORCH_CHECK(w8.scalar_type() == at::kByte && w8.dim() == 4 && w8.size(2) == 64 && w8.size(3) == 16 &&
-                  w8.is_contiguous(),
-              "w8 uint8 [N/16, K/64, 64, 16] contiguous");
-  *N = w8.size(0) * 16;
-  *K = w8.size(1) * 64;
-  check_cuda(wscale, "wscale");
-  TORCH_CHECK(wscale.scalar_type() == at::kFloat && wscale.dim() == 1 && wscale.size(0) == *N &&
-                  wscale.is_contiguous(),
-              "wscale fp32 [N] contiguous");
-  check_aligned16(w8, "w8");
-  same_device(x, w8);
-  same_device(x, wscale);
+at::Tensor skinny_glu_il(const at::Tensor& x, const at::Tensor& wt, const at::Tensor& ssq_in, double eps) {
+  SkinnyParams p{};
+  fill_w(p, x, wt, false, true);
+  return glu_il_step(p, x, ssq_in, eps);
 }
 
-static void check_ssq(const at::Tensor& sq, const at::Tensor& x, KsFuse* fz, double eps) {
-  check_cuda(sq, "ssq_in");
-  TORCH_CHECK(sq.scalar_type() == at::kFloat && sq.dim() == 2 && sq.size(0) == 16 && sq.is_contiguous() &&
-                  sq.size(1) >= 1 && sq.size(1) <= 512,
-              "ssq_in fp32 [16, nbp <= 512] contiguous");
-  same_device(x, sq);
-  fz->ssq_in = sq.data_ptr<float>();
-  fz->nbp = static_cast<int>(sq.size(1));
-  fz->eps = static_cast<float>(eps);
+at::Tensor skinny_glu_il_f8(const at::Tensor& x, const at::Tensor& w8, const at::Tensor& wscale,
+                            const at::Tensor& ssq_in, double eps) {
+  SkinnyParams p{};
+  fill_w8(p, x, w8, wscale);
+  return glu_il_step(p, x, ssq_in, eps);
+}
+
+// skinny_fused / skinny_fused_f8 (`p` arrives with the weight set): fused decode-layer projection
+// (M <= 16, skinny.hip KsFuse):
+//   * res given: returns (s = bf16(bf16(x w^T) + res) [M, N], ssq [16, N/16] fp32 partial sums of
+//     s^2 per (row, 16-column workgroup)) -- the o / down projection producing the residual;
+//   * ssq_in given: x is a residual stream s and w a weight with the RMSNorm weight folded in
+//     (w o norm_w, ops/decode.py): returns rstd[m] * (s w^T), rstd = rsqrt(sum(ssq_in[m]) / K +
+//     eps) -- RMSNorm(s) @ W^T without a norm launch: the qkv projection, or with `glu` (bf16
+//     weights) the gate|up projection with the SwiGLU epilogue (w = [gate; up], output [M, F]).
+static std::tuple<at::Tensor, at::Tensor> fused_step(SkinnyParams& p, const at::Tensor& x,
+                                                     const c10::optional<at::Tensor>& res,
+                                                     const c10::optional<at::Tensor>& ssq_in, double eps, bool glu) {
+  fill_x(p, x, 16, p.K);
+  if (ssq_in.has_value()) fill_ssq_in(p, x, *ssq_in, 16, 512, eps);
+  c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
+  if (glu) {
+    TORCH_CHECK(ssq_in.has_value() && !res.has_value(), "glu: normalised input, no residual");
+    TORCH_CHECK(p.N % 128 == 0 && skinny_lds_bytes(p.M, p.K) <= kSkLdsNormX, "glu: 2F % 128 == 0, x fits LDS");
+    p.glu_out = true;
+    auto m = alloc_y(p, x);
+    launch_skinny_gemm(p, cur_stream(x));
+    return {m, at::Tensor()};
+  }
+  // (a plain fp8 projection -- the LM head -- may be any width: one workgroup per 16 columns)
+  const bool wide_ok = p.layout == SkinnyW::kTiledF8 && !res.has_value() && !ssq_in.has_value();
+  TORCH_CHECK(wide_ok ? (p.N % 16 == 0 && p.K % 1024 == 0) : skinny_use_ksplit(p.N, p.K),
+              "fused skinny: N % 16 == 0, K % 1024 == 0, N < 16384 (but a plain fp8 projection)");
+  auto y = alloc_y(p, x);
+  at::Tensor ssq;
+  if (res.has_value()) ssq = fill_res(p, x, *res, 16, p.N / 16);
+  launch_skinny_ksplit(p, true, cur_stream(x));
+  return {y, ssq};
+}
+
+std::tuple<at::Tensor, at::Tensor> skinny_fused(const at::Tensor& x, const at::Tensor& w,
+                                                const c10::optional<at::Tensor>& res,
+                                                const c10::optional<at::Tensor>& ssq_in, double eps,
+                                                bool glu) {
+  SkinnyParams p{};
+  fill_w(p, x, w, true, true);
+  return fused_step(p, x, res, ssq_in, eps, glu);
 }
 
 std::tuple<at::Tensor, at::Tensor> skinny_fused_f8(const at::Tensor& x, const at::Tensor& w8,
                                                    const at::Tensor& wscale,
                                                    const c10::optional<at::Tensor>& res,
                                                    const c10::optional<at::Tensor>& ssq_in, double eps) {
-  check_bf16(x, "x");
-  TORCH_CHECK(x.dim() == 2 && x.stride(1) == 1 && x.stride(0) % 8 == 0, "x [M, K], 16-byte aligned rows");
-  int64_t N = 0, K = 0;
-  check_w8(w8, wscale, x, &N, &K);
-  const int64_t M = x.size(0);
-  TORCH_CHECK(M >= 1 && M <= 16 && x.size(1) == K, "fp8 skinny: 1 <= M <= 16, x [M, K]");
-  // (a plain projection -- the LM head -- may be any width: one workgroup per 16 columns)
-  const bool plain = !res.has_value() && !ssq_in.has_value();
-  TORCH_CHECK(N < (1ll << 30) && K < (1ll << 30) &&
-                  (plain ? (N % 16 == 0 && K % 1024 == 0) : skinny_use_ksplit((int)N, (int)K)),
-              "fp8 skinny: N % 16 == 0, K % 1024 == 0 (fused forms: N < 16384)");
-  check_aligned16(x, "x");
-  KsFuse fz{};
-  fz.wscale = wscale.data_ptr<float>();
-  const bool nin = ssq_in.has_value();
-  if (nin) check_ssq(*ssq_in, x, &fz, eps);
-  c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
-  auto y = at::empty({M, N}, x.options());
-  at::Tensor ssq;
-  if (res.has_value()) {
-    const at::Tensor& r = *res;
-    check_bf16(r, "res");
-    TORCH_CHECK(r.dim() == 2 && r.size(0) == M && r.size(1) == N && r.stride(1) == 1, "res [M, N]");
-    same_device(x, r);
-    fz.res = cbp(r);
-    fz.ldr = r.stride(0);
-    ssq = at::empty({16, N / 16}, x.options().dtype(at::kFloat));
-    fz.ssq_out = ssq.data_ptr<float>();
-  }
-  launch_skinny_ks_fused_f8(cbp(x), x.stride(0), w8.data_ptr<uint8_t>(), bp(y), y.stride(0), (int)M, (int)N,
-                            (int)K, fz, res.has_value(), nin, cur_stream(x));
-  return {y, ssq};
-}
-
-// fp8 form of skinny64 (17..64 rows, csrc/skinny64.hip F8): w8 the e4m3 tiled copy
-// [N/16, K/64, 64, 16] with per-row scales `wscale` (ops/decode.py fp8_tiled_weight; gate|up: the
-// plain [gate; up] row order, norm weight folded in). Same epilogue contract as skinny64.
-std::tuple<at::Tensor, at::Tensor> skinny64_f8(const at::Tensor& x, const at::Tensor& w8, const at::Tensor& wscale,
-                                               const c10::optional<at::Tensor>& res,
-                                               const c10::optional<at::Tensor>& ssq_in, double eps, bool glu) {
-  check_bf16(x, "x");
-  int64_t N = 0, K = 0;
-  check_w8(w8, wscale, x, &N, &K);
-  TORCH_CHECK(x.dim() == 2 && x.stride(1) == 1 && x.stride(0) % 8 == 0, "x [M, K], unit inner stride");
-  const int64_t M = x.size(0);
-  TORCH_CHECK(M >= 1 && M <= 64 && x.size(1) == K, "fp8 skinny64: 1 <= M <= 64, x [M, K]");
-  TORCH_CHECK(N < (1ll << 30) && K < (1ll << 30) && m64_shape_ok((int)N, (int)K, glu),
-              "fp8 skinny64: K % 256 == 0 and N % 128 == 0");
-  check_aligned16(x, "x");
-  const float* sq = nullptr;
-  int nbp = 0;
-  if (ssq_in.has_value()) {
-    const at::Tensor& t = *ssq_in;
-    check_cuda(t, "ssq_in");
-    TORCH_CHECK(t.scalar_type() == at::kFloat && t.dim() == 2 && t.size(0) == M && t.is_contiguous() &&
-                    t.size(1) >= 1 && t.size(1) <= 64,
-                "ssq_in fp32 [M, nbp <= 64] contiguous");
-    same_device(x, t);
-    sq = t.data_ptr<float>();
-    nbp = static_cast<int>(t.size(1));
-  }
-  TORCH_CHECK(!(res.has_value() && (sq || glu)), "fp8 skinny64: residual output takes a plain input");
-  c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
-  auto st = cur_stream(x);
-  const uint8_t* wp = w8.data_ptr<uint8_t>();
-  const float* wsc = wscale.data_ptr<float>();
-  if (glu) {
-    auto m = at::empty({M, N / 2}, x.options());
-    launch_m64_gemm_f8(cbp(x), x.stride(0), wp, bp(m), m.stride(0), nullptr, (int)M, (int)N, (int)K, 1, true, sq,
-                       nbp, static_cast<float>(eps), wsc, st);
-    return {m, at::Tensor()};
-  }
-  const int S = m64_splits((int)N, (int)K);
-  TORCH_CHECK(S > 1 || !(sq || res.has_value()),
-              "fp8 skinny64: the residual / normalised-input epilogue needs a split-K shape");
-  auto y = at::empty({M, N}, x.options());
-  at::Tensor ws;
-  if (S > 1) ws = at::empty({S, M, N}, x.options().dtype(at::kFloat));
-  const bf16_t* rp = nullptr;
-  int64_t ldr = 0;
-  at::Tensor ssq;
-  if (res.has_value()) {
-    const at::Tensor& r = *res;
-    check_bf16(r, "res");
-    TORCH_CHECK(r.dim() == 2 && r.size(0) == M && r.size(1) == N && r.stride(1) == 1, "res [M, N]");
-    same_device(x, r);
-    rp = cbp(r);
-    ldr = r.stride(0);
-    ssq = at::empty({M, (N + 1023) / 1024}, x.options().dtype(at::kFloat));
-  }
-  float* sqo = ssq.defined() ? ssq.data_ptr<float>() : nullptr;
-  launch_m64_gemm_f8(cbp(x), x.stride(0), wp, bp(y), y.stride(0), S > 1 ? ws.data_ptr<float>() : nullptr, (int)M,
-                     (int)N, (int)K, S, false, sq, nbp, static_cast<float>(eps), wsc, st);
-  if (S > 1)
-    launch_m64_reduce(ws.data_ptr<float>(), S, (int)M, (int)N, bp(y), y.stride(0), rp, ldr, sq, nbp, (int)K,
-                      static_cast<float>(eps), sqo, st);
-  return {y, ssq};
-}
-
-at::Tensor skinny_glu_il_f8(const at::Tensor& x, const at::Tensor& w8, const at::Tensor& wscale,
-                            const at::Tensor& ssq_in, double eps) {
-  check_bf16(x, "x");
-  TORCH_CHECK(x.dim() == 2 && x.stride(1) == 1 && x.stride(0) % 8 == 0, "x [M, K]");
-  int64_t N = 0, K = 0;
-  check_w8(w8, wscale, x, &N, &K);
-  const int64_t M = x.size(0);
-  TORCH_CHECK(M >= 1 && M <= 16 && x.size(1) == K, "fp8 glu: 1 <= M <= 16, x [M, K]");
-  TORCH_CHECK(K % 512 == 0 && N % 32 == 0 && N < (1ll << 30) && K < (1ll << 30) &&
-                  M * (K + 8) * 2 <= 148 * 1024,
-              "fp8 glu: K % 512 == 0, 2F % 32 == 0, x fits LDS");
-  check_aligned16(x, "x");
-  KsFuse fz{};
-  fz.wscale = wscale.data_ptr<float>();
-  check_ssq(ssq_in, x, &fz, eps);
-  c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
-  auto m = at::empty({M, N / 2}, x.options());
-  launch_skinny_glu_il_f8(cbp(x), x.stride(0), w8.data_ptr<uint8_t>(), bp(m), m.stride(0), (int)M, (int)N,
-                          (int)K, fz, cur_stream(x));
-  return m;
-}
-
-// Fused decode-layer projection (M <= 16, skinny.hip KsFuse):
-//   * res given: returns (s = bf16(bf16(x w^T) + res) [M, N], ssq [16, N/16] fp32 partial sums of
-//     s^2 per (row, 16-column workgroup)) -- the o / down projection producing the residual;
-//   * ssq_in given: x is a residual stream s and w a weight with the RMSNorm weight folded in
-//     (w o norm_w, ops/decode.py): returns rstd[m] * (s w^T), rstd = rsqrt(sum(ssq_in[m]) / K +
-//     eps) -- RMSNorm(s) @ W^T without a norm launch: the qkv projection, or with `glu` the
-//     gate|up projection with the SwiGLU epilogue (w = [gate; up], output [M, F]).
-std::tuple<at::Tensor, at::Tensor> skinny_fused(const at::Tensor& x, const at::Tensor& w,
-                                                const c10::optional<at::Tensor>& res,
-                                                const c10::optional<at::Tensor>& ssq_in, double eps,
-                                                bool glu) {
-  check_bf16(x, "x");
-  check_bf16(w, "w");
-  // w: [N, K] row-major, or the tiled layout [N / 16, K / 32, 4, 16, 8] (skinny64.hip TW)
-  const bool tiled = w.dim() == 5;
-  TORCH_CHECK(x.dim() == 2 && x.stride(1) == 1 && x.stride(0) % 8 == 0 &&
-                  (tiled ? (w.size(2) == 4 && w.size(3) == 16 && w.size(4) == 8 && w.is_contiguous())
-                         : (w.dim() == 2 && w.stride(1) == 1 && w.stride(0) % 8 == 0)),
-              "x [M, K] / w [N, K] (unit inner stride, 16-byte aligned rows) or tiled [N/16, K/32, 4, 16, 8]");
-  const int64_t M = x.size(0), N = tiled ? w.size(0) * 16 : w.size(0), K = tiled ? w.size(1) * 32 : w.size(1);
-  TORCH_CHECK(M >= 1 && M <= 16 && x.size(1) == K, "fused skinny: 1 <= M <= 16, x [M, K]");
-  TORCH_CHECK(N < (1ll << 30) && K < (1ll << 30), "shape too large");
-  check_aligned16(x, "x");
-  check_aligned16(w, "w");
-  same_device(x, w);
-  const bool nin = ssq_in.has_value();
-  KsFuse fz{};
-  if (nin) {
-    const at::Tensor& sq = *ssq_in;
-    check_cuda(sq, "ssq_in");
-    TORCH_CHECK(sq.scalar_type() == at::kFloat && sq.dim() == 2 && sq.size(0) == 16 && sq.is_contiguous() &&
-                    sq.size(1) >= 1 && sq.size(1) <= 512,
-                "ssq_in fp32 [16, nbp <= 512] contiguous");
-    same_device(x, sq);
-    fz.ssq_in = sq.data_ptr<float>();
-    fz.nbp = static_cast<int>(sq.size(1));
-    fz.eps = static_cast<float>(eps);
-  }
-  c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
-  if (glu) {
-    TORCH_CHECK(nin && !res.has_value(), "glu: normalised input, no residual");
-    TORCH_CHECK(N % 128 == 0 && M * (K + 8) * 2 <= 148 * 1024, "glu: 2F % 128 == 0, x fits LDS");
-    auto m = at::empty({M, N / 2}, x.options());
-    launch_skinny_glu_normin(cbp(x), x.stride(0), cbp(w), tiled ? K : w.stride(0), bp(m), m.stride(0),
-                             (int)M, (int)N, (int)K, fz, tiled, cur_stream(x));
-    return {m, at::Tensor()};
-  }
-  TORCH_CHECK(skinny_use_ksplit((int)N, (int)K), "fused skinny: N < 16384, N % 16 == 0, K % 1024 == 0");
-  auto y = at::empty({M, N}, x.options());
-  at::Tensor ssq;
-  if (res.has_value()) {
-    const at::Tensor& r = *res;
-    check_bf16(r, "res");
-    TORCH_CHECK(r.dim() == 2 && r.size(0) == M && r.size(1) == N && r.stride(1) == 1, "res [M, N]");
-    same_device(x, r);
-    fz.res = cbp(r);
-    fz.ldr = r.stride(0);
-    ssq = at::empty({16, N / 16}, x.options().dtype(at::kFloat));
-    fz.ssq_out = ssq.data_ptr<float>();
-  }
-  launch_skinny_ks_fused(cbp(x), x.stride(0), cbp(w), tiled ? K : w.stride(0), bp(y), y.stride(0),
-                         (int)M, (int)N, (int)K, fz, res.has_value(), nin, tiled, cur_stream(x));
-  return {y, ssq};
+  SkinnyParams p{};
+  fill_w8(p, x, w8, wscale);
+  return fused_step(p, x, res, ssq_in, eps, false);
 }
 
 // Decode gate|up with the SwiGLU epilogue on the in-workgroup split-K kernel: w = [gate; up]
 // (2F rows) -> m = silu(x gate^T) * (x up^T) [M, F], one workgroup per 16 features.
 at::Tensor skinny_glu_ks(const at::Tensor& x, const at::Tensor& w) {
-  check_bf16(x, "x");
-  check_bf16(w, "w");
-  TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && x.stride(1) == 1 && w.stride(1) == 1,
-              "x [M, K] / w [2F, K] with unit inner stride");
-  const int64_t M = x.size(0), N = w.size(0), K = w.size(1);
-  TORCH_CHECK(M >= 1 && M <= 64, "skinny GLU: 1 <= M <= 64");
-  TORCH_CHECK(x.size(1) == K, "x width must be K");
-  TORCH_CHECK(N < (1ll << 30) && K < (1ll << 30) && skinny_glu_ks_ok((int)N, (int)K),
-              "skinny GLU: K % 512 == 0 and 2F % 32 == 0");
-  TORCH_CHECK(x.stride(0) % 8 == 0 && w.stride(0) % 8 == 0, "16-byte aligned rows");
-  check_aligned16(x, "x");
-  check_aligned16(w, "w");
-  same_device(x, w);
+  SkinnyParams p{};
+  fill_w(p, x, w, true, false);
+  fill_x(p, x, 64, p.K);
+  TORCH_CHECK(skinny_glu_ks_ok(p.N, p.K), "skinny GLU: K % 512 == 0 and 2F % 32 == 0");
   c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
-  auto m = at::empty({M, N / 2}, x.options());
-  launch_skinny_glu_ks(cbp(x), x.stride(0), cbp(w), w.stride(0), bp(m), m.stride(0), (int)M,
-                       (int)N, (int)K, cur_stream(x));
+  p.glu_out = true;
+  auto m = alloc_y(p, x);
+  launch_skinny_ksplit(p, false, cur_stream(x));
   return m;
 }
-
 
 // y[M, N] = x[M, K] @ w[N, K]^T for M <= 16 (decode). With `swiglu`, x is the fused gate|up
 // output gu[M, 2K] and the kernel applies silu(g) * u while staging it. `counters` (int32,
 // zero-initialised once, re-armed by the kernel) holds one split-K arrival counter per 128
-// output columns.
+// output columns. With `glu_out`, w = [gate; up] (2F rows) -> silu(x gate^T) * (x up^T) [M, F].
 at::Tensor skinny_gemm(const at::Tensor& x, const at::Tensor& w, at::Tensor& counters, bool swiglu,
                        bool glu_out) {
-  check_bf16(x, "x");
-  check_bf16(w, "w");
   check_i32(counters, "counters");
-  TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && x.stride(1) == 1 && w.stride(1) == 1,
-              "x [M, K] / w [N, K] with unit inner stride");
-  const int64_t M = x.size(0), N = w.size(0), K = w.size(1);
-  // 17..64 rows: only the in-workgroup split-K kernel (narrow N, no fused swiglu input)
-  TORCH_CHECK(M >= 1 && (M <= 16 || (M <= 64 && !swiglu && !glu_out && skinny_use_ksplit((int)N, (int)K))),
+  SkinnyParams p{};
+  fill_w(p, x, w, true, false);
+  fill_x(p, x, 64, swiglu ? 2 * p.K : p.K);
+  // narrow N, no fused swiglu input: the in-workgroup split-K kernel, the only one at 17..64 rows
+  const bool ksplit = !swiglu && !glu_out && skinny_use_ksplit(p.N, p.K);
+  TORCH_CHECK(p.M <= 16 || ksplit,
               "skinny GEMM: 1 <= M <= 16 (<= 64 on the split-K path: N < 16384, K % 1024 == 0)");
-  TORCH_CHECK(x.size(1) == (swiglu ? 2 * K : K), "x width must be K (2K with swiglu)");
-  TORCH_CHECK(K % 256 == 0 && N % 16 == 0, "skinny GEMM: K % 256 == 0 and N % 16 == 0");
-  TORCH_CHECK(x.stride(0) % 8 == 0 && w.stride(0) % 8 == 0, "16-byte aligned rows");
-  TORCH_CHECK(N < (1ll << 30) && K < (1ll << 30), "shape too large");
-  check_aligned16(x, "x");
-  check_aligned16(w, "w");
-  same_device(x, w);
+  TORCH_CHECK(p.K % 256 == 0 && p.N % 16 == 0, "skinny GEMM: K % 256 == 0 and N % 16 == 0");
   same_device(x, counters);
-  const int64_t nb = (N + 127) / 128;
-  TORCH_CHECK(counters.is_contiguous() && counters.numel() >= nb, "counters: one per 128 columns");
+  TORCH_CHECK(counters.is_contiguous() && counters.numel() >= (p.N + 127) / 128, "counters: one per 128 columns");
+  p.counters = reinterpret_cast<unsigned*>(counters.data_ptr<int>());
+  p.swiglu = swiglu;
+  p.glu_out = glu_out;
   c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
-  if (glu_out) {  // w = [gate; up] (2F rows) -> silu(x gate^T) * (x up^T) [M, F]
-    TORCH_CHECK(!swiglu && N % 128 == 0, "glu_out: 2F rows with F % 64 == 0, no swiglu input");
-    TORCH_CHECK(M * (K + 8) * 2 <= 152 * 1024, "skinny GEMM: x exceeds LDS");
-    auto m = at::empty({M, N / 2}, x.options());
-    launch_skinny_gemm(cbp(x), x.stride(0), cbp(w), w.stride(0), bp(m), m.stride(0), nullptr,
-                       reinterpret_cast<unsigned*>(counters.data_ptr<int>()), (int)M, (int)N,
-                       (int)K, 1, false, true, cur_stream(x));
-    return m;
+  if (glu_out) {
+    TORCH_CHECK(!swiglu && p.N % 128 == 0, "glu_out: 2F rows with F % 64 == 0, no swiglu input");
+    TORCH_CHECK(skinny_lds_bytes(p.M, p.K) <= kSkLdsGluMax, "skinny GEMM: x exceeds LDS");
   }
-  auto y = at::empty({M, N}, x.options());
-  if (!swiglu && skinny_use_ksplit((int)N, (int)K)) {  // narrow N: in-workgroup split-K
-    launch_skinny_ksplit(cbp(x), x.stride(0), cbp(w), w.stride(0), bp(y), y.stride(0), (int)M,
-                         (int)N, (int)K, cur_stream(x));
-    return y;
-  }
-  const int S = skinny_splits((int)M, (int)N, (int)K);
-  TORCH_CHECK(M * (K / S + 8) * 2 <= 160 * 1024, "skinny GEMM: x slice exceeds LDS");
   at::Tensor ws;
-  if (S > 1) ws = at::empty({S, M, N}, x.options().dtype(at::kFloat));
-  launch_skinny_gemm(cbp(x), x.stride(0), cbp(w), w.stride(0), bp(y), y.stride(0),
-                     S > 1 ? ws.data_ptr<float>() : nullptr,
-                     reinterpret_cast<unsigned*>(counters.data_ptr<int>()), (int)M, (int)N, (int)K,
-                     S, swiglu, false, cur_stream(x));
+  if (!glu_out && !ksplit) {
+    const int S = skinny_splits(p.M, p.N, p.K);
+    TORCH_CHECK(skinny_lds_bytes(p.M, p.K / S) <= kSkLdsMax, "skinny GEMM: x slice exceeds LDS");
+    if (S > 1) {
+      ws = at::empty({S, p.M, p.N}, x.options().dtype(at::kFloat));
+      p.ws = ws.data_ptr<float>();
+    }
+  }
+  auto y = alloc_y(p, x);
+  if (ksplit) launch_skinny_ksplit(p, false, cur_stream(x));
+  else launch_skinny_gemm(p, cur_stream(x));
   return y;
 }
 

@@ -20,27 +20,13 @@
 //     ticket counter, re-armed by that workgroup: no memset, graph-capture safe) sums them in a
 //     FIXED order: deterministic.
 #include "common.h"
+#include "skinny_geom.h"
 #include "skinny_params.h"
 #include "skinny_ks.h"
 
-#include <cstdlib>
+#include <type_traits>
 
 namespace dla {
-
-namespace {
-
-constexpr int kSkWaves = 8;           // waves per workgroup; each owns 16 output columns
-constexpr int kSkCols = 16 * kSkWaves;  // output columns (weight rows) per workgroup
-constexpr int kSkUnroll = 8;          // k-steps (32 each) of weight loads in flight per wave
-constexpr int kSkChunk = 32 * kSkUnroll;
-
-// Non-temporal loads on the TILED decode weight streams (each byte read once per step by one CU):
-// 3.54 vs 3.70 ms/token at B=8 (profiles/r3_decode_tiled.md). On the row-major layout nt lost
-// (4.31 vs 4.19 ms/token: the weights rotated past the Infinity Cache), so the row-major kernels
-// use default-policy loads. (Its DLA_DECODE_NT A/B switch was removed in round 6.)
-static bool decode_nt() { return true; }
-
-}  // namespace
 
 // grid: (ceil(N / 128), S), 8 waves. LDS: M x (kc + 8) bf16 (row pad of 16 B keeps the 16-row fragment
 // reads on distinct banks).
@@ -250,68 +236,63 @@ __global__ __launch_bounds__(64 * kSkWaves) void skinny_gemm_kernel(
   }
 }
 
-int skinny_splits(int M, int N, int K) {
-  // Column blocks >= 128 (8 waves each: >= 4 waves per CU): no split (an in-kernel split-K combine costs each
-  // workgroup an agent-scope release, measured 1.5-2x slower at 900-4000 workgroups). Otherwise
-  // the smallest split count (K-slices a multiple of kSkChunk) giving >= `target` workgroups
-  // (DLA_SKINNY_WG, default 256: one 8-wave workgroup per CU).
-  static const int target = [] {
-    const char* e = getenv("DLA_SKINNY_WG");
-    return e ? atoi(e) : 256;
-  }();
-  const int nb = (N + kSkCols - 1) / kSkCols;
-  if (nb >= 128) return 1;
-  const int chunks = K / kSkChunk;
-  int best = chunks;
-  for (int s = 1; s <= chunks; ++s) {
-    if (chunks % s) continue;
-    const int kc = K / s;
-    if (static_cast<int64_t>(M) * (kc + 8) * 2 > 65536) continue;
-    best = s;
-    if (static_cast<int64_t>(nb) * s >= target) break;
+// Non-temporal loads on the TILED decode weight streams (each byte read once per step by one CU):
+// 3.54 vs 3.70 ms/token at B=8 (profiles/r3_decode_tiled.md). On the row-major layout nt lost
+// (4.31 vs 4.19 ms/token: the weights rotated past the Infinity Cache), so the row-major kernels
+// use default-policy loads: every launcher below passes NT = TW.
+template <SkinnyW L>
+using sk_layout = std::integral_constant<SkinnyW, L>;
+template <int N>
+using sk_int = std::integral_constant<int, N>;
+
+// f(layout) with the weight layout as an integral constant
+template <class F>
+static void skinny_layout_dispatch(SkinnyW layout, F f) {
+  switch (layout) {
+    case SkinnyW::kTiledF8: f(sk_layout<SkinnyW::kTiledF8>{}); break;
+    case SkinnyW::kTiled: f(sk_layout<SkinnyW::kTiled>{}); break;
+    default: f(sk_layout<SkinnyW::kRowMajor>{}); break;
   }
-  return best;
 }
 
-size_t skinny_lds_bytes(int M, int kc) { return static_cast<size_t>(M) * (kc + 8) * sizeof(bf16_t); }
-
-template <bool NT>
-void launch_skinny_gemm_t(const bf16_t* x, int64_t ldx, const bf16_t* W, int64_t ldw, bf16_t* y,
-                          int64_t ldy, float* ws, unsigned* counters, int M, int N, int K, int S,
-                          bool swiglu, bool glu_out, hipStream_t st) {
-  const int kc = K / S;
-  dim3 grid((N + kSkCols - 1) / kSkCols, S);
-  const size_t lds = skinny_lds_bytes(M, kc);
-  static bool attr_set = [] {  // S = 1 at K = 4096 stages up to 16 x 4104 bf16 (> 64 KB default)
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&skinny_gemm_kernel<false, false, NT>),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&skinny_gemm_kernel<true, false, NT>),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    // the GLU variant also holds an 8 KB static exchange tile: dynamic + static <= 160 KB
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&skinny_gemm_kernel<false, true, NT>),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
-    (void)hipGetLastError();  // never leave a sticky error for the caller's next launch check
-    return true;
-  }();
-  (void)attr_set;
-  if (glu_out) {  // N = 2F weight rows -> F outputs, 64 per block, never split
-    dim3 g2(N / 2 / 64, 1);
-    skinny_gemm_kernel<false, true, NT><<<g2, 64 * kSkWaves, skinny_lds_bytes(M, K), st>>>(
-        x, ldx, W, ldw, y, ldy, ws, counters, M, N, K, K);
-    return;
-  }
-  if (swiglu)
-    skinny_gemm_kernel<true, false, NT><<<grid, 64 * kSkWaves, lds, st>>>(
-        x, ldx, W, ldw, y, ldy, ws, counters, M, N, K, kc);
-  else
-    skinny_gemm_kernel<false, false, NT><<<grid, 64 * kSkWaves, lds, st>>>(
-        x, ldx, W, ldw, y, ldy, ws, counters, M, N, K, kc);
+// S = 1 at K = 4096 stages up to 16 x 4104 bf16 (> 64 KB default): raise the kernel's dynamic LDS
+// limit once per process
+template <class K>
+static void skinny_lds_limit(K* kernel, int64_t bytes) {
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            static_cast<int>(bytes));
+  (void)hipGetLastError();  // never leave a sticky error for the caller's next launch check
 }
 
-void launch_skinny_gemm(const bf16_t* x, int64_t ldx, const bf16_t* W, int64_t ldw, bf16_t* y,
-                        int64_t ldy, float* ws, unsigned* counters, int M, int N, int K, int S,
-                        bool swiglu, bool glu_out, hipStream_t st) {
-  launch_skinny_gemm_t<false>(x, ldx, W, ldw, y, ldy, ws, counters, M, N, K, S, swiglu, glu_out, st);
+void launch_skinny_gemm(const SkinnyParams& p, hipStream_t st) {
+  // glu_out: N = 2F weight rows -> F outputs, 64 per block, never split
+  const int S = p.glu_out ? 1 : skinny_splits(p.M, p.N, p.K);
+  const KsFuse fz{nullptr, 0, nullptr, p.ssq_in, p.nbp, p.eps, nullptr, 0};
+  auto launch = [&](auto swiglu, auto glu, auto npre, auto tw) {
+    constexpr bool GLU = decltype(glu)::value, NPRE = decltype(npre)::value, TW = decltype(tw)::value;
+    auto* kernel = &skinny_gemm_kernel<decltype(swiglu)::value, GLU, TW, NPRE, TW>;
+    static const bool attr_set = [kernel] {
+      skinny_lds_limit(kernel, NPRE ? kSkLdsNormMax : GLU ? kSkLdsGluMax : kSkLdsMax);
+      return true;
+    }();
+    (void)attr_set;
+    const int kc = p.K / S;
+    const dim3 grid(GLU ? p.N / 2 / 64 : (p.N + kSkCols - 1) / kSkCols, S);
+    kernel<<<grid, 64 * kSkWaves, skinny_lds_bytes(p.M, kc), st>>>(
+        p.x, p.ldx, static_cast<const bf16_t*>(p.w), p.ldw, p.y, p.ldy, p.ws, p.counters, p.M, p.N, p.K, kc, fz);
+  };
+  constexpr std::true_type yes{};
+  constexpr std::false_type no{};
+  if (p.glu_out && p.ssq_in != nullptr) {  // the fused decode layer's gate|up (KsFuse NIN)
+    if (p.layout == SkinnyW::kTiled) launch(no, yes, yes, yes);
+    else launch(no, yes, yes, no);
+  } else if (p.glu_out) {
+    launch(no, yes, no, no);
+  } else if (p.swiglu) {
+    launch(yes, no, no, no);
+  } else {
+    launch(no, no, no, no);
+  }
 }
 
 // Narrow outputs (N <= ~16K: qkv, o, down at Llama-3-8B): ONE workgroup per 16 output columns,
@@ -332,110 +313,59 @@ template <int DEPTH, bool NT, bool GLU, int MT = 1, int UNR = kKsUnroll, bool RE
 __global__ __launch_bounds__(512) void skinny_ksplit_kernel(
     const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __restrict__ W, int64_t ldw,
     bf16_t* __restrict__ y, int64_t ldy, int M, int N, int K, KsFuse fz = KsFuse{}) {
-  ks_body<DEPTH, NT, GLU, MT, UNR, RES, NIN, TW, false, F8>(blockIdx.x, gridDim.x, x, ldx, W, ldw, y, ldy, M,
+  ks_body<DEPTH, NT, GLU, MT, UNR, RES, NIN, TW, F8>(blockIdx.x, gridDim.x, x, ldx, W, ldw, y, ldy, M,
                                                              N, K, fz);
 }
 
-// fused decode-layer launches (KsFuse): the residual-producing projection and the
-// norm-consuming qkv projection on the in-workgroup split-K kernel, the gate|up GLU on the LDS
-// kernel. M <= 16.
-// ks_body's branch-free ring (KsFuse::straight) on every shape it covers; its A/B switch went
-// in round 6 (3.557 / 3.554 vs 3.581 / 3.569 ms/token at B = 8, profiles/r5_decode_fp8.md)
-static int ks_straight() { return 1; }
-
-template <bool TW, bool NT, bool F8 = false>
-static void launch_ks_fused_t(const bf16_t* x, int64_t ldx, const bf16_t* W, int64_t ldw, bf16_t* y,
-                              int64_t ldy, int M, int N, int K, const KsFuse& fz, bool res, bool nin,
-                              hipStream_t st) {
-  static const int deep_k = [] {
-    const char* e = getenv("DLA_SKINNY_DEEP_K");
-    return e ? atoi(e) : 8192;
-  }();
-  const int nb = N / 16;
-  const bool deep = K >= deep_k;
-  KsFuse f = fz;
-  f.straight = ks_straight();
-#define DLA_KSF(D, R, NI) skinny_ksplit_kernel<D, NT, false, 1, kKsUnroll, R, NI, TW, F8><<<nb, 512, 0, st>>>(x, ldx, W, ldw, y, ldy, M, N, K, f)
-  if (res && nin) {
-    if (deep) DLA_KSF(4, true, true); else DLA_KSF(2, true, true);
-  } else if (res) {
-    if (deep) DLA_KSF(4, true, false); else DLA_KSF(2, true, false);
-  } else if (nin) {
-    if (deep) DLA_KSF(4, false, true); else DLA_KSF(2, false, true);
-  } else {
-    if (deep) DLA_KSF(4, false, false); else DLA_KSF(2, false, false);
+// `fused`: the decode-layer launches (KsFuse) -- the residual-producing projection (res) and the
+// norm-consuming qkv projection (ssq_in), or a plain one, on any weight layout, M <= 16. They run
+// ks_body's branch-free ring (KsFuse::straight) on every shape it covers; its A/B switch went in
+// round 6 (3.557 / 3.554 vs 3.581 / 3.569 ms/token at B = 8, profiles/r5_decode_fp8.md). Ring
+// depth: skinny_ks_depth; fp8 weights (e4m3 tiled copy + per-row scales, ks_body F8: the o / down /
+// qkv projections at half the weight bytes) skinny_ks_f8_depth.
+// Otherwise the plain projection, or with glu_out gate|up (N = 2F weight rows) -> m = silu(gate) *
+// up [M, F] on F / 16 workgroups, of a row-major weight at M <= 64, the ring as ks_body's default.
+void launch_skinny_ksplit(const SkinnyParams& p, bool fused, hipStream_t st) {
+  const KsFuse fz{p.res, p.ldr, p.ssq_out, p.ssq_in, p.nbp, p.eps, p.wscale, fused ? 1 : 0};
+  const int nb = p.glu_out ? p.N / 32 : p.N / 16;
+  auto launch = [&](auto depth, auto mt, auto glu, auto res, auto nin, auto lay) {
+    constexpr int MT = decltype(mt)::value;
+    constexpr bool TW = decltype(lay)::value != SkinnyW::kRowMajor, F8 = decltype(lay)::value == SkinnyW::kTiledF8;
+    skinny_ksplit_kernel<decltype(depth)::value, TW, decltype(glu)::value, MT, MT == 1 ? kKsUnroll : 2,
+                         decltype(res)::value, decltype(nin)::value, TW, F8><<<nb, 512, 0, st>>>(
+        p.x, p.ldx, static_cast<const bf16_t*>(p.w), p.ldw, p.y, p.ldy, p.M, p.N, p.K, fz);
+  };
+  constexpr std::true_type yes{};
+  constexpr std::false_type no{};
+  if (fused) {
+    skinny_layout_dispatch(p.layout, [&](auto lay) {
+      auto epilogue = [&](auto depth) {
+        if (p.res != nullptr && p.ssq_in != nullptr) launch(depth, sk_int<1>{}, no, yes, yes, lay);
+        else if (p.res != nullptr) launch(depth, sk_int<1>{}, no, yes, no, lay);
+        else if (p.ssq_in != nullptr) launch(depth, sk_int<1>{}, no, no, yes, lay);
+        else launch(depth, sk_int<1>{}, no, no, no, lay);
+      };
+      const int depth = p.layout == SkinnyW::kTiledF8 ? skinny_ks_f8_depth() : skinny_ks_depth(p.K);
+      if (depth == 4) epilogue(sk_int<4>{});
+      else epilogue(sk_int<2>{});
+    });
+    return;
   }
-#undef DLA_KSF
-}
-
-// tiled: W in the tiled layout (ldw unused)
-void launch_skinny_ks_fused(const bf16_t* x, int64_t ldx, const bf16_t* W, int64_t ldw, bf16_t* y,
-                            int64_t ldy, int M, int N, int K, const KsFuse& fz, bool res, bool nin,
-                            bool tiled, hipStream_t st) {
-  // DLA_DECODE_NT=1: non-temporal weight loads on the tiled stream (A/B)
-  if (tiled && decode_nt()) launch_ks_fused_t<true, true>(x, ldx, W, ldw, y, ldy, M, N, K, fz, res, nin, st);
-  else if (tiled) launch_ks_fused_t<true, false>(x, ldx, W, ldw, y, ldy, M, N, K, fz, res, nin, st);
-  else launch_ks_fused_t<false, false>(x, ldx, W, ldw, y, ldy, M, N, K, fz, res, nin, st);
-}
-
-// fp8 weights (e4m3 tiled copy + per-row scales in fz.wscale, ks_body F8): the o / down / qkv
-// projections of the decode layer at half the weight bytes. The ring keeps the bf16 kernel's
-// chunk count in flight, i.e. half its bytes: a 4-deep ring everywhere.
-void launch_skinny_ks_fused_f8(const bf16_t* x, int64_t ldx, const uint8_t* W8, bf16_t* y, int64_t ldy,
-                               int M, int N, int K, const KsFuse& fz, bool res, bool nin, hipStream_t st) {
-  const bf16_t* W = reinterpret_cast<const bf16_t*>(W8);
-  const int nb = N / 16;
-  // DLA_KS_F8_DEPTH (2 or 4): ring depth. Graph decode, Llama-3-8B B=8, same box: 2.62 ms/token
-  // at depth 2 vs 2.73 at 4 (fewer VGPRs, more resident waves beat more bytes in flight per wave)
-  static const int depth = [] {
-    const char* e = getenv("DLA_KS_F8_DEPTH");
-    return (e && atoi(e) == 4) ? 4 : 2;
-  }();
-  KsFuse f = fz;
-  f.straight = ks_straight();
-#define DLA_KSF8(D, NTV, R, NI) skinny_ksplit_kernel<D, NTV, false, 1, kKsUnroll, R, NI, true, true><<<nb, 512, 0, st>>>(x, ldx, W, K, y, ldy, M, N, K, f)
-#define DLA_KSF8_NT(D)                           \
-  if (decode_nt()) {                             \
-    if (res && nin) DLA_KSF8(D, true, true, true);   \
-    else if (res) DLA_KSF8(D, true, true, false);    \
-    else if (nin) DLA_KSF8(D, true, false, true);    \
-    else DLA_KSF8(D, true, false, false);            \
-  } else {                                       \
-    if (res && nin) DLA_KSF8(D, false, true, true);  \
-    else if (res) DLA_KSF8(D, false, true, false);   \
-    else if (nin) DLA_KSF8(D, false, false, true);   \
-    else DLA_KSF8(D, false, false, false);           \
-  }
-  if (depth == 2) {
-    DLA_KSF8_NT(2)
-  } else {
-    DLA_KSF8_NT(4)
-  }
-#undef DLA_KSF8_NT
-#undef DLA_KSF8
-}
-
-template <bool TW, bool NT>
-static void launch_glu_normin_t(const bf16_t* x, int64_t ldx, const bf16_t* W, int64_t ldw, bf16_t* y,
-                                int64_t ldy, int M, int N, int K, const KsFuse& fz, hipStream_t st) {
-  static bool attr_set = [] {
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&skinny_gemm_kernel<false, true, NT, true, TW>),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    (void)hipGetLastError();
-    return true;
-  }();
-  (void)attr_set;
-  dim3 g2(N / 2 / 64, 1);
-  skinny_gemm_kernel<false, true, NT, true, TW><<<g2, 64 * kSkWaves, skinny_lds_bytes(M, K), st>>>(
-      x, ldx, W, ldw, y, ldy, nullptr, nullptr, M, N, K, K, fz);
-}
-
-void launch_skinny_glu_normin(const bf16_t* x, int64_t ldx, const bf16_t* W, int64_t ldw, bf16_t* y,
-                              int64_t ldy, int M, int N, int K, const KsFuse& fz, bool tiled,
-                              hipStream_t st) {
-  if (tiled && decode_nt()) launch_glu_normin_t<true, true>(x, ldx, W, ldw, y, ldy, M, N, K, fz, st);
-  else if (tiled) launch_glu_normin_t<true, false>(x, ldx, W, ldw, y, ldy, M, N, K, fz, st);
-  else launch_glu_normin_t<false, false>(x, ldx, W, ldw, y, ldy, M, N, K, fz, st);
+  constexpr sk_layout<SkinnyW::kRowMajor> rm{};
+  auto rows = [&](auto glu) {
+    if (p.M <= 16) {
+      if constexpr (!decltype(glu)::value) {
+        if (skinny_ks_depth(p.K) == 4) return launch(sk_int<4>{}, sk_int<1>{}, glu, no, no, rm);
+      }
+      launch(sk_int<2>{}, sk_int<1>{}, glu, no, no, rm);
+    } else if (p.M <= 32) {
+      launch(sk_int<2>{}, sk_int<2>{}, glu, no, no, rm);
+    } else {
+      launch(sk_int<2>{}, sk_int<4>{}, glu, no, no, rm);
+    }
+  };
+  if (p.glu_out) rows(yes);
+  else rows(no);
 }
 
 // Decode gate|up (M <= 16) over an INTERLEAVED tiled weight (ops/decode.py `glu_weight`): tile t
@@ -571,102 +501,31 @@ __global__ __launch_bounds__(512) void skinny_glu_il_kernel(const bf16_t* __rest
   }
 }
 
-// gate|up over the interleaved tiled weight (2F rows -> [M, F]); waves per workgroup: the largest
-// of 8..4 dividing the tile count with >= 256 workgroups, else 8
-template <int DEPTH, bool F8 = false>
-static void launch_glu_il_d(const bf16_t* x, int64_t ldx, const bf16_t* Wt, bf16_t* y, int64_t ldy, int M,
-                            int ntiles, int K, const KsFuse& fz, int w, hipStream_t st) {
-  static bool attr_set = [] {
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&skinny_glu_il_kernel<DEPTH, F8>),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    (void)hipGetLastError();
-    return true;
-  }();
-  (void)attr_set;
-  skinny_glu_il_kernel<DEPTH, F8><<<(ntiles + w - 1) / w, 64 * w, skinny_lds_bytes(M, K), st>>>(
-      x, ldx, Wt, y, ldy, M, ntiles, K, fz);
-}
-
-// fp8 gate|up (interleaved e4m3 tiled copy, fz.wscale): the ring keeps 4 slots of half-size loads
-void launch_skinny_glu_il_f8(const bf16_t* x, int64_t ldx, const uint8_t* Wt8, bf16_t* y, int64_t ldy,
-                             int M, int N, int K, const KsFuse& fz, hipStream_t st) {
-  const int ntiles = N / 16;
-  int w = 8;
-  for (int c : {8, 7, 6, 5, 4}) {
-    if (ntiles % c == 0 && ntiles / c >= 256) { w = c; break; }
-  }
-  // DLA_GLU_IL_F8_DEPTH (2, 3 or 4): ring depth; same A/B: 2.712 / 2.710 / 2.729 ms/token
-  static const int depth = [] {
-    const char* e = getenv("DLA_GLU_IL_F8_DEPTH");
-    const int d = e ? atoi(e) : 3;
-    return d < 2 ? 2 : (d > 4 ? 4 : d);
-  }();
-  const bf16_t* W = reinterpret_cast<const bf16_t*>(Wt8);
-  if (depth == 2) launch_glu_il_d<2, true>(x, ldx, W, y, ldy, M, ntiles, K, fz, w, st);
-  else if (depth == 3) launch_glu_il_d<3, true>(x, ldx, W, y, ldy, M, ntiles, K, fz, w, st);
-  else launch_glu_il_d<4, true>(x, ldx, W, y, ldy, M, ntiles, K, fz, w, st);
-}
-
-void launch_skinny_glu_il(const bf16_t* x, int64_t ldx, const bf16_t* Wt, bf16_t* y, int64_t ldy, int M,
-                          int N, int K, const KsFuse& fz, hipStream_t st) {
-  // DLA_GLU_IL_DEPTH (2, 3 or 4) and DLA_GLU_IL_WAVES (0 = auto) for A/B runs
-  static const int depth = [] {
-    const char* e = getenv("DLA_GLU_IL_DEPTH");
-    const int d = e ? atoi(e) : 2;
-    return d < 2 ? 2 : (d > 4 ? 4 : d);
-  }();
-  static const int waves = [] {
-    const char* e = getenv("DLA_GLU_IL_WAVES");
-    const int v = e ? atoi(e) : 0;
-    return (v >= 1 && v <= 8) ? v : 0;
-  }();
-  const int ntiles = N / 16;
-  int w = 8;
-  for (int c : {8, 7, 6, 5, 4}) {
-    if (ntiles % c == 0 && ntiles / c >= 256) { w = c; break; }
-  }
-  if (waves > 0 && M <= 4 * waves) w = waves;  // the rstd waves cover 4 rows each
-  if (depth == 4) launch_glu_il_d<4>(x, ldx, Wt, y, ldy, M, ntiles, K, fz, w, st);
-  else if (depth == 3) launch_glu_il_d<3>(x, ldx, Wt, y, ldy, M, ntiles, K, fz, w, st);
-  else launch_glu_il_d<2>(x, ldx, Wt, y, ldy, M, ntiles, K, fz, w, st);
-}
-
-bool skinny_use_ksplit(int N, int K) {
-  return (N + kSkCols - 1) / kSkCols < 128 && (K % (8 * kKsChunk)) == 0 && N % 16 == 0;
-}
-
-bool skinny_glu_ks_ok(int N, int K) { return (K % (4 * kKsChunk)) == 0 && N % 32 == 0; }
-
-template <bool NT, bool GLU>
-static void launch_ks(const bf16_t* x, int64_t ldx, const bf16_t* W, int64_t ldw, bf16_t* y,
-                      int64_t ldy, int M, int N, int K, int nb, hipStream_t st) {
-  // M <= 16: a 2-deep ring (84 VGPRs: 5-6 waves per SIMD, every qkv block resident in one round);
-  // a 4-deep ring (152 VGPRs) measured slower at qkv (16.0 vs 14.8 us in a decode step)
-  // long K (the 14336-deep down projection: 14 ring slots per wave, one workgroup per CU) keeps
-  // a 4-deep ring in flight (DLA_SKINNY_DEEP_K, default 8192: K at or above it)
-  static const int deep_k = [] {
-    const char* e = getenv("DLA_SKINNY_DEEP_K");
-    return e ? atoi(e) : 8192;
-  }();
-  if (M <= 16 && !GLU && K >= deep_k)
-    skinny_ksplit_kernel<4, NT, GLU, 1><<<nb, 512, 0, st>>>(x, ldx, W, ldw, y, ldy, M, N, K);
-  else if (M <= 16)
-    skinny_ksplit_kernel<2, NT, GLU, 1><<<nb, 512, 0, st>>>(x, ldx, W, ldw, y, ldy, M, N, K);
-  else if (M <= 32)
-    skinny_ksplit_kernel<2, NT, GLU, 2, 2><<<nb, 512, 0, st>>>(x, ldx, W, ldw, y, ldy, M, N, K);
-  else
-    skinny_ksplit_kernel<2, NT, GLU, 4, 2><<<nb, 512, 0, st>>>(x, ldx, W, ldw, y, ldy, M, N, K);
-}
-
-void launch_skinny_ksplit(const bf16_t* x, int64_t ldx, const bf16_t* W, int64_t ldw, bf16_t* y,
-                          int64_t ldy, int M, int N, int K, hipStream_t st) {
-  launch_ks<false, false>(x, ldx, W, ldw, y, ldy, M, N, K, N / 16, st);
-}
-
-// gate|up (N = 2F weight rows) -> m = silu(gate) * up [M, F], F / 16 workgroups
-void launch_skinny_glu_ks(const bf16_t* x, int64_t ldx, const bf16_t* W, int64_t ldw, bf16_t* y,
-                          int64_t ldy, int M, int N, int K, hipStream_t st) {
-  launch_ks<false, true>(x, ldx, W, ldw, y, ldy, M, N, K, N / 32, st);
+// gate|up over the interleaved tiled weight (2F rows -> [M, F]); waves per workgroup and ring depth
+// in skinny_geom.h (fp8: the interleaved e4m3 tiled copy, fz.wscale)
+void launch_skinny_glu_il(const SkinnyParams& p, hipStream_t st) {
+  const bool f8 = p.layout == SkinnyW::kTiledF8;
+  const int ntiles = p.N / 16, w = glu_il_waves(ntiles, p.M, f8);
+  const KsFuse fz{nullptr, 0, nullptr, p.ssq_in, p.nbp, p.eps, p.wscale, 0};
+  auto launch = [&](auto depth, auto f8c) {
+    auto* kernel = &skinny_glu_il_kernel<decltype(depth)::value, decltype(f8c)::value>;
+    static const bool attr_set = [kernel] {
+      skinny_lds_limit(kernel, kSkLdsNormMax);
+      return true;
+    }();
+    (void)attr_set;
+    kernel<<<(ntiles + w - 1) / w, 64 * w, skinny_lds_bytes(p.M, p.K), st>>>(
+        p.x, p.ldx, static_cast<const bf16_t*>(p.w), p.y, p.ldy, p.M, ntiles, p.K, fz);
+  };
+  auto ring = [&](auto f8c) {
+    switch (glu_il_depth(f8)) {
+      case 2: launch(sk_int<2>{}, f8c); break;
+      case 3: launch(sk_int<3>{}, f8c); break;
+      default: launch(sk_int<4>{}, f8c); break;
+    }
+  };
+  if (f8) ring(std::true_type{});
+  else ring(std::false_type{});
 }
 
 }  // namespace dla

@@ -21,18 +21,16 @@
 //   * the gate|up projection (wide, no split) applies RMSNorm's row factor and SwiGLU in its
 //     own epilogue.
 #include "common.h"
+#include "skinny_geom.h"
+#include "skinny_params.h"
 
-#include <cstdlib>
 #include <type_traits>
 
 namespace dla {
 
 namespace {
 
-constexpr int kM64Waves = 8;
-constexpr int kM64Ck = 256;             // k per x chunk and per weight ring slot
 constexpr int kM64Steps = kM64Ck / 32;  // MFMA k-steps per chunk
-constexpr int kM64Ld = kM64Ck + 8;      // LDS row stride in bf16 (16-byte pad)
 constexpr int kM64MaxNbp = 64;          // row-norm partials per row (N / 128 <= 64: H <= 8192)
 constexpr int kM64RegNbp = 8;           // partials held in registers (reduce-launch producers: N / 1024)
 
@@ -303,16 +301,12 @@ __global__ __launch_bounds__(256) void m64_reduce_kernel(const float* __restrict
   }
 }
 
-// Split-K count: the most splits that keep the grid within one workgroup per CU. A grid of 1.5
-// workgroups per CU (the qkv projection at Llama-3-8B: 48 column blocks x 8 splits = 384) leaves
-// half the CUs streaming twice the bytes of the rest; 48 x 4 = 192 workgroups ran the same GEMM +
-// reduce in 21.4 vs 26.9 us (B = 64, a round-4 probe since removed). DLA_M64_WG=n (A/B) restores the
-// round-3 rule: the fewest splits whose grid reaches n workgroups.
-int m64_splits(int N, int K) {
-  static const int target = [] {
-    const char* e = getenv("DLA_M64_WG");
-    return e ? atoi(e) : 0;
-  }();
+template <int N>
+using m64_int = std::integral_constant<int, N>;
+
+// split count of a launch (skinny_geom.h m64_splits on this device's CU count); the gate|up
+// projection is wide and never splits
+int m64_num_splits(const SkinnyParams& p) {
   static const int cus = [] {
     int dev = 0, n = 0;
     if (hipGetDevice(&dev) != hipSuccess ||
@@ -321,164 +315,74 @@ int m64_splits(int N, int K) {
     (void)hipGetLastError();
     return n;
   }();
-  const int nb = N / (16 * kM64Waves);
-  const int chunks = K / kM64Ck;
-  // split counts the reduce kernel is instantiated for
-  if (target > 0) {
-    for (int s : {1, 2, 4, 7, 8, 14, 16}) {
-      if (chunks % s) continue;
-      if (nb * s >= target) return s;
-    }
-    for (int s : {16, 14, 8, 7, 4, 2}) if (chunks % s == 0) return s;
-    return 1;
-  }
-  // (a grid of fewer column blocks than CUs always splits at least once, as the round-3 rule did:
-  // the residual / norm epilogues live in the reduce launch)
-  int best = 1;
-  for (int s : {2, 4, 7, 8, 14, 16})
-    if (chunks % s == 0 && (nb * s <= cus || (best == 1 && nb < cus))) best = s;
-  return best;
+  return p.glu_out ? 1 : m64_splits(p.N, p.K, cus);
 }
 
-bool m64_shape_ok(int N, int K, bool glu) {
-  return K % kM64Ck == 0 && N % 128 == 0;
-}
-
-size_t m64_lds_bytes(int M) {
-  const int mt = M <= 32 ? 2 : 4;
-  return static_cast<size_t>(2 * 16 * mt * kM64Ld) * sizeof(bf16_t);
-}
-
-template <int MT, bool GLU, bool NIN, bool TW, int NW, bool NTL, int DEPTH = 2, bool F8 = false>
-static void m64_launch_w(const bf16_t* x, int64_t ldx, const bf16_t* W, int64_t ldw, bf16_t* y,
-                         int64_t ldy, float* ws, int M, int N, int K, int S, const float* ssq_in,
-                         int nbp, float eps, hipStream_t st, const float* wsc = nullptr) {
-  const size_t lds = static_cast<size_t>(2 * 16 * MT * kM64Ld) * sizeof(bf16_t);
-  static bool attr = [] {
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&m64_gemm_kernel<MT, GLU, NIN, TW, DEPTH, NW, NTL, F8>),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-    (void)hipGetLastError();
-    return true;
-  }();
-  (void)attr;
-  dim3 grid(GLU ? N / 2 / (8 * NW) : N / (16 * NW), S);
-  m64_gemm_kernel<MT, GLU, NIN, TW, DEPTH, NW, NTL, F8><<<grid, 64 * NW, lds, st>>>(
-      x, ldx, W, ldw, y, ldy, ws, M, N, K, K / S, ssq_in, nbp, eps, wsc);
-}
-
+// The GEMM (S > 1: fp32 slabs into p.ws), then the split-K reduce with the res / ssq_in epilogue.
 // NW = 8 waves per workgroup (gate|up: 64 features per workgroup). 4 waves (448 gate|up
 // workgroups at Llama-3-8B, two per CU) measured 55.0 vs 53.2 us: README "Tried".
-template <int MT, bool GLU, bool NIN, bool TW>
-static void m64_launch(const bf16_t* x, int64_t ldx, const bf16_t* W, int64_t ldw, bf16_t* y,
-                       int64_t ldy, float* ws, int M, int N, int K, int S, const float* ssq_in,
-                       int nbp, float eps, hipStream_t st) {
-  // non-temporal loads on the tiled weight stream (see skinny.hip decode_nt)
-  constexpr bool nt = true;
-  // two weight chunks in flight per wave on the tiled nt stream (3 or 4 measured 5.10 / 5.27 vs
-  // 5.01 ms/token at B = 64: more bytes in flight only lengthen the queues; removed)
-  if constexpr (TW) {
-    if (nt) {
-      m64_launch_w<MT, GLU, NIN, TW, kM64Waves, true>(x, ldx, W, ldw, y, ldy, ws, M, N, K, S, ssq_in, nbp, eps, st);
-      return;
+// Non-temporal loads on the tiled weight streams only (see skinny.hip), two weight chunks in flight
+// per wave on the bf16 ones (3 or 4 measured 5.10 / 5.27 vs 5.01 ms/token at B = 64: more bytes in
+// flight only lengthen the queues; removed), m64_f8_depth on the e4m3 tiled copy (p.wscale its
+// per-row scales).
+void launch_m64(const SkinnyParams& p, hipStream_t st) {
+  const int S = m64_num_splits(p);
+  auto gemm = [&](auto mt, auto glu, auto nin, auto tw, auto f8, auto depth) {
+    constexpr int MT = decltype(mt)::value;
+    constexpr bool GLU = decltype(glu)::value, NIN = decltype(nin)::value, TW = decltype(tw)::value;
+    auto* kernel = &m64_gemm_kernel<MT, GLU, NIN, TW, decltype(depth)::value, kM64Waves, TW, decltype(f8)::value>;
+    static const bool attr = [kernel] {
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                static_cast<int>(kM64LdsMax));
+      (void)hipGetLastError();
+      return true;
+    }();
+    (void)attr;
+    const dim3 grid(GLU ? p.N / 2 / (8 * kM64Waves) : p.N / (16 * kM64Waves), S);
+    // the plain rows leave res / ssq_in to the reduce launch
+    kernel<<<grid, 64 * kM64Waves, m64_lds_bytes(MT), st>>>(
+        p.x, p.ldx, static_cast<const bf16_t*>(p.w), p.ldw, p.y, p.ldy, p.ws, p.M, p.N, p.K, p.K / S,
+        NIN ? p.ssq_in : nullptr, NIN ? p.nbp : 0, NIN ? p.eps : 0.f, p.wscale);
+  };
+  constexpr std::true_type yes{};
+  constexpr std::false_type no{};
+  auto epilogue = [&](auto mt, auto tw, auto f8, auto depth) {
+    if (p.glu_out && p.ssq_in != nullptr) gemm(mt, yes, yes, tw, f8, depth);
+    else if (p.glu_out) gemm(mt, yes, no, tw, f8, depth);
+    else gemm(mt, no, no, tw, f8, depth);
+  };
+  auto weight = [&](auto mt) {
+    if (p.layout == SkinnyW::kRowMajor) return epilogue(mt, no, no, m64_int<2>{});
+    if (p.layout == SkinnyW::kTiled) return epilogue(mt, yes, no, m64_int<2>{});
+    switch (m64_f8_depth()) {
+      case 2: epilogue(mt, yes, yes, m64_int<2>{}); break;
+      case 4: epilogue(mt, yes, yes, m64_int<4>{}); break;
+      default: epilogue(mt, yes, yes, m64_int<3>{}); break;
     }
-  }
-  m64_launch_w<MT, GLU, NIN, TW, kM64Waves, false>(x, ldx, W, ldw, y, ldy, ws, M, N, K, S, ssq_in, nbp, eps, st);
-}
+  };
+  if (m64_row_tiles(p.M) == 2) weight(m64_int<2>{});
+  else weight(m64_int<4>{});
+  if (S == 1) return;
 
-// fp8 weights (tiled, nt): DLA_M64_F8_DEPTH = weight chunks in flight per wave (2, 3 or 4; a chunk
-// is half the bf16 bytes, so the same bytes in flight take twice the chunks)
-template <int MT, bool GLU, bool NIN>
-static void m64_launch_f8(const bf16_t* x, int64_t ldx, const uint8_t* W8, bf16_t* y, int64_t ldy, float* ws,
-                          int M, int N, int K, int S, const float* ssq_in, int nbp, float eps,
-                          const float* wsc, hipStream_t st) {
-  static const int depth = [] {
-    const char* e = getenv("DLA_M64_F8_DEPTH");
-    const int d = e ? atoi(e) : 3;
-    return d >= 2 && d <= 4 ? d : 3;
-  }();
-  const bf16_t* W = reinterpret_cast<const bf16_t*>(W8);
-  if (depth == 2)
-    m64_launch_w<MT, GLU, NIN, true, kM64Waves, true, 2, true>(x, ldx, W, 0, y, ldy, ws, M, N, K, S, ssq_in, nbp, eps, st, wsc);
-  else if (depth == 4)
-    m64_launch_w<MT, GLU, NIN, true, kM64Waves, true, 4, true>(x, ldx, W, 0, y, ldy, ws, M, N, K, S, ssq_in, nbp, eps, st, wsc);
-  else
-    m64_launch_w<MT, GLU, NIN, true, kM64Waves, true, 3, true>(x, ldx, W, 0, y, ldy, ws, M, N, K, S, ssq_in, nbp, eps, st, wsc);
-}
-
-template <int MT>
-static void m64_dispatch_f8(const bf16_t* x, int64_t ldx, const uint8_t* W8, bf16_t* y, int64_t ldy, float* ws,
-                            int M, int N, int K, int S, bool glu, const float* ssq_in, int nbp, float eps,
-                            const float* wsc, hipStream_t st) {
-  if (glu && ssq_in)
-    m64_launch_f8<MT, true, true>(x, ldx, W8, y, ldy, ws, M, N, K, 1, ssq_in, nbp, eps, wsc, st);
-  else if (glu)
-    m64_launch_f8<MT, true, false>(x, ldx, W8, y, ldy, ws, M, N, K, 1, nullptr, 0, 0.f, wsc, st);
-  else
-    m64_launch_f8<MT, false, false>(x, ldx, W8, y, ldy, ws, M, N, K, S, nullptr, 0, 0.f, wsc, st);
-}
-
-// fp8 form of launch_m64_gemm: W8 the e4m3 tiled copy, wsc its per-row scales
-void launch_m64_gemm_f8(const bf16_t* x, int64_t ldx, const uint8_t* W8, bf16_t* y, int64_t ldy, float* ws,
-                        int M, int N, int K, int S, bool glu, const float* ssq_in, int nbp, float eps,
-                        const float* wsc, hipStream_t st) {
-  if (M <= 32) m64_dispatch_f8<2>(x, ldx, W8, y, ldy, ws, M, N, K, S, glu, ssq_in, nbp, eps, wsc, st);
-  else m64_dispatch_f8<4>(x, ldx, W8, y, ldy, ws, M, N, K, S, glu, ssq_in, nbp, eps, wsc, st);
-}
-
-template <int MT, bool TW>
-static void m64_dispatch(const bf16_t* x, int64_t ldx, const bf16_t* W, int64_t ldw, bf16_t* y,
-                         int64_t ldy, float* ws, int M, int N, int K, int S, bool glu,
-                         const float* ssq_in, int nbp, float eps, hipStream_t st) {
-  if (glu && ssq_in)
-    m64_launch<MT, true, true, TW>(x, ldx, W, ldw, y, ldy, ws, M, N, K, 1, ssq_in, nbp, eps, st);
-  else if (glu)
-    m64_launch<MT, true, false, TW>(x, ldx, W, ldw, y, ldy, ws, M, N, K, 1, nullptr, 0, 0.f, st);
-  else
-    m64_launch<MT, false, false, TW>(x, ldx, W, ldw, y, ldy, ws, M, N, K, S, nullptr, 0, 0.f, st);
-}
-
-// GEMM (S > 1: fp32 slabs into ws) -- the reduce is a separate launch (launch_m64_reduce).
-// tiled: W is the tiled layout (ldw unused).
-void launch_m64_gemm(const bf16_t* x, int64_t ldx, const bf16_t* W, int64_t ldw, bf16_t* y,
-                     int64_t ldy, float* ws, int M, int N, int K, int S, bool glu,
-                     const float* ssq_in, int nbp, float eps, bool tiled, hipStream_t st) {
-  if (M <= 32) {
-    if (tiled) m64_dispatch<2, true>(x, ldx, W, ldw, y, ldy, ws, M, N, K, S, glu, ssq_in, nbp, eps, st);
-    else m64_dispatch<2, false>(x, ldx, W, ldw, y, ldy, ws, M, N, K, S, glu, ssq_in, nbp, eps, st);
-  } else {
-    if (tiled) m64_dispatch<4, true>(x, ldx, W, ldw, y, ldy, ws, M, N, K, S, glu, ssq_in, nbp, eps, st);
-    else m64_dispatch<4, false>(x, ldx, W, ldw, y, ldy, ws, M, N, K, S, glu, ssq_in, nbp, eps, st);
-  }
-}
-
-template <int MODE>
-static void m64_reduce_s(const float* ws, int S, int M, int N, bf16_t* y, int64_t ldy, const bf16_t* res,
-                         int64_t ldr, const float* ssq_in, int nbp, int knorm, float eps, float* ssq_out,
-                         hipStream_t st) {
-  dim3 grid((N + 1023) / 1024, M);
-#define DLA_M64R(SS) \
-  m64_reduce_kernel<MODE, SS><<<grid, 256, 0, st>>>(ws, M, N, y, ldy, res, ldr, ssq_in, nbp, knorm, eps, ssq_out)
-  switch (S) {
-    case 2: DLA_M64R(2); break;
-    case 4: DLA_M64R(4); break;
-    case 7: DLA_M64R(7); break;
-    case 8: DLA_M64R(8); break;
-    case 14: DLA_M64R(14); break;
-    case 16: DLA_M64R(16); break;
-    default: DLA_M64R(1); break;  // S == 1 never reaches the reduce (checked by the caller)
-  }
-#undef DLA_M64R
-}
-
-void launch_m64_reduce(const float* ws, int S, int M, int N, bf16_t* y, int64_t ldy, const bf16_t* res,
-                       int64_t ldr, const float* ssq_in, int nbp, int knorm, float eps, float* ssq_out,
-                       hipStream_t st) {
-  if (res)
-    m64_reduce_s<2>(ws, S, M, N, y, ldy, res, ldr, nullptr, 0, 0, 0.f, ssq_out, st);
-  else if (ssq_in)
-    m64_reduce_s<1>(ws, S, M, N, y, ldy, nullptr, 0, ssq_in, nbp, knorm, eps, nullptr, st);
-  else
-    m64_reduce_s<0>(ws, S, M, N, y, ldy, nullptr, 0, nullptr, 0, 0, 0.f, nullptr, st);
+  const dim3 rgrid((p.N + 1023) / 1024, p.M);
+  auto reduce = [&](auto mode, auto s) {
+    m64_reduce_kernel<decltype(mode)::value, decltype(s)::value><<<rgrid, 256, 0, st>>>(
+        p.ws, p.M, p.N, p.y, p.ldy, p.res, p.ldr, p.ssq_in, p.nbp, p.K, p.eps, p.ssq_out);
+  };
+  auto splits = [&](auto mode) {
+    switch (S) {  // the split counts m64_splits chooses from
+      case 2: reduce(mode, m64_int<2>{}); break;
+      case 4: reduce(mode, m64_int<4>{}); break;
+      case 7: reduce(mode, m64_int<7>{}); break;
+      case 8: reduce(mode, m64_int<8>{}); break;
+      case 14: reduce(mode, m64_int<14>{}); break;
+      case 16: reduce(mode, m64_int<16>{}); break;
+      default: break;
+    }
+  };
+  if (p.res != nullptr) splits(m64_int<2>{});
+  else if (p.ssq_in != nullptr) splits(m64_int<1>{});
+  else splits(m64_int<0>{});
 }
 
 // W [N, K] (row stride ldw) -> the tiled layout [N/16, K/32, 4, 16, 8] (see TW above; glu_il: gate /

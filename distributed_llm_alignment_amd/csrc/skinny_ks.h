@@ -1,8 +1,9 @@
-// In-workgroup split-K skinny GEMM body (decode projections, M <= 64 rows), shared by the
-// standalone csrc/skinny.hip kernels and the fused decode qkv + attention kernel (csrc/decode.hip):
-// `bx` is the workgroup's column block, `nblk` the number of such blocks. 512 threads (8 waves).
+// In-workgroup split-K skinny GEMM body (decode projections, M <= 64 rows) of the csrc/skinny.hip
+// kernels: `bx` is the workgroup's column block, `nblk` the number of such blocks. 512 threads
+// (8 waves).
 #pragma once
 #include "common.h"
+#include "skinny_geom.h"
 #include "skinny_params.h"
 
 namespace dla {
@@ -61,13 +62,6 @@ __device__ __forceinline__ void ks_rstd(const KsPart& p, const KsFuse& fz, int M
 
 }  // namespace
 
-constexpr int kKsUnroll = 4;  // k-steps per chunk (one 16-byte W and x load per lane each)
-constexpr int kKsChunk = 32 * kKsUnroll;
-
-// WT: the plain output is stored write-through (`sc1`, two columns per 4-byte store), for a
-// consumer in another workgroup of the same launch that reads it with `sc1` loads after a counter
-// hand-off (decode.hip decode_qkv_attn_kernel; MI355X_MICROARCH inter-workgroup visibility, the
-// release-free valid form)
 typedef uint32_t ks_u32x4 __attribute__((ext_vector_type(4)));
 
 template <bool NT>
@@ -82,14 +76,14 @@ __device__ __forceinline__ ks_u32x4 load_w8(const uint8_t* p) {
 // one 16-byte load feeds two MFMAs and the stream is half the bf16 bytes (ops/decode.py
 // fp8_tiled_weight); y[:, n] = wscale[n] * (x . w8[n]).
 template <int DEPTH, bool NT, bool GLU, int MT = 1, int UNR = kKsUnroll, bool RES = false, bool NIN = false,
-          bool TW = false, bool WT = false, bool F8 = false>
+          bool TW = false, bool F8 = false>
 __device__ __forceinline__ void ks_body(
     const int bx, const int nblk, const bf16_t* __restrict__ x, int64_t ldx,
     const bf16_t* __restrict__ W, int64_t ldw, bf16_t* __restrict__ y, int64_t ldy, int M, int N, int K,
     const KsFuse& fz) {
   constexpr int CH = 32 * UNR;  // k per ring slot
   static_assert(!(RES || NIN) || (MT == 1 && !GLU), "fused residual / norm: M <= 16, plain output");
-  static_assert(!F8 || (TW && !GLU && !WT && MT == 1 && UNR % 2 == 0), "fp8 weights: tiled, plain rows");
+  static_assert(!F8 || (TW && !GLU && MT == 1 && UNR % 2 == 0), "fp8 weights: tiled, plain rows");
   constexpr int UB = F8 ? UNR / 2 : UNR;  // weight loads per ring slot
   __shared__ float red[8][4 * MT][64];
   __shared__ float rstd_s[16];
@@ -220,31 +214,6 @@ __device__ __forceinline__ void ks_body(
     for (int i = 0; i < 4; ++i) red[wave][4 * t + i][lane] = acc[t][i];
   if constexpr (NIN) ks_rstd(part, fz, M, K, wave, lane, rstd_s);
   __syncthreads();
-  if constexpr (WT && !GLU && !RES) {
-    static_assert(MT == 1, "write-through epilogue: one row tile");
-    if (threadIdx.x < 128) {
-      const int e = threadIdx.x;
-      const int ti = e >> 5, l = (e & 31) * 2;  // columns l, l + 1 of row group ti
-      const int m = 4 * (l >> 4) + ti, n = bx * 16 + (l & 15);
-      float t0 = 0.f, t1 = 0.f;
-#pragma unroll
-      for (int w = 0; w < 8; ++w) {
-        t0 += red[w][ti][l];
-        t1 += red[w][ti][l + 1];
-      }
-      if constexpr (NIN) {
-        const float rs = m < M ? rstd_s[m] : 0.f;
-        t0 *= rs;
-        t1 *= rs;
-      }
-      if (m < M) {
-        const uint32_t pk = static_cast<uint32_t>(f2bf(t0)) | (static_cast<uint32_t>(f2bf(t1)) << 16);
-        __hip_atomic_store(reinterpret_cast<uint32_t*>(y + m * ldy + n), pk, __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-      }
-    }
-    return;
-  }
   for (int e = threadIdx.x; e < 256 * MT; e += 512) {
     const int ti = e >> 6, l = e & 63;  // ti = 4 t + i
     const int m = 16 * (ti >> 2) + 4 * (l >> 4) + (ti & 3), n = bx * 16 + (l & 15);
