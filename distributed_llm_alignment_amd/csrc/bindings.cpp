@@ -12,6 +12,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstdlib>
 #include <tuple>
@@ -73,6 +74,13 @@ void launch_group_advantages(const float*, int, int, bool, float, float*, float*
 void launch_grpo_loss(const float*, const float*, const float*, const float*, const float*,
                       const float*, int, int, float, float, float, int, float, float*, float*,
                       float*, float*, hipStream_t);
+void launch_grpo_loss_w(const float*, const float*, const float*, const float*, const float*,
+                        const float*, const float*, int, int, float, float, float, int, float,
+                        float*, float*, float*, float*, hipStream_t);
+void launch_ppo_policy_loss_w(const float*, const float*, const float*, const float*, const float*,
+                              int64_t, float, float*, float*, float*, hipStream_t);
+void launch_rollout_is_weights(const float*, const float*, const float*, int, int, float, float, int,
+                               int, float*, float*, float*, hipStream_t);
 void launch_adamw(bf16_t*, float*, const void*, bool, float*, float*, int64_t, float, float,
                   float, float, float, int, const float*, float, hipStream_t);
 void launch_grad_sumsq(const void*, bool, int64_t, float*, float*, bool, hipStream_t);
@@ -854,26 +862,49 @@ std::tuple<at::Tensor, at::Tensor> gae(const at::Tensor& rewards, const at::Tens
   return {adv, ret};
 }
 
-std::tuple<at::Tensor, at::Tensor, at::Tensor> ppo_policy_loss(const at::Tensor& lp,
-                                                               const at::Tensor& old,
-                                                               const at::Tensor& adv,
-                                                               const at::Tensor& mask,
-                                                               double eps) {
+// w: the importance weights of ppo_policy_loss_w (a grid like lp), or nullptr
+static std::tuple<at::Tensor, at::Tensor, at::Tensor> ppo_policy_loss_impl(
+    const at::Tensor& lp, const at::Tensor& old, const at::Tensor& adv, const at::Tensor& mask,
+    const at::Tensor* w, double eps) {
   check_f32(lp, "lp");
   TORCH_CHECK(lp.is_contiguous(), "lp contiguous");
   check_grid(old, lp, "old");
   check_grid(adv, lp, "adv");
   check_grid(mask, lp, "mask");
+  if (w != nullptr) {
+    check_grid(*w, lp, "w");
+    same_device(lp, *w);
+  }
   c10::hip::HIPGuardMasqueradingAsCUDA g(lp.device());
   auto opt = lp.options();
   auto loss = at::empty({}, opt);
   auto dlp = at::empty_like(lp);
   auto metrics = at::empty({3}, opt);
-  launch_ppo_policy_loss(lp.data_ptr<float>(), old.data_ptr<float>(), adv.data_ptr<float>(),
-                         mask.data_ptr<float>(), lp.numel(), static_cast<float>(eps),
-                         loss.data_ptr<float>(), dlp.data_ptr<float>(), metrics.data_ptr<float>(),
-                         cur_stream(lp));
+  if (w != nullptr)
+    launch_ppo_policy_loss_w(lp.data_ptr<float>(), old.data_ptr<float>(), adv.data_ptr<float>(),
+                             mask.data_ptr<float>(), w->data_ptr<float>(), lp.numel(),
+                             static_cast<float>(eps), loss.data_ptr<float>(), dlp.data_ptr<float>(),
+                             metrics.data_ptr<float>(), cur_stream(lp));
+  else
+    launch_ppo_policy_loss(lp.data_ptr<float>(), old.data_ptr<float>(), adv.data_ptr<float>(),
+                           mask.data_ptr<float>(), lp.numel(), static_cast<float>(eps),
+                           loss.data_ptr<float>(), dlp.data_ptr<float>(), metrics.data_ptr<float>(),
+                           cur_stream(lp));
   return {loss, dlp, metrics};
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor> ppo_policy_loss(const at::Tensor& lp,
+                                                               const at::Tensor& old,
+                                                               const at::Tensor& adv,
+                                                               const at::Tensor& mask,
+                                                               double eps) {
+  return ppo_policy_loss_impl(lp, old, adv, mask, nullptr, eps);
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor> ppo_policy_loss_w(
+    const at::Tensor& lp, const at::Tensor& old, const at::Tensor& adv, const at::Tensor& mask,
+    const at::Tensor& w, double eps) {
+  return ppo_policy_loss_impl(lp, old, adv, mask, &w, eps);
 }
 
 std::tuple<at::Tensor, at::Tensor> ppo_value_loss(const at::Tensor& values, const at::Tensor& old,
@@ -913,15 +944,20 @@ std::tuple<at::Tensor, at::Tensor> group_advantages(const at::Tensor& scores, in
 // lp / old / ref / mask: [S, T] fp32 grids, adv [S] (one value per rollout), denom: optional
 // device [1] replacing the final divisor. mode: 0 sequence, 1 token, 2 constant (S * max_len).
 // Returns (loss, dloss/dlp, metrics[4]); no host read of any device value.
-std::tuple<at::Tensor, at::Tensor, at::Tensor> grpo_loss(
+// w: the importance weights of grpo_loss_w (a grid like lp), or nullptr.
+static std::tuple<at::Tensor, at::Tensor, at::Tensor> grpo_loss_impl(
     const at::Tensor& lp, const at::Tensor& old, const at::Tensor& ref, const at::Tensor& adv,
-    const at::Tensor& mask, const c10::optional<at::Tensor>& denom, double clip_low,
-    double clip_high, double beta, int64_t mode, double max_len) {
+    const at::Tensor& mask, const at::Tensor* w, const c10::optional<at::Tensor>& denom,
+    double clip_low, double clip_high, double beta, int64_t mode, double max_len) {
   check_f32(lp, "lp");
   TORCH_CHECK(lp.dim() == 2 && lp.is_contiguous(), "lp [S, T] contiguous");
   check_grid(old, lp, "old");
   check_grid(ref, lp, "ref");
   check_grid(mask, lp, "mask");
+  if (w != nullptr) {
+    check_grid(*w, lp, "w");
+    same_device(lp, *w);
+  }
   check_f32(adv, "adv");
   TORCH_CHECK(adv.is_contiguous() && adv.numel() == lp.size(0), "adv must be [S] contiguous");
   TORCH_CHECK(mode >= 0 && mode <= 2, "grpo_loss mode must be 0 (sequence), 1 (token), 2 (constant)");
@@ -942,13 +978,71 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> grpo_loss(
   auto dlp = at::empty_like(lp);
   auto metrics = at::empty({4}, opt);
   auto part = at::empty({5, S}, opt);
-  launch_grpo_loss(lp.data_ptr<float>(), old.data_ptr<float>(), ref.data_ptr<float>(),
-                   adv.data_ptr<float>(), mask.data_ptr<float>(), dn, S, T,
-                   static_cast<float>(1.0 - clip_low), static_cast<float>(1.0 + clip_high),
-                   static_cast<float>(beta), static_cast<int>(mode), static_cast<float>(max_len),
-                   part.data_ptr<float>(), loss.data_ptr<float>(), dlp.data_ptr<float>(),
-                   metrics.data_ptr<float>(), cur_stream(lp));
+  const float lo = static_cast<float>(1.0 - clip_low), hi = static_cast<float>(1.0 + clip_high);
+  if (w != nullptr)
+    launch_grpo_loss_w(lp.data_ptr<float>(), old.data_ptr<float>(), ref.data_ptr<float>(),
+                       adv.data_ptr<float>(), mask.data_ptr<float>(), w->data_ptr<float>(), dn, S, T,
+                       lo, hi, static_cast<float>(beta), static_cast<int>(mode),
+                       static_cast<float>(max_len), part.data_ptr<float>(), loss.data_ptr<float>(),
+                       dlp.data_ptr<float>(), metrics.data_ptr<float>(), cur_stream(lp));
+  else
+    launch_grpo_loss(lp.data_ptr<float>(), old.data_ptr<float>(), ref.data_ptr<float>(),
+                     adv.data_ptr<float>(), mask.data_ptr<float>(), dn, S, T, lo, hi,
+                     static_cast<float>(beta), static_cast<int>(mode), static_cast<float>(max_len),
+                     part.data_ptr<float>(), loss.data_ptr<float>(), dlp.data_ptr<float>(),
+                     metrics.data_ptr<float>(), cur_stream(lp));
   return {loss, dlp, metrics};
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor> grpo_loss(
+    const at::Tensor& lp, const at::Tensor& old, const at::Tensor& ref, const at::Tensor& adv,
+    const at::Tensor& mask, const c10::optional<at::Tensor>& denom, double clip_low,
+    double clip_high, double beta, int64_t mode, double max_len) {
+  return grpo_loss_impl(lp, old, ref, adv, mask, nullptr, denom, clip_low, clip_high, beta, mode,
+                        max_len);
+}
+
+// grpo_loss with detached per-token importance weights w [S, T] on the policy-gradient term.
+std::tuple<at::Tensor, at::Tensor, at::Tensor> grpo_loss_w(
+    const at::Tensor& lp, const at::Tensor& old, const at::Tensor& ref, const at::Tensor& adv,
+    const at::Tensor& mask, const at::Tensor& w, const c10::optional<at::Tensor>& denom,
+    double clip_low, double clip_high, double beta, int64_t mode, double max_len) {
+  return grpo_loss_impl(lp, old, ref, adv, mask, &w, denom, clip_low, clip_high, beta, mode,
+                        max_len);
+}
+
+// trainer_lp / rollout_lp / mask: [S, T] fp32 grids. level: 0 token, 1 sequence (length-normalised);
+// mode: 0 truncate at cap, 1 mask outside [floor, cap]. Returns (w [S, T], metrics[5]); no host
+// read of any device value.
+std::tuple<at::Tensor, at::Tensor> rollout_is_weights(const at::Tensor& trainer_lp,
+                                                      const at::Tensor& rollout_lp,
+                                                      const at::Tensor& mask, double cap,
+                                                      double floor, int64_t level, int64_t mode) {
+  check_f32(trainer_lp, "trainer_lp");
+  TORCH_CHECK(trainer_lp.dim() == 2 && trainer_lp.is_contiguous(), "trainer_lp [S, T] contiguous");
+  check_grid(rollout_lp, trainer_lp, "rollout_lp");
+  check_grid(mask, trainer_lp, "mask");
+  same_device(trainer_lp, rollout_lp);
+  same_device(trainer_lp, mask);
+  TORCH_CHECK(std::isfinite(cap) && cap > 0, "rollout_is_weights: cap must be finite and > 0");
+  TORCH_CHECK(floor >= 0 && floor <= cap, "rollout_is_weights: floor must lie in [0, cap]");
+  TORCH_CHECK(level == 0 || level == 1, "rollout_is_weights level must be 0 (token) or 1 (sequence)");
+  TORCH_CHECK(mode == 0 || mode == 1, "rollout_is_weights mode must be 0 (truncate) or 1 (mask)");
+  TORCH_CHECK(trainer_lp.size(0) > 0 && trainer_lp.size(0) < (1ll << 31) &&
+                  trainer_lp.size(1) < (1ll << 31),
+              "rollout_is_weights grid size");
+  c10::hip::HIPGuardMasqueradingAsCUDA g(trainer_lp.device());
+  auto opt = trainer_lp.options();
+  const int S = static_cast<int>(trainer_lp.size(0)), T = static_cast<int>(trainer_lp.size(1));
+  auto w = at::empty_like(trainer_lp);
+  auto metrics = at::empty({5}, opt);
+  auto part = at::empty({5, S}, opt);
+  launch_rollout_is_weights(trainer_lp.data_ptr<float>(), rollout_lp.data_ptr<float>(),
+                            mask.data_ptr<float>(), S, T, static_cast<float>(cap),
+                            static_cast<float>(floor), static_cast<int>(level),
+                            static_cast<int>(mode), part.data_ptr<float>(), w.data_ptr<float>(),
+                            metrics.data_ptr<float>(), cur_stream(trainer_lp));
+  return {w, metrics};
 }
 
 std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> kl_penalty_pg(const at::Tensor& lp,
@@ -1081,6 +1175,9 @@ TORCH_LIBRARY(dla, m) {
   m.def("ppo_value_loss(Tensor values, Tensor old, Tensor returns, Tensor mask, float clip) -> (Tensor, Tensor)");
   m.def("group_advantages(Tensor scores, int G, bool scale_std, float eps) -> (Tensor, Tensor)");
   m.def("grpo_loss(Tensor lp, Tensor old, Tensor ref, Tensor adv, Tensor mask, Tensor? denom, float clip_low, float clip_high, float beta, int mode, float max_len) -> (Tensor, Tensor, Tensor)");
+  m.def("grpo_loss_w(Tensor lp, Tensor old, Tensor ref, Tensor adv, Tensor mask, Tensor w, Tensor? denom, float clip_low, float clip_high, float beta, int mode, float max_len) -> (Tensor, Tensor, Tensor)");
+  m.def("ppo_policy_loss_w(Tensor lp, Tensor old, Tensor adv, Tensor mask, Tensor w, float eps) -> (Tensor, Tensor, Tensor)");
+  m.def("rollout_is_weights(Tensor trainer_lp, Tensor rollout_lp, Tensor mask, float cap, float floor, int level, int mode) -> (Tensor, Tensor)");
   m.def("kl_penalty_pg(Tensor lp, Tensor lr, Tensor reward, float kl_coef) -> (Tensor, Tensor, Tensor, Tensor)");
   m.def("adamw_step(Tensor(a!)? param, Tensor(b!)? master, Tensor grad, Tensor(c!) m, Tensor(d!) v, float lr, float b1, float b2, float eps, float wd, int step, Tensor? clip, float grad_scale) -> ()");
   m.def("grad_sumsq(Tensor grad, Tensor(a!) out, bool accumulate) -> ()");
@@ -1120,6 +1217,9 @@ TORCH_LIBRARY_IMPL(dla, CUDA, m) {
   m.impl("ppo_value_loss", &dla::ppo_value_loss);
   m.impl("group_advantages", &dla::group_advantages);
   m.impl("grpo_loss", &dla::grpo_loss);
+  m.impl("grpo_loss_w", &dla::grpo_loss_w);
+  m.impl("ppo_policy_loss_w", &dla::ppo_policy_loss_w);
+  m.impl("rollout_is_weights", &dla::rollout_is_weights);
   m.impl("adamw_step", &dla::adamw_step);
   m.impl("grad_sumsq", &dla::grad_sumsq);
   m.impl("clip_coef", &dla::clip_coef);

@@ -10,6 +10,8 @@
 //                                                                   train_rlhf.py:149-153
 //   gae / ppo_policy_loss / ppo_value_loss : token-level actor-critic PPO (below)
 //   group_advantages / grpo_loss : critic-free group-relative policy optimisation (below)
+//   rollout_is_weights / grpo_loss_w / ppo_policy_loss_w : truncated importance weights for the
+//                     rollout engine / trainer mismatch and the surrogates that take them (below)
 // Batch dimensions here are small (pairs per micro-batch), so each loss is a single
 // 256-thread block; the point is fusing fwd+bwd+metrics into one launch with no host sync.
 #include "common.h"
@@ -210,14 +212,25 @@ __global__ __launch_bounds__(64) void gae_kernel(const float* __restrict__ r, co
   }
 }
 
+// The product of a detached importance weight with a policy-gradient term, rounded on its own: it
+// is never contracted into a neighbouring add, so w = 1 (1.0f * x is exact) leaves every weighted
+// kernel below bitwise equal to its unweighted instantiation.
+__device__ __forceinline__ float is_mul(float w, float x) {
+#pragma clang fp contract(off)
+  return w * x;
+}
+
 // Clipped surrogate over masked tokens (fwd + bwd in one launch):
 //   rho = exp(lp - lp_old); loss = sum m * max(-A rho, -A clip(rho, 1-eps, 1+eps)) / sum m
 //   dlp = m * (-A rho if the unclipped branch is the max else 0) / sum m
 //   metrics: [0] clip fraction, [1] approx KL  mean((rho - 1) - log rho), [2] token count
+// W (ppo_policy_loss_w): a detached per-token weight w multiplies the surrogate and its gradient
+// (truncated importance sampling); the divisor stays sum m and the metrics stay unweighted.
+template <bool W>
 __global__ __launch_bounds__(1024) void ppo_policy_loss_kernel(
     const float* __restrict__ lp, const float* __restrict__ old, const float* __restrict__ adv,
     const float* __restrict__ m, int64_t n, float eps, float* __restrict__ loss,
-    float* __restrict__ dlp, float* __restrict__ metrics) {
+    float* __restrict__ dlp, float* __restrict__ metrics, const float* __restrict__ w) {
   __shared__ float scratch[16];
   float cnt = 0.f, l = 0.f, cf = 0.f, kl = 0.f;
   for (int64_t i = threadIdx.x; i < n; i += 1024) {
@@ -225,7 +238,11 @@ __global__ __launch_bounds__(1024) void ppo_policy_loss_kernel(
     const float d = lp[i] - old[i];
     const float rho = __expf(d), a = adv[i];
     const float l1 = -a * rho, l2 = -a * fminf(fmaxf(rho, 1.f - eps), 1.f + eps);
-    l += mi * fmaxf(l1, l2);
+    if constexpr (W) {
+      l += mi * is_mul(w[i], fmaxf(l1, l2));
+    } else {
+      l += mi * fmaxf(l1, l2);
+    }
     cnt += mi;
     cf += mi * (fabsf(rho - 1.f) > eps ? 1.f : 0.f);
     kl += mi * ((rho - 1.f) - d);
@@ -239,7 +256,11 @@ __global__ __launch_bounds__(1024) void ppo_policy_loss_kernel(
     const float d = lp[i] - old[i];
     const float rho = __expf(d), a = adv[i];
     const float l1 = -a * rho, l2 = -a * fminf(fmaxf(rho, 1.f - eps), 1.f + eps);
-    dlp[i] = l1 >= l2 ? m[i] * l1 * inv : 0.f;
+    if constexpr (W) {
+      dlp[i] = l1 >= l2 ? m[i] * w[i] * l1 * inv : 0.f;
+    } else {
+      dlp[i] = l1 >= l2 ? m[i] * l1 * inv : 0.f;
+    }
   }
   if (threadIdx.x == 0) {
     loss[0] = l * inv;
@@ -322,11 +343,14 @@ __global__ __launch_bounds__(64) void group_advantages_kernel(const float* __res
 // sum m*((rho - 1) - d), sum m*k3.
 //   d = lp - old; rho = exp(d); pg = max(-A rho, -A clamp(rho, lo, hi)), lo = 1 - clip_low, hi = 1 + clip_high
 //   dr = ref - lp; k3 = exp(dr) - dr - 1; per = pg + beta * k3          (A = adv[s], per rollout)
+// W (grpo_loss_w): a detached per-token weight w [S, T] multiplies pg and its gradient only
+// (truncated importance sampling): per = w pg + beta k3. Divisors and metrics stay unweighted.
 struct GrpoTok {
   float per, l1, l2, rho, d, edr, k3;
 };
+template <bool W>
 __device__ __forceinline__ GrpoTok grpo_token(float lp, float old, float ref, float a, float lo,
-                                              float hi, float beta) {
+                                              float hi, float beta, float w) {
   GrpoTok t;
   t.d = lp - old;
   t.rho = expf(t.d);
@@ -335,16 +359,22 @@ __device__ __forceinline__ GrpoTok grpo_token(float lp, float old, float ref, fl
   const float dr = ref - lp;
   t.edr = expf(dr);
   t.k3 = t.edr - dr - 1.f;
-  t.per = fmaxf(t.l1, t.l2) + beta * t.k3;
+  if constexpr (W) {
+    // the unweighted instantiation compiles its sum to fma(beta, k3, pg): the same fma here
+    t.per = fmaf(beta, t.k3, is_mul(w, fmaxf(t.l1, t.l2)));
+  } else {
+    t.per = fmaxf(t.l1, t.l2) + beta * t.k3;
+  }
   return t;
 }
 
 constexpr int kGrpoThreads = 256;
 
+template <bool W>
 __global__ __launch_bounds__(kGrpoThreads) void grpo_partials_kernel(
     const float* __restrict__ lp, const float* __restrict__ old, const float* __restrict__ ref,
     const float* __restrict__ adv, const float* __restrict__ m, int S, int T, float lo, float hi,
-    float beta, float* __restrict__ part) {
+    float beta, float* __restrict__ part, const float* __restrict__ w) {
   __shared__ float scratch[kGrpoThreads / 64];
   const int s = blockIdx.x;
   const int64_t base = static_cast<int64_t>(s) * T;
@@ -352,7 +382,8 @@ __global__ __launch_bounds__(kGrpoThreads) void grpo_partials_kernel(
   float cnt = 0.f, l = 0.f, cf = 0.f, akl = 0.f, klr = 0.f;
   for (int t = threadIdx.x; t < T; t += kGrpoThreads) {
     const float mi = m[base + t];
-    const GrpoTok k = grpo_token(lp[base + t], old[base + t], ref[base + t], a, lo, hi, beta);
+    const GrpoTok k = grpo_token<W>(lp[base + t], old[base + t], ref[base + t], a, lo, hi, beta,
+                                    W ? w[base + t] : 1.f);
     cnt += mi;
     l += mi * k.per;
     cf += mi * ((k.rho < lo || k.rho > hi) ? 1.f : 0.f);
@@ -381,12 +412,15 @@ __global__ __launch_bounds__(kGrpoThreads) void grpo_partials_kernel(
 //   mode 2 constant (Dr. GRPO): sum_s l_s / (S * max_len)
 //   denom (optional, device [1]) replaces the final divisor (micro-batches of one rollout batch)
 //   dlp = m * w_s * [(l1 >= l2 ? l1 : 0) - beta * (exp(dr) - 1)] / divisor, w_s = 1/max(c_s,1) in mode 0
+//         (W: the importance weight multiplies the (l1 >= l2 ? l1 : 0) term)
 //   metrics: [0] clipfrac, [1] approx KL, [2] k3 KL to the reference (token means), [3] tokens
+template <bool W>
 __global__ __launch_bounds__(kGrpoThreads) void grpo_grad_kernel(
     const float* __restrict__ lp, const float* __restrict__ old, const float* __restrict__ ref,
     const float* __restrict__ adv, const float* __restrict__ m, const float* __restrict__ part,
     const float* __restrict__ denom, int S, int T, float lo, float hi, float beta, int mode,
-    float max_len, float* __restrict__ loss, float* __restrict__ dlp, float* __restrict__ metrics) {
+    float max_len, float* __restrict__ loss, float* __restrict__ dlp, float* __restrict__ metrics,
+    const float* __restrict__ w) {
   __shared__ float scratch[kGrpoThreads / 64];
   const int s = blockIdx.x;
   float cnt = 0.f;
@@ -421,8 +455,111 @@ __global__ __launch_bounds__(kGrpoThreads) void grpo_grad_kernel(
   const float a = adv[s];
   const float scale = (mode == 0 ? 1.f / fmaxf(part[s], 1.f) : 1.f) / div;
   for (int t = threadIdx.x; t < T; t += kGrpoThreads) {
-    const GrpoTok k = grpo_token(lp[base + t], old[base + t], ref[base + t], a, lo, hi, beta);
-    dlp[base + t] = m[base + t] * scale * ((k.l1 >= k.l2 ? k.l1 : 0.f) - beta * (k.edr - 1.f));
+    const GrpoTok k = grpo_token<W>(lp[base + t], old[base + t], ref[base + t], a, lo, hi, beta, 1.f);
+    const float pg = k.l1 >= k.l2 ? k.l1 : 0.f;
+    if constexpr (W) {
+      // w pg as fma(w, pg, 0): rounded on its own (w = 1 leaves pg exact) and not a product the
+      // compiler pairs or contracts with its neighbours, so the rest of the expression compiles as
+      // it does in the unweighted instantiation, in the unrolled loop and in the remainder loop
+      dlp[base + t] = m[base + t] * scale * (fmaf(w[base + t], pg, 0.f) - beta * (k.edr - 1.f));
+    } else {
+      dlp[base + t] = m[base + t] * scale * (pg - beta * (k.edr - 1.f));
+    }
+  }
+}
+
+// ==============================================================================================
+// Truncated importance weights for the rollout engine / trainer mismatch: the surrogate of every
+// action token is multiplied by a detached w = min(pi_trainer_old(a) / pi_rollout(a), C).
+// ==============================================================================================
+
+// Launch 1 of 2: one workgroup per row writes the row's weights and five partials part[k * S + s]:
+// token count, sum w, sum w^2, #{r > C}, #{r < F} (mask mode).
+//   d = trainer_lp - rollout_lp;  level 0 (token): l = d;  level 1 (sequence): l = sum_t m d / max(c_s, 1)
+//   r = exp(l);  mode 0 (truncate): w = min(r, C);  mode 1 (mask): w = F <= r <= C ? r : 0
+// Entries outside the mask are never read into a sum (the rollout grid holds zeros there) and get
+// w = 0. exp overflowing to inf is still compared and clamped correctly: every output is finite.
+constexpr int kIsThreads = 256;
+
+__global__ __launch_bounds__(kIsThreads) void rollout_is_rows_kernel(
+    const float* __restrict__ tlp, const float* __restrict__ rlp, const float* __restrict__ m, int S,
+    int T, float cap, float floor_, int level, int mode, float* __restrict__ w,
+    float* __restrict__ part) {
+  __shared__ float scratch[kIsThreads / 64];
+  const int s = blockIdx.x;
+  const int64_t base = static_cast<int64_t>(s) * T;
+  float rseq = 0.f;
+  if (level == 1) {  // the length-normalised (geometric-mean) ratio of the row
+    float a = 0.f, c = 0.f;
+    for (int t = threadIdx.x; t < T; t += kIsThreads) {
+      const float mi = m[base + t];
+      if (mi != 0.f) {
+        a += tlp[base + t] - rlp[base + t];
+        c += mi;
+      }
+    }
+    a = block_sum<kIsThreads>(a, scratch);
+    c = block_sum<kIsThreads>(c, scratch);
+    rseq = expf(a / fmaxf(c, 1.f));
+  }
+  float cnt = 0.f, sw = 0.f, sw2 = 0.f, nhi = 0.f, nlo = 0.f;
+  for (int t = threadIdx.x; t < T; t += kIsThreads) {
+    const float mi = m[base + t];
+    float wi = 0.f;
+    if (mi != 0.f) {
+      const float r = level == 1 ? rseq : expf(tlp[base + t] - rlp[base + t]);
+      const bool high = r > cap, low = mode == 1 && r < floor_;
+      wi = mode == 0 ? fminf(r, cap) : ((high || low) ? 0.f : r);
+      cnt += mi;
+      sw += wi;
+      sw2 += wi * wi;
+      nhi += high ? 1.f : 0.f;
+      nlo += low ? 1.f : 0.f;
+    }
+    w[base + t] = wi;
+  }
+  cnt = block_sum<kIsThreads>(cnt, scratch);
+  sw = block_sum<kIsThreads>(sw, scratch);
+  sw2 = block_sum<kIsThreads>(sw2, scratch);
+  nhi = block_sum<kIsThreads>(nhi, scratch);
+  nlo = block_sum<kIsThreads>(nlo, scratch);
+  if (threadIdx.x == 0) {
+    part[s] = cnt;
+    part[S + s] = sw;
+    part[2 * S + s] = sw2;
+    part[3 * S + s] = nhi;
+    part[4 * S + s] = nlo;
+  }
+}
+
+// Launch 2 of 2: one workgroup sums the S partials in a fixed order (no float atomics: two runs are
+// bitwise equal) and writes, over the n action tokens,
+//   metrics: [0] mean w, [1] #{r > C} / n, [2] #{r < F} / n, [3] ESS fraction
+//            min((sum w)^2 / (n sum w^2), 1) (0 when sum w^2 = 0), [4] n           (n -> max(n, 1) in divisors)
+__global__ __launch_bounds__(kIsThreads) void rollout_is_metrics_kernel(const float* __restrict__ part,
+                                                                        int S,
+                                                                        float* __restrict__ metrics) {
+  __shared__ float scratch[kIsThreads / 64];
+  float cnt = 0.f, sw = 0.f, sw2 = 0.f, nhi = 0.f, nlo = 0.f;
+  for (int i = threadIdx.x; i < S; i += kIsThreads) {
+    cnt += part[i];
+    sw += part[S + i];
+    sw2 += part[2 * S + i];
+    nhi += part[3 * S + i];
+    nlo += part[4 * S + i];
+  }
+  cnt = block_sum<kIsThreads>(cnt, scratch);
+  sw = block_sum<kIsThreads>(sw, scratch);
+  sw2 = block_sum<kIsThreads>(sw2, scratch);
+  nhi = block_sum<kIsThreads>(nhi, scratch);
+  nlo = block_sum<kIsThreads>(nlo, scratch);
+  if (threadIdx.x == 0) {
+    const float n1 = fmaxf(cnt, 1.f);
+    metrics[0] = sw / n1;
+    metrics[1] = nhi / n1;
+    metrics[2] = nlo / n1;
+    metrics[3] = sw2 > 0.f ? fminf((sw * sw) / (n1 * sw2), 1.f) : 0.f;  // <= 1 (Cauchy-Schwarz) up to rounding
+    metrics[4] = cnt;
   }
 }
 
@@ -436,9 +573,25 @@ void launch_grpo_loss(const float* lp, const float* old, const float* ref, const
                       const float* m, const float* denom, int S, int T, float lo, float hi,
                       float beta, int mode, float max_len, float* part, float* loss, float* dlp,
                       float* metrics, hipStream_t st) {
-  grpo_partials_kernel<<<S, kGrpoThreads, 0, st>>>(lp, old, ref, adv, m, S, T, lo, hi, beta, part);
-  grpo_grad_kernel<<<S, kGrpoThreads, 0, st>>>(lp, old, ref, adv, m, part, denom, S, T, lo, hi, beta,
-                                              mode, max_len, loss, dlp, metrics);
+  grpo_partials_kernel<false><<<S, kGrpoThreads, 0, st>>>(lp, old, ref, adv, m, S, T, lo, hi, beta,
+                                                           part, nullptr);
+  grpo_grad_kernel<false><<<S, kGrpoThreads, 0, st>>>(lp, old, ref, adv, m, part, denom, S, T, lo, hi,
+                                                      beta, mode, max_len, loss, dlp, metrics, nullptr);
+}
+void launch_grpo_loss_w(const float* lp, const float* old, const float* ref, const float* adv,
+                        const float* m, const float* w, const float* denom, int S, int T, float lo,
+                        float hi, float beta, int mode, float max_len, float* part, float* loss,
+                        float* dlp, float* metrics, hipStream_t st) {
+  grpo_partials_kernel<true><<<S, kGrpoThreads, 0, st>>>(lp, old, ref, adv, m, S, T, lo, hi, beta,
+                                                          part, w);
+  grpo_grad_kernel<true><<<S, kGrpoThreads, 0, st>>>(lp, old, ref, adv, m, part, denom, S, T, lo, hi,
+                                                     beta, mode, max_len, loss, dlp, metrics, w);
+}
+void launch_rollout_is_weights(const float* tlp, const float* rlp, const float* m, int S, int T,
+                               float cap, float floor_, int level, int mode, float* part, float* w,
+                               float* metrics, hipStream_t st) {
+  rollout_is_rows_kernel<<<S, kIsThreads, 0, st>>>(tlp, rlp, m, S, T, cap, floor_, level, mode, w, part);
+  rollout_is_metrics_kernel<<<1, kIsThreads, 0, st>>>(part, S, metrics);
 }
 void launch_gae(const float* r, const float* v, const float* m, int S, int T, float gamma,
                 float lam, float* adv, float* ret, hipStream_t st) {
@@ -448,7 +601,12 @@ void launch_gae(const float* r, const float* v, const float* m, int S, int T, fl
 void launch_ppo_policy_loss(const float* lp, const float* old, const float* adv, const float* m,
                             int64_t n, float eps, float* loss, float* dlp, float* metrics,
                             hipStream_t st) {
-  ppo_policy_loss_kernel<<<1, 1024, 0, st>>>(lp, old, adv, m, n, eps, loss, dlp, metrics);
+  ppo_policy_loss_kernel<false><<<1, 1024, 0, st>>>(lp, old, adv, m, n, eps, loss, dlp, metrics, nullptr);
+}
+void launch_ppo_policy_loss_w(const float* lp, const float* old, const float* adv, const float* m,
+                              const float* w, int64_t n, float eps, float* loss, float* dlp,
+                              float* metrics, hipStream_t st) {
+  ppo_policy_loss_kernel<true><<<1, 1024, 0, st>>>(lp, old, adv, m, n, eps, loss, dlp, metrics, w);
 }
 void launch_ppo_value_loss(const float* val, const float* old, const float* ret, const float* m,
                            int64_t n, float clip, float* loss, float* dval, hipStream_t st) {

@@ -7,6 +7,7 @@ benchmarks and tests share one implementation.
   rlhf_loss        reference train_rlhf.py:127-153 (REINFORCE with KL-shaped reward)
   ppo_rollout_stats / ppo_loss  token-level actor-critic PPO (GAE, clipped surrogate + value
                    loss) for `ppo.algorithm: ppo` (north-star config; not in the reference)
+  rollout_is_stats truncated importance weights (rollout engine vs trainer) for the two below
   grpo_rollout_stats / grpo_loss  critic-free group-relative policy optimisation (group
                    advantages, token-level clipped surrogate + k3 KL to the reference) for
                    `ppo.algorithm: grpo` (not in the reference)
@@ -159,16 +160,33 @@ def rollout_mismatch(rollout_lp: torch.Tensor, trainer_lp: torch.Tensor, act: to
     return {"rollout_kl": d.sum() / act.sum().clamp(min=1), "rollout_logp_absdiff_max": d.abs().max()}
 
 
+def rollout_is_stats(rollout_logp: torch.Tensor, trainer_lp: torch.Tensor, act: torch.Tensor,
+                     cap: float = 2.0, floor: Optional[float] = None, level: str = "token",
+                     mode: str = "truncate"):
+    """The `is_weight` / `rollout_is` entries of the PPO / GRPO stats: the truncated importance
+    weights of one rollout batch (`ops.rollout_is_weights` of the trainer's own old-policy
+    log-probs against the rollout engine's, both [S, T] action grids) and their metrics
+    `rollout_is_mean`, `rollout_is_frac_high`, `rollout_is_frac_low`, `rollout_is_ess` (device
+    tensors: no host sync)."""
+    w, met = ops.rollout_is_weights(trainer_lp, rollout_logp, act, cap, floor, level, mode)
+    return {"is_weight": w, "rollout_is": {f"rollout_{k}": v for k, v in met.items() if k != "tokens"}}
+
+
 @torch.no_grad()
 def ppo_rollout_stats(policy, ref, critic, seqs, mask, prompt_len: int, scores, kl_coef: float = 0.1,
                       gamma: float = 1.0, lam: float = 0.95, whiten: bool = True,
-                      old_logp: Optional[torch.Tensor] = None):
+                      old_logp: Optional[torch.Tensor] = None, rollout_logp: Optional[torch.Tensor] = None,
+                      is_cap: float = 2.0, is_floor: Optional[float] = None, is_level: str = "token",
+                      is_mode: str = "truncate"):
     """Token-level PPO targets for one batch of rollouts (actor-critic; the north-star
     "PPO RLHF (actor + critic + reward)" config). Per-token reward = -kl_coef * (logp - logp_ref)
     on every action, plus the reward-model score on the last action; GAE(gamma, lam) over the
     critic's values; advantages whitened over the action tokens. `old_logp` ([S, T] action grid,
     e.g. `rollout_logp_grid` of the rollout engine's log-probs): used as the old-policy log-probs,
-    in the KL reward too, instead of a policy forward over the rollouts."""
+    in the KL reward too, instead of a policy forward over the rollouts. `rollout_logp` (the same
+    kind of grid) instead leaves the old-policy log-probs and the KL reward the trainer's own and
+    adds `is_weight` / `rollout_is` (`rollout_is_stats` with the four `is_*` settings): truncated
+    importance weights for `ppo_loss`, computed once per rollout batch."""
     old_lp = old_logp.float() if old_logp is not None else policy.token_logprobs(seqs, mask)
     ref_lp = ref.token_logprobs(seqs, mask)
     values = critic(seqs, mask)
@@ -185,8 +203,11 @@ def ppo_rollout_stats(policy, ref, critic, seqs, mask, prompt_len: int, scores, 
         mu = (adv * act).sum() / n
         var = (((adv - mu) ** 2) * act).sum() / n
         adv = (adv - mu) * torch.rsqrt(var + 1e-8) * act
-    return {"old_logp": old_lp, "values": values, "advantages": adv, "returns": ret, "act": act,
-            "kl": kl.sum(1) / act.sum(1).clamp(min=1), "scores": scores.float()}
+    out = {"old_logp": old_lp, "values": values, "advantages": adv, "returns": ret, "act": act,
+           "kl": kl.sum(1) / act.sum(1).clamp(min=1), "scores": scores.float()}
+    if rollout_logp is not None:
+        out.update(rollout_is_stats(rollout_logp, old_lp, act, is_cap, is_floor, is_level, is_mode))
+    return out
 
 
 # The actor and the critic of a PPO minibatch are independent until the summed loss: the critic's
@@ -235,7 +256,8 @@ def ppo_loss(policy, critic, seqs, mask, stats: Dict[str, torch.Tensor], clip_ep
              log_entropy: bool = False):
     """Clipped surrogate (HIP fused fwd+bwd) + vf_coef * clipped value loss on one minibatch,
     minus entropy_coef * the mean policy entropy over action tokens (`metrics["entropy"]`, also
-    with `log_entropy` alone). Run its backward through `ppo_backward` (joins the critic's stream
+    with `log_entropy` alone). `stats["is_weight"]` (optional) weights the surrogate per token.
+    Run its backward through `ppo_backward` (joins the critic's stream
     afterwards)."""
     cs = ppo_critic_stream(seqs.device)
     main = torch.cuda.current_stream(seqs.device) if cs is not None else None
@@ -245,7 +267,8 @@ def ppo_loss(policy, critic, seqs, mask, stats: Dict[str, torch.Tensor], clip_ep
             v = critic(seqs, mask)
             vl = ops.ppo_value_loss(v, stats["values"], stats["returns"], stats["act"], value_clip)
     lp, bonus, entropy = token_logprobs_entropy(policy, seqs, mask, stats["act"], entropy_coef, log_entropy)
-    pl, pm = ops.ppo_policy_loss(lp, stats["old_logp"], stats["advantages"], stats["act"], clip_eps)
+    pl, pm = ops.ppo_policy_loss(lp, stats["old_logp"], stats["advantages"], stats["act"], clip_eps,
+                                 is_weight=stats.get("is_weight"))
     if cs is None:
         v = critic(seqs, mask)
         vl = ops.ppo_value_loss(v, stats["values"], stats["returns"], stats["act"], value_clip)
@@ -274,23 +297,31 @@ def ppo_backward(loss: torch.Tensor) -> None:
 @torch.no_grad()
 def grpo_rollout_stats(policy, ref, seqs, mask, prompt_len: int, scores, G: int, beta: float = 0.04,
                        scale_std: bool = True, need_old: bool = False,
-                       old_logp: Optional[torch.Tensor] = None):
+                       old_logp: Optional[torch.Tensor] = None, rollout_logp: Optional[torch.Tensor] = None,
+                       is_cap: float = 2.0, is_floor: Optional[float] = None, is_level: str = "token",
+                       is_mode: str = "truncate"):
     """GRPO targets for one batch of group rollouts (rows p*G .. p*G+G-1 sample prompt p). The
     reward is the reward-model score alone (the KL lives in the loss); a rollout's advantage is its
     score standardised inside its group. The reference's token log-probs are skipped entirely
     when beta == 0, and the old policy's are computed only with `need_old` (more than one update
     per rollout batch; a single on-policy update uses old = logp.detach()). `old_logp` ([S, T]
     action grid, e.g. `rollout_logp_grid` of the rollout engine's log-probs): returned as the
-    old-policy log-probs, whatever `need_old`, with no policy forward."""
+    old-policy log-probs, whatever `need_old`, with no policy forward. `rollout_logp` (the same
+    kind of grid) instead keeps the old-policy log-probs the trainer's own (the forward always
+    runs, as with `need_old`) and adds `is_weight` / `rollout_is` (`rollout_is_stats` with the four
+    `is_*` settings): truncated importance weights for `grpo_loss`, computed once per rollout batch."""
     act = action_mask(mask, prompt_len)
     adv, gm = ops.group_advantages(scores, G, scale_std)
     ref_lp = ref.token_logprobs(seqs, mask) if beta != 0 else None
     if old_logp is not None:
         old_logp = old_logp.float()
-    elif need_old:
+    elif need_old or rollout_logp is not None:
         old_logp = policy.token_logprobs(seqs, mask)
-    return {"act": act, "advantages": adv, "ref_logp": ref_lp, "old_logp": old_logp,
-            "scores": scores.float(), "reward_std": gm["reward_std"], "frac_zero_std": gm["frac_zero_std"]}
+    out = {"act": act, "advantages": adv, "ref_logp": ref_lp, "old_logp": old_logp,
+           "scores": scores.float(), "reward_std": gm["reward_std"], "frac_zero_std": gm["frac_zero_std"]}
+    if rollout_logp is not None:
+        out.update(rollout_is_stats(rollout_logp, old_logp, act, is_cap, is_floor, is_level, is_mode))
+    return out
 
 
 def grpo_loss(policy, seqs, mask, stats: Dict[str, torch.Tensor], clip_low: float = 0.2,
@@ -300,11 +331,13 @@ def grpo_loss(policy, seqs, mask, stats: Dict[str, torch.Tensor], clip_low: floa
     """Token-level clipped surrogate + beta * k3 KL to the reference (HIP fused fwd+bwd) on one
     (micro-)batch of rollouts; `stats` from `grpo_rollout_stats`, sliced to the same rows.
     `entropy_coef` / `log_entropy` / `n_act`: the entropy bonus and metric of
-    `token_logprobs_entropy`."""
+    `token_logprobs_entropy`. `stats["is_weight"]` (optional) weights the policy-gradient term per
+    token."""
     lp, bonus, entropy = token_logprobs_entropy(policy, seqs, mask, stats["act"], entropy_coef, log_entropy,
                                                 n_act)
     loss, m = ops.grpo_loss(lp, stats.get("old_logp"), stats.get("ref_logp"), stats["advantages"],
-                            stats["act"], clip_low, clip_high, beta, loss_type, max_len, denom)
+                            stats["act"], clip_low, clip_high, beta, loss_type, max_len, denom,
+                            is_weight=stats.get("is_weight"))
     if bonus is not None:
         loss = loss - bonus
     if entropy is not None:

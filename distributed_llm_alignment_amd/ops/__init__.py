@@ -8,7 +8,7 @@ from .linear import (accumulate_weight_grad, enable_fp8_inference, fp8_inference
                      linear_add)
 from .logprob import linear_logprob, linear_logprob_entropy, seq_reduce, sequence_logprob, shifted_targets, token_nll
 from .losses import (dpo_loss, ensemble_kl, gae, group_advantages, grpo_loss, kl_penalty_pg,
-                     pairwise_loss, ppo_policy_loss, ppo_value_loss)
+                     pairwise_loss, ppo_policy_loss, ppo_value_loss, rollout_is_weights)
 from .norm import add_norm, layer_norm, rms_norm
 
 __all__ = [
@@ -16,6 +16,6 @@ __all__ = [
     "_ext", "decode", "moe", "gelu_new", "swiglu", "swiglu_mlp", "swiglu_mlp_ok", "RotaryCache", "attention_core", "qkv_attention",
     "ref_attention", "linear_logprob", "linear_logprob_entropy", "seq_reduce", "sequence_logprob", "shifted_targets",
     "token_nll", "dpo_loss", "ensemble_kl", "kl_penalty_pg", "pairwise_loss", "gae",
-    "ppo_policy_loss", "ppo_value_loss", "group_advantages", "grpo_loss", "add_norm", "layer_norm", "rms_norm", "linear", "linear_add",
+    "ppo_policy_loss", "ppo_value_loss", "group_advantages", "grpo_loss", "rollout_is_weights", "add_norm", "layer_norm", "rms_norm", "linear", "linear_add",
     "accumulate_weight_grad",
 ]

@@ -10,9 +10,12 @@ host sync); CPU paths are the literal reference formulas:
     reference's REINFORCE above stays the default RLHF algorithm)
   * group_advantages / grpo_loss: critic-free group-relative policy optimisation (GRPO and its
     DAPO / Dr. GRPO normalisations; not in the reference)
+  * rollout_is_weights: truncated importance weights for the rollout engine / trainer mismatch,
+    taken by grpo_loss / ppo_policy_loss as `is_weight` (not in the reference)
 """
 from __future__ import annotations
 
+import math
 from typing import Dict, Optional, Tuple
 
 import torch
@@ -194,20 +197,46 @@ class _PPOPolicyFn(torch.autograd.Function):
         return dlp * gloss, None, None, None, None
 
 
+class _PPOPolicyWFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, lp, old, adv, mask, w, eps):
+        loss, dlp, metrics = _ext.require().ppo_policy_loss_w(lp, old, adv, mask, w, eps)
+        ctx.save_for_backward(dlp)
+        ctx.mark_non_differentiable(metrics)
+        return loss, metrics
+
+    @staticmethod
+    def backward(ctx, gloss, _gm):
+        (dlp,) = ctx.saved_tensors
+        return dlp * gloss, None, None, None, None, None
+
+
 def ppo_policy_loss(logp: torch.Tensor, old_logp: torch.Tensor, advantages: torch.Tensor,
-                    mask: torch.Tensor, clip_eps: float = 0.2):
+                    mask: torch.Tensor, clip_eps: float = 0.2, *, is_weight: Optional[torch.Tensor] = None):
     """Clipped surrogate, mean over masked tokens of max(-A rho, -A clip(rho, 1 +- eps)),
-    rho = exp(logp - old_logp). Returns (loss, {clipfrac, approx_kl}) (device tensors)."""
+    rho = exp(logp - old_logp). Returns (loss, {clipfrac, approx_kl}) (device tensors).
+    `is_weight` (a detached grid like `logp`, e.g. from `rollout_is_weights`) multiplies every
+    token's surrogate; the divisor stays the masked-token count and the metrics stay unweighted."""
     lp = logp.float().contiguous()
     old = old_logp.detach().float().contiguous()
     a = advantages.detach().float().contiguous()
     m = mask.detach().float().contiguous()
+    w = None
+    if is_weight is not None:
+        w = is_weight.detach().float().contiguous()
+        if w.shape != lp.shape:
+            raise ValueError(f"ppo_policy_loss: is_weight {tuple(w.shape)} must have logp's shape {tuple(lp.shape)}")
     if _ext.use_native(lp):
-        loss, met = _PPOPolicyFn.apply(lp, old, a, m, float(clip_eps))
+        if w is None:
+            loss, met = _PPOPolicyFn.apply(lp, old, a, m, float(clip_eps))
+        else:
+            loss, met = _PPOPolicyWFn.apply(lp, old, a, m, w, float(clip_eps))
         return loss, {"clipfrac": met[0], "approx_kl": met[1]}
     n = m.sum().clamp(min=1)
     rho = torch.exp(lp - old)
     per = torch.maximum(-a * rho, -a * rho.clamp(1 - clip_eps, 1 + clip_eps))
+    if w is not None:
+        per = w * per
     loss = (per * m).sum() / n
     with torch.no_grad():
         clipfrac = (((rho - 1).abs() > clip_eps).float() * m).sum() / n
@@ -281,7 +310,8 @@ def group_advantages(scores: torch.Tensor, G: int, scale_std: bool = True, eps: 
 
 def _ref_grpo_loss(logp, old_logp, ref_logp, adv, mask, clip_low: float = 0.2,
                    clip_high: Optional[float] = None, beta: float = 0.04, loss_type: str = "sequence",
-                   max_len: Optional[int] = None, denom: Optional[torch.Tensor] = None):
+                   max_len: Optional[int] = None, denom: Optional[torch.Tensor] = None,
+                   is_weight: Optional[torch.Tensor] = None):
     """The torch formula of `grpo_loss` (any device, differentiable in `logp` through autograd)."""
     clip_high = clip_low if clip_high is None else clip_high
     lp = logp.float()
@@ -291,6 +321,8 @@ def _ref_grpo_loss(logp, old_logp, ref_logp, adv, mask, clip_low: float = 0.2,
     d = lp - old
     rho = torch.exp(d)
     per = torch.maximum(-a * rho, -a * rho.clamp(1 - clip_low, 1 + clip_high))
+    if is_weight is not None:
+        per = is_weight.detach().float() * per
     kl = torch.zeros_like(per)
     if ref_logp is not None:
         dr = ref_logp.detach().float() - lp
@@ -331,10 +363,26 @@ class _GRPOFn(torch.autograd.Function):
         return (dlp * gloss,) + (None,) * 10
 
 
+class _GRPOWFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, lp, old, ref, adv, mask, w, denom, clip_low, clip_high, beta, mode, max_len):
+        loss, dlp, metrics = _ext.require().grpo_loss_w(lp, old, ref, adv, mask, w, denom, clip_low,
+                                                        clip_high, beta, mode, max_len)
+        ctx.save_for_backward(dlp)
+        ctx.mark_non_differentiable(metrics)
+        return loss, metrics
+
+    @staticmethod
+    def backward(ctx, gloss, _gm):
+        (dlp,) = ctx.saved_tensors
+        return (dlp * gloss,) + (None,) * 11
+
+
 def grpo_loss(logp: torch.Tensor, old_logp: Optional[torch.Tensor], ref_logp: Optional[torch.Tensor],
               adv: torch.Tensor, mask: torch.Tensor, clip_low: float = 0.2,
               clip_high: Optional[float] = None, beta: float = 0.04, loss_type: str = "sequence",
-              max_len: Optional[int] = None, denom: Optional[torch.Tensor] = None
+              max_len: Optional[int] = None, denom: Optional[torch.Tensor] = None, *,
+              is_weight: Optional[torch.Tensor] = None
               ) -> Tuple[torch.Tensor, Dict[str, torch.Tensor]]:
     """GRPO objective on [S, T] fp32 grids (`mask`: action tokens), `adv` [S] one value per rollout.
 
@@ -346,8 +394,10 @@ def grpo_loss(logp: torch.Tensor, old_logp: Optional[torch.Tensor], ref_logp: Op
     `old_logp=None`: on-policy (old = logp.detach()); `ref_logp=None` only with beta == 0;
     `clip_high=None`: clip_low. `denom` (fp32 device tensor [1]) replaces the final divisor, so the
     micro-batches of one rollout batch share the whole batch's normaliser without a host sync
-    (sequence mode: the full batch's S). Returns (loss, metrics) with device tensors `clipfrac`,
-    `approx_kl`, `kl_ref` (token means over the mask) and `tokens`."""
+    (sequence mode: the full batch's S). `is_weight` ([S, T], detached, e.g. from
+    `rollout_is_weights`) multiplies pg only: per = w pg + beta kl; the divisors stay the
+    action-token counts and the metrics stay unweighted. Returns (loss, metrics) with device
+    tensors `clipfrac`, `approx_kl`, `kl_ref` (token means over the mask) and `tokens`."""
     if loss_type not in GRPO_LOSS_TYPES:
         raise ValueError(f"grpo_loss: loss_type must be one of {'|'.join(GRPO_LOSS_TYPES)}, got {loss_type!r}")
     if loss_type == "constant" and max_len is None and denom is None:
@@ -356,15 +406,101 @@ def grpo_loss(logp: torch.Tensor, old_logp: Optional[torch.Tensor], ref_logp: Op
         raise ValueError("grpo_loss: ref_logp=None is allowed only with beta == 0")
     clip_high = clip_low if clip_high is None else clip_high
     lp = logp.float().contiguous()
+    w = None
+    if is_weight is not None:
+        w = is_weight.detach().float().contiguous()
+        if w.shape != lp.shape:
+            raise ValueError(f"grpo_loss: is_weight {tuple(w.shape)} must have logp's shape {tuple(lp.shape)}")
     if not _ext.use_native(lp):
         return _ref_grpo_loss(lp, old_logp, ref_logp, adv, mask, clip_low, clip_high,
-                              beta, loss_type, max_len, denom)
+                              beta, loss_type, max_len, denom, w)
     # absent operands alias logp: d = 0 (rho = 1) on-policy, dr = 0 (kl = 0) without a reference
     old = lp.detach() if old_logp is None else old_logp.detach().float().contiguous()
     ref = lp.detach() if ref_logp is None else ref_logp.detach().float().contiguous()
     a = adv.detach().float().contiguous().view(-1)
     m = mask.detach().float().contiguous()
     dn = denom.detach().float().reshape(1) if denom is not None else None
-    loss, met = _GRPOFn.apply(lp, old, ref, a, m, dn, float(clip_low), float(clip_high), float(beta),
-                              GRPO_LOSS_TYPES.index(loss_type), float(max_len or 0))
+    tail = (dn, float(clip_low), float(clip_high), float(beta), GRPO_LOSS_TYPES.index(loss_type),
+            float(max_len or 0))
+    if w is None:
+        loss, met = _GRPOFn.apply(lp, old, ref, a, m, *tail)
+    else:
+        loss, met = _GRPOWFn.apply(lp, old, ref, a, m, w, *tail)
     return loss, {"clipfrac": met[0], "approx_kl": met[1], "kl_ref": met[2], "tokens": met[3]}
+
+
+# ------------------------------------------- truncated importance weights (rollout / trainer)
+# The rollout engine (bf16 / fp8 decode kernels, possibly one step stale) is not the policy the
+# trainer differentiates. Truncated importance sampling keeps the trainer's own old-policy
+# log-probs for the PPO ratio and multiplies every action token's surrogate by a detached, capped
+# w = min(pi_trainer_old(a) / pi_rollout(a), C); the masked variant drops tokens outside [F, C].
+ROLLOUT_IS_LEVELS = ("token", "sequence")
+ROLLOUT_IS_MODES = ("truncate", "mask")
+
+
+def _rollout_is_args(cap, floor, level, mode):
+    if level not in ROLLOUT_IS_LEVELS:
+        raise ValueError(f"rollout_is_weights: level must be {'|'.join(ROLLOUT_IS_LEVELS)}, got {level!r}")
+    if mode not in ROLLOUT_IS_MODES:
+        raise ValueError(f"rollout_is_weights: mode must be {'|'.join(ROLLOUT_IS_MODES)}, got {mode!r}")
+    cap = float(cap)
+    if not (math.isfinite(cap) and cap > 0):
+        raise ValueError(f"rollout_is_weights: cap must be finite and > 0, got {cap!r}")
+    floor = 1.0 / cap if floor is None else float(floor)
+    if not 0 <= floor <= cap:
+        raise ValueError(f"rollout_is_weights: floor must lie in [0, cap = {cap}], got {floor!r}")
+    return cap, floor
+
+
+def _ref_rollout_is_weights(trainer_lp, rollout_lp, mask, cap: float = 2.0, floor: Optional[float] = None,
+                            level: str = "token", mode: str = "truncate"):
+    """The torch formula of `rollout_is_weights` (any device): (w [S, T], metrics [5])."""
+    cap, floor = _rollout_is_args(cap, floor, level, mode)
+    m = mask.detach().float()
+    on = m != 0
+    d = torch.where(on, trainer_lp.detach().float() - rollout_lp.detach().float(), torch.zeros_like(m))
+    if level == "sequence":
+        d = (d.sum(1, keepdim=True) / m.sum(1, keepdim=True).clamp(min=1)).expand_as(m)
+    r = torch.exp(d)
+    high = (r > cap) & on
+    low = (r < floor) & on if mode == "mask" else torch.zeros_like(on)
+    w = r.clamp(max=cap) if mode == "truncate" else torch.where(high | low, torch.zeros_like(r), r)
+    w = torch.where(on, w, torch.zeros_like(w))
+    n = m.sum()
+    n1 = n.clamp(min=1)
+    sw, sw2 = w.sum(), (w * w).sum()
+    # a fraction: <= 1 by Cauchy-Schwarz, clamped against the last rounding
+    ess = torch.where(sw2 > 0, (sw * sw / (n1 * sw2.clamp(min=torch.finfo(torch.float32).tiny))).clamp(max=1),
+                      torch.zeros_like(sw))
+    return w, torch.stack([sw / n1, high.float().sum() / n1, low.float().sum() / n1, ess, n])
+
+
+@torch.no_grad()
+def rollout_is_weights(trainer_lp: torch.Tensor, rollout_lp: torch.Tensor, mask: torch.Tensor,
+                       cap: float = 2.0, floor: Optional[float] = None, level: str = "token",
+                       mode: str = "truncate") -> Tuple[torch.Tensor, Dict[str, torch.Tensor]]:
+    """Truncated importance weights (no gradient) on [S, T] fp32 action grids: `trainer_lp` the
+    trainer's own old-policy log-probs, `rollout_lp` the rollout engine's, `mask` the action tokens.
+
+        d = trainer_lp - rollout_lp;  token: l = d;  sequence: l_s = sum_t m d / max(sum_t m, 1)
+        r = exp(l);  truncate: w = min(r, cap);  mask: w = r if floor <= r <= cap else 0;  w = 0 off the mask
+
+    The sequence level is the length-normalised (geometric-mean) ratio, not the product.
+    `floor=None`: 1 / cap (mask mode only). Returns (w, metrics) with device tensors over the n
+    action tokens: `is_mean`, `is_frac_high` (r > cap), `is_frac_low` (r < floor, mask mode; else 0),
+    `is_ess` = (sum w)^2 / (n sum w^2) (at most 1; 0 when every w is 0) and `tokens` = n. One fused HIP op (two launches, no
+    atomics, no host sync) on the GPU."""
+    cap, floor = _rollout_is_args(cap, floor, level, mode)
+    t = trainer_lp.detach().float().contiguous()
+    r = rollout_lp.detach().float().contiguous()
+    m = mask.detach().float().contiguous()
+    if t.dim() != 2 or r.shape != t.shape or m.shape != t.shape:
+        raise ValueError(f"rollout_is_weights: three [S, T] grids of one shape, got {tuple(t.shape)}, "
+                         f"{tuple(r.shape)}, {tuple(m.shape)}")
+    if _ext.use_native(t):
+        w, met = _ext.require().rollout_is_weights(t, r, m, cap, floor, ROLLOUT_IS_LEVELS.index(level),
+                                                   ROLLOUT_IS_MODES.index(mode))
+    else:
+        w, met = _ref_rollout_is_weights(t, r, m, cap, floor, level, mode)
+    return w, {"is_mean": met[0], "is_frac_high": met[1], "is_frac_low": met[2], "is_ess": met[3],
+               "tokens": met[4]}

@@ -42,7 +42,7 @@ per-token policy entropy comes out of the LM-head log-prob kernels' own vocabula
 minibatch's action tokens and `train/entropy` is logged. With both off a run launches exactly the
 kernels it launched before. The REINFORCE loop works on sequence log-probs and has no entropy term.
 
-`ppo.rollout_logprobs: off|monitor|old` (default off), for `ppo` and `grpo`: the fused sampler also
+`ppo.rollout_logprobs: off|monitor|old|correct` (default off), for `ppo` and `grpo`: the fused sampler also
 returns the log-prob of every sampled token under the engine that sampled it
 (`generate(return_logprobs=True)`; temperature 1, full vocabulary, like `token_logprobs`). `monitor`
 leaves the update alone and logs `train/rollout_kl` (mean over action tokens of logp_rollout -
@@ -50,11 +50,25 @@ logp_trainer) and `train/rollout_logp_absdiff_max`: how far fp8 / stale / differ
 rollouts are from the trainer's policy. `old` uses them AS the old-policy log-probs (in PPO's KL
 reward too) and skips the trainer's old-policy forward over the rollouts. With `off` the rollouts
 do not request them and a run launches exactly the kernels it launched before.
+
+`correct` is truncated importance sampling: the trainer keeps its own old-policy log-probs (ratio,
+clip and PPO's KL reward as with `off`; GRPO runs the old-policy forward even on-policy, as
+`monitor` does) and multiplies every action token's surrogate by a detached weight, computed once
+per rollout batch by one fused HIP op and sliced into minibatches and micro-batches:
+    w = min(exp(l), C),  l = logp_trainer_old - logp_rollout     (`rollout_is_mode: truncate`)
+    w = exp(l) if F <= exp(l) <= C else 0                        (`rollout_is_mode: mask`)
+with C = `ppo.rollout_is_cap` (default 2.0), F = `ppo.rollout_is_floor` (default 1 / C), and
+`ppo.rollout_is_level: token` (default) or `sequence`, where l is the row's mean over its action
+tokens (the length-normalised ratio, not the product). The weight multiplies the policy-gradient
+term only; the k3 KL term, every divisor (action-token counts, never sum w) and clipfrac /
+approx_kl / kl stay unweighted. Logged: `train/rollout_is_mean`, `train/rollout_is_frac_high`,
+`train/rollout_is_frac_low`, `train/rollout_is_ess`, and `monitor`'s two metrics.
 """
 from __future__ import annotations
 
 import argparse
 import contextlib
+import math
 import random
 from pathlib import Path
 from typing import Dict, List
@@ -66,7 +80,7 @@ from ..models import (build_reward_model, build_value_model, generate, load_caus
                       load_reward_checkpoint)
 from ..objectives import (grpo_denominator, grpo_loss, grpo_rollout_stats, ppo_backward, ppo_loss,
                           ppo_rollout_stats, rlhf_loss, rollout_logp_grid, rollout_mismatch)
-from ..ops.losses import GRPO_LOSS_TYPES
+from ..ops.losses import GRPO_LOSS_TYPES, ROLLOUT_IS_LEVELS, ROLLOUT_IS_MODES
 from ..parallel.dist import barrier, split_for_rank
 from ..utils.checkpoint import save_state
 from ..utils.config import add_config_args, config_from_args
@@ -98,7 +112,7 @@ def load_prompts(cfg: Dict[str, str]) -> List[str]:
     return [r["prompt"] for r in read_jsonl(path) if r.get("prompt")]
 
 
-ROLLOUT_LOGPROBS = ("off", "monitor", "old")
+ROLLOUT_LOGPROBS = ("off", "monitor", "old", "correct")
 
 
 def rollout_logprobs_mode(ppo: Dict, algo: str) -> str:
@@ -111,6 +125,29 @@ def rollout_logprobs_mode(ppo: Dict, algo: str) -> str:
         raise ValueError("ppo.rollout_logprobs needs token-level log-probs (ppo.algorithm: ppo|grpo); "
                          "the reinforce loop works on sequence log-probs")
     return mode
+
+
+def rollout_is_settings(ppo: Dict) -> Dict:
+    """`ppo.rollout_is_cap / _floor / _level / _mode` (for `rollout_logprobs: correct`) as the
+    `is_*` keyword arguments of `ppo_rollout_stats` / `grpo_rollout_stats`; bad values raise."""
+    try:
+        cap = float(ppo.get("rollout_is_cap", 2.0))
+        floor = ppo.get("rollout_is_floor")
+        floor = None if floor is None else float(floor)
+    except (TypeError, ValueError):
+        raise ValueError(f"ppo.rollout_is_cap / ppo.rollout_is_floor must be numbers, got "
+                         f"{ppo.get('rollout_is_cap')!r} / {ppo.get('rollout_is_floor')!r}") from None
+    level = str(ppo.get("rollout_is_level", "token")).lower()
+    mode = str(ppo.get("rollout_is_mode", "truncate")).lower()
+    if not (math.isfinite(cap) and cap > 0):
+        raise ValueError(f"ppo.rollout_is_cap must be finite and > 0, got {cap!r}")
+    if floor is not None and not 0 <= floor <= cap:
+        raise ValueError(f"ppo.rollout_is_floor must lie in [0, rollout_is_cap = {cap}], got {floor!r}")
+    if level not in ROLLOUT_IS_LEVELS:
+        raise ValueError(f"ppo.rollout_is_level must be {'|'.join(ROLLOUT_IS_LEVELS)}, got {level!r}")
+    if mode not in ROLLOUT_IS_MODES:
+        raise ValueError(f"ppo.rollout_is_mode must be {'|'.join(ROLLOUT_IS_MODES)}, got {mode!r}")
+    return {"is_cap": cap, "is_floor": floor, "is_level": level, "is_mode": mode}
 
 
 def _tokenize_left(tok, texts, max_len, device):
@@ -179,6 +216,7 @@ def main(argv=None) -> int:
     if algo not in ("reinforce", "ppo", "grpo"):
         raise ValueError(f"ppo.algorithm must be reinforce|ppo|grpo, got {algo!r}")
     want_logp = rollout_logprobs_mode(ppo, algo) != "off"
+    rollout_is_settings(ppo)  # bad ppo.rollout_is_* values fail here, before any rollout
 
     # reward inputs built on the device when the reward tokenizer equals the policy's (no
     # decode / re-tokenise round trip through the host; training/handoff.py), else the
@@ -286,6 +324,10 @@ def reinforce_update(policy, ref, engine, seqs, mask, scores, kl_coef: float, mi
     return tot, {"kl": kl}
 
 
+# the per-rollout entries of the GRPO stats that minibatches and micro-batches slice
+GRPO_ROWS = ("act", "advantages", "ref_logp", "old_logp", "is_weight")
+
+
 def grpo_update(policy, engine, seqs, mask, stats, clip_low: float, clip_high, beta: float,
                 loss_type: str, max_len, micro: int = 0, entropy_coef: float = 0.0,
                 log_entropy: bool = False):
@@ -294,9 +336,10 @@ def grpo_update(policy, engine, seqs, mask, stats, clip_low: float, clip_high, b
     the whole minibatch's divisor (`denom`, a device tensor: no host sync), so their gradients sum
     to the full minibatch's; every micro-batch but the last runs under `engine.no_sync()`. The
     entropy bonus (`ppo.entropy_coef`) is likewise normalised by the whole minibatch's
-    action-token count. Returns (loss, metrics) with token-weighted metric means."""
+    action-token count. `stats["is_weight"]` (optional) is sliced with the other per-rollout
+    entries. Returns (loss, metrics) with token-weighted metric means."""
     n = seqs.shape[0]
-    rows = ("act", "advantages", "ref_logp", "old_logp")
+    rows = GRPO_ROWS
     if micro <= 0 or micro >= n:
         loss, m = grpo_loss(policy, seqs, mask, stats, clip_low, clip_high, beta, loss_type, max_len,
                             entropy_coef=entropy_coef, log_entropy=log_entropy)
@@ -336,20 +379,25 @@ def _grpo_loop(ctx, config, ppo, policy, ref, rm, rollout, engine, steps, group,
     entropy_coef, log_entropy = float(ppo.get("entropy_coef", 0.0) or 0.0), bool(ppo.get("log_entropy", False))
     need_old = epochs * nmb > 1  # a single update per rollout batch is on-policy: rho = 1
     lp_mode = rollout_logprobs_mode(ppo, "grpo")
-    rows = ("act", "advantages", "ref_logp", "old_logp")
+    is_kw = rollout_is_settings(ppo) if lp_mode == "correct" else {}
+    rows = GRPO_ROWS
     running = RunningLoss()
     pending = rollout()
     for step in range(steps):
         seqs, mask, scores, tp, rlp = pending
         # monitor: the trainer's own old-policy log-probs are computed even on-policy, to compare;
         # old: the rollout engine's ARE the old-policy log-probs (rho reflects fp8 / stale /
-        # rounding mismatch, which the clip handles) and the policy forward is skipped
+        # rounding mismatch, which the clip handles) and the policy forward is skipped;
+        # correct: the trainer's own stay the old-policy log-probs (computed even on-policy) and
+        # the gap goes into detached truncated importance weights on every action token
         stats = grpo_rollout_stats(policy.model, ref.model, seqs, mask, tp, scores, group, beta, scale_std,
                                    need_old or lp_mode == "monitor",
-                                   old_logp=rlp if lp_mode == "old" else None)
-        mism = rollout_mismatch(rlp, stats["old_logp"], stats["act"]) if lp_mode == "monitor" else {}
-        if lp_mode == "monitor" and not need_old:
-            stats["old_logp"] = None  # the update itself stays the on-policy one
+                                   old_logp=rlp if lp_mode == "old" else None,
+                                   rollout_logp=rlp if lp_mode == "correct" else None, **is_kw)
+        mism = rollout_mismatch(rlp, stats["old_logp"], stats["act"]) if lp_mode in ("monitor", "correct") else {}
+        mism.update(stats.get("rollout_is", {}))
+        if lp_mode in ("monitor", "correct") and not need_old:
+            stats["old_logp"] = None  # the update itself stays the on-policy one (rho = 1 exactly)
         S = seqs.shape[0]
         bounds = [(i * S // nmb, (i + 1) * S // nmb) for i in range(nmb)]
         for ep in range(epochs):
@@ -407,20 +455,23 @@ def _ppo_loop(ctx, config, ppo, policy, ref, rm, rollout, engine, steps, kl_coef
     overlap = bool(ppo.get("async_rollouts", False))
     entropy_coef, log_entropy = float(ppo.get("entropy_coef", 0.0) or 0.0), bool(ppo.get("log_entropy", False))
     lp_mode = rollout_logprobs_mode(ppo, "ppo")
+    is_kw = rollout_is_settings(ppo) if lp_mode == "correct" else {}
     running = RunningLoss()
     pending = rollout()
     for step in range(steps):
         seqs, mask, scores, tp, rlp = pending
         stats = ppo_rollout_stats(policy.model, ref.model, critic, seqs, mask, tp, scores, kl_coef,
-                                  gamma, lam, old_logp=rlp if lp_mode == "old" else None)
-        mism = rollout_mismatch(rlp, stats["old_logp"], stats["act"]) if lp_mode == "monitor" else {}
+                                  gamma, lam, old_logp=rlp if lp_mode == "old" else None,
+                                  rollout_logp=rlp if lp_mode == "correct" else None, **is_kw)
+        mism = rollout_mismatch(rlp, stats["old_logp"], stats["act"]) if lp_mode in ("monitor", "correct") else {}
+        mism.update(stats.get("rollout_is", {}))
         S = seqs.shape[0]
         bounds = [(i * S // nmb, (i + 1) * S // nmb) for i in range(nmb)]
         for ep in range(epochs):
             for mi, (a, b) in enumerate(bounds):
                 if b <= a:
                     continue
-                mb = {k: v[a:b] for k, v in stats.items() if k in ("old_logp", "values", "advantages", "returns", "act")}
+                mb = {k: v[a:b] for k, v in stats.items() if k in ("old_logp", "values", "advantages", "returns", "act", "is_weight")}
                 loss, m = ppo_loss(policy.model, critic, seqs[a:b], mask[a:b], mb, clip, vclip, vf_coef,
                                    entropy_coef, log_entropy)
                 ppo_backward(loss)

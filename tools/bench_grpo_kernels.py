@@ -15,6 +15,12 @@
                 ...), median of the rounds, effective GB/s over the bytes each must move; plus the
                 eager torch entropy of the same logits (fp32 log_softmax), for scale.
 
+  rollout_is    the truncated importance weights at S = 64, T = 768: `rollout_is_weights` (token and
+                sequence level) and the raw `grpo_loss` op with and without the weight grid
+                (`grpo_loss_w`), interleaved, median of the rounds, with the bytes each moves, against
+                the composed torch formulas on the GPU. With an extension that lacks the new ops
+                (an older build through DLA_EXT_PATH) only the unweighted loss is timed.
+
 Prints one JSON line per kernel (per shape for `logprob`). `--bench` selects one of them."""
 from __future__ import annotations
 
@@ -107,7 +113,7 @@ def bench_logprob(dla_ops, dev, rows, V, rounds, iters):
 
 def main() -> int:
     ap = argparse.ArgumentParser()
-    ap.add_argument("--bench", choices=("all", "kv_replicate", "grpo_loss", "logprob"), default="all")
+    ap.add_argument("--bench", choices=("all", "kv_replicate", "grpo_loss", "logprob", "rollout_is"), default="all")
     ap.add_argument("--vocab", type=int, default=128256)
     ap.add_argument("--logprob-rows", type=int, nargs="+", default=[6144, 8192])
     ap.add_argument("--rounds", type=int, default=5, help="logprob: interleaved rounds per pair")
@@ -137,6 +143,8 @@ def main() -> int:
     if a.bench in ("all", "logprob"):
         for rows in a.logprob_rows:
             bench_logprob(dla_ops, dev, rows, a.vocab, a.rounds, a.iters)
+    if a.bench in ("all", "rollout_is"):
+        bench_rollout_is(a, dla_ops, dev)
     return 0
 
 
@@ -208,6 +216,85 @@ def bench_grpo_loss(a, ops, dev, _ref_grpo_loss):
         out[f"{lt}_grad_max_diff"] = float((g1 - g2).abs().max())
         out[f"{lt}_fused_ms"] = round(timed(fused, 50), 4)
         out[f"{lt}_composed_ms"] = round(timed(composed, 50), 4)
+    print(json.dumps(out), flush=True)
+
+
+def bench_rollout_is(a, dla_ops, dev):
+    from distributed_llm_alignment_amd.ops import losses
+
+    S, T = a.rollouts, a.tokens
+    g = torch.Generator(device=dev).manual_seed(0)
+    lp = -torch.rand(S, T, device=dev, generator=g) * 3
+    old = lp + 0.3 * torch.randn(S, T, device=dev, generator=g)
+    ref = lp + 0.2 * torch.randn(S, T, device=dev, generator=g)
+    rlp = old + 0.3 * torch.randn(S, T, device=dev, generator=g)  # the rollout engine's log-probs
+    mask = (torch.rand(S, T, device=dev, generator=g) > 0.3).float()
+    adv = torch.randn(S, device=dev, generator=g)
+    grid = S * T * 4
+    tail = (None, 0.2, 0.28, 0.04, 0, float(T))
+    out = {"bench": "rollout_is", "S": S, "T": T, "grid_bytes": grid, "rounds": a.rounds, "iters": a.iters,
+           # passes over one [S, T] fp32 grid: partials read 4 (+ w), grad reads 4 (+ w) and writes 1
+           "grpo_loss_bytes": 9 * grid, "grpo_loss_w_bytes": 11 * grid,
+           # token level reads 3 and writes 1; the sequence level reads the mask and both log-probs once more
+           "is_token_bytes": 4 * grid, "is_sequence_bytes": 7 * grid}
+
+    def plain():
+        return dla_ops.grpo_loss(lp, old, ref, adv, mask, *tail)
+
+    has_new = hasattr(losses, "rollout_is_weights")
+    try:
+        dla_ops.rollout_is_weights
+    except (AttributeError, RuntimeError):
+        has_new = False
+    if not has_new:  # an older extension: the unweighted loss alone, same harness
+        ts = sorted(timed(plain, a.iters, warmup=1) for _ in range(a.rounds))
+        out["grpo_loss_ms"] = round(ts[len(ts) // 2], 4)
+        print(json.dumps(out), flush=True)
+        return
+    w, _ = dla_ops.rollout_is_weights(old, rlp, mask, 2.0, 0.5, 0, 0)
+
+    def weighted():
+        return dla_ops.grpo_loss_w(lp, old, ref, adv, mask, w, *tail)
+
+    ta, tb = interleaved(plain, weighted, a.rounds, a.iters)
+    out.update(grpo_loss_ms=round(ta, 4), grpo_loss_w_ms=round(tb, 4), w_ratio=round(tb / ta, 4),
+               grpo_loss_w_gb_s=round(11 * grid / tb / 1e6, 1))
+    ones = dla_ops.grpo_loss_w(lp, old, ref, adv, mask, torch.ones_like(w), *tail)
+    out["w_ones_bitwise_equal_unweighted"] = all(torch.equal(x, y) for x, y in zip(ones, plain()))
+    for level, name in ((0, "token"), (1, "sequence")):
+        def fused():
+            return dla_ops.rollout_is_weights(old, rlp, mask, 2.0, 0.5, level, 0)
+
+        def composed():
+            return losses._ref_rollout_is_weights(old, rlp, mask, 2.0, 0.5, name, "truncate")
+
+        (w1, m1), (w2, m2) = fused(), composed()
+        out[f"is_{name}_w_max_diff"] = float((w1 - w2).abs().max())
+        out[f"is_{name}_metrics_max_diff"] = float((m1 - m2).abs().max())
+        tf, tc = interleaved(fused, composed, a.rounds, a.iters)
+        out[f"is_{name}_ms"] = round(tf, 4)
+        out[f"is_{name}_composed_ms"] = round(tc, 4)
+        out[f"is_{name}_gb_s"] = round(out[f"is_{name}_bytes"] / tf / 1e6, 1)
+
+    def fused_step():  # what `correct` adds to a step plus the weighted loss, through the wrappers
+        x = lp.detach().requires_grad_(True)
+        wi, _ = losses.rollout_is_weights(old, rlp, mask)
+        loss, _ = losses.grpo_loss(x, old, ref, adv, mask, 0.2, 0.28, 0.04, "sequence", T, is_weight=wi)
+        loss.backward()
+        return loss, x.grad
+
+    def composed_step():
+        x = lp.detach().requires_grad_(True)
+        wi, _ = losses._ref_rollout_is_weights(old, rlp, mask)
+        loss, _ = losses._ref_grpo_loss(x, old, ref, adv, mask, 0.2, 0.28, 0.04, "sequence", T, is_weight=wi)
+        loss.backward()
+        return loss, x.grad
+
+    (l1, g1), (l2, g2) = fused_step(), composed_step()
+    out["step_loss_diff"] = float((l1 - l2).detach().abs())
+    out["step_grad_max_diff"] = float((g1 - g2).abs().max())
+    tf, tc = interleaved(fused_step, composed_step, a.rounds, a.iters)
+    out.update(step_fused_ms=round(tf, 4), step_composed_ms=round(tc, 4))
     print(json.dumps(out), flush=True)
 
 
