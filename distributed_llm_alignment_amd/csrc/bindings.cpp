@@ -45,6 +45,18 @@ void launch_logprob_fwd(const bf16_t*, int64_t, int, int64_t, int64_t, const int
 void launch_logprob_bwd(bf16_t*, int64_t, int, int64_t, int64_t, const int64_t*, const float*,
                         const float*, hipStream_t);
 void launch_row_lse(const bf16_t*, int64_t, int, int64_t, float*, hipStream_t);
+void launch_logprob_fwd_temp(const bf16_t*, int64_t, int, int64_t, int64_t, const int64_t*, float*, float*,
+                             float, hipStream_t);
+void launch_logprob_bwd_temp(bf16_t*, int64_t, int, int64_t, int64_t, const int64_t*, const float*,
+                             const float*, float, hipStream_t);
+bool launch_logprob_bwd_t_temp(bf16_t*, int64_t, int, int64_t, int64_t, const int64_t*, const float*,
+                               const float*, bf16_t*, float, hipStream_t);
+void launch_logprob_entropy_fwd_temp(const bf16_t*, int64_t, int, int64_t, int64_t, const int64_t*, float*,
+                                     float*, float*, float, hipStream_t);
+void launch_logprob_entropy_bwd_temp(bf16_t*, int64_t, int, int64_t, int64_t, const int64_t*, const float*,
+                                     const float*, const float*, const float*, float, hipStream_t);
+bool launch_logprob_entropy_bwd_t_temp(bf16_t*, int64_t, int, int64_t, int64_t, const int64_t*, const float*,
+                                       const float*, const float*, const float*, bf16_t*, float, hipStream_t);
 bool launch_logprob_bwd_t(bf16_t*, int64_t, int, int64_t, int64_t, const int64_t*, const float*,
                           const float*, bf16_t*, hipStream_t);
 void launch_logprob_entropy_fwd(const bf16_t*, int64_t, int, int64_t, int64_t, const int64_t*, float*,
@@ -608,8 +620,17 @@ static void check_logits(const at::Tensor& logits) {
   TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1, "logits must be [N, V] row-major");
 }
 
-std::tuple<at::Tensor, at::Tensor> logprob_fwd(const at::Tensor& logits, const at::Tensor& tgt,
-                                               int64_t vocab_offset) {
+// The *_temp ops are the same ops on softmax(inv_temp * logits), inv_temp = float(1.0 / temperature)
+// formed by the caller (the divide in double, rounded once); `inv` below is null for the plain ops,
+// which launch the kernels they always launched.
+static float checked_inv_temp(double inv_temp) {
+  const float i = static_cast<float>(inv_temp);
+  TORCH_CHECK(std::isfinite(i) && i > 0.f, "inv_temp must be finite and > 0, got ", inv_temp);
+  return i;
+}
+
+static std::tuple<at::Tensor, at::Tensor> logprob_fwd_impl(const at::Tensor& logits, const at::Tensor& tgt,
+                                                           int64_t vocab_offset, const float* inv) {
   check_logits(logits);
   TORCH_CHECK(tgt.scalar_type() == at::kLong && tgt.is_contiguous() && tgt.numel() == logits.size(0),
               "targets int64 [N]");
@@ -618,14 +639,30 @@ std::tuple<at::Tensor, at::Tensor> logprob_fwd(const at::Tensor& logits, const a
   auto opt = logits.options().dtype(at::kFloat);
   auto logp = at::empty({logits.size(0)}, opt);
   auto lse = at::empty({logits.size(0)}, opt);
-  launch_logprob_fwd(cbp(logits), logits.stride(0), static_cast<int>(logits.size(1)),
-                     vocab_offset, logits.size(0), tgt.data_ptr<int64_t>(), logp.data_ptr<float>(),
-                     lse.data_ptr<float>(), cur_stream(logits));
+  if (inv)
+    launch_logprob_fwd_temp(cbp(logits), logits.stride(0), static_cast<int>(logits.size(1)), vocab_offset,
+                            logits.size(0), tgt.data_ptr<int64_t>(), logp.data_ptr<float>(),
+                            lse.data_ptr<float>(), *inv, cur_stream(logits));
+  else
+    launch_logprob_fwd(cbp(logits), logits.stride(0), static_cast<int>(logits.size(1)),
+                       vocab_offset, logits.size(0), tgt.data_ptr<int64_t>(), logp.data_ptr<float>(),
+                       lse.data_ptr<float>(), cur_stream(logits));
   return {logp, lse};
 }
 
-void logprob_bwd(at::Tensor& logits, const at::Tensor& tgt, const at::Tensor& lse,
-                 const at::Tensor& grad, int64_t vocab_offset) {
+std::tuple<at::Tensor, at::Tensor> logprob_fwd(const at::Tensor& logits, const at::Tensor& tgt,
+                                               int64_t vocab_offset) {
+  return logprob_fwd_impl(logits, tgt, vocab_offset, nullptr);
+}
+
+std::tuple<at::Tensor, at::Tensor> logprob_fwd_temp(const at::Tensor& logits, const at::Tensor& tgt,
+                                                    double inv_temp, int64_t vocab_offset) {
+  const float i = checked_inv_temp(inv_temp);
+  return logprob_fwd_impl(logits, tgt, vocab_offset, &i);
+}
+
+static void logprob_bwd_impl(at::Tensor& logits, const at::Tensor& tgt, const at::Tensor& lse,
+                             const at::Tensor& grad, int64_t vocab_offset, const float* inv) {
   check_logits(logits);
   check_f32(lse, "lse");
   check_f32(grad, "grad");
@@ -633,16 +670,32 @@ void logprob_bwd(at::Tensor& logits, const at::Tensor& tgt, const at::Tensor& ls
   TORCH_CHECK(tgt.scalar_type() == at::kLong && tgt.numel() == N && tgt.is_contiguous(), "targets");
   TORCH_CHECK(lse.numel() == N && grad.numel() == N && grad.is_contiguous(), "lse/grad shape");
   c10::hip::HIPGuardMasqueradingAsCUDA g(logits.device());
-  launch_logprob_bwd(bp(logits), logits.stride(0), static_cast<int>(logits.size(1)), vocab_offset,
-                     N, tgt.data_ptr<int64_t>(), lse.data_ptr<float>(), grad.data_ptr<float>(),
-                     cur_stream(logits));
+  if (inv)
+    launch_logprob_bwd_temp(bp(logits), logits.stride(0), static_cast<int>(logits.size(1)), vocab_offset, N,
+                            tgt.data_ptr<int64_t>(), lse.data_ptr<float>(), grad.data_ptr<float>(), *inv,
+                            cur_stream(logits));
+  else
+    launch_logprob_bwd(bp(logits), logits.stride(0), static_cast<int>(logits.size(1)), vocab_offset,
+                       N, tgt.data_ptr<int64_t>(), lse.data_ptr<float>(), grad.data_ptr<float>(),
+                       cur_stream(logits));
+}
+
+void logprob_bwd(at::Tensor& logits, const at::Tensor& tgt, const at::Tensor& lse,
+                 const at::Tensor& grad, int64_t vocab_offset) {
+  logprob_bwd_impl(logits, tgt, lse, grad, vocab_offset, nullptr);
+}
+
+void logprob_bwd_temp(at::Tensor& logits, const at::Tensor& tgt, const at::Tensor& lse,
+                      const at::Tensor& grad, double inv_temp, int64_t vocab_offset) {
+  const float i = checked_inv_temp(inv_temp);
+  logprob_bwd_impl(logits, tgt, lse, grad, vocab_offset, &i);
 }
 
 // logprob_bwd with the transposed gradient as a second output: logits <- dlogits (in place) and
 // returns dlogitsT [V, N] (the LM head's TN weight-gradient operand). An empty tensor when the
 // shape is outside the kernel (N, V or the row stride not a multiple of 8): run logprob_bwd.
-at::Tensor logprob_bwd_t(at::Tensor& logits, const at::Tensor& tgt, const at::Tensor& lse,
-                         const at::Tensor& grad, int64_t vocab_offset) {
+static at::Tensor logprob_bwd_t_impl(at::Tensor& logits, const at::Tensor& tgt, const at::Tensor& lse,
+                                     const at::Tensor& grad, int64_t vocab_offset, const float* inv) {
   check_logits(logits);
   check_f32(lse, "lse");
   check_f32(grad, "grad");
@@ -653,19 +706,35 @@ at::Tensor logprob_bwd_t(at::Tensor& logits, const at::Tensor& tgt, const at::Te
   if (N == 0 || N % 8 != 0 || V % 8 != 0 || logits.stride(0) % 8 != 0) return at::empty({0}, logits.options());
   c10::hip::HIPGuardMasqueradingAsCUDA g(logits.device());
   auto outT = at::empty({V, N}, logits.options());
-  const bool ok = launch_logprob_bwd_t(bp(logits), logits.stride(0), static_cast<int>(V), N, vocab_offset,
-                                       tgt.data_ptr<int64_t>(), lse.data_ptr<float>(), grad.data_ptr<float>(),
-                                       bp(outT), cur_stream(logits));
+  const bool ok =
+      inv ? launch_logprob_bwd_t_temp(bp(logits), logits.stride(0), static_cast<int>(V), N, vocab_offset,
+                                      tgt.data_ptr<int64_t>(), lse.data_ptr<float>(), grad.data_ptr<float>(),
+                                      bp(outT), *inv, cur_stream(logits))
+          : launch_logprob_bwd_t(bp(logits), logits.stride(0), static_cast<int>(V), N, vocab_offset,
+                                 tgt.data_ptr<int64_t>(), lse.data_ptr<float>(), grad.data_ptr<float>(),
+                                 bp(outT), cur_stream(logits));
   TORCH_CHECK(ok, "logprob_bwd_t: shape");
   return outT;
+}
+
+at::Tensor logprob_bwd_t(at::Tensor& logits, const at::Tensor& tgt, const at::Tensor& lse,
+                         const at::Tensor& grad, int64_t vocab_offset) {
+  return logprob_bwd_t_impl(logits, tgt, lse, grad, vocab_offset, nullptr);
+}
+
+at::Tensor logprob_bwd_t_temp(at::Tensor& logits, const at::Tensor& tgt, const at::Tensor& lse,
+                              const at::Tensor& grad, double inv_temp, int64_t vocab_offset) {
+  const float i = checked_inv_temp(inv_temp);
+  return logprob_bwd_t_impl(logits, tgt, lse, grad, vocab_offset, &i);
 }
 
 // The entropy twins: the forward also emits the local shard's softmax entropy per row (every row,
 // whatever its target) from the same read; the backwards add grad_ent's term given the GLOBAL lse
 // and entropy. logp and lse are bitwise logprob_fwd's.
-std::tuple<at::Tensor, at::Tensor, at::Tensor> logprob_entropy_fwd(const at::Tensor& logits,
-                                                                   const at::Tensor& tgt,
-                                                                   int64_t vocab_offset) {
+static std::tuple<at::Tensor, at::Tensor, at::Tensor> logprob_entropy_fwd_impl(const at::Tensor& logits,
+                                                                               const at::Tensor& tgt,
+                                                                               int64_t vocab_offset,
+                                                                               const float* inv) {
   check_logits(logits);
   TORCH_CHECK(tgt.scalar_type() == at::kLong && tgt.is_contiguous() && tgt.numel() == logits.size(0),
               "targets int64 [N]");
@@ -675,11 +744,30 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> logprob_entropy_fwd(const at::Ten
   auto logp = at::empty({logits.size(0)}, opt);
   auto lse = at::empty({logits.size(0)}, opt);
   auto ent = at::empty({logits.size(0)}, opt);
-  launch_logprob_entropy_fwd(cbp(logits), logits.stride(0), static_cast<int>(logits.size(1)),
-                             vocab_offset, logits.size(0), tgt.data_ptr<int64_t>(),
-                             logp.data_ptr<float>(), lse.data_ptr<float>(), ent.data_ptr<float>(),
-                             cur_stream(logits));
+  if (inv)
+    launch_logprob_entropy_fwd_temp(cbp(logits), logits.stride(0), static_cast<int>(logits.size(1)),
+                                    vocab_offset, logits.size(0), tgt.data_ptr<int64_t>(),
+                                    logp.data_ptr<float>(), lse.data_ptr<float>(), ent.data_ptr<float>(), *inv,
+                                    cur_stream(logits));
+  else
+    launch_logprob_entropy_fwd(cbp(logits), logits.stride(0), static_cast<int>(logits.size(1)),
+                               vocab_offset, logits.size(0), tgt.data_ptr<int64_t>(),
+                               logp.data_ptr<float>(), lse.data_ptr<float>(), ent.data_ptr<float>(),
+                               cur_stream(logits));
   return {logp, lse, ent};
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor> logprob_entropy_fwd(const at::Tensor& logits,
+                                                                   const at::Tensor& tgt,
+                                                                   int64_t vocab_offset) {
+  return logprob_entropy_fwd_impl(logits, tgt, vocab_offset, nullptr);
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor> logprob_entropy_fwd_temp(const at::Tensor& logits,
+                                                                        const at::Tensor& tgt, double inv_temp,
+                                                                        int64_t vocab_offset) {
+  const float i = checked_inv_temp(inv_temp);
+  return logprob_entropy_fwd_impl(logits, tgt, vocab_offset, &i);
 }
 
 static void check_entropy_bwd(const at::Tensor& logits, const at::Tensor& tgt, const at::Tensor& lse,
@@ -703,31 +791,69 @@ static void check_entropy_bwd(const at::Tensor& logits, const at::Tensor& tgt, c
   same_device(logits, grad_ent);
 }
 
+static void logprob_entropy_bwd_impl(at::Tensor& logits, const at::Tensor& tgt, const at::Tensor& lse,
+                                     const at::Tensor& ent, const at::Tensor& grad_logp,
+                                     const at::Tensor& grad_ent, int64_t vocab_offset, const float* inv) {
+  check_entropy_bwd(logits, tgt, lse, ent, grad_logp, grad_ent);
+  c10::hip::HIPGuardMasqueradingAsCUDA g(logits.device());
+  if (inv)
+    launch_logprob_entropy_bwd_temp(bp(logits), logits.stride(0), static_cast<int>(logits.size(1)), vocab_offset,
+                                    logits.size(0), tgt.data_ptr<int64_t>(), lse.data_ptr<float>(),
+                                    ent.data_ptr<float>(), grad_logp.data_ptr<float>(),
+                                    grad_ent.data_ptr<float>(), *inv, cur_stream(logits));
+  else
+    launch_logprob_entropy_bwd(bp(logits), logits.stride(0), static_cast<int>(logits.size(1)), vocab_offset,
+                               logits.size(0), tgt.data_ptr<int64_t>(), lse.data_ptr<float>(),
+                               ent.data_ptr<float>(), grad_logp.data_ptr<float>(),
+                               grad_ent.data_ptr<float>(), cur_stream(logits));
+}
+
 void logprob_entropy_bwd(at::Tensor& logits, const at::Tensor& tgt, const at::Tensor& lse,
                          const at::Tensor& ent, const at::Tensor& grad_logp, const at::Tensor& grad_ent,
                          int64_t vocab_offset) {
-  check_entropy_bwd(logits, tgt, lse, ent, grad_logp, grad_ent);
-  c10::hip::HIPGuardMasqueradingAsCUDA g(logits.device());
-  launch_logprob_entropy_bwd(bp(logits), logits.stride(0), static_cast<int>(logits.size(1)), vocab_offset,
-                             logits.size(0), tgt.data_ptr<int64_t>(), lse.data_ptr<float>(),
-                             ent.data_ptr<float>(), grad_logp.data_ptr<float>(),
-                             grad_ent.data_ptr<float>(), cur_stream(logits));
+  logprob_entropy_bwd_impl(logits, tgt, lse, ent, grad_logp, grad_ent, vocab_offset, nullptr);
 }
 
-at::Tensor logprob_entropy_bwd_t(at::Tensor& logits, const at::Tensor& tgt, const at::Tensor& lse,
-                                 const at::Tensor& ent, const at::Tensor& grad_logp,
-                                 const at::Tensor& grad_ent, int64_t vocab_offset) {
+void logprob_entropy_bwd_temp(at::Tensor& logits, const at::Tensor& tgt, const at::Tensor& lse,
+                              const at::Tensor& ent, const at::Tensor& grad_logp, const at::Tensor& grad_ent,
+                              double inv_temp, int64_t vocab_offset) {
+  const float i = checked_inv_temp(inv_temp);
+  logprob_entropy_bwd_impl(logits, tgt, lse, ent, grad_logp, grad_ent, vocab_offset, &i);
+}
+
+static at::Tensor logprob_entropy_bwd_t_impl(at::Tensor& logits, const at::Tensor& tgt, const at::Tensor& lse,
+                                             const at::Tensor& ent, const at::Tensor& grad_logp,
+                                             const at::Tensor& grad_ent, int64_t vocab_offset,
+                                             const float* inv) {
   check_entropy_bwd(logits, tgt, lse, ent, grad_logp, grad_ent);
   const int64_t N = logits.size(0), V = logits.size(1);
   if (N == 0 || N % 8 != 0 || V % 8 != 0 || logits.stride(0) % 8 != 0) return at::empty({0}, logits.options());
   c10::hip::HIPGuardMasqueradingAsCUDA g(logits.device());
   auto outT = at::empty({V, N}, logits.options());
-  const bool ok = launch_logprob_entropy_bwd_t(bp(logits), logits.stride(0), static_cast<int>(V), N,
-                                               vocab_offset, tgt.data_ptr<int64_t>(), lse.data_ptr<float>(),
-                                               ent.data_ptr<float>(), grad_logp.data_ptr<float>(),
-                                               grad_ent.data_ptr<float>(), bp(outT), cur_stream(logits));
+  const bool ok =
+      inv ? launch_logprob_entropy_bwd_t_temp(bp(logits), logits.stride(0), static_cast<int>(V), N, vocab_offset,
+                                              tgt.data_ptr<int64_t>(), lse.data_ptr<float>(),
+                                              ent.data_ptr<float>(), grad_logp.data_ptr<float>(),
+                                              grad_ent.data_ptr<float>(), bp(outT), *inv, cur_stream(logits))
+          : launch_logprob_entropy_bwd_t(bp(logits), logits.stride(0), static_cast<int>(V), N, vocab_offset,
+                                         tgt.data_ptr<int64_t>(), lse.data_ptr<float>(), ent.data_ptr<float>(),
+                                         grad_logp.data_ptr<float>(), grad_ent.data_ptr<float>(), bp(outT),
+                                         cur_stream(logits));
   TORCH_CHECK(ok, "logprob_entropy_bwd_t: shape");
   return outT;
+}
+
+at::Tensor logprob_entropy_bwd_t(at::Tensor& logits, const at::Tensor& tgt, const at::Tensor& lse,
+                                 const at::Tensor& ent, const at::Tensor& grad_logp,
+                                 const at::Tensor& grad_ent, int64_t vocab_offset) {
+  return logprob_entropy_bwd_t_impl(logits, tgt, lse, ent, grad_logp, grad_ent, vocab_offset, nullptr);
+}
+
+at::Tensor logprob_entropy_bwd_t_temp(at::Tensor& logits, const at::Tensor& tgt, const at::Tensor& lse,
+                                      const at::Tensor& ent, const at::Tensor& grad_logp,
+                                      const at::Tensor& grad_ent, double inv_temp, int64_t vocab_offset) {
+  const float i = checked_inv_temp(inv_temp);
+  return logprob_entropy_bwd_t_impl(logits, tgt, lse, ent, grad_logp, grad_ent, vocab_offset, &i);
 }
 
 at::Tensor row_lse(const at::Tensor& logits) {
@@ -1164,6 +1290,12 @@ TORCH_LIBRARY(dla, m) {
   m.def("logprob_entropy_fwd(Tensor logits, Tensor targets, int vocab_offset=0) -> (Tensor, Tensor, Tensor)");
   m.def("logprob_entropy_bwd(Tensor(a!) logits, Tensor targets, Tensor lse, Tensor ent, Tensor grad_logp, Tensor grad_ent, int vocab_offset=0) -> ()");
   m.def("logprob_entropy_bwd_t(Tensor(a!) logits, Tensor targets, Tensor lse, Tensor ent, Tensor grad_logp, Tensor grad_ent, int vocab_offset=0) -> Tensor");
+  m.def("logprob_fwd_temp(Tensor logits, Tensor targets, float inv_temp, int vocab_offset=0) -> (Tensor, Tensor)");
+  m.def("logprob_bwd_temp(Tensor(a!) logits, Tensor targets, Tensor lse, Tensor grad, float inv_temp, int vocab_offset=0) -> ()");
+  m.def("logprob_bwd_t_temp(Tensor(a!) logits, Tensor targets, Tensor lse, Tensor grad, float inv_temp, int vocab_offset=0) -> Tensor");
+  m.def("logprob_entropy_fwd_temp(Tensor logits, Tensor targets, float inv_temp, int vocab_offset=0) -> (Tensor, Tensor, Tensor)");
+  m.def("logprob_entropy_bwd_temp(Tensor(a!) logits, Tensor targets, Tensor lse, Tensor ent, Tensor grad_logp, Tensor grad_ent, float inv_temp, int vocab_offset=0) -> ()");
+  m.def("logprob_entropy_bwd_t_temp(Tensor(a!) logits, Tensor targets, Tensor lse, Tensor ent, Tensor grad_logp, Tensor grad_ent, float inv_temp, int vocab_offset=0) -> Tensor");
   m.def("row_lse(Tensor logits) -> Tensor");
   m.def("ensemble_kl(Tensor(a!) s_logits, Tensor t_logits, Tensor s_lse, Tensor t_lse, Tensor? grad, bool write_grad) -> Tensor");
   m.def("seq_reduce(Tensor lp, Tensor mask) -> (Tensor, Tensor)");
@@ -1205,6 +1337,12 @@ TORCH_LIBRARY_IMPL(dla, CUDA, m) {
   m.impl("logprob_entropy_fwd", &dla::logprob_entropy_fwd);
   m.impl("logprob_entropy_bwd", &dla::logprob_entropy_bwd);
   m.impl("logprob_entropy_bwd_t", &dla::logprob_entropy_bwd_t);
+  m.impl("logprob_fwd_temp", &dla::logprob_fwd_temp);
+  m.impl("logprob_bwd_temp", &dla::logprob_bwd_temp);
+  m.impl("logprob_bwd_t_temp", &dla::logprob_bwd_t_temp);
+  m.impl("logprob_entropy_fwd_temp", &dla::logprob_entropy_fwd_temp);
+  m.impl("logprob_entropy_bwd_temp", &dla::logprob_entropy_bwd_temp);
+  m.impl("logprob_entropy_bwd_t_temp", &dla::logprob_entropy_bwd_t_temp);
   m.impl("row_lse", &dla::row_lse);
   m.impl("ensemble_kl", &dla::ensemble_kl);
   m.impl("seq_reduce", &dla::seq_reduce);

@@ -27,6 +27,10 @@ void launch_sample_split(const void*, bool, int64_t, int64_t, int, int, float, i
 void launch_sample_logp(const void*, bool, int64_t, int64_t, int, float, int, float, bool,
                         const int64_t*, int64_t*, float*, hipStream_t);
 size_t sample_workspace_bytes_logp(int64_t, int);
+void launch_sample_logp_tempered(const void*, bool, int64_t, int64_t, int, float, int, float, const int64_t*,
+                                 int64_t*, float*, hipStream_t);
+void launch_sample_split_logp_tempered(const void*, bool, int64_t, int64_t, int, int, float, int, float,
+                                       const int64_t*, int64_t*, float*, void*, hipStream_t);
 void launch_sample_split_logp(const void*, bool, int64_t, int64_t, int, int, float, int, float,
                               const int64_t*, int64_t*, float*, void*, hipStream_t);
 
@@ -648,6 +652,38 @@ std::tuple<at::Tensor, at::Tensor> sample_tokens_logp(const at::Tensor& logits, 
   return {out, logp};
 }
 
+// sample_tokens_logp with the log-prob at the DRAW temperature: logp = log softmax(logits *
+// inv_temp)[token] over the full vocabulary (no top-k / top-p filter), the quantity
+// token_logprobs(temperature=) returns. Tokens are sample_tokens' bit for bit. greedy or
+// temperature <= 0 has no draw temperature: sample_tokens_logp's result.
+std::tuple<at::Tensor, at::Tensor> sample_tokens_logp_tempered(const at::Tensor& logits, double temperature,
+                                                               int64_t top_k, double top_p, bool greedy,
+                                                               const at::Tensor& rng) {
+  if (greedy || !(temperature > 0.0)) return sample_tokens_logp(logits, temperature, top_k, top_p, greedy, rng);
+  check_sample_args(logits, top_p, rng);
+  const int64_t B = logits.size(0), V = logits.size(1);
+  c10::hip::HIPGuardMasqueradingAsCUDA g(logits.device());
+  auto out = at::empty({B}, logits.options().dtype(at::kLong));
+  auto logp = at::empty({B}, logits.options().dtype(at::kFloat));
+  const float inv_t = static_cast<float>(1.0 / temperature);
+  const bool is_bf16 = logits.scalar_type() == at::kBFloat16;
+  const int G = sample_split_chunks(logits.data_ptr(), logits.stride(0), B, (int)V, inv_t,
+                                    (int)top_k, static_cast<float>(top_p), greedy);
+  if (G > 0) {
+    auto ws = at::empty({(int64_t)sample_workspace_bytes_logp(B, G)},
+                        logits.options().dtype(at::kByte));
+    launch_sample_split_logp_tempered(logits.data_ptr(), is_bf16, logits.stride(0), B, (int)V, G, inv_t,
+                                      (int)top_k, static_cast<float>(top_p), rng.data_ptr<int64_t>(),
+                                      out.data_ptr<int64_t>(), logp.data_ptr<float>(), ws.data_ptr(),
+                                      cur_stream(logits));
+    return {out, logp};
+  }
+  launch_sample_logp_tempered(logits.data_ptr(), is_bf16, logits.stride(0), B, (int)V, inv_t, (int)top_k,
+                              static_cast<float>(top_p), rng.data_ptr<int64_t>(), out.data_ptr<int64_t>(),
+                              logp.data_ptr<float>(), cur_stream(logits));
+  return {out, logp};
+}
+
 // Shared-prefill replication: keys / values [0, Tp) of every layer of the P-row prefill cache
 // (src_k / src_v [L, P, Tp, Hkv, D]) go to rows p*G .. p*G+G-1 of the P*G-row decode cache
 // (dst_k / dst_v [L, P*G, Tmax >= Tp, Hkv, D]); any strides with D contiguous and 16-byte
@@ -700,6 +736,7 @@ TORCH_LIBRARY_FRAGMENT(dla, m) {
   m.def("decode_attn_rope_group(Tensor qkv, Tensor cos, Tensor sin, Tensor pos, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor slot, Tensor kv_len, Tensor? kv_start, int window, float scale, int Hq, int Hkv, int D, int rot, int group_size, int prefix_len) -> Tensor");
   m.def("sample_tokens(Tensor logits, float temperature, int top_k, float top_p, bool greedy, Tensor rng) -> Tensor");
   m.def("sample_tokens_logp(Tensor logits, float temperature, int top_k, float top_p, bool greedy, Tensor rng) -> (Tensor, Tensor)");
+  m.def("sample_tokens_logp_tempered(Tensor logits, float temperature, int top_k, float top_p, bool greedy, Tensor rng) -> (Tensor, Tensor)");
   m.def("skinny_gemm(Tensor x, Tensor w, Tensor(a!) counters, bool swiglu, bool glu_out=False) -> Tensor");
   m.def("skinny_glu_ks(Tensor x, Tensor w) -> Tensor");
   m.def("skinny_fused(Tensor x, Tensor w, Tensor? res, Tensor? ssq_in, float eps, bool glu) -> (Tensor, Tensor)");
@@ -719,6 +756,7 @@ TORCH_LIBRARY_IMPL(dla, CUDA, m) {
   m.impl("decode_attn_rope_group", &dla::decode_attn_rope_group);
   m.impl("sample_tokens", &dla::sample_tokens);
   m.impl("sample_tokens_logp", &dla::sample_tokens_logp);
+  m.impl("sample_tokens_logp_tempered", &dla::sample_tokens_logp_tempered);
   m.impl("rope_cache_write", &dla::rope_cache_write);
   m.impl("decode_attn_rope", &dla::decode_attn_rope);
   m.impl("skinny_gemm", &dla::skinny_gemm);

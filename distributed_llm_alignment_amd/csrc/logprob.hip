@@ -51,16 +51,103 @@ __device__ __forceinline__ void lse_merge_u(float& m, float& s, float& u, float 
   m = mn;
 }
 
+// x * i in the TEMP instantiations, x itself in the others.
+template <bool TEMP>
+__device__ __forceinline__ float scaled(float x, float i) {
+#pragma clang fp contract(off)  // a product rounded on its own, never fused into the caller's sum
+  if constexpr (TEMP) return x * i;
+  return x;
+}
+
+// The (max, sum-exp) merge of the tempered kernels: the sums are of exp(i (z_v - m)) with m the max
+// of the RAW logits, so moving the reference point scales the difference, exp((m - mn) * i). Spelled
+// out with contraction off in the rounding logprob_fwd_kernel's lse_merge compiles to (see
+// lse_merge_u), so that at i = 1 (a multiply by 1.0f is exact) the tempered kernels give the plain
+// kernels' bits; tests/test_logprob_temperature_gpu.py holds them equal.
+__device__ __forceinline__ void lse_merge_t(float& m, float& s, float m2, float s2, bool fused, float i) {
+#pragma clang fp contract(off)
+  const float mn = fmaxf(m, m2);
+  if (mn == -INFINITY) return;
+  const float e1 = __expf((m - mn) * i), e2 = __expf((m2 - mn) * i);
+  const float a = s * e1;
+  s = fused ? __builtin_fmaf(s2, e2, a) : a + s2 * e2;
+  m = mn;
+}
+
+// ent_shift at inverse temperature i: u is a sum of exp(d) d with d = i (z_v - m). The scaled
+// difference is rounded on its own; the rest is ent_shift's expression, contraction as there.
+__device__ __forceinline__ float ent_shift_t(float u, float s, float m, float mn, float e, float i) {
+  return m == -INFINITY ? 0.f : e * (u + scaled<true>(m - mn, i) * s);
+}
+
+__device__ __forceinline__ void lse_merge_ut(float& m, float& s, float& u, float m2, float s2, float u2,
+                                             bool fused, float i) {
+#pragma clang fp contract(off)
+  const float mn = fmaxf(m, m2);
+  if (mn == -INFINITY) return;
+  const float e1 = __expf((m - mn) * i), e2 = __expf((m2 - mn) * i);
+  u = ent_shift_t(u, s, m, mn, e1, i) + ent_shift_t(u2, s2, m2, mn, e2, i);
+  const float a = s * e1;
+  s = fused ? __builtin_fmaf(s2, e2, a) : a + s2 * e2;
+  m = mn;
+}
+
 // ENT: also accumulate u (u_out). The (m, s) arithmetic rounds as with the flag off (contraction
 // is switched off wherever s is updated next to u). With the flag on or off a -inf logit (a masked
 // vocabulary entry) adds exactly 0, also while the lane's running max is still -inf; only a row
 // of nothing but -inf has no lse.
-template <bool VEC, bool ENT = false>
+// TEMP: the sums of softmax(it * z), it = 1 / temperature: m stays the max of the RAW logits, every
+// exponent argument is a scaled DIFFERENCE, d = (z_v - m) * it, so s = sum_v exp(d) and
+// u = sum_v exp(d) d. Contraction is off throughout and the merges are lse_merge_t / lse_merge_ut:
+// at it = 1 this is the flag-off arithmetic bit for bit.
+template <bool VEC, bool ENT = false, bool TEMP = false>
 __device__ __forceinline__ void row_lse(const bf16_t* __restrict__ row, int V, float& m_out,
-                                        float& s_out, float* u_out = nullptr) {
+                                        float& s_out, float* u_out = nullptr, float it = 1.f) {
   __shared__ float sm[4], ss[4], su[ENT ? 4 : 1];
   float m = -INFINITY, s = 0.f, u = 0.f;
-  if constexpr (VEC) {
+  if constexpr (TEMP && VEC) {
+#pragma clang fp contract(off)
+    const int nv = V >> 3;
+    for (int i = threadIdx.x; i < nv; i += 256) {
+      bf16x8 a = load_bf16x8(row + i * 8);
+      float x[8];
+      float lm = -INFINITY;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        x[j] = bf2f(a[j]);
+        lm = fmaxf(lm, x[j]);
+      }
+      if (lm == -INFINITY) continue;
+      if (lm > m) {
+        const float e = __expf((m - lm) * it);
+        if constexpr (ENT) u = ent_shift_t(u, s, m, lm, e, it);
+        s *= e;
+        m = lm;
+      }
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float d = (x[j] - m) * it;
+        const float e = __expf(d);
+        s += e;
+        if constexpr (ENT) u = __builtin_fmaf(e, fmaxf(d, ENT_DMIN), u);
+      }
+    }
+  } else if constexpr (TEMP) {
+#pragma clang fp contract(off)
+    for (int i = threadIdx.x; i < V; i += 256) {
+      const float x = bf2f(row[i]);
+      if (x > m) {
+        const float e = __expf((m - x) * it);
+        if constexpr (ENT) u = ent_shift_t(u, s, m, x, e, it);
+        s *= e;
+        m = x;
+      }
+      const float d = (x - m) * it;
+      const float e = x == -INFINITY ? 0.f : __expf(d);  // (d is NaN while m is still -inf)
+      s += e;
+      if constexpr (ENT) u = __builtin_fmaf(e, fmaxf(d, ENT_DMIN), u);
+    }
+  } else if constexpr (VEC) {
     const int nv = V >> 3;
     for (int i = threadIdx.x; i < nv; i += 256) {
       bf16x8 a = load_bf16x8(row + i * 8);
@@ -126,7 +213,12 @@ __device__ __forceinline__ void row_lse(const bf16_t* __restrict__ row, int V, f
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
-    if constexpr (ENT) {
+    if constexpr (TEMP && ENT) {
+      const float u2 = __shfl_xor(u, o, 64);
+      lse_merge_ut(m, s, u, m2, s2, u2, o != 1, it);
+    } else if constexpr (TEMP) {
+      lse_merge_t(m, s, m2, s2, o != 1, it);
+    } else if constexpr (ENT) {
       const float u2 = __shfl_xor(u, o, 64);
       lse_merge_u(m, s, u, m2, s2, u2, o != 1);
     } else {
@@ -145,7 +237,9 @@ __device__ __forceinline__ void row_lse(const bf16_t* __restrict__ row, int V, f
   if constexpr (ENT) u = su[0];
 #pragma unroll
   for (int i = 1; i < 4; ++i) {
-    if constexpr (ENT) lse_merge_u(m, s, u, sm[i], ss[i], su[i], true);
+    if constexpr (TEMP && ENT) lse_merge_ut(m, s, u, sm[i], ss[i], su[i], true, it);
+    else if constexpr (TEMP) lse_merge_t(m, s, sm[i], ss[i], true, it);
+    else if constexpr (ENT) lse_merge_u(m, s, u, sm[i], ss[i], su[i], true);
     else lse_merge(m, s, sm[i], ss[i]);
   }
   m_out = m;
@@ -158,23 +252,26 @@ __device__ __forceinline__ void row_lse(const bf16_t* __restrict__ row, int V, f
 // local shard) is always written. off = 0, V = full vocab for the unsharded LM head.
 // ENT: ent_out[r] = entropy of the local shard's softmax, from the same read of the row, for
 // every row whatever its target.
-template <bool VEC, bool ENT = false>
+// TEMP: the same of softmax(inv_temp * logits): lse = inv_temp m + log s, logp = inv_temp z_t - lse,
+// ent = log s - u / s with s, u at the scaled differences (row_lse).
+template <bool VEC, bool ENT = false, bool TEMP = false>
 __global__ __launch_bounds__(256) void logprob_fwd_kernel(const bf16_t* __restrict__ logits,
                                                            int64_t ld, int V, int64_t off,
                                                            const int64_t* __restrict__ tgt,
                                                            float* __restrict__ logp,
                                                            float* __restrict__ lse_out,
-                                                           float* __restrict__ ent_out = nullptr) {
+                                                           float* __restrict__ ent_out = nullptr,
+                                                           float inv_temp = 1.f) {
   const int64_t r = blockIdx.x;
   const bf16_t* row = logits + r * ld;
   float m, s, u = 0.f;
-  row_lse<VEC, ENT>(row, V, m, s, &u);
+  row_lse<VEC, ENT, TEMP>(row, V, m, s, &u, inv_temp);
   if (threadIdx.x == 0) {
-    const float lse = m + __logf(s);
+    const float lse = scaled<TEMP>(m, inv_temp) + __logf(s);
     lse_out[r] = lse;
     if constexpr (ENT) ent_out[r] = __logf(s) - u / s;
     const int64_t t = tgt[r] - off;
-    logp[r] = (tgt[r] >= 0 && t >= 0 && t < V) ? bf2f(row[t]) - lse : 0.f;
+    logp[r] = (tgt[r] >= 0 && t >= 0 && t < V) ? scaled<TEMP>(bf2f(row[t]), inv_temp) - lse : 0.f;
   }
 }
 
@@ -182,6 +279,10 @@ __global__ __launch_bounds__(256) void logprob_fwd_kernel(const bf16_t* __restri
 // lse is the GLOBAL (all-shard) log-sum-exp. Ignored rows (tgt < 0) -> 0; z = -inf -> 0.
 // ENT adds the entropy gradient, e = dL/dent[r] and H = the GLOBAL entropy ent_in[r]:
 //   logits[r, v] <- g (1[v == t] - p) - e p (z - lse + H),  p = exp(z - lse);  z = -inf -> 0.
+// TEMP (softmax(i z), i = inv_temp, y = i z): dz_v = i [ g (1[v == t] - p) - e p (y - lse + H) ],
+// p = exp(y - lse), lse and H those of the tempered distribution. The callers fold i into the
+// per-row scalars (g i, e i) and pass y = z i as `z`; the expressions below are then the same, and
+// at i = 1 so are the bits.
 template <bool ENT>
 __device__ __forceinline__ float dlogit(float z, bool hit, float gr, float lse, float er, float H) {
 #pragma clang fp contract(off)  // one rounding per operation in every kernel that inlines this
@@ -191,22 +292,23 @@ __device__ __forceinline__ float dlogit(float z, bool hit, float gr, float lse, 
   return z == -INFINITY ? 0.f : d - er * p * (z - lse + H);
 }
 
-template <bool VEC, bool ENT = false>
+template <bool VEC, bool ENT = false, bool TEMP = false>
 __global__ __launch_bounds__(256) void logprob_bwd_kernel(bf16_t* __restrict__ logits, int64_t ld,
                                                            int V, int64_t off,
                                                            const int64_t* __restrict__ tgt,
                                                            const float* __restrict__ lse_in,
                                                            const float* __restrict__ g,
                                                            const float* __restrict__ ent_in = nullptr,
-                                                           const float* __restrict__ ge = nullptr) {
+                                                           const float* __restrict__ ge = nullptr,
+                                                           float inv_temp = 1.f) {
   const int64_t r = blockIdx.x;
   bf16_t* row = logits + r * ld;
   const int64_t t = tgt[r] - off;
-  const float gr = tgt[r] >= 0 ? g[r] : 0.f;
+  const float gr = scaled<TEMP>(tgt[r] >= 0 ? g[r] : 0.f, inv_temp);
   const float lse = lse_in[r];
   float er = 0.f, H = 0.f;
   if constexpr (ENT) {
-    er = tgt[r] >= 0 ? ge[r] : 0.f;
+    er = scaled<TEMP>(tgt[r] >= 0 ? ge[r] : 0.f, inv_temp);
     H = ent_in[r];
   }
   if constexpr (VEC) {
@@ -216,13 +318,13 @@ __global__ __launch_bounds__(256) void logprob_bwd_kernel(bf16_t* __restrict__ l
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const int v = i * 8 + j;
-        o[j] = f2bf(dlogit<ENT>(bf2f(a[j]), v == t, gr, lse, er, H));
+        o[j] = f2bf(dlogit<ENT>(scaled<TEMP>(bf2f(a[j]), inv_temp), v == t, gr, lse, er, H));
       }
       store_bf16x8(row + i * 8, o);
     }
   } else {
     for (int v = threadIdx.x; v < V; v += 256)
-      row[v] = f2bf(dlogit<ENT>(bf2f(row[v]), v == t, gr, lse, er, H));
+      row[v] = f2bf(dlogit<ENT>(scaled<TEMP>(bf2f(row[v]), inv_temp), v == t, gr, lse, er, H));
   }
 }
 
@@ -234,14 +336,15 @@ __global__ __launch_bounds__(256) void logprob_bwd_kernel(bf16_t* __restrict__ l
 // 64 rows x 64 columns; grid (ceil(V / 256), rows / 64); rows % 8 == 0, V % 8 == 0, ld % 8 == 0.
 // ENT: the entropy gradient too (dlogit<true>); two more per-row scalars live inside the unrolled
 // row loop, the 16 bf16x8 vectors per lane are unchanged.
-template <bool ENT = false>
+template <bool ENT = false, bool TEMP = false>
 __global__ __launch_bounds__(256) void logprob_bwd_t_kernel(bf16_t* __restrict__ logits, int64_t ld, int V,
                                                              int64_t off, const int64_t* __restrict__ tgt,
                                                              const float* __restrict__ lse_in,
                                                              const float* __restrict__ g,
                                                              bf16_t* __restrict__ outT, int64_t rows,
                                                              const float* __restrict__ ent_in = nullptr,
-                                                             const float* __restrict__ ge = nullptr) {
+                                                             const float* __restrict__ ge = nullptr,
+                                                             float inv_temp = 1.f) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int64_t r = static_cast<int64_t>(blockIdx.y) * 64 + (lane >> 3) * 8;
   const int c = blockIdx.x * 256 + w * 64 + (lane & 7) * 8;
@@ -252,15 +355,16 @@ __global__ __launch_bounds__(256) void logprob_bwd_t_kernel(bf16_t* __restrict__
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
     const int64_t t = tgt[r + i] - off;
-    const float gr = tgt[r + i] >= 0 ? g[r + i] : 0.f;
+    const float gr = scaled<TEMP>(tgt[r + i] >= 0 ? g[r + i] : 0.f, inv_temp);
     const float lse = lse_in[r + i];
     float er = 0.f, H = 0.f;
     if constexpr (ENT) {
-      er = tgt[r + i] >= 0 ? ge[r + i] : 0.f;
+      er = scaled<TEMP>(tgt[r + i] >= 0 ? ge[r + i] : 0.f, inv_temp);
       H = ent_in[r + i];
     }
 #pragma unroll
-    for (int j = 0; j < 8; ++j) o[i][j] = f2bf(dlogit<ENT>(bf2f(a[i][j]), c + j == t, gr, lse, er, H));
+    for (int j = 0; j < 8; ++j)
+      o[i][j] = f2bf(dlogit<ENT>(scaled<TEMP>(bf2f(a[i][j]), inv_temp), c + j == t, gr, lse, er, H));
     store_bf16x8(logits + (r + i) * ld + c, o[i]);
   }
   bf16x8 tt[8];
@@ -361,6 +465,78 @@ bool launch_logprob_bwd_t(bf16_t* logits, int64_t ld, int V, int64_t rows, int64
   if (rows == 0) return true;
   const dim3 grid((V + 255) / 256, static_cast<unsigned>((rows + 63) / 64));
   logprob_bwd_t_kernel<false><<<grid, 256, 0, st>>>(logits, ld, V, off, tgt, lse, g, outT, rows);
+  return true;
+}
+
+// The tempered twins (TEMP instantiations): the same launches with inv_temp = 1 / temperature.
+void launch_logprob_fwd_temp(const bf16_t* logits, int64_t ld, int V, int64_t off, int64_t rows,
+                             const int64_t* tgt, float* logp, float* lse, float inv_temp, hipStream_t st) {
+  if (rows == 0) return;
+  const bool vec = (V % 8 == 0) && (ld % 8 == 0);
+  if (vec)
+    logprob_fwd_kernel<true, false, true><<<rows, 256, 0, st>>>(logits, ld, V, off, tgt, logp, lse, nullptr,
+                                                                inv_temp);
+  else
+    logprob_fwd_kernel<false, false, true><<<rows, 256, 0, st>>>(logits, ld, V, off, tgt, logp, lse, nullptr,
+                                                                 inv_temp);
+}
+
+void launch_logprob_bwd_temp(bf16_t* logits, int64_t ld, int V, int64_t off, int64_t rows, const int64_t* tgt,
+                             const float* lse, const float* g, float inv_temp, hipStream_t st) {
+  if (rows == 0) return;
+  const bool vec = (V % 8 == 0) && (ld % 8 == 0);
+  if (vec)
+    logprob_bwd_kernel<true, false, true><<<rows, 256, 0, st>>>(logits, ld, V, off, tgt, lse, g, nullptr,
+                                                                nullptr, inv_temp);
+  else
+    logprob_bwd_kernel<false, false, true><<<rows, 256, 0, st>>>(logits, ld, V, off, tgt, lse, g, nullptr,
+                                                                 nullptr, inv_temp);
+}
+
+void launch_logprob_entropy_fwd_temp(const bf16_t* logits, int64_t ld, int V, int64_t off, int64_t rows,
+                                     const int64_t* tgt, float* logp, float* lse, float* ent, float inv_temp,
+                                     hipStream_t st) {
+  if (rows == 0) return;
+  const bool vec = (V % 8 == 0) && (ld % 8 == 0);
+  if (vec)
+    logprob_fwd_kernel<true, true, true><<<rows, 256, 0, st>>>(logits, ld, V, off, tgt, logp, lse, ent,
+                                                               inv_temp);
+  else
+    logprob_fwd_kernel<false, true, true><<<rows, 256, 0, st>>>(logits, ld, V, off, tgt, logp, lse, ent,
+                                                                inv_temp);
+}
+
+void launch_logprob_entropy_bwd_temp(bf16_t* logits, int64_t ld, int V, int64_t off, int64_t rows,
+                                     const int64_t* tgt, const float* lse, const float* ent, const float* g,
+                                     const float* ge, float inv_temp, hipStream_t st) {
+  if (rows == 0) return;
+  const bool vec = (V % 8 == 0) && (ld % 8 == 0);
+  if (vec)
+    logprob_bwd_kernel<true, true, true><<<rows, 256, 0, st>>>(logits, ld, V, off, tgt, lse, g, ent, ge,
+                                                               inv_temp);
+  else
+    logprob_bwd_kernel<false, true, true><<<rows, 256, 0, st>>>(logits, ld, V, off, tgt, lse, g, ent, ge,
+                                                                inv_temp);
+}
+
+bool launch_logprob_entropy_bwd_t_temp(bf16_t* logits, int64_t ld, int V, int64_t rows, int64_t off,
+                                       const int64_t* tgt, const float* lse, const float* ent, const float* g,
+                                       const float* ge, bf16_t* outT, float inv_temp, hipStream_t st) {
+  if (rows % 8 != 0 || V % 8 != 0 || ld % 8 != 0) return false;
+  if (rows == 0) return true;
+  const dim3 grid((V + 255) / 256, static_cast<unsigned>((rows + 63) / 64));
+  logprob_bwd_t_kernel<true, true><<<grid, 256, 0, st>>>(logits, ld, V, off, tgt, lse, g, outT, rows, ent, ge,
+                                                         inv_temp);
+  return true;
+}
+
+bool launch_logprob_bwd_t_temp(bf16_t* logits, int64_t ld, int V, int64_t rows, int64_t off, const int64_t* tgt,
+                               const float* lse, const float* g, bf16_t* outT, float inv_temp, hipStream_t st) {
+  if (rows % 8 != 0 || V % 8 != 0 || ld % 8 != 0) return false;
+  if (rows == 0) return true;
+  const dim3 grid((V + 255) / 256, static_cast<unsigned>((rows + 63) / 64));
+  logprob_bwd_t_kernel<false, true><<<grid, 256, 0, st>>>(logits, ld, V, off, tgt, lse, g, outT, rows, nullptr,
+                                                          nullptr, inv_temp);
   return true;
 }
 

@@ -196,11 +196,17 @@ __device__ __forceinline__ float logp_value(float d, float s1, float gmax) {
   return (gmax - gmax == 0.f) ? d - logf(s1) : 0.f;
 }
 
+// LTEMP (with LOGP): the log-prob at the DRAW temperature instead, log softmax(x * inv_temp)[token]
+// over the full vocabulary. The draw pass already forms z = (x - gmax) * inv_temp; its exp summed
+// over every entry, whatever tau, is the mass (a NaN logit counts as -inf), and z of the pick
+// replaces x_t - gmax. Same accumulators, same fixed reduction order as the temperature-1 sum.
+__device__ __forceinline__ float logp_term_z(float z) { return z == z ? __expf(z) : 0.f; }
+
 // LOGP: also write logp[r], the row's temperature-1 log-softmax at the returned token (the
 // engine's model log-prob of the draw). Its mass sum S1 rides the draw pass (step 4) as a second
 // per-thread accumulator over the same contiguous segments, reduced by block_sum: shuffles and a
 // fixed LDS order, so two launches give the same bits. !LOGP compiles to the kernel without it.
-template <typename T, bool VEC, bool LOGP>
+template <typename T, bool VEC, bool LOGP, bool LTEMP = false>
 __global__ __launch_bounds__(kSampNT) void sample_kernel(const T* __restrict__ logits, int64_t ld_,
                                                           int V, float inv_temp, int top_k,
                                                           float top_p, bool greedy,
@@ -237,7 +243,10 @@ __global__ __launch_bounds__(kSampNT) void sample_kernel(const T* __restrict__ l
   for (int i = 1; i < kSampNT / 64; ++i) argmax = min(argmax, amin[i]);
   if (argmax == 0x7fffffff) argmax = 0;  // no finite logit in the row (all -inf / NaN): token 0
   if (greedy || inv_temp <= 0.f) {
-    if constexpr (LOGP) {  // one more pass for S1; the token is the max, so x_t - gmax = 0
+    // one more pass for S1; the token is the max, so x_t - gmax = 0. Always the temperature-1 sum:
+    // no draw temperature exists here, and sample_tokens_logp_tempered sends greedy /
+    // temperature <= 0 calls to the !LTEMP instantiation, so LTEMP never enters this branch.
+    if constexpr (LOGP) {
       float s1 = 0.f;
       for_each_logit<VEC>(row, V, [&](int, float x) { s1 += logp_term(x, gmax); });
       s1 = block_sum<kSampNT>(s1, sc);
@@ -320,7 +329,8 @@ __global__ __launch_bounds__(kSampNT) void sample_kernel(const T* __restrict__ l
       for (int j = 0; j < 8; ++j) {
         const float z = (x[j] - gmax) * inv_temp;
         mine += z >= tau ? __expf(z) : 0.f;
-        if constexpr (LOGP) mine1 += logp_term(x[j], gmax);
+        if constexpr (LOGP && LTEMP) mine1 += logp_term_z(z);
+        else if constexpr (LOGP) mine1 += logp_term(x[j], gmax);
       }
     }
   } else {
@@ -328,14 +338,15 @@ __global__ __launch_bounds__(kSampNT) void sample_kernel(const T* __restrict__ l
       const float xv = ld(row, v);
       const float z = (xv - gmax) * inv_temp;
       mine += z >= tau ? __expf(z) : 0.f;
-      if constexpr (LOGP) mine1 += logp_term(xv, gmax);
+      if constexpr (LOGP && LTEMP) mine1 += logp_term_z(z);
+      else if constexpr (LOGP) mine1 += logp_term(xv, gmax);
     }
   }
-  [[maybe_unused]] __shared__ float dsel;  // LOGP: x_t - gmax of the picked token
+  [[maybe_unused]] __shared__ float dsel;  // LOGP: x_t - gmax of the picked token; LTEMP: its z
   [[maybe_unused]] float mass1 = 0.f;  // LOGP: S1
   if constexpr (LOGP) {
     mass1 = block_sum<kSampNT>(mine1, sc);
-    if (tid == 0) dsel = 0.f;  // the argmax fallback below: x_t = gmax
+    if (tid == 0) dsel = 0.f;  // the argmax fallback below: x_t = gmax (z = 0 as well)
   }
   tm[tid] = mine;
   if (tid == 0) ans = -1;
@@ -362,7 +373,7 @@ __global__ __launch_bounds__(kSampNT) void sample_kernel(const T* __restrict__ l
     }
     ans = pick;
     if constexpr (LOGP) {
-      if (pick >= 0) dsel = ld(row, pick) - gmax;
+      if (pick >= 0) dsel = LTEMP ? (ld(row, pick) - gmax) * inv_temp : ld(row, pick) - gmax;
     }
   }
   __syncthreads();
@@ -632,10 +643,11 @@ __global__ __launch_bounds__(kSampNT) void split_resolve_kernel(int G, int top_k
   if (tid == 0) ws.state[r] = s;
 }
 
-// LOGP: the chunk's share of the temperature-1 full-vocabulary mass S1 goes to csum [B, G] (a
+// LOGP: the chunk's share of the full-vocabulary mass behind `logp` goes to csum [B, G] (a
 // workspace region of its own behind the SplitWs ones); split_pick_kernel adds the G partials in
-// index order.
-template <typename T, bool LOGP>
+// index order. The mass is S1, the temperature-1 sum of exp(x - gmax), or under LTEMP the tempered
+// sum of exp(z), z = (x - gmax) * inv_t, over every entry whatever tau.
+template <typename T, bool LOGP, bool LTEMP = false>
 __global__ __launch_bounds__(kSplitNT) void split_mass_kernel(const T* __restrict__ logits,
                                                               int64_t ld_, int V, int G,
                                                               float inv_t, bool has_tau,
@@ -659,7 +671,8 @@ __global__ __launch_bounds__(kSplitNT) void split_mass_kernel(const T* __restric
     for (int j = 0; j < 8; ++j) {
       const float z = (x[j] - gmax) * inv_t;
       acc += z >= tau ? __expf(z) : 0.f;
-      if constexpr (LOGP) acc1 += logp_term(x[j], gmax);
+      if constexpr (LOGP && LTEMP) acc1 += logp_term_z(z);
+      else if constexpr (LOGP) acc1 += logp_term(x[j], gmax);
     }
   }
   const float tot = block_sum<kSplitNT>(acc, red);
@@ -670,7 +683,7 @@ __global__ __launch_bounds__(kSplitNT) void split_mass_kernel(const T* __restric
   }
 }
 
-template <typename T, bool LOGP>
+template <typename T, bool LOGP, bool LTEMP = false>
 __global__ __launch_bounds__(kSplitNT) void split_pick_kernel(const T* __restrict__ logits,
                                                               int64_t ld_, int V, int G,
                                                               float inv_t, bool has_tau,
@@ -681,7 +694,7 @@ __global__ __launch_bounds__(kSplitNT) void split_pick_kernel(const T* __restric
                                                               float* __restrict__ logp) {
   __shared__ float tm[kSplitNT];
   __shared__ int ans;
-  [[maybe_unused]] __shared__ float dsel;  // LOGP: x_t - gmax of the picked token
+  [[maybe_unused]] __shared__ float dsel;  // LOGP: x_t - gmax of the picked token; LTEMP: its z
   const int r = blockIdx.x, tid = threadIdx.x;
   float gmax;
   int argmax;
@@ -714,7 +727,7 @@ __global__ __launch_bounds__(kSplitNT) void split_pick_kernel(const T* __restric
   }
   if (tid == 0) ans = -1;
   if constexpr (LOGP) {
-    if (tid == 0) dsel = 0.f;  // the argmax fallback below: x_t = gmax
+    if (tid == 0) dsel = 0.f;  // the argmax fallback below: x_t = gmax (z = 0 as well)
   }
   const T* row = logits + int64_t(r) * ld_;
   float mine = 0.f;
@@ -752,7 +765,7 @@ __global__ __launch_bounds__(kSplitNT) void split_pick_kernel(const T* __restric
     }
     ans = pick;
     if constexpr (LOGP) {
-      if (pick >= 0) dsel = ld(row, pick) - gmax;
+      if (pick >= 0) dsel = LTEMP ? (ld(row, pick) - gmax) * inv_t : ld(row, pick) - gmax;
     }
   }
   __syncthreads();
@@ -790,7 +803,7 @@ size_t sample_workspace_bytes_logp(int64_t rows, int G) {
   return G > 0 ? split_ws_bytes(rows, G) + align256(size_t(rows) * G * 4) : 0;
 }
 
-template <typename T, bool LOGP>
+template <typename T, bool LOGP, bool LTEMP = false>
 static void launch_split(const T* lg, int64_t ld_, int64_t rows, int V, int G, float inv_t,
                          int top_k, float top_p, const int64_t* rng, int64_t* out, float* logp,
                          void* wsp, hipStream_t st) {
@@ -806,21 +819,21 @@ static void launch_split(const T* lg, int64_t ld_, int64_t rows, int V, int G, f
     const int first_phase = p == 0 ? (need_k ? kKCoarse : kPCoarse) : kDone;
     split_resolve_kernel<<<rows, kSampNT, 0, st>>>(G, top_k, top_p, need_p, first_phase, ws);
   }
-  split_mass_kernel<T, LOGP><<<grid, kSplitNT, 0, st>>>(lg, ld_, V, G, inv_t, passes > 0, ws, csum);
-  split_pick_kernel<T, LOGP><<<rows, kSplitNT, 0, st>>>(lg, ld_, V, G, inv_t, passes > 0, rng, ws,
-                                                        out, csum, logp);
+  split_mass_kernel<T, LOGP, LTEMP><<<grid, kSplitNT, 0, st>>>(lg, ld_, V, G, inv_t, passes > 0, ws, csum);
+  split_pick_kernel<T, LOGP, LTEMP><<<rows, kSplitNT, 0, st>>>(lg, ld_, V, G, inv_t, passes > 0, rng, ws,
+                                                               out, csum, logp);
 }
 
-template <bool LOGP>
+template <bool LOGP, bool LTEMP = false>
 static void sample_split_any(const void* logits, bool is_bf16, int64_t ld_, int64_t rows, int V,
                              int G, float inv_temp, int top_k, float top_p, const int64_t* rng,
                              int64_t* out, float* logp, void* ws, hipStream_t st) {
   if (rows == 0) return;
   if (is_bf16)
-    launch_split<bf16_t, LOGP>(static_cast<const bf16_t*>(logits), ld_, rows, V, G, inv_temp,
+    launch_split<bf16_t, LOGP, LTEMP>(static_cast<const bf16_t*>(logits), ld_, rows, V, G, inv_temp,
                                top_k, top_p, rng, out, logp, ws, st);
   else
-    launch_split<float, LOGP>(static_cast<const float*>(logits), ld_, rows, V, G, inv_temp, top_k,
+    launch_split<float, LOGP, LTEMP>(static_cast<const float*>(logits), ld_, rows, V, G, inv_temp, top_k,
                               top_p, rng, out, logp, ws, st);
 }
 
@@ -839,7 +852,16 @@ void launch_sample_split_logp(const void* logits, bool is_bf16, int64_t ld_, int
                          ws, st);
 }
 
-template <bool LOGP>
+// ws: sample_workspace_bytes_logp(rows, G) bytes. The draw-temperature log-prob (LTEMP); the
+// caller sends greedy / temperature <= 0 calls, which have no draw temperature, to the plain one.
+void launch_sample_split_logp_tempered(const void* logits, bool is_bf16, int64_t ld_, int64_t rows, int V,
+                                       int G, float inv_temp, int top_k, float top_p, const int64_t* rng,
+                                       int64_t* out, float* logp, void* ws, hipStream_t st) {
+  sample_split_any<true, true>(logits, is_bf16, ld_, rows, V, G, inv_temp, top_k, top_p, rng, out, logp,
+                               ws, st);
+}
+
+template <bool LOGP, bool LTEMP = false>
 static void sample_any(const void* logits, bool is_bf16, int64_t ld_, int64_t rows, int V,
                        float inv_temp, int top_k, float top_p, bool greedy, const int64_t* rng,
                        int64_t* out, float* logp, hipStream_t st) {
@@ -847,7 +869,7 @@ static void sample_any(const void* logits, bool is_bf16, int64_t ld_, int64_t ro
   const bool vec = V % 8 == 0 && ld_ % 8 == 0 &&
                    reinterpret_cast<uintptr_t>(logits) % 16 == 0;
 #define DLA_SAMPLE(T, VV)                                                                  \
-  sample_kernel<T, VV, LOGP><<<rows, kSampNT, 0, st>>>(static_cast<const T*>(logits), ld_, V, \
+  sample_kernel<T, VV, LOGP, LTEMP><<<rows, kSampNT, 0, st>>>(static_cast<const T*>(logits), ld_, V, \
                                                        inv_temp, top_k, top_p, greedy, rng, out, \
                                                        logp)
   if (is_bf16) {
@@ -872,6 +894,12 @@ void launch_sample_logp(const void* logits, bool is_bf16, int64_t ld_, int64_t r
                         int64_t* out, float* logp, hipStream_t st) {
   sample_any<true>(logits, is_bf16, ld_, rows, V, inv_temp, top_k, top_p, greedy, rng, out, logp,
                    st);
+}
+
+void launch_sample_logp_tempered(const void* logits, bool is_bf16, int64_t ld_, int64_t rows, int V,
+                                 float inv_temp, int top_k, float top_p, const int64_t* rng, int64_t* out,
+                                 float* logp, hipStream_t st) {
+  sample_any<true, true>(logits, is_bf16, ld_, rows, V, inv_temp, top_k, top_p, false, rng, out, logp, st);
 }
 
 }  // namespace dla

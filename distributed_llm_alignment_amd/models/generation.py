@@ -214,12 +214,32 @@ def _graph_ok(model: CausalLM, cache: KVCache) -> bool:
             and ops._ext.use_native(cache.k))
 
 
+# which log-prob `generate(return_logprobs=True)` asks the sampler for
+_LOGP_OFF, _LOGP_PLAIN, _LOGP_TEMPERED = 0, 1, 2
+
+
+def _logp_sampler(mode: int):
+    return ops.decode.sample_tokens_logp_tempered if mode == _LOGP_TEMPERED else ops.decode.sample_tokens_logp
+
+
+def _logp_mode(return_logprobs: bool, logprob_temperature, do_sample: bool, temperature: float) -> int:
+    """None / 1.0: the temperature-1 log-prob (`sample_tokens_logp`); the draw temperature of a
+    sampling call: the log-prob at that temperature (`sample_tokens_logp_tempered`); anything else
+    is not something the sampler's passes can produce."""
+    if logprob_temperature is None or float(logprob_temperature) == 1.0:
+        return _LOGP_PLAIN if return_logprobs else _LOGP_OFF
+    if not (do_sample and temperature > 0 and float(logprob_temperature) == float(temperature)):
+        raise ValueError(f"logprob_temperature must be None, 1.0 or the sampling temperature "
+                         f"({temperature!r} with do_sample={do_sample}), got {logprob_temperature!r}")
+    return _LOGP_TEMPERED if return_logprobs else _LOGP_OFF
+
+
 class _DecodeGraph:
     """One captured decode step: embed -> layers (device-indexed cache writes, decode kernel)
     -> norm -> LM head -> fused sampler -> finished/pad bookkeeping, all on device."""
 
     def __init__(self, model, cache, B, max_new, eos, pad, greedy, temperature, top_k, top_p, seed,
-                 logprobs: bool = False):
+                 logprobs: int = 0):
         dev = cache.k.device
         self.model, self.cache = model, cache
         self.tok = torch.zeros((B, 1), dtype=torch.long, device=dev)
@@ -227,8 +247,10 @@ class _DecodeGraph:
         self.out = torch.full((B, max_new), pad, dtype=torch.long, device=dev)
         self.gen_mask = torch.zeros((B, max_new), dtype=torch.long, device=dev)
         # the sampling engine's log-prob of every emitted token (0 for finished rows); only with
-        # `logprobs`, which also selects the sampler op that produces them
+        # `logprobs`, which also selects the sampler op that produces them (_LOGP_PLAIN: at
+        # temperature 1, _LOGP_TEMPERED: at the draw temperature)
         self.logp = torch.zeros((B, max_new), dtype=torch.float32, device=dev) if logprobs else None
+        self.logp_op = _logp_sampler(logprobs) if logprobs else None
         self.col = torch.zeros(1, dtype=torch.long, device=dev)
         self.rng = torch.tensor([seed, 0], dtype=torch.long, device=dev)
         self.eos, self.pad = eos, pad
@@ -243,7 +265,7 @@ class _DecodeGraph:
     def sample(self, logits):
         t, k, p, g = self.args
         if self.logp is not None:
-            nxt, lp = ops.decode.sample_tokens_logp(logits, t, k, p, g, self.rng)
+            nxt, lp = self.logp_op(logits, t, k, p, g, self.rng)
             self.logp.index_copy_(1, self.col, torch.where(self.finished, torch.zeros_like(lp), lp).unsqueeze(1))
         else:
             nxt = ops.decode.sample_tokens(logits, t, k, p, g, self.rng)
@@ -370,7 +392,8 @@ def generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional[
              pad_token_id: Optional[int] = None, generator: Optional[torch.Generator] = None,
              return_mask: bool = False, use_graph: Optional[bool] = None, seed: Optional[int] = None,
              weight_dtype: str = "bf16", num_return_sequences: int = 1, share_prefill: bool = True,
-             group_attention: bool = False, return_logprobs: bool = False):
+             group_attention: bool = False, return_logprobs: bool = False,
+             logprob_temperature: Optional[float] = None):
     """Left-padded prompts [B, Tp] -> sequences [B, Tp + n] (n <= max_new_tokens).
 
     `num_return_sequences=G` (group rollouts, GRPO): G samples per prompt, output [B*G, Tp + n]
@@ -393,6 +416,11 @@ def generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional[
     `temperature` / `top_k` / `top_p` shaped the draw; on the GPU it comes out of the fused
     sampler's own passes, `ops.decode.sample_tokens_logp`), and exactly 0 where the generation
     mask is 0. Return order: `seqs[, mask][, logp]`.
+    `logprob_temperature`: None or 1.0 keeps that; the sampling `temperature` itself (with
+    `do_sample`) returns log softmax(logits / temperature)[token] instead, still over the full
+    vocabulary (no top-k / top-p filter), the quantity `token_logprobs(temperature=)` returns
+    (`ops.decode.sample_tokens_logp_tempered`); the tokens are the same. Any other value raises
+    ValueError.
 
     On MI355X the prompt is prefilled with the flash-attention kernel, then every new token is
     ONE replay of a captured hipGraph (decode kernel + fused sampler, no host sync except an
@@ -412,11 +440,12 @@ def generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional[
         input_ids = input_ids.repeat_interleave(G, 0)
         attention_mask = attention_mask.repeat_interleave(G, 0) if attention_mask is not None else None
         G = 1
+    lp_mode = _logp_mode(bool(return_logprobs), logprob_temperature, do_sample, temperature)
     f8 = weight_dtype == "fp8" or ops.decode.fp8_enabled()
     with ops.decode.fp8_weights(f8), ops.fp8_inference_scope(model, f8 and PREFILL_FP8):
         return _generate(model, input_ids, attention_mask, max_new_tokens, do_sample, temperature, top_p,
                          top_k, eos_token_id, pad_token_id, generator, return_mask, use_graph, seed, G,
-                         bool(group_attention) and G > 1, bool(return_logprobs))
+                         bool(group_attention) and G > 1, lp_mode)
 
 
 def _generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor],
@@ -424,7 +453,7 @@ def _generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional
               eos_token_id: Optional[int], pad_token_id: Optional[int],
               generator: Optional[torch.Generator], return_mask: bool, use_graph: Optional[bool],
               seed: Optional[int], G: int = 1, group_attention: bool = False,
-              return_logprobs: bool = False):
+              return_logprobs: int = _LOGP_OFF):
     if DECODE_GATHER and model.layers_sharded():
         # ZeRO-3 policy: gather it once for the whole rollout (fused decode kernels + captured
         # graph) instead of an all-gather per layer per token
@@ -530,8 +559,8 @@ def _generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional
             logits = model.logits(last)
             lp = None
             if return_logprobs:  # native on the GPU; sample_next + log_softmax off it
-                nxt, lp = ops.decode.sample_tokens_logp(logits, temperature, top_k, top_p, greedy, rng,
-                                                        generator)
+                nxt, lp = _logp_sampler(return_logprobs)(logits, temperature, top_k, top_p, greedy, rng,
+                                                         generator)
                 if ops._ext.use_native(logits):
                     rng[1:].add_(1)
             elif ops._ext.use_native(logits):

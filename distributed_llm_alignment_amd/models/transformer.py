@@ -583,21 +583,24 @@ class CausalLM(nn.Module):
             lg = tp_all_gather_last(lg, self.tp)
         return lg
 
-    def _token_logprob(self, h2: torch.Tensor, targets: torch.Tensor) -> torch.Tensor:
-        """Per-token log p(target) from final hidden rows [N, H] (fused HIP LM-head path)."""
+    def _token_logprob(self, h2: torch.Tensor, targets: torch.Tensor, temperature: float = 1.0) -> torch.Tensor:
+        """Per-token log p(target) from final hidden rows [N, H] (fused HIP LM-head path), of
+        softmax(logits / temperature)."""
         if self.vocab_parallel is not None:
             from ..parallel.tensor_parallel import vocab_parallel_logprob
 
-            return vocab_parallel_logprob(h2, self.head_weight, targets, self.vocab_parallel[0], self.tp)
-        return ops.linear_logprob(h2, self.head_weight, targets)
+            return vocab_parallel_logprob(h2, self.head_weight, targets, self.vocab_parallel[0], self.tp,
+                                          temperature=temperature)
+        return ops.linear_logprob(h2, self.head_weight, targets, temperature=temperature)
 
-    def _token_logprob_entropy(self, h2: torch.Tensor, targets: torch.Tensor):
+    def _token_logprob_entropy(self, h2: torch.Tensor, targets: torch.Tensor, temperature: float = 1.0):
         """`_token_logprob` plus the per-row policy entropy from the same vocabulary pass."""
         if self.vocab_parallel is not None:
             from ..parallel.tensor_parallel import vocab_parallel_logprob_entropy
 
-            return vocab_parallel_logprob_entropy(h2, self.head_weight, targets, self.vocab_parallel[0], self.tp)
-        return ops.linear_logprob_entropy(h2, self.head_weight, targets)
+            return vocab_parallel_logprob_entropy(h2, self.head_weight, targets, self.vocab_parallel[0], self.tp,
+                                                  temperature=temperature)
+        return ops.linear_logprob_entropy(h2, self.head_weight, targets, temperature=temperature)
 
     def aux_loss(self):
         if not self.cfg.is_moe:
@@ -613,13 +616,17 @@ class CausalLM(nn.Module):
             return tgt, mask
         return sp.local(sp.pad(tgt, -100)), (None if mask is None else sp.local(sp.pad(mask, 0)))
 
-    def _masked_token_logprob(self, h: torch.Tensor, tgt: torch.Tensor, with_entropy: bool = False):
+    def _masked_token_logprob(self, h: torch.Tensor, tgt: torch.Tensor, with_entropy: bool = False,
+                              temperature: float = 1.0):
         """[S, T', H] hidden + [S, T'] targets (-100 = ignore) -> [S, T'] fp32 log-probs (0 where
         ignored); the LM-head bias models (phi-2) go through full logits. `with_entropy`: also the
-        entropy of each position's next-token distribution (0 where ignored)."""
+        entropy of each position's next-token distribution (0 where ignored). `temperature`: both of
+        softmax(logits / temperature)."""
         S, T, H = h.shape
         if self.lm_head_bias is not None:
             lg = self.logits(h).float()
+            if temperature != 1.0:
+                lg = lg * ops.logprob.inv_temperature(temperature)
             lsm = torch.log_softmax(lg, -1)
             lp = lsm.gather(-1, tgt.clamp(min=0).unsqueeze(-1)).squeeze(-1)
             lp = torch.where(tgt >= 0, lp, torch.zeros_like(lp))
@@ -628,9 +635,9 @@ class CausalLM(nn.Module):
             ent = -(lsm.exp() * lsm.masked_fill(lsm == float("-inf"), 0.0)).sum(-1)
             return lp, torch.where(tgt >= 0, ent, torch.zeros_like(ent))
         if with_entropy:
-            lp, ent = self._token_logprob_entropy(h.reshape(S * T, H), tgt.reshape(-1))
+            lp, ent = self._token_logprob_entropy(h.reshape(S * T, H), tgt.reshape(-1), temperature)
             return lp.view(S, T), ent.view(S, T)
-        return self._token_logprob(h.reshape(S * T, H), tgt.reshape(-1)).view(S, T)
+        return self._token_logprob(h.reshape(S * T, H), tgt.reshape(-1), temperature).view(S, T)
 
     def sequence_logprob(self, input_ids, attention_mask=None, reduction: str = "mean"):
         """Reference `compute_logprobs` (train_dpo.py:31-39): masked mean log p per sequence."""
@@ -639,19 +646,22 @@ class CausalLM(nn.Module):
         lp = self._masked_token_logprob(h, tgt)
         return sp_seq_reduce(self.sp, lp, mask, reduction == "mean")
 
-    def token_logprobs(self, input_ids, attention_mask=None, with_entropy: bool = False):
+    def token_logprobs(self, input_ids, attention_mask=None, with_entropy: bool = False,
+                       temperature: float = 1.0):
         """[S, T] log p(x_{t+1} | x_<=t) at every scored position (0 elsewhere): the per-action
         grid of token-level RL objectives (PPO). `with_entropy`: returns (lp, ent), ent [S, T] the
-        entropy of p(. | x_<=t) at the same positions, from the same LM-head pass."""
+        entropy of p(. | x_<=t) at the same positions, from the same LM-head pass. `temperature`:
+        p = softmax(logits / temperature), the distribution a sampler at that temperature draws
+        from (applied in fp32 inside the LM-head row kernels)."""
         h = self(input_ids, attention_mask)
         tgt, _ = self._sp_targets(ops.shifted_targets(input_ids, attention_mask)[0])
         if with_entropy:
-            lp, ent = self._masked_token_logprob(h, tgt, True)
+            lp, ent = self._masked_token_logprob(h, tgt, True, temperature)
             if self.sp is not None:
                 lp = self.sp.gather(lp, dim=1)[:, :input_ids.shape[1]]
                 ent = self.sp.gather(ent, dim=1)[:, :input_ids.shape[1]]
             return lp, ent
-        lp = self._masked_token_logprob(h, tgt)
+        lp = self._masked_token_logprob(h, tgt, temperature=temperature)
         if self.sp is not None:
             lp = self.sp.gather(lp, dim=1)[:, :input_ids.shape[1]]
         return lp

@@ -172,12 +172,18 @@ def rollout_is_stats(rollout_logp: torch.Tensor, trainer_lp: torch.Tensor, act: 
     return {"is_weight": w, "rollout_is": {f"rollout_{k}": v for k, v in met.items() if k != "tokens"}}
 
 
+def _temp_kw(temperature: float) -> dict:
+    """`token_logprobs` keywords for the step's log-prob temperature: none at 1.0, so a default
+    run makes the calls (and launches the kernels) it always made."""
+    return {} if temperature == 1.0 else {"temperature": float(temperature)}
+
+
 @torch.no_grad()
 def ppo_rollout_stats(policy, ref, critic, seqs, mask, prompt_len: int, scores, kl_coef: float = 0.1,
                       gamma: float = 1.0, lam: float = 0.95, whiten: bool = True,
                       old_logp: Optional[torch.Tensor] = None, rollout_logp: Optional[torch.Tensor] = None,
                       is_cap: float = 2.0, is_floor: Optional[float] = None, is_level: str = "token",
-                      is_mode: str = "truncate"):
+                      is_mode: str = "truncate", temperature: float = 1.0):
     """Token-level PPO targets for one batch of rollouts (actor-critic; the north-star
     "PPO RLHF (actor + critic + reward)" config). Per-token reward = -kl_coef * (logp - logp_ref)
     on every action, plus the reward-model score on the last action; GAE(gamma, lam) over the
@@ -186,9 +192,12 @@ def ppo_rollout_stats(policy, ref, critic, seqs, mask, prompt_len: int, scores, 
     in the KL reward too, instead of a policy forward over the rollouts. `rollout_logp` (the same
     kind of grid) instead leaves the old-policy log-probs and the KL reward the trainer's own and
     adds `is_weight` / `rollout_is` (`rollout_is_stats` with the four `is_*` settings): truncated
-    importance weights for `ppo_loss`, computed once per rollout batch."""
-    old_lp = old_logp.float() if old_logp is not None else policy.token_logprobs(seqs, mask)
-    ref_lp = ref.token_logprobs(seqs, mask)
+    importance weights for `ppo_loss`, computed once per rollout batch. `temperature`: every
+    log-prob here (policy, reference) is of softmax(logits / temperature); grids passed in must be
+    at the same temperature."""
+    tkw = _temp_kw(temperature)
+    old_lp = old_logp.float() if old_logp is not None else policy.token_logprobs(seqs, mask, **tkw)
+    ref_lp = ref.token_logprobs(seqs, mask, **tkw)
     values = critic(seqs, mask)
     act = action_mask(mask, prompt_len)
     kl = (old_lp - ref_lp) * act
@@ -230,17 +239,18 @@ def ppo_critic_stream(device: torch.device):
 
 
 def token_logprobs_entropy(policy, seqs, mask, act, entropy_coef: float = 0.0, log_entropy: bool = False,
-                           n_act: Optional[torch.Tensor] = None):
+                           n_act: Optional[torch.Tensor] = None, temperature: float = 1.0):
     """Token log-probs of a PPO / GRPO (micro-)batch and, when `entropy_coef != 0` or
     `log_entropy`, the policy entropy from the same LM-head pass: returns (lp, bonus, entropy).
     `bonus` = entropy_coef * sum(ent * act) / n_act (None when the coefficient is 0: the entropy is
     then detached and the plain backward kernels run); `n_act`, a device tensor (no host sync), is
     the action-token count the bonus is normalised by -- the whole minibatch's for micro-batches,
     this batch's own by default. `entropy` is this batch's detached mean over action tokens (None
-    when off)."""
+    when off). `temperature`: log-probs and entropy of softmax(logits / temperature)."""
+    tkw = _temp_kw(temperature)
     if entropy_coef == 0 and not log_entropy:
-        return policy.token_logprobs(seqs, mask), None, None
-    lp, ent = policy.token_logprobs(seqs, mask, with_entropy=True)
+        return policy.token_logprobs(seqs, mask, **tkw), None, None
+    lp, ent = policy.token_logprobs(seqs, mask, with_entropy=True, **tkw)
     if entropy_coef == 0:
         ent = ent.detach()
     tot = (ent * act).sum()
@@ -253,10 +263,11 @@ def token_logprobs_entropy(policy, seqs, mask, act, entropy_coef: float = 0.0, l
 
 def ppo_loss(policy, critic, seqs, mask, stats: Dict[str, torch.Tensor], clip_eps: float = 0.2,
              value_clip: float = 0.2, vf_coef: float = 0.1, entropy_coef: float = 0.0,
-             log_entropy: bool = False):
+             log_entropy: bool = False, temperature: float = 1.0):
     """Clipped surrogate (HIP fused fwd+bwd) + vf_coef * clipped value loss on one minibatch,
     minus entropy_coef * the mean policy entropy over action tokens (`metrics["entropy"]`, also
     with `log_entropy` alone). `stats["is_weight"]` (optional) weights the surrogate per token.
+    `temperature`: the policy's log-probs and entropy at that temperature (as in `stats`).
     Run its backward through `ppo_backward` (joins the critic's stream
     afterwards)."""
     cs = ppo_critic_stream(seqs.device)
@@ -266,7 +277,8 @@ def ppo_loss(policy, critic, seqs, mask, stats: Dict[str, torch.Tensor], clip_ep
         with torch.cuda.stream(cs):
             v = critic(seqs, mask)
             vl = ops.ppo_value_loss(v, stats["values"], stats["returns"], stats["act"], value_clip)
-    lp, bonus, entropy = token_logprobs_entropy(policy, seqs, mask, stats["act"], entropy_coef, log_entropy)
+    lp, bonus, entropy = token_logprobs_entropy(policy, seqs, mask, stats["act"], entropy_coef, log_entropy,
+                                                temperature=temperature)
     pl, pm = ops.ppo_policy_loss(lp, stats["old_logp"], stats["advantages"], stats["act"], clip_eps,
                                  is_weight=stats.get("is_weight"))
     if cs is None:
@@ -299,7 +311,7 @@ def grpo_rollout_stats(policy, ref, seqs, mask, prompt_len: int, scores, G: int,
                        scale_std: bool = True, need_old: bool = False,
                        old_logp: Optional[torch.Tensor] = None, rollout_logp: Optional[torch.Tensor] = None,
                        is_cap: float = 2.0, is_floor: Optional[float] = None, is_level: str = "token",
-                       is_mode: str = "truncate"):
+                       is_mode: str = "truncate", temperature: float = 1.0):
     """GRPO targets for one batch of group rollouts (rows p*G .. p*G+G-1 sample prompt p). The
     reward is the reward-model score alone (the KL lives in the loss); a rollout's advantage is its
     score standardised inside its group. The reference's token log-probs are skipped entirely
@@ -309,14 +321,16 @@ def grpo_rollout_stats(policy, ref, seqs, mask, prompt_len: int, scores, G: int,
     old-policy log-probs, whatever `need_old`, with no policy forward. `rollout_logp` (the same
     kind of grid) instead keeps the old-policy log-probs the trainer's own (the forward always
     runs, as with `need_old`) and adds `is_weight` / `rollout_is` (`rollout_is_stats` with the four
-    `is_*` settings): truncated importance weights for `grpo_loss`, computed once per rollout batch."""
+    `is_*` settings): truncated importance weights for `grpo_loss`, computed once per rollout batch. `temperature`:
+    every log-prob here is of softmax(logits / temperature); grids passed in must be at the same."""
+    tkw = _temp_kw(temperature)
     act = action_mask(mask, prompt_len)
     adv, gm = ops.group_advantages(scores, G, scale_std)
-    ref_lp = ref.token_logprobs(seqs, mask) if beta != 0 else None
+    ref_lp = ref.token_logprobs(seqs, mask, **tkw) if beta != 0 else None
     if old_logp is not None:
         old_logp = old_logp.float()
     elif need_old or rollout_logp is not None:
-        old_logp = policy.token_logprobs(seqs, mask)
+        old_logp = policy.token_logprobs(seqs, mask, **tkw)
     out = {"act": act, "advantages": adv, "ref_logp": ref_lp, "old_logp": old_logp,
            "scores": scores.float(), "reward_std": gm["reward_std"], "frac_zero_std": gm["frac_zero_std"]}
     if rollout_logp is not None:
@@ -327,14 +341,15 @@ def grpo_rollout_stats(policy, ref, seqs, mask, prompt_len: int, scores, G: int,
 def grpo_loss(policy, seqs, mask, stats: Dict[str, torch.Tensor], clip_low: float = 0.2,
               clip_high: Optional[float] = None, beta: float = 0.04, loss_type: str = "sequence",
               max_len: Optional[int] = None, denom: Optional[torch.Tensor] = None,
-              entropy_coef: float = 0.0, log_entropy: bool = False, n_act: Optional[torch.Tensor] = None):
+              entropy_coef: float = 0.0, log_entropy: bool = False, n_act: Optional[torch.Tensor] = None,
+              temperature: float = 1.0):
     """Token-level clipped surrogate + beta * k3 KL to the reference (HIP fused fwd+bwd) on one
     (micro-)batch of rollouts; `stats` from `grpo_rollout_stats`, sliced to the same rows.
     `entropy_coef` / `log_entropy` / `n_act`: the entropy bonus and metric of
     `token_logprobs_entropy`. `stats["is_weight"]` (optional) weights the policy-gradient term per
-    token."""
+    token. `temperature`: the policy's log-probs and entropy at that temperature (as in `stats`)."""
     lp, bonus, entropy = token_logprobs_entropy(policy, seqs, mask, stats["act"], entropy_coef, log_entropy,
-                                                n_act)
+                                                n_act, temperature=temperature)
     loss, m = ops.grpo_loss(lp, stats.get("old_logp"), stats.get("ref_logp"), stats["advantages"],
                             stats["act"], clip_low, clip_high, beta, loss_type, max_len, denom,
                             is_weight=stats.get("is_weight"))

@@ -120,6 +120,28 @@ def sample_tokens_logp(logits: torch.Tensor, temperature: float, top_k: int, top
     return tok, torch.log_softmax(x, dim=-1).gather(-1, tok.unsqueeze(-1)).squeeze(-1)
 
 
+def sample_tokens_logp_tempered(logits: torch.Tensor, temperature: float, top_k: int, top_p: float, greedy: bool,
+                                rng: torch.Tensor, generator: Optional[torch.Generator] = None):
+    """`sample_tokens_logp` with the log-prob at the DRAW temperature: logp =
+    log_softmax(logits * inv_temp, -1)[token], inv_temp = fp32(1 / temperature), over the full
+    vocabulary (no top-k / top-p filter): the quantity `CausalLM.token_logprobs(temperature=)`
+    returns. The tokens are bitwise those of `sample_tokens`. `greedy` or `temperature <= 0` has no
+    draw temperature and returns `sample_tokens_logp`'s result. On the GPU the mass sum rides the
+    draw pass, which already forms (x - max) * inv_temp (`torch.ops.dla.sample_tokens_logp_tempered`)."""
+    if greedy or not temperature > 0:
+        return sample_tokens_logp(logits, temperature, top_k, top_p, greedy, rng, generator)
+    if _ext.use_native(logits):
+        tok, lp = _ext.require().sample_tokens_logp_tempered(logits, float(temperature), int(top_k), float(top_p),
+                                                             bool(greedy), rng)
+        return tok, lp
+    from ..models.generation import sample_next
+    from .logprob import inv_temperature
+
+    x = logits.float()
+    tok = sample_next(x, not greedy, temperature, top_p, top_k, generator)
+    return tok, torch.log_softmax(x * inv_temperature(temperature), dim=-1).gather(-1, tok.unsqueeze(-1)).squeeze(-1)
+
+
 def kv_replicate(src_k, src_v, dst_k, dst_v, G: int) -> None:
     """Shared-prefill replication for group rollouts: keys / values [0, Tp) of every layer of the
     P-row prefill cache (`src_*` [L, P, Tp, Hkv, D], or the layer-split list of [P, Tp, Hkv, D]) are

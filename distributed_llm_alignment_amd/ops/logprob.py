@@ -18,11 +18,17 @@ from the same vocabulary pass (a third online accumulator in the row kernel) and
 gradient written by the same in-place dlogits pass: the policy entropy of PPO / GRPO without an
 fp32 [N, V] softmax.
 
+Both take `temperature` (default 1.0): the log-prob and entropy of softmax(logits / temperature),
+the distribution a sampler at that temperature draws from. The row kernels apply
+inv_temp = float(1 / temperature) in fp32 to the bf16 logits the GEMM wrote (the `*_temp` ops);
+at 1.0 the plain ops run, kernel for kernel.
+
 `sequence_logprob(...)` adds the masked per-sequence reduction (length-normalised mean by default,
 exactly the reference's `/ mask.sum(1).clamp(min=1)`, or sum) as a HIP kernel pair.
 """
 from __future__ import annotations
 
+import math
 import os
 from typing import Optional
 
@@ -40,8 +46,19 @@ _NO_GRAD_CHUNK = 8192
 LOGPROB_T = os.environ.get("DLA_LOGPROB_T", "1") != "0"
 
 
-def _ref_linear_logprob(hidden, weight, targets):
+def inv_temperature(temperature: float) -> float:
+    """The fp32 scalar the tempered kernels multiply by: 1 / temperature, the divide in double and
+    rounded once to fp32 (returned widened, as the ops take it)."""
+    t = float(temperature)
+    if not (t > 0.0 and math.isfinite(t)):
+        raise ValueError(f"temperature must be a finite number > 0, got {temperature!r}")
+    return torch.tensor(1.0 / t, dtype=torch.float64).float().item()
+
+
+def _ref_linear_logprob(hidden, weight, targets, temperature: float = 1.0):
     logits = F.linear(hidden, weight).float()
+    if temperature != 1.0:
+        logits = logits * inv_temperature(temperature)
     lse = torch.logsumexp(logits, dim=-1)
     safe = targets.clamp(min=0)
     lp = logits.gather(-1, safe.unsqueeze(-1)).squeeze(-1) - lse
@@ -50,13 +67,19 @@ def _ref_linear_logprob(hidden, weight, targets):
 
 class _LinearLogprobFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, hidden, weight, targets):
+    def forward(ctx, hidden, weight, targets, inv_temp=None):
+        # inv_temp: None = the plain ops; a float = the tempered twins (see `inv_temperature`)
         ops = _ext.require()
         need_grad = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
         N = hidden.shape[0]
+        ctx.inv_temp = inv_temp
+
+        def fwd(lg, tg):
+            return ops.logprob_fwd(lg, tg) if inv_temp is None else ops.logprob_fwd_temp(lg, tg, inv_temp)
+
         if need_grad:
             logits = F.linear(hidden, weight)
-            logp, lse = ops.logprob_fwd(logits, targets)
+            logp, lse = fwd(logits, targets)
             ctx.save_for_backward(hidden, targets, lse, logits)
             ctx.weight = weight  # (on ctx: see ops.linear._LinearMainGradFn)
             return logp
@@ -64,7 +87,7 @@ class _LinearLogprobFn(torch.autograd.Function):
         for s in range(0, N, _NO_GRAD_CHUNK):
             e = min(N, s + _NO_GRAD_CHUNK)
             lg = F.linear(hidden[s:e], weight)
-            lp, _ = ops.logprob_fwd(lg, targets[s:e])
+            lp, _ = fwd(lg, targets[s:e])
             logp[s:e] = lp
         return logp
 
@@ -73,6 +96,7 @@ class _LinearLogprobFn(torch.autograd.Function):
         ops = _ext.require()
         hidden, targets, lse, logits = ctx.saved_tensors
         weight = ctx.weight
+        it = ctx.inv_temp
         from .linear import _tn_ok, accumulate_weight_grad
 
         g = g.float().contiguous()
@@ -83,31 +107,42 @@ class _LinearLogprobFn(torch.autograd.Function):
             # the LM head's weight gradient runs as a TN GEMM on dlogits^T: write it from the
             # same pass that turns the logits into dlogits (undefined when the shape is outside
             # the kernel -> in-place kernel + transpose inside accumulate_weight_grad)
-            dlt = ops.logprob_bwd_t(logits, targets, lse, g)
+            dlt = (ops.logprob_bwd_t(logits, targets, lse, g) if it is None
+                   else ops.logprob_bwd_t_temp(logits, targets, lse, g, it))
             if not dlt.numel():
                 dlt = None
         if dlt is None:
-            ops.logprob_bwd(logits, targets, lse, g)
+            if it is None:
+                ops.logprob_bwd(logits, targets, lse, g)
+            else:
+                ops.logprob_bwd_temp(logits, targets, lse, g, it)
         dlogits = logits  # rewritten in place
         dh = input_grad(dlogits, weight) if ctx.needs_input_grad[0] else None
         dw = None
         if ctx.needs_input_grad[1]:
             if not accumulate_weight_grad(weight, dlogits, hidden, dyt=dlt):
                 dw = dlogits.t() @ hidden
-        return dh, dw, None
+        return dh, dw, None, None
 
 
-def linear_logprob(hidden: torch.Tensor, weight: torch.Tensor, targets: torch.Tensor) -> torch.Tensor:
-    """hidden [N, H], weight [V, H], targets [N] (int64, <0 = ignore) -> logp [N] fp32."""
+def linear_logprob(hidden: torch.Tensor, weight: torch.Tensor, targets: torch.Tensor,
+                   temperature: float = 1.0) -> torch.Tensor:
+    """hidden [N, H], weight [V, H], targets [N] (int64, <0 = ignore) -> logp [N] fp32, of
+    softmax(hidden @ W^T / temperature)."""
     if _ext.use_native(hidden):
-        return _LinearLogprobFn.apply(hidden.contiguous(), weight, targets.contiguous())
-    return _ref_linear_logprob(hidden, weight, targets)
+        if temperature == 1.0:
+            return _LinearLogprobFn.apply(hidden.contiguous(), weight, targets.contiguous(), None)
+        return _LinearLogprobFn.apply(hidden.contiguous(), weight, targets.contiguous(),
+                                      inv_temperature(temperature))
+    return _ref_linear_logprob(hidden, weight, targets, temperature)
 
 
-def _ref_linear_logprob_entropy(hidden, weight, targets):
-    """The formula of record: logp as `_ref_linear_logprob`, ent = -sum_v p_v (z_v - lse) (fp32),
-    both 0 on ignored rows; a -inf logit has p = 0 and adds exactly 0."""
-    logits = F.linear(hidden, weight).float()
+def _ref_logits_logprob_entropy(logits, targets, temperature: float = 1.0):
+    """The formula of record on fp32 logits: logp as `_ref_linear_logprob`, ent = -sum_v p_v (z_v - lse)
+    (fp32), both 0 on ignored rows; a -inf logit has p = 0 and adds exactly 0. With a temperature z is
+    the fp32 logits times `inv_temperature(temperature)`."""
+    if temperature != 1.0:
+        logits = logits * inv_temperature(temperature)
     lse = torch.logsumexp(logits, dim=-1)
     safe = targets.clamp(min=0)
     lp = logits.gather(-1, safe.unsqueeze(-1)).squeeze(-1) - lse
@@ -117,20 +152,30 @@ def _ref_linear_logprob_entropy(hidden, weight, targets):
     return torch.where(targets >= 0, lp, zero), torch.where(targets >= 0, ent, zero)
 
 
+def _ref_linear_logprob_entropy(hidden, weight, targets, temperature: float = 1.0):
+    return _ref_logits_logprob_entropy(F.linear(hidden, weight).float(), targets, temperature)
+
+
 class _LinearLogprobEntropyFn(torch.autograd.Function):
     """`_LinearLogprobFn` with the row entropy as a second output of the same vocabulary pass; its
     gradient goes into the same in-place dlogits pass. With no gradient arriving for the entropy
     (logging only) the backward runs the plain log-prob kernels."""
 
     @staticmethod
-    def forward(ctx, hidden, weight, targets):
+    def forward(ctx, hidden, weight, targets, inv_temp=None):
         ops = _ext.require()
         ctx.set_materialize_grads(False)
         need_grad = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
         N = hidden.shape[0]
+        ctx.inv_temp = inv_temp
+
+        def fwd(lg, tg):
+            return (ops.logprob_entropy_fwd(lg, tg) if inv_temp is None
+                    else ops.logprob_entropy_fwd_temp(lg, tg, inv_temp))
+
         if need_grad:
             logits = F.linear(hidden, weight)
-            logp, lse, ent = ops.logprob_entropy_fwd(logits, targets)
+            logp, lse, ent = fwd(logits, targets)
             ent = ent.masked_fill_(targets < 0, 0.0)
             ctx.save_for_backward(hidden, targets, lse, ent, logits)
             ctx.weight = weight  # (on ctx: see ops.linear._LinearMainGradFn)
@@ -140,7 +185,7 @@ class _LinearLogprobEntropyFn(torch.autograd.Function):
         for s in range(0, N, _NO_GRAD_CHUNK):
             e = min(N, s + _NO_GRAD_CHUNK)
             lg = F.linear(hidden[s:e], weight)
-            lp, _, en = ops.logprob_entropy_fwd(lg, targets[s:e])
+            lp, _, en = fwd(lg, targets[s:e])
             logp[s:e] = lp
             ent[s:e] = en
         return logp, ent.masked_fill_(targets < 0, 0.0)
@@ -150,8 +195,9 @@ class _LinearLogprobEntropyFn(torch.autograd.Function):
         ops = _ext.require()
         hidden, targets, lse, ent, logits = ctx.saved_tensors
         weight = ctx.weight
+        it = ctx.inv_temp
         if g is None and ge is None:
-            return None, None, None
+            return None, None, None, None
         from .linear import _tn_ok, accumulate_weight_grad
 
         g = torch.zeros_like(lse) if g is None else g.float().contiguous()
@@ -161,31 +207,44 @@ class _LinearLogprobEntropyFn(torch.autograd.Function):
         if (LOGPROB_T and ctx.needs_input_grad[1] and mg is not None and not getattr(weight, "_dla_shared", False)
                 and _tn_ok(mg, logits.shape[0])):
             # as in _LinearLogprobFn: dlogits^T from the same pass (empty outside the kernel's shapes)
-            dlt = (ops.logprob_bwd_t(logits, targets, lse, g) if ge is None
-                   else ops.logprob_entropy_bwd_t(logits, targets, lse, ent, g, ge))
+            if it is None:
+                dlt = (ops.logprob_bwd_t(logits, targets, lse, g) if ge is None
+                       else ops.logprob_entropy_bwd_t(logits, targets, lse, ent, g, ge))
+            else:
+                dlt = (ops.logprob_bwd_t_temp(logits, targets, lse, g, it) if ge is None
+                       else ops.logprob_entropy_bwd_t_temp(logits, targets, lse, ent, g, ge, it))
             if not dlt.numel():
                 dlt = None
         if dlt is None:
-            if ge is None:
-                ops.logprob_bwd(logits, targets, lse, g)
+            if it is None:
+                if ge is None:
+                    ops.logprob_bwd(logits, targets, lse, g)
+                else:
+                    ops.logprob_entropy_bwd(logits, targets, lse, ent, g, ge)
+            elif ge is None:
+                ops.logprob_bwd_temp(logits, targets, lse, g, it)
             else:
-                ops.logprob_entropy_bwd(logits, targets, lse, ent, g, ge)
+                ops.logprob_entropy_bwd_temp(logits, targets, lse, ent, g, ge, it)
         dlogits = logits  # rewritten in place
         dh = input_grad(dlogits, weight) if ctx.needs_input_grad[0] else None
         dw = None
         if ctx.needs_input_grad[1]:
             if not accumulate_weight_grad(weight, dlogits, hidden, dyt=dlt):
                 dw = dlogits.t() @ hidden
-        return dh, dw, None
+        return dh, dw, None, None
 
 
-def linear_logprob_entropy(hidden: torch.Tensor, weight: torch.Tensor, targets: torch.Tensor):
+def linear_logprob_entropy(hidden: torch.Tensor, weight: torch.Tensor, targets: torch.Tensor,
+                           temperature: float = 1.0):
     """hidden [N, H], weight [V, H], targets [N] (int64, <0 = ignore) -> (logp, ent), fp32 [N]:
-    `linear_logprob` plus the entropy of softmax(hidden @ W^T) per row (0 where ignored),
-    differentiable through both."""
+    `linear_logprob` plus the entropy of softmax(hidden @ W^T / temperature) per row (0 where
+    ignored), differentiable through both."""
     if _ext.use_native(hidden):
-        return _LinearLogprobEntropyFn.apply(hidden.contiguous(), weight, targets.contiguous())
-    return _ref_linear_logprob_entropy(hidden, weight, targets)
+        if temperature == 1.0:
+            return _LinearLogprobEntropyFn.apply(hidden.contiguous(), weight, targets.contiguous(), None)
+        return _LinearLogprobEntropyFn.apply(hidden.contiguous(), weight, targets.contiguous(),
+                                             inv_temperature(temperature))
+    return _ref_linear_logprob_entropy(hidden, weight, targets, temperature)
 
 
 class _SeqReduceFn(torch.autograd.Function):

@@ -478,10 +478,17 @@ def vocab_parallel_embedding(ids: torch.Tensor, weight_l: torch.Tensor, off: int
 
 
 # ------------------------------------------------------------- vocabulary-parallel log-prob
-def _local_fwd(logits_l, targets, off):
+# `it` throughout: None = temperature 1 (the plain ops), else ops.logprob.inv_temperature(tau): the
+# shards then emit the tempered lse_l / logp_l / H_l and the composition below is unchanged
+# (logp_l + lse_l is already the tempered target logit).
+def _local_fwd(logits_l, targets, off, it=None):
     if _ext.use_native(logits_l):
+        if it is not None:
+            return _ext.require().logprob_fwd_temp(logits_l, targets, it, int(off))
         return _ext.require().logprob_fwd(logits_l, targets, int(off))
     lf = logits_l.float()
+    if it is not None:
+        lf = lf * it
     lse = torch.logsumexp(lf, -1)
     t = targets - off
     own = (targets >= 0) & (t >= 0) & (t < lf.shape[-1])
@@ -489,11 +496,17 @@ def _local_fwd(logits_l, targets, off):
     return torch.where(own, tl - lse, torch.zeros_like(tl)), lse
 
 
-def _local_bwd(logits_l, targets, lse, g, off):
+def _local_bwd(logits_l, targets, lse, g, off, it=None):
     if _ext.use_native(logits_l):
-        _ext.require().logprob_bwd(logits_l, targets, lse, g.float().contiguous(), int(off))
+        if it is not None:
+            _ext.require().logprob_bwd_temp(logits_l, targets, lse, g.float().contiguous(), it, int(off))
+        else:
+            _ext.require().logprob_bwd(logits_l, targets, lse, g.float().contiguous(), int(off))
         return logits_l
     lf = logits_l.float()
+    if it is not None:
+        lf = lf * it
+        g = g.float() * it
     p = torch.exp(lf - lse.unsqueeze(-1))
     t = targets - off
     own = (targets >= 0) & (t >= 0) & (t < lf.shape[-1])
@@ -505,9 +518,10 @@ def _local_bwd(logits_l, targets, lse, g, off):
 
 class _VPLogprobFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, hidden, weight_l, targets, off, group):
+    def forward(ctx, hidden, weight_l, targets, off, group, it=None):
         logits_l = F.linear(hidden, weight_l)
-        logp_l, lse_l = _local_fwd(logits_l, targets, off)
+        logp_l, lse_l = _local_fwd(logits_l, targets, off, it)
+        ctx.it = it
         V_l = weight_l.shape[0]
         t = targets - off
         own = (targets >= 0) & (t >= 0) & (t < V_l)
@@ -532,7 +546,7 @@ class _VPLogprobFn(torch.autograd.Function):
     def backward(ctx, g):
         hidden, targets, lse, logits_l = ctx.saved_tensors
         weight_l = ctx.weight_l
-        dlog = _local_bwd(logits_l, targets, lse, g, ctx.off)
+        dlog = _local_bwd(logits_l, targets, lse, g, ctx.off, ctx.it)
         dh, work = None, None
         if ctx.needs_input_grad[0]:
             from ..ops.linear import input_grad
@@ -548,33 +562,52 @@ class _VPLogprobFn(torch.autograd.Function):
                 dw = dlog.t() @ hidden
         if work is not None:
             work.wait()
-        return dh, dw, None, None, None
+        return dh, dw, None, None, None, None
 
 
-def vocab_parallel_logprob(hidden, weight_l, targets, off: int, group) -> torch.Tensor:
-    return _VPLogprobFn.apply(hidden.contiguous(), weight_l, targets.contiguous(), off, group)
+def _inv_temp_or_none(temperature: float):
+    from ..ops.logprob import inv_temperature
+
+    return None if temperature == 1.0 else inv_temperature(temperature)
+
+
+def vocab_parallel_logprob(hidden, weight_l, targets, off: int, group, temperature: float = 1.0) -> torch.Tensor:
+    return _VPLogprobFn.apply(hidden.contiguous(), weight_l, targets.contiguous(), off, group,
+                              _inv_temp_or_none(temperature))
 
 
 # The entropy twins. Shard l emits its local lse_l and the entropy H_l of its OWN softmax; with
 # w_l = exp(lse_l - lse) the global entropy is H = lse - sum_l w_l (lse_l - H_l) (each shard's
 # sum_v p_v z_v is w_l (lse_l - H_l)). The backward formula holds per shard given the global lse
 # and H, so no extra kernel: dz_j = g (1[j == t] - p_j) - e p_j (z_j - lse + H).
-def _local_fwd_entropy(logits_l, targets, off):
+def _local_fwd_entropy(logits_l, targets, off, it=None):
     if _ext.use_native(logits_l):
+        if it is not None:
+            return _ext.require().logprob_entropy_fwd_temp(logits_l, targets, it, int(off))
         return _ext.require().logprob_entropy_fwd(logits_l, targets, int(off))
-    logp, lse = _local_fwd(logits_l, targets, off)
+    logp, lse = _local_fwd(logits_l, targets, off, it)
     lf = logits_l.float()
+    if it is not None:
+        lf = lf * it
     lsm = lf - lse.unsqueeze(-1)
     ent = -(torch.exp(lsm) * lsm.masked_fill(lf == float("-inf"), 0.0)).sum(-1)
     return logp, lse, ent
 
 
-def _local_bwd_entropy(logits_l, targets, lse, ent, g, ge, off):
+def _local_bwd_entropy(logits_l, targets, lse, ent, g, ge, off, it=None):
     if _ext.use_native(logits_l):
-        _ext.require().logprob_entropy_bwd(logits_l, targets, lse, ent, g.float().contiguous(),
-                                           ge.float().contiguous(), int(off))
+        if it is not None:
+            _ext.require().logprob_entropy_bwd_temp(logits_l, targets, lse, ent, g.float().contiguous(),
+                                                    ge.float().contiguous(), it, int(off))
+        else:
+            _ext.require().logprob_entropy_bwd(logits_l, targets, lse, ent, g.float().contiguous(),
+                                               ge.float().contiguous(), int(off))
         return logits_l
     lf = logits_l.float()
+    if it is not None:
+        lf = lf * it
+        g = g.float() * it
+        ge = ge.float() * it
     p = torch.exp(lf - lse.unsqueeze(-1))
     t = targets - off
     own = (targets >= 0) & (t >= 0) & (t < lf.shape[-1])
@@ -589,10 +622,11 @@ def _local_bwd_entropy(logits_l, targets, lse, ent, g, ge, off):
 
 class _VPLogprobEntropyFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, hidden, weight_l, targets, off, group):
+    def forward(ctx, hidden, weight_l, targets, off, group, it=None):
         ctx.set_materialize_grads(False)
         logits_l = F.linear(hidden, weight_l)
-        logp_l, lse_l, ent_l = _local_fwd_entropy(logits_l, targets, off)
+        logp_l, lse_l, ent_l = _local_fwd_entropy(logits_l, targets, off, it)
+        ctx.it = it
         V_l = weight_l.shape[0]
         t = targets - off
         own = (targets >= 0) & (t >= 0) & (t < V_l)
@@ -623,9 +657,9 @@ class _VPLogprobEntropyFn(torch.autograd.Function):
         weight_l = ctx.weight_l
         g = torch.zeros_like(lse) if g is None else g
         if ge is None:  # entropy only logged: the plain backward
-            dlog = _local_bwd(logits_l, targets, lse, g, ctx.off)
+            dlog = _local_bwd(logits_l, targets, lse, g, ctx.off, ctx.it)
         else:
-            dlog = _local_bwd_entropy(logits_l, targets, lse, ent, g, ge, ctx.off)
+            dlog = _local_bwd_entropy(logits_l, targets, lse, ent, g, ge, ctx.off, ctx.it)
         dh, work = None, None
         if ctx.needs_input_grad[0]:
             from ..ops.linear import input_grad
@@ -641,12 +675,13 @@ class _VPLogprobEntropyFn(torch.autograd.Function):
                 dw = dlog.t() @ hidden
         if work is not None:
             work.wait()
-        return dh, dw, None, None, None
+        return dh, dw, None, None, None, None
 
 
-def vocab_parallel_logprob_entropy(hidden, weight_l, targets, off: int, group):
+def vocab_parallel_logprob_entropy(hidden, weight_l, targets, off: int, group, temperature: float = 1.0):
     """(logp, ent) [N] fp32 over the vocabulary-parallel head, both 0 on ignored rows."""
-    return _VPLogprobEntropyFn.apply(hidden.contiguous(), weight_l, targets.contiguous(), off, group)
+    return _VPLogprobEntropyFn.apply(hidden.contiguous(), weight_l, targets.contiguous(), off, group,
+                                     _inv_temp_or_none(temperature))
 
 
 # ------------------------------------------------------------------------- model sharding

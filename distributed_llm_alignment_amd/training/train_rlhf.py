@@ -63,6 +63,19 @@ tokens (the length-normalised ratio, not the product). The weight multiplies the
 term only; the k3 KL term, every divisor (action-token counts, never sum w) and clipfrac /
 approx_kl / kl stay unweighted. Logged: `train/rollout_is_mean`, `train/rollout_is_frac_high`,
 `train/rollout_is_frac_low`, `train/rollout_is_ess`, and `monitor`'s two metrics.
+
+`ppo.logprob_temperature: 1.0 | <float > 0> | rollout` (default 1.0), for `ppo` and `grpo`: the ONE
+temperature of every log-prob of the step. The rollouts are drawn from softmax(z / T_gen); at 1.0
+the trainer optimises softmax(z), a different distribution. `rollout` resolves to
+`generation_params.temperature` when `do_sample` is set (else 1.0). The policy's, old policy's and
+reference's `token_logprobs`, the entropy (bonus and `train/entropy`) and the rollout engine's
+log-probs (`generate(logprob_temperature=)`) are then all of softmax(z / T), and through them the
+ratio, the clip, the k3 KL, PPO's KL reward, `rollout_kl` and the importance weights of `correct`.
+The temperature is applied in fp32 inside the LM-head row kernels and the sampler's draw pass, on
+the bf16 logits the GEMM wrote. With `rollout_logprobs` on, the value must be 1.0 or the rollout
+temperature (the sampler has no other). `train/logprob_temperature` is logged once when the key is
+set. At 1.0 (or absent) a run launches exactly the kernels it launched before. The log-prob is
+over the full vocabulary: with `top_p < 1` / `top_k` it is still not the filtered draw distribution.
 """
 from __future__ import annotations
 
@@ -125,6 +138,45 @@ def rollout_logprobs_mode(ppo: Dict, algo: str) -> str:
         raise ValueError("ppo.rollout_logprobs needs token-level log-probs (ppo.algorithm: ppo|grpo); "
                          "the reinforce loop works on sequence log-probs")
     return mode
+
+
+def generation_params(ppo: Dict) -> Dict:
+    """`ppo.generation_params` as the rollouts use it: a copy with `do_sample` defaulted to True."""
+    gen = dict(ppo.get("generation_params") or {"max_new_tokens": 256})
+    gen.setdefault("do_sample", True)
+    return gen
+
+
+def draw_temperature(gen: Dict) -> float:
+    """The temperature the rollouts are drawn at (`gen` from `generation_params`): its
+    `temperature` when sampling, 1.0 for greedy decoding (no draw temperature)."""
+    t = float(gen.get("temperature", 1.0))
+    return t if gen["do_sample"] and t > 0 else 1.0
+
+
+def logprob_temperature(ppo: Dict, algo: str) -> float:
+    """`ppo.logprob_temperature` resolved to a float (`rollout` -> the draw temperature); bad
+    values, and values the algorithm or the sampler cannot honour, raise."""
+    v = ppo.get("logprob_temperature", 1.0)
+    gen = generation_params(ppo)
+    if isinstance(v, str) and v.strip().lower() == "rollout":
+        t = draw_temperature(gen)
+    else:
+        if isinstance(v, bool) or v is None:
+            raise ValueError(f"ppo.logprob_temperature must be a number > 0 or 'rollout', got {v!r}")
+        try:
+            t = float(v)
+        except (TypeError, ValueError):
+            raise ValueError(f"ppo.logprob_temperature must be a number > 0 or 'rollout', got {v!r}") from None
+    if not (math.isfinite(t) and t > 0):
+        raise ValueError(f"ppo.logprob_temperature must be finite and > 0, got {v!r}")
+    if t != 1.0 and algo == "reinforce":
+        raise ValueError("ppo.logprob_temperature needs token-level log-probs (ppo.algorithm: ppo|grpo); "
+                         "the reinforce loop works on sequence log-probs at temperature 1")
+    if rollout_logprobs_mode(ppo, algo) != "off" and t not in (1.0, draw_temperature(gen)):
+        raise ValueError(f"ppo.rollout_logprobs needs ppo.logprob_temperature 1.0 or the rollout temperature "
+                         f"({draw_temperature(gen)}): the sampler returns no other log-prob; got {t!r}")
+    return t
 
 
 def rollout_is_settings(ppo: Dict) -> Dict:
@@ -197,8 +249,7 @@ def main(argv=None) -> int:
         parallelize(ctx, m)
 
     prompts = load_prompts(config["sampling"])
-    gen = dict(ppo.get("generation_params", {"max_new_tokens": 256}))
-    gen.setdefault("do_sample", True)
+    gen = generation_params(ppo)
     engine = make_engine(ctx, policy.model, lr=ppo.get("learning_rate", 1e-6), betas=(0.9, 0.95),
                          weight_decay=ppo.get("weight_decay", 0.01),
                          max_grad_norm=ppo.get("max_grad_norm", 1.0))
@@ -217,6 +268,7 @@ def main(argv=None) -> int:
         raise ValueError(f"ppo.algorithm must be reinforce|ppo|grpo, got {algo!r}")
     want_logp = rollout_logprobs_mode(ppo, algo) != "off"
     rollout_is_settings(ppo)  # bad ppo.rollout_is_* values fail here, before any rollout
+    lp_temp = logprob_temperature(ppo, algo)  # likewise
 
     # reward inputs built on the device when the reward tokenizer equals the policy's (no
     # decode / re-tokenise round trip through the host; training/handoff.py), else the
@@ -241,7 +293,8 @@ def main(argv=None) -> int:
                                     weight_dtype=ppo.get("rollout_weight_dtype", "bf16"),
                                     num_return_sequences=group, share_prefill=bool(ppo.get("share_prefill", True)),
                                     group_attention=bool(ppo.get("group_attention", False)),
-                                    return_logprobs=want_logp)
+                                    return_logprobs=want_logp,
+                                    logprob_temperature=lp_temp if want_logp and lp_temp != 1.0 else None)
         if group > 1:  # the reward hand-off sees one prompt row per rollout
             mine = [p for p in mine for _ in range(group)]
             ids, am = ids.repeat_interleave(group, 0), am.repeat_interleave(group, 0)
@@ -330,19 +383,20 @@ GRPO_ROWS = ("act", "advantages", "ref_logp", "old_logp", "is_weight")
 
 def grpo_update(policy, engine, seqs, mask, stats, clip_low: float, clip_high, beta: float,
                 loss_type: str, max_len, micro: int = 0, entropy_coef: float = 0.0,
-                log_entropy: bool = False):
+                log_entropy: bool = False, temperature: float = 1.0):
     """Backward of the GRPO loss over one minibatch of rollouts. micro > 0
     (`ppo.update_micro_batch`): gradient-accumulated micro-batches of `micro` rollouts that share
     the whole minibatch's divisor (`denom`, a device tensor: no host sync), so their gradients sum
     to the full minibatch's; every micro-batch but the last runs under `engine.no_sync()`. The
     entropy bonus (`ppo.entropy_coef`) is likewise normalised by the whole minibatch's
     action-token count. `stats["is_weight"]` (optional) is sliced with the other per-rollout
-    entries. Returns (loss, metrics) with token-weighted metric means."""
+    entries. `temperature`: the log-prob temperature of `grpo_loss`. Returns (loss, metrics) with
+    token-weighted metric means."""
     n = seqs.shape[0]
     rows = GRPO_ROWS
     if micro <= 0 or micro >= n:
         loss, m = grpo_loss(policy, seqs, mask, stats, clip_low, clip_high, beta, loss_type, max_len,
-                            entropy_coef=entropy_coef, log_entropy=log_entropy)
+                            entropy_coef=entropy_coef, log_entropy=log_entropy, temperature=temperature)
         loss.backward()
         return loss.detach(), m
     denom = grpo_denominator(stats["act"], loss_type, max_len)
@@ -356,7 +410,7 @@ def grpo_update(policy, engine, seqs, mask, stats, clip_low: float, clip_high, b
         ctx = engine.no_sync() if i < len(bounds) - 1 else contextlib.nullcontext()
         with ctx:
             loss, m = grpo_loss(policy, seqs[s0:s1], mask[s0:s1], mb, clip_low, clip_high, beta, loss_type,
-                                max_len, denom, entropy_coef, log_entropy, tokens)
+                                max_len, denom, entropy_coef, log_entropy, tokens, temperature=temperature)
             loss.backward()
         tot = tot + loss.detach()
         for k in acc:
@@ -380,6 +434,8 @@ def _grpo_loop(ctx, config, ppo, policy, ref, rm, rollout, engine, steps, group,
     need_old = epochs * nmb > 1  # a single update per rollout batch is on-policy: rho = 1
     lp_mode = rollout_logprobs_mode(ppo, "grpo")
     is_kw = rollout_is_settings(ppo) if lp_mode == "correct" else {}
+    lp_temp = logprob_temperature(ppo, "grpo")
+    log_temp = "logprob_temperature" in ppo  # logged once, and only when the key is set
     rows = GRPO_ROWS
     running = RunningLoss()
     pending = rollout()
@@ -393,7 +449,8 @@ def _grpo_loop(ctx, config, ppo, policy, ref, rm, rollout, engine, steps, group,
         stats = grpo_rollout_stats(policy.model, ref.model, seqs, mask, tp, scores, group, beta, scale_std,
                                    need_old or lp_mode == "monitor",
                                    old_logp=rlp if lp_mode == "old" else None,
-                                   rollout_logp=rlp if lp_mode == "correct" else None, **is_kw)
+                                   rollout_logp=rlp if lp_mode == "correct" else None, **is_kw,
+                                   temperature=lp_temp)
         mism = rollout_mismatch(rlp, stats["old_logp"], stats["act"]) if lp_mode in ("monitor", "correct") else {}
         mism.update(stats.get("rollout_is", {}))
         if lp_mode in ("monitor", "correct") and not need_old:
@@ -406,7 +463,7 @@ def _grpo_loop(ctx, config, ppo, policy, ref, rm, rollout, engine, steps, group,
                     continue
                 mb = {k: (stats[k][a:b] if stats.get(k) is not None else None) for k in rows}
                 loss, m = grpo_update(policy.model, engine, seqs[a:b], mask[a:b], mb, clip_low, clip_high,
-                                      beta, loss_type, gen_len, micro, entropy_coef, log_entropy)
+                                      beta, loss_type, gen_len, micro, entropy_coef, log_entropy, lp_temp)
                 last = ep == epochs - 1 and mi == len(bounds) - 1
                 if last and overlap and step + 1 < steps:
                     pending = rollout()  # overlaps the in-flight gradient collectives (see _ppo_loop)
@@ -422,9 +479,10 @@ def _grpo_loop(ctx, config, ppo, policy, ref, rm, rollout, engine, steps, group,
                             "train/clipfrac": m["clipfrac"], "train/approx_kl": m["approx_kl"],
                             **({"train/entropy": m["entropy"]} if "entropy" in m else {}),
                             **{f"train/{k}": v for k, v in mism.items()},
+                            **({"train/logprob_temperature": lp_temp} if log_temp else {}),
                             "train/grad_norm": engine.last_grad_norm,
                             "train/comm_exposed_ms": engine.comm_timer.last_step_ms()}, step + 1)
-            running = RunningLoss()
+            running, log_temp = RunningLoss(), False
     barrier()
     save_state(config["logging"]["output_dir"], [policy.model, ref.model, rm], engine, None, steps,
                policy.tokenizer)
@@ -456,13 +514,16 @@ def _ppo_loop(ctx, config, ppo, policy, ref, rm, rollout, engine, steps, kl_coef
     entropy_coef, log_entropy = float(ppo.get("entropy_coef", 0.0) or 0.0), bool(ppo.get("log_entropy", False))
     lp_mode = rollout_logprobs_mode(ppo, "ppo")
     is_kw = rollout_is_settings(ppo) if lp_mode == "correct" else {}
+    lp_temp = logprob_temperature(ppo, "ppo")
+    log_temp = "logprob_temperature" in ppo  # logged once, and only when the key is set
     running = RunningLoss()
     pending = rollout()
     for step in range(steps):
         seqs, mask, scores, tp, rlp = pending
         stats = ppo_rollout_stats(policy.model, ref.model, critic, seqs, mask, tp, scores, kl_coef,
                                   gamma, lam, old_logp=rlp if lp_mode == "old" else None,
-                                  rollout_logp=rlp if lp_mode == "correct" else None, **is_kw)
+                                  rollout_logp=rlp if lp_mode == "correct" else None, **is_kw,
+                                  temperature=lp_temp)
         mism = rollout_mismatch(rlp, stats["old_logp"], stats["act"]) if lp_mode in ("monitor", "correct") else {}
         mism.update(stats.get("rollout_is", {}))
         S = seqs.shape[0]
@@ -473,7 +534,7 @@ def _ppo_loop(ctx, config, ppo, policy, ref, rm, rollout, engine, steps, kl_coef
                     continue
                 mb = {k: v[a:b] for k, v in stats.items() if k in ("old_logp", "values", "advantages", "returns", "act", "is_weight")}
                 loss, m = ppo_loss(policy.model, critic, seqs[a:b], mask[a:b], mb, clip, vclip, vf_coef,
-                                   entropy_coef, log_entropy)
+                                   entropy_coef, log_entropy, temperature=lp_temp)
                 ppo_backward(loss)
                 last = ep == epochs - 1 and mi == len(bounds) - 1
                 if last and overlap and step + 1 < steps:
@@ -493,9 +554,10 @@ def _ppo_loop(ctx, config, ppo, policy, ref, rm, rollout, engine, steps, kl_coef
                             "train/clipfrac": m["clipfrac"], "train/approx_kl": m["approx_kl"],
                             **({"train/entropy": m["entropy"]} if "entropy" in m else {}),
                             **{f"train/{k}": v for k, v in mism.items()},
+                            **({"train/logprob_temperature": lp_temp} if log_temp else {}),
                             "train/grad_norm": engine.last_grad_norm,
                             "train/comm_exposed_ms": engine.comm_timer.last_step_ms()}, step + 1)
-            running = RunningLoss()
+            running, log_temp = RunningLoss(), False
     barrier()
     out = save_state(config["logging"]["output_dir"], [policy.model, ref.model, rm, critic], engine, None,
                      steps, policy.tokenizer)

@@ -13,7 +13,11 @@
                 logprob_fwd / logprob_entropy_fwd, logprob_bwd / logprob_entropy_bwd,
                 logprob_bwd_t / logprob_entropy_bwd_t, the two arms of a pair interleaved (A B A B
                 ...), median of the rounds, effective GB/s over the bytes each must move; plus the
-                eager torch entropy of the same logits (fp32 log_softmax), for scale.
+                eager torch entropy of the same logits (fp32 log_softmax), for scale. Then every
+                one of the six against its tempered twin (`*_temp`, `--temperature`, default 0.7),
+                interleaved the same way: `<kernel>_ms` / `<kernel>_temp_ms` / `<kernel>_temp_ratio`
+                under "temp". With an extension that lacks the twins (an older build through
+                DLA_EXT_PATH) only the plain kernels are timed.
 
   rollout_is    the truncated importance weights at S = 64, T = 768: `rollout_is_weights` (token and
                 sequence level) and the raw `grpo_loss` op with and without the weight grid
@@ -65,7 +69,7 @@ def interleaved(fa, fb, rounds, iters):
     return ta[len(ta) // 2], tb[len(tb) // 2]
 
 
-def bench_logprob(dla_ops, dev, rows, V, rounds, iters):
+def bench_logprob(dla_ops, dev, rows, V, rounds, iters, temperature=0.7):
     g = torch.Generator(device=dev).manual_seed(0)
     logits = torch.empty((rows, V), device=dev, dtype=torch.bfloat16)
     for s in range(0, rows, 1024):  # 3 * randn without an fp32 [rows, V] transient
@@ -97,6 +101,29 @@ def bench_logprob(dla_ops, dev, rows, V, rounds, iters):
                        lambda: dla_ops.logprob_entropy_bwd_t(work, tgt, lse, ent, gl, ge), rounds, iters)
     out.update(bwd_t_ms=round(a, 4), entropy_bwd_t_ms=round(b, 4), bwd_t_ratio=round(b / a, 4),
                bwd_t_gb_s=gbs(a, 3), entropy_bwd_t_gb_s=gbs(b, 3))
+    if hasattr(dla_ops, "logprob_fwd_temp"):  # the tempered twins, each against its plain kernel
+        it = float(torch.tensor(1.0 / temperature, dtype=torch.float64).float())
+        pairs = [
+            ("fwd", 1, lambda: dla_ops.logprob_fwd(logits, tgt), lambda: dla_ops.logprob_fwd_temp(logits, tgt, it)),
+            ("entropy_fwd", 1, lambda: dla_ops.logprob_entropy_fwd(logits, tgt),
+             lambda: dla_ops.logprob_entropy_fwd_temp(logits, tgt, it)),
+            ("bwd", 2, lambda: dla_ops.logprob_bwd(work, tgt, lse, gl),
+             lambda: dla_ops.logprob_bwd_temp(work, tgt, lse, gl, it)),
+            ("entropy_bwd", 2, lambda: dla_ops.logprob_entropy_bwd(work, tgt, lse, ent, gl, ge),
+             lambda: dla_ops.logprob_entropy_bwd_temp(work, tgt, lse, ent, gl, ge, it)),
+            ("bwd_t", 3, lambda: dla_ops.logprob_bwd_t(work, tgt, lse, gl),
+             lambda: dla_ops.logprob_bwd_t_temp(work, tgt, lse, gl, it)),
+            ("entropy_bwd_t", 3, lambda: dla_ops.logprob_entropy_bwd_t(work, tgt, lse, ent, gl, ge),
+             lambda: dla_ops.logprob_entropy_bwd_t_temp(work, tgt, lse, ent, gl, ge, it)),
+        ]
+        temp = {"temperature": temperature}
+        for name, passes, plain, tempered in pairs:
+            a, b = interleaved(plain, tempered, rounds, iters)
+            temp.update({f"{name}_ms": round(a, 4), f"{name}_temp_ms": round(b, 4),
+                         f"{name}_temp_ratio": round(b / a, 4), f"{name}_temp_gb_s": gbs(b, passes)})
+        lp1, lse1 = dla_ops.logprob_fwd_temp(logits, tgt, 1.0)
+        temp["unit_temperature_bitwise_equal"] = bool(torch.equal(lp1, lp0) and torch.equal(lse1, lse0))
+        out["temp"] = temp
     del work
 
     def eager():
@@ -117,6 +144,7 @@ def main() -> int:
     ap.add_argument("--vocab", type=int, default=128256)
     ap.add_argument("--logprob-rows", type=int, nargs="+", default=[6144, 8192])
     ap.add_argument("--rounds", type=int, default=5, help="logprob: interleaved rounds per pair")
+    ap.add_argument("--temperature", type=float, default=0.7, help="logprob: temperature of the tempered arms")
     ap.add_argument("--layers", type=int, default=32)
     ap.add_argument("--prompts", type=int, default=8)
     ap.add_argument("--group", type=int, default=8)
@@ -142,7 +170,7 @@ def main() -> int:
         bench_grpo_loss(a, ops, dev, _ref_grpo_loss)
     if a.bench in ("all", "logprob"):
         for rows in a.logprob_rows:
-            bench_logprob(dla_ops, dev, rows, a.vocab, a.rounds, a.iters)
+            bench_logprob(dla_ops, dev, rows, a.vocab, a.rounds, a.iters, a.temperature)
     if a.bench in ("all", "rollout_is"):
         bench_rollout_is(a, dla_ops, dev)
     return 0

@@ -77,6 +77,10 @@ def main() -> int:
                     help="ppo / grpo: ppo.rollout_logprobs (the sampler's token log-probs: monitor = log "
                          "rollout_kl / rollout_logp_absdiff_max against the trainer's, old = use them as old_logp, "
                          "correct = truncated importance weights on every action token)")
+    ap.add_argument("--logprob-temperature", default="1.0",
+                    help="ppo / grpo: ppo.logprob_temperature, a number > 0 or 'rollout' (the 0.7 the rollouts "
+                         "are drawn at): the one temperature of every log-prob of the step, applied inside the "
+                         "LM-head row kernels and the sampler")
     ap.add_argument("--rollout-is-cap", type=float, default=2.0, help="correct: ppo.rollout_is_cap")
     ap.add_argument("--rollout-is-floor", type=float, default=None, help="correct: ppo.rollout_is_floor (default 1 / cap)")
     ap.add_argument("--rollout-is-level", choices=("token", "sequence"), default="token")
@@ -107,6 +111,10 @@ def main() -> int:
         return grpo_main(a)
     if a.rollout_logprobs != "off":
         ap.error("--rollout-logprobs needs token-level log-probs: --algorithm ppo or grpo")
+    try:
+        _lp_temp(a, "reinforce")  # (the reinforce loop has no log-prob temperature: only 1.0 resolves)
+    except ValueError as exc:
+        ap.error(f"--logprob-temperature needs --algorithm ppo or grpo ({exc})")
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from distributed_llm_alignment_amd.models import build_model, generate, get_config
     from distributed_llm_alignment_amd.models.reward import RewardModel
@@ -278,6 +286,23 @@ def _is_kw(a, rollout_is_settings):
                                 "rollout_is_level": a.rollout_is_level, "rollout_is_mode": a.rollout_is_mode})
 
 
+GEN_TEMPERATURE = 0.7  # the draw temperature of every arm's rollouts
+
+
+def _lp_temp(a, algo: str) -> float:
+    """--logprob-temperature resolved as the trainer resolves ppo.logprob_temperature."""
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    from distributed_llm_alignment_amd.training.train_rlhf import logprob_temperature
+
+    v = a.logprob_temperature
+    try:
+        v = float(v)
+    except ValueError:
+        pass
+    return logprob_temperature({"logprob_temperature": v, "rollout_logprobs": a.rollout_logprobs,
+                                "generation_params": {"temperature": GEN_TEMPERATURE, "do_sample": True}}, algo)
+
+
 def ppo_main(a) -> int:
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from distributed_llm_alignment_amd.models import build_model, generate, get_config
@@ -344,15 +369,17 @@ def ppo_main(a) -> int:
     exposed = []  # the update's gradient-collective wait nothing overlapped, ms per step
     lp_mode, mism = rollout_logprobs_mode({"rollout_logprobs": a.rollout_logprobs}, "ppo"), {}
     is_kw = _is_kw(a, rollout_is_settings) if lp_mode == "correct" else {}
+    lp_temp = _lp_temp(a, "ppo")
 
     def step(record):
         ids = torch.randint(3, cfg.vocab_size, (a.batch, a.prompt), device=dev, generator=g)
         am = torch.ones_like(ids)
         torch.cuda.reset_peak_memory_stats(dev)
         t0 = sync()
-        seqs, mask, *rlp = generate(pol, ids, am, max_new_tokens=a.new, do_sample=True, temperature=0.7,
+        seqs, mask, *rlp = generate(pol, ids, am, max_new_tokens=a.new, do_sample=True, temperature=GEN_TEMPERATURE,
                                     top_p=0.9, eos_token_id=-1, return_mask=True, seed=3,
-                                    weight_dtype=a.rollout_dtype, return_logprobs=lp_mode != "off")
+                                    weight_dtype=a.rollout_dtype, return_logprobs=lp_mode != "off",
+                                    logprob_temperature=lp_temp if lp_mode != "off" and lp_temp != 1.0 else None)
         rlp = rollout_logp_grid(rlp[0], a.prompt, seqs.shape[1]) if rlp else None
         t1 = sync()
         phase_peak("generate")
@@ -363,7 +390,8 @@ def ppo_main(a) -> int:
         phase_peak("score")
         stats = ppo_rollout_stats(pol, ref, critic, seqs, mask, a.prompt, scores, 0.05, 1.0, 0.95,
                                   old_logp=rlp if lp_mode == "old" else None,
-                                  rollout_logp=rlp if lp_mode == "correct" else None, **is_kw)
+                                  rollout_logp=rlp if lp_mode == "correct" else None, **is_kw,
+                                  temperature=lp_temp)
         if lp_mode in ("monitor", "correct"):
             mism.update(rollout_mismatch(rlp, stats["old_logp"], stats["act"]))
             mism.update(stats.get("rollout_is", {}))
@@ -378,7 +406,7 @@ def ppo_main(a) -> int:
             for lo, hi in bounds:
                 mb = {k: v[lo:hi] for k, v in stats.items() if k in ("old_logp", "values", "advantages", "returns", "act", "is_weight")}
                 loss, m = ppo_loss(pol, critic, seqs[lo:hi], mask[lo:hi], mb, 0.2, 0.2, 0.1, a.entropy_coef,
-                                   a.log_entropy)
+                                   a.log_entropy, temperature=lp_temp)
                 ppo_backward(loss)
                 eng.step()
                 ceng.step()
@@ -405,7 +433,7 @@ def ppo_main(a) -> int:
         health["entropy"] = round(float(m["entropy"]), 5)
     health.update({k: float(v) for k, v in mism.items()})  # the last step's
     print(json.dumps({"bench": "ppo_step", "model": cfg.name, "rollouts_per_step": a.batch,
-                      "rollout_logprobs": lp_mode,
+                      "rollout_logprobs": lp_mode, "logprob_temperature": lp_temp,
                       "entropy_coef": a.entropy_coef, "log_entropy": a.log_entropy,
                       "rollout_dtype": a.rollout_dtype, "frozen_fp8": a.frozen_fp8,
                       "zero_shape": a.zero_shape, "ppo_epochs": a.ppo_epochs, "minibatches": a.minibatches,
@@ -469,6 +497,7 @@ def grpo_main(a) -> int:
     peaks = {}
     lp_mode, mism = rollout_logprobs_mode({"rollout_logprobs": a.rollout_logprobs}, "grpo"), {}
     is_kw = _is_kw(a, rollout_is_settings) if lp_mode == "correct" else {}
+    lp_temp = _lp_temp(a, "grpo")
 
     def sync():
         torch.cuda.synchronize()
@@ -484,11 +513,12 @@ def grpo_main(a) -> int:
         am = torch.ones_like(ids)
         torch.cuda.reset_peak_memory_stats(dev)
         t0 = sync()
-        seqs, mask, *rlp = generate(pol, ids, am, max_new_tokens=a.new, do_sample=True, temperature=0.7,
+        seqs, mask, *rlp = generate(pol, ids, am, max_new_tokens=a.new, do_sample=True, temperature=GEN_TEMPERATURE,
                                     top_p=0.9, eos_token_id=-1, return_mask=True, seed=3,
                                     weight_dtype=a.rollout_dtype, num_return_sequences=G,
                                     share_prefill=bool(a.share_prefill),
-                                    group_attention=bool(a.group_attention), return_logprobs=lp_mode != "off")
+                                    group_attention=bool(a.group_attention), return_logprobs=lp_mode != "off",
+                                    logprob_temperature=lp_temp if lp_mode != "off" and lp_temp != 1.0 else None)
         rlp = rollout_logp_grid(rlp[0], a.prompt, seqs.shape[1]) if rlp else None
         t1 = sync()
         phase_peak("generate")
@@ -500,7 +530,8 @@ def grpo_main(a) -> int:
         # one update per rollout batch, as train_rlhf's loop at ppo_epochs = num_minibatches = 1
         stats = grpo_rollout_stats(pol, ref, seqs, mask, a.prompt, scores, G, a.kl_coef, True,
                                    lp_mode == "monitor", old_logp=rlp if lp_mode == "old" else None,
-                                   rollout_logp=rlp if lp_mode == "correct" else None, **is_kw)
+                                   rollout_logp=rlp if lp_mode == "correct" else None, **is_kw,
+                                   temperature=lp_temp)
         if lp_mode in ("monitor", "correct"):
             mism.update(rollout_mismatch(rlp, stats["old_logp"], stats["act"]))
             mism.update(stats.get("rollout_is", {}))
@@ -509,7 +540,7 @@ def grpo_main(a) -> int:
         phase_peak("stats")
         pol.train()
         loss, m = grpo_update(pol, eng, seqs, mask, stats, 0.2, None, a.kl_coef, a.loss_type, a.new, a.micro,
-                              a.entropy_coef, a.log_entropy)
+                              a.entropy_coef, a.log_entropy, lp_temp)
         eng.step()
         t4 = sync()
         phase_peak("update")
@@ -533,7 +564,7 @@ def grpo_main(a) -> int:
         health["entropy"] = round(float(m["entropy"]), 5)
     health.update({k: float(v) for k, v in mism.items()})  # the last step's
     print(json.dumps({"bench": "grpo_step", "model": cfg.name, "rollouts_per_step": a.batch, "group": G,
-                      "rollout_logprobs": lp_mode,
+                      "rollout_logprobs": lp_mode, "logprob_temperature": lp_temp,
                       "share_prefill": bool(a.share_prefill), "group_attention": bool(a.group_attention),
                       "loss_type": a.loss_type, "kl_coef": a.kl_coef,
                       "entropy_coef": a.entropy_coef, "log_entropy": a.log_entropy,
