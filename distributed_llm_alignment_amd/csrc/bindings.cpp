@@ -57,6 +57,12 @@ void launch_logprob_entropy_bwd_temp(bf16_t*, int64_t, int, int64_t, int64_t, co
                                      const float*, const float*, const float*, float, hipStream_t);
 bool launch_logprob_entropy_bwd_t_temp(bf16_t*, int64_t, int, int64_t, int64_t, const int64_t*, const float*,
                                        const float*, const float*, const float*, bf16_t*, float, hipStream_t);
+void launch_logprob_fwd_keep(const bf16_t*, int64_t, int, int64_t, const int64_t*, float*, float*,
+                             const uint8_t*, const int64_t*, float, hipStream_t);
+void launch_logprob_bwd_keep(bf16_t*, int64_t, int, int64_t, const int64_t*, const float*, const float*,
+                             const uint8_t*, const int64_t*, float, hipStream_t);
+bool launch_logprob_bwd_t_keep(bf16_t*, int64_t, int, int64_t, const int64_t*, const float*, const float*,
+                               bf16_t*, const uint8_t*, const int64_t*, float, hipStream_t);
 bool launch_logprob_bwd_t(bf16_t*, int64_t, int, int64_t, int64_t, const int64_t*, const float*,
                           const float*, bf16_t*, hipStream_t);
 void launch_logprob_entropy_fwd(const bf16_t*, int64_t, int, int64_t, int64_t, const int64_t*, float*,
@@ -728,6 +734,86 @@ at::Tensor logprob_bwd_t_temp(at::Tensor& logits, const at::Tensor& tgt, const a
   return logprob_bwd_t_impl(logits, tgt, lse, grad, vocab_offset, &i);
 }
 
+// The kept-set twins of the *_temp ops: row r is taken over the vocabulary entries whose bit is set
+// in row keep_rows[r] of keep (uint8 [M, V / 8], bit j of byte i = entry 8 i + j; keep_rows[r] < 0 =
+// the full vocabulary). Equal, bit for bit, to the *_temp ops on logits with the dropped entries
+// written as -inf, without that write. keep_rows[r] < keep.size(0) is the caller's precondition (a
+// check would need a sync). No vocab shard.
+static void check_keep(const at::Tensor& logits, const at::Tensor& keep, const at::Tensor& keep_rows) {
+  const int64_t N = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(V % 8 == 0, "keep mask: the vocabulary size must be a multiple of 8 (V % 8 == 0), got ", V);
+  TORCH_CHECK(logits.stride(0) % 8 == 0, "keep mask: the logits row stride must be a multiple of 8 (ld % 8 == 0)");
+  check_aligned16(logits, "logits");
+  TORCH_CHECK(keep.is_cuda() && keep.scalar_type() == at::kByte && keep.dim() == 2 && keep.is_contiguous(),
+              "keep must be a contiguous uint8 [M, V / 8] tensor on the GPU");
+  TORCH_CHECK(keep.size(1) * 8 == V, "keep.size(1) * 8 must equal V");
+  TORCH_CHECK(keep_rows.is_cuda() && keep_rows.scalar_type() == at::kLong && keep_rows.dim() == 1 &&
+                  keep_rows.size(0) == N && keep_rows.is_contiguous(),
+              "keep_rows must be int64 [N]");
+  same_device(logits, keep);
+  same_device(logits, keep_rows);
+}
+
+std::tuple<at::Tensor, at::Tensor> logprob_fwd_keep(const at::Tensor& logits, const at::Tensor& tgt,
+                                                    const at::Tensor& keep, const at::Tensor& keep_rows,
+                                                    double inv_temp) {
+  const float i = checked_inv_temp(inv_temp);
+  check_logits(logits);
+  check_keep(logits, keep, keep_rows);
+  TORCH_CHECK(tgt.scalar_type() == at::kLong && tgt.is_contiguous() && tgt.numel() == logits.size(0),
+              "targets int64 [N]");
+  same_device(logits, tgt);
+  c10::hip::HIPGuardMasqueradingAsCUDA g(logits.device());
+  auto opt = logits.options().dtype(at::kFloat);
+  auto logp = at::empty({logits.size(0)}, opt);
+  auto lse = at::empty({logits.size(0)}, opt);
+  launch_logprob_fwd_keep(cbp(logits), logits.stride(0), static_cast<int>(logits.size(1)), logits.size(0),
+                          tgt.data_ptr<int64_t>(), logp.data_ptr<float>(), lse.data_ptr<float>(),
+                          keep.data_ptr<uint8_t>(), keep_rows.data_ptr<int64_t>(), i, cur_stream(logits));
+  return {logp, lse};
+}
+
+void logprob_bwd_keep(at::Tensor& logits, const at::Tensor& tgt, const at::Tensor& lse, const at::Tensor& grad,
+                      const at::Tensor& keep, const at::Tensor& keep_rows, double inv_temp) {
+  const float i = checked_inv_temp(inv_temp);
+  check_logits(logits);
+  check_keep(logits, keep, keep_rows);
+  check_f32(lse, "lse");
+  check_f32(grad, "grad");
+  const int64_t N = logits.size(0);
+  TORCH_CHECK(tgt.scalar_type() == at::kLong && tgt.numel() == N && tgt.is_contiguous(), "targets");
+  TORCH_CHECK(lse.numel() == N && grad.numel() == N && grad.is_contiguous() && lse.is_contiguous(),
+              "lse/grad shape");
+  c10::hip::HIPGuardMasqueradingAsCUDA g(logits.device());
+  launch_logprob_bwd_keep(bp(logits), logits.stride(0), static_cast<int>(logits.size(1)), N,
+                          tgt.data_ptr<int64_t>(), lse.data_ptr<float>(), grad.data_ptr<float>(),
+                          keep.data_ptr<uint8_t>(), keep_rows.data_ptr<int64_t>(), i, cur_stream(logits));
+}
+
+// Empty outside the transposing kernel's shapes (N % 8 != 0), as logprob_bwd_t: run logprob_bwd_keep.
+at::Tensor logprob_bwd_t_keep(at::Tensor& logits, const at::Tensor& tgt, const at::Tensor& lse,
+                              const at::Tensor& grad, const at::Tensor& keep, const at::Tensor& keep_rows,
+                              double inv_temp) {
+  const float i = checked_inv_temp(inv_temp);
+  check_logits(logits);
+  check_keep(logits, keep, keep_rows);
+  check_f32(lse, "lse");
+  check_f32(grad, "grad");
+  const int64_t N = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(tgt.scalar_type() == at::kLong && tgt.numel() == N && tgt.is_contiguous(), "targets");
+  TORCH_CHECK(lse.numel() == N && grad.numel() == N && grad.is_contiguous() && lse.is_contiguous(),
+              "lse/grad shape");
+  if (N == 0 || N % 8 != 0) return at::empty({0}, logits.options());
+  c10::hip::HIPGuardMasqueradingAsCUDA g(logits.device());
+  auto outT = at::empty({V, N}, logits.options());
+  const bool ok = launch_logprob_bwd_t_keep(bp(logits), logits.stride(0), static_cast<int>(V), N,
+                                            tgt.data_ptr<int64_t>(), lse.data_ptr<float>(),
+                                            grad.data_ptr<float>(), bp(outT), keep.data_ptr<uint8_t>(),
+                                            keep_rows.data_ptr<int64_t>(), i, cur_stream(logits));
+  TORCH_CHECK(ok, "logprob_bwd_t_keep: shape");
+  return outT;
+}
+
 // The entropy twins: the forward also emits the local shard's softmax entropy per row (every row,
 // whatever its target) from the same read; the backwards add grad_ent's term given the GLOBAL lse
 // and entropy. logp and lse are bitwise logprob_fwd's.
@@ -1293,6 +1379,9 @@ TORCH_LIBRARY(dla, m) {
   m.def("logprob_fwd_temp(Tensor logits, Tensor targets, float inv_temp, int vocab_offset=0) -> (Tensor, Tensor)");
   m.def("logprob_bwd_temp(Tensor(a!) logits, Tensor targets, Tensor lse, Tensor grad, float inv_temp, int vocab_offset=0) -> ()");
   m.def("logprob_bwd_t_temp(Tensor(a!) logits, Tensor targets, Tensor lse, Tensor grad, float inv_temp, int vocab_offset=0) -> Tensor");
+  m.def("logprob_fwd_keep(Tensor logits, Tensor targets, Tensor keep, Tensor keep_rows, float inv_temp) -> (Tensor, Tensor)");
+  m.def("logprob_bwd_keep(Tensor(a!) logits, Tensor targets, Tensor lse, Tensor grad, Tensor keep, Tensor keep_rows, float inv_temp) -> ()");
+  m.def("logprob_bwd_t_keep(Tensor(a!) logits, Tensor targets, Tensor lse, Tensor grad, Tensor keep, Tensor keep_rows, float inv_temp) -> Tensor");
   m.def("logprob_entropy_fwd_temp(Tensor logits, Tensor targets, float inv_temp, int vocab_offset=0) -> (Tensor, Tensor, Tensor)");
   m.def("logprob_entropy_bwd_temp(Tensor(a!) logits, Tensor targets, Tensor lse, Tensor ent, Tensor grad_logp, Tensor grad_ent, float inv_temp, int vocab_offset=0) -> ()");
   m.def("logprob_entropy_bwd_t_temp(Tensor(a!) logits, Tensor targets, Tensor lse, Tensor ent, Tensor grad_logp, Tensor grad_ent, float inv_temp, int vocab_offset=0) -> Tensor");
@@ -1340,6 +1429,9 @@ TORCH_LIBRARY_IMPL(dla, CUDA, m) {
   m.impl("logprob_fwd_temp", &dla::logprob_fwd_temp);
   m.impl("logprob_bwd_temp", &dla::logprob_bwd_temp);
   m.impl("logprob_bwd_t_temp", &dla::logprob_bwd_t_temp);
+  m.impl("logprob_fwd_keep", &dla::logprob_fwd_keep);
+  m.impl("logprob_bwd_keep", &dla::logprob_bwd_keep);
+  m.impl("logprob_bwd_t_keep", &dla::logprob_bwd_t_keep);
   m.impl("logprob_entropy_fwd_temp", &dla::logprob_entropy_fwd_temp);
   m.impl("logprob_entropy_bwd_temp", &dla::logprob_entropy_bwd_temp);
   m.impl("logprob_entropy_bwd_t_temp", &dla::logprob_entropy_bwd_t_temp);

@@ -33,6 +33,8 @@ void launch_sample_split_logp_tempered(const void*, bool, int64_t, int64_t, int,
                                        const int64_t*, int64_t*, float*, void*, hipStream_t);
 void launch_sample_split_logp(const void*, bool, int64_t, int64_t, int, int, float, int, float,
                               const int64_t*, int64_t*, float*, void*, hipStream_t);
+void launch_sample_keep(const void*, bool, int64_t, int64_t, int, int, float, int, float, const int64_t*,
+                        int64_t*, float*, uint8_t*, void*, hipStream_t);
 
 void launch_kv_replicate(const bf16_t*, const bf16_t*, bf16_t*, bf16_t*, int, int, int, int, int,
                          int, const int64_t*, const int64_t*, hipStream_t);
@@ -684,6 +686,38 @@ std::tuple<at::Tensor, at::Tensor> sample_tokens_logp_tempered(const at::Tensor&
   return {out, logp};
 }
 
+// sample_tokens plus the set every token was drawn from: keep uint8 [B, V / 8], bit j (LSB first) of
+// byte i = vocabulary entry 8 i + j kept by the top-k / top-p filter (the z >= -64 window without a
+// filter), and logp [B] fp32 = the log-prob under that FILTERED distribution at the draw
+// temperature, z_t - log(kept mass). Tokens are sample_tokens' bit for bit; the launch count is
+// sample_tokens'. A greedy / temperature <= 0 call has no kept set and is rejected.
+std::tuple<at::Tensor, at::Tensor, at::Tensor> sample_tokens_keep(const at::Tensor& logits, double temperature,
+                                                                  int64_t top_k, double top_p,
+                                                                  const at::Tensor& rng) {
+  check_sample_args(logits, top_p, rng);
+  TORCH_CHECK(temperature > 0.0, "sample_tokens_keep: temperature must be > 0 (a greedy call has no kept set)");
+  const int64_t B = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(V % 8 == 0, "sample_tokens_keep: the vocabulary size must be a multiple of 8 (V % 8 == 0), got ", V);
+  TORCH_CHECK(logits.stride(0) % 8 == 0, "sample_tokens_keep: the row stride must be a multiple of 8");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(logits.data_ptr()) % 16 == 0,
+              "sample_tokens_keep: logits must be 16-byte aligned");
+  c10::hip::HIPGuardMasqueradingAsCUDA g(logits.device());
+  auto out = at::empty({B}, logits.options().dtype(at::kLong));
+  auto logp = at::empty({B}, logits.options().dtype(at::kFloat));
+  auto keep = at::empty({B, V / 8}, logits.options().dtype(at::kByte));
+  const float inv_t = static_cast<float>(1.0 / temperature);
+  const bool is_bf16 = logits.scalar_type() == at::kBFloat16;
+  const int G = sample_split_chunks(logits.data_ptr(), logits.stride(0), B, (int)V, inv_t, (int)top_k,
+                                    static_cast<float>(top_p), false);
+  at::Tensor ws;
+  if (G > 0) ws = at::empty({(int64_t)sample_workspace_bytes(B, G)}, logits.options().dtype(at::kByte));
+  launch_sample_keep(logits.data_ptr(), is_bf16, logits.stride(0), B, (int)V, G, inv_t, (int)top_k,
+                     static_cast<float>(top_p), rng.data_ptr<int64_t>(), out.data_ptr<int64_t>(),
+                     logp.data_ptr<float>(), keep.data_ptr<uint8_t>(), G > 0 ? ws.data_ptr() : nullptr,
+                     cur_stream(logits));
+  return {out, logp, keep};
+}
+
 // Shared-prefill replication: keys / values [0, Tp) of every layer of the P-row prefill cache
 // (src_k / src_v [L, P, Tp, Hkv, D]) go to rows p*G .. p*G+G-1 of the P*G-row decode cache
 // (dst_k / dst_v [L, P*G, Tmax >= Tp, Hkv, D]); any strides with D contiguous and 16-byte
@@ -737,6 +771,7 @@ TORCH_LIBRARY_FRAGMENT(dla, m) {
   m.def("sample_tokens(Tensor logits, float temperature, int top_k, float top_p, bool greedy, Tensor rng) -> Tensor");
   m.def("sample_tokens_logp(Tensor logits, float temperature, int top_k, float top_p, bool greedy, Tensor rng) -> (Tensor, Tensor)");
   m.def("sample_tokens_logp_tempered(Tensor logits, float temperature, int top_k, float top_p, bool greedy, Tensor rng) -> (Tensor, Tensor)");
+  m.def("sample_tokens_keep(Tensor logits, float temperature, int top_k, float top_p, Tensor rng) -> (Tensor, Tensor, Tensor)");
   m.def("skinny_gemm(Tensor x, Tensor w, Tensor(a!) counters, bool swiglu, bool glu_out=False) -> Tensor");
   m.def("skinny_glu_ks(Tensor x, Tensor w) -> Tensor");
   m.def("skinny_fused(Tensor x, Tensor w, Tensor? res, Tensor? ssq_in, float eps, bool glu) -> (Tensor, Tensor)");
@@ -757,6 +792,7 @@ TORCH_LIBRARY_IMPL(dla, CUDA, m) {
   m.impl("sample_tokens", &dla::sample_tokens);
   m.impl("sample_tokens_logp", &dla::sample_tokens_logp);
   m.impl("sample_tokens_logp_tempered", &dla::sample_tokens_logp_tempered);
+  m.impl("sample_tokens_keep", &dla::sample_tokens_keep);
   m.impl("rope_cache_write", &dla::rope_cache_write);
   m.impl("decode_attn_rope", &dla::decode_attn_rope);
   m.impl("skinny_gemm", &dla::skinny_gemm);

@@ -100,9 +100,15 @@ __device__ __forceinline__ void lse_merge_ut(float& m, float& s, float& u, float
 // exponent argument is a scaled DIFFERENCE, d = (z_v - m) * it, so s = sum_v exp(d) and
 // u = sum_v exp(d) d. Contraction is off throughout and the merges are lse_merge_t / lse_merge_ut:
 // at it = 1 this is the flag-off arithmetic bit for bit.
-template <bool VEC, bool ENT = false, bool TEMP = false>
+// MASK (TEMP && VEC && !ENT only): the row's packed keep mask km, one byte per 8-logit vector, bit j
+// (LSB first) for lane value j; a cleared bit turns the fp32 value into -inf right after the
+// conversion and nothing else changes, so the sums are those of the row with its dropped entries
+// written as -inf, bit for bit. km == nullptr (a row without a mask) is the flag-off loop.
+template <bool VEC, bool ENT = false, bool TEMP = false, bool MASK = false>
 __device__ __forceinline__ void row_lse(const bf16_t* __restrict__ row, int V, float& m_out,
-                                        float& s_out, float* u_out = nullptr, float it = 1.f) {
+                                        float& s_out, float* u_out = nullptr, float it = 1.f,
+                                        const uint8_t* __restrict__ km = nullptr) {
+  static_assert(!MASK || (TEMP && VEC && !ENT), "the keep mask exists for the vectorised tempered kernels only");
   __shared__ float sm[4], ss[4], su[ENT ? 4 : 1];
   float m = -INFINITY, s = 0.f, u = 0.f;
   if constexpr (TEMP && VEC) {
@@ -110,11 +116,16 @@ __device__ __forceinline__ void row_lse(const bf16_t* __restrict__ row, int V, f
     const int nv = V >> 3;
     for (int i = threadIdx.x; i < nv; i += 256) {
       bf16x8 a = load_bf16x8(row + i * 8);
+      [[maybe_unused]] unsigned kb = 0xffu;
+      if constexpr (MASK) {
+        if (km) kb = km[i];
+      }
       float x[8];
       float lm = -INFINITY;
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         x[j] = bf2f(a[j]);
+        if constexpr (MASK) x[j] = (kb >> j) & 1u ? x[j] : -INFINITY;
         lm = fmaxf(lm, x[j]);
       }
       if (lm == -INFINITY) continue;
@@ -254,24 +265,40 @@ __device__ __forceinline__ void row_lse(const bf16_t* __restrict__ row, int V, f
 // every row whatever its target.
 // TEMP: the same of softmax(inv_temp * logits): lse = inv_temp m + log s, logp = inv_temp z_t - lse,
 // ent = log s - u / s with s, u at the scaled differences (row_lse).
-template <bool VEC, bool ENT = false, bool TEMP = false>
+// MASK: row r reads row keep_rows[r] of keep [M, V / 8] (keep_rows[r] < 0: no mask, the flag-off
+// arithmetic); lse and logp are over the kept set, logp = -inf for a target outside it.
+template <bool VEC, bool ENT = false, bool TEMP = false, bool MASK = false>
 __global__ __launch_bounds__(256) void logprob_fwd_kernel(const bf16_t* __restrict__ logits,
                                                            int64_t ld, int V, int64_t off,
                                                            const int64_t* __restrict__ tgt,
                                                            float* __restrict__ logp,
                                                            float* __restrict__ lse_out,
                                                            float* __restrict__ ent_out = nullptr,
-                                                           float inv_temp = 1.f) {
+                                                           float inv_temp = 1.f,
+                                                           const uint8_t* __restrict__ keep = nullptr,
+                                                           const int64_t* __restrict__ keep_rows = nullptr) {
   const int64_t r = blockIdx.x;
   const bf16_t* row = logits + r * ld;
   float m, s, u = 0.f;
-  row_lse<VEC, ENT, TEMP>(row, V, m, s, &u, inv_temp);
+  [[maybe_unused]] const uint8_t* km = nullptr;
+  if constexpr (MASK) {
+    const int64_t kr = keep_rows[r];  // row-uniform: one row per block
+    if (kr >= 0) km = keep + kr * (V >> 3);
+  }
+  row_lse<VEC, ENT, TEMP, MASK>(row, V, m, s, &u, inv_temp, km);
   if (threadIdx.x == 0) {
     const float lse = scaled<TEMP>(m, inv_temp) + __logf(s);
     lse_out[r] = lse;
     if constexpr (ENT) ent_out[r] = __logf(s) - u / s;
     const int64_t t = tgt[r] - off;
-    logp[r] = (tgt[r] >= 0 && t >= 0 && t < V) ? scaled<TEMP>(bf2f(row[t]), inv_temp) - lse : 0.f;
+    if constexpr (MASK) {
+      float zt = 0.f;
+      const bool own = tgt[r] >= 0 && t >= 0 && t < V;
+      if (own) zt = (!km || ((km[t >> 3] >> (t & 7)) & 1u)) ? bf2f(row[t]) : -INFINITY;
+      logp[r] = own ? scaled<TEMP>(zt, inv_temp) - lse : 0.f;
+    } else {
+      logp[r] = (tgt[r] >= 0 && t >= 0 && t < V) ? scaled<TEMP>(bf2f(row[t]), inv_temp) - lse : 0.f;
+    }
   }
 }
 
@@ -292,7 +319,8 @@ __device__ __forceinline__ float dlogit(float z, bool hit, float gr, float lse, 
   return z == -INFINITY ? 0.f : d - er * p * (z - lse + H);
 }
 
-template <bool VEC, bool ENT = false, bool TEMP = false>
+// MASK (VEC && TEMP && !ENT): as in the forward; a dropped entry is a -inf logit, so it gets exactly 0.
+template <bool VEC, bool ENT = false, bool TEMP = false, bool MASK = false>
 __global__ __launch_bounds__(256) void logprob_bwd_kernel(bf16_t* __restrict__ logits, int64_t ld,
                                                            int V, int64_t off,
                                                            const int64_t* __restrict__ tgt,
@@ -300,9 +328,17 @@ __global__ __launch_bounds__(256) void logprob_bwd_kernel(bf16_t* __restrict__ l
                                                            const float* __restrict__ g,
                                                            const float* __restrict__ ent_in = nullptr,
                                                            const float* __restrict__ ge = nullptr,
-                                                           float inv_temp = 1.f) {
+                                                           float inv_temp = 1.f,
+                                                           const uint8_t* __restrict__ keep = nullptr,
+                                                           const int64_t* __restrict__ keep_rows = nullptr) {
+  static_assert(!MASK || (TEMP && VEC && !ENT), "the keep mask exists for the vectorised tempered kernels only");
   const int64_t r = blockIdx.x;
   bf16_t* row = logits + r * ld;
+  [[maybe_unused]] const uint8_t* km = nullptr;
+  if constexpr (MASK) {
+    const int64_t kr = keep_rows[r];  // row-uniform: one row per block
+    if (kr >= 0) km = keep + kr * (V >> 3);
+  }
   const int64_t t = tgt[r] - off;
   const float gr = scaled<TEMP>(tgt[r] >= 0 ? g[r] : 0.f, inv_temp);
   const float lse = lse_in[r];
@@ -315,10 +351,16 @@ __global__ __launch_bounds__(256) void logprob_bwd_kernel(bf16_t* __restrict__ l
     const int nv = V >> 3;
     for (int i = threadIdx.x; i < nv; i += 256) {
       bf16x8 a = load_bf16x8(row + i * 8), o;
+      [[maybe_unused]] unsigned kb = 0xffu;
+      if constexpr (MASK) {
+        if (km) kb = km[i];
+      }
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const int v = i * 8 + j;
-        o[j] = f2bf(dlogit<ENT>(scaled<TEMP>(bf2f(a[j]), inv_temp), v == t, gr, lse, er, H));
+        float x = bf2f(a[j]);
+        if constexpr (MASK) x = (kb >> j) & 1u ? x : -INFINITY;
+        o[j] = f2bf(dlogit<ENT>(scaled<TEMP>(x, inv_temp), v == t, gr, lse, er, H));
       }
       store_bf16x8(row + i * 8, o);
     }
@@ -336,7 +378,8 @@ __global__ __launch_bounds__(256) void logprob_bwd_kernel(bf16_t* __restrict__ l
 // 64 rows x 64 columns; grid (ceil(V / 256), rows / 64); rows % 8 == 0, V % 8 == 0, ld % 8 == 0.
 // ENT: the entropy gradient too (dlogit<true>); two more per-row scalars live inside the unrolled
 // row loop, the 16 bf16x8 vectors per lane are unchanged.
-template <bool ENT = false, bool TEMP = false>
+// MASK: the lane loads one mask byte for each of its 8 rows (byte c / 8 of row keep_rows[r + i]).
+template <bool ENT = false, bool TEMP = false, bool MASK = false>
 __global__ __launch_bounds__(256) void logprob_bwd_t_kernel(bf16_t* __restrict__ logits, int64_t ld, int V,
                                                              int64_t off, const int64_t* __restrict__ tgt,
                                                              const float* __restrict__ lse_in,
@@ -344,7 +387,10 @@ __global__ __launch_bounds__(256) void logprob_bwd_t_kernel(bf16_t* __restrict__
                                                              bf16_t* __restrict__ outT, int64_t rows,
                                                              const float* __restrict__ ent_in = nullptr,
                                                              const float* __restrict__ ge = nullptr,
-                                                             float inv_temp = 1.f) {
+                                                             float inv_temp = 1.f,
+                                                             const uint8_t* __restrict__ keep = nullptr,
+                                                             const int64_t* __restrict__ keep_rows = nullptr) {
+  static_assert(!MASK || (TEMP && !ENT), "the keep mask exists for the tempered kernels only");
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int64_t r = static_cast<int64_t>(blockIdx.y) * 64 + (lane >> 3) * 8;
   const int c = blockIdx.x * 256 + w * 64 + (lane & 7) * 8;
@@ -352,6 +398,14 @@ __global__ __launch_bounds__(256) void logprob_bwd_t_kernel(bf16_t* __restrict__
   bf16x8 a[8], o[8];
 #pragma unroll
   for (int i = 0; i < 8; ++i) a[i] = load_bf16x8(logits + (r + i) * ld + c);
+  [[maybe_unused]] unsigned kb[8];
+  if constexpr (MASK) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int64_t kr = keep_rows[r + i];
+      kb[i] = kr >= 0 ? keep[kr * (V >> 3) + (c >> 3)] : 0xffu;
+    }
+  }
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
     const int64_t t = tgt[r + i] - off;
@@ -363,8 +417,11 @@ __global__ __launch_bounds__(256) void logprob_bwd_t_kernel(bf16_t* __restrict__
       H = ent_in[r + i];
     }
 #pragma unroll
-    for (int j = 0; j < 8; ++j)
-      o[i][j] = f2bf(dlogit<ENT>(scaled<TEMP>(bf2f(a[i][j]), inv_temp), c + j == t, gr, lse, er, H));
+    for (int j = 0; j < 8; ++j) {
+      float x = bf2f(a[i][j]);
+      if constexpr (MASK) x = (kb[i] >> j) & 1u ? x : -INFINITY;
+      o[i][j] = f2bf(dlogit<ENT>(scaled<TEMP>(x, inv_temp), c + j == t, gr, lse, er, H));
+    }
     store_bf16x8(logits + (r + i) * ld + c, o[i]);
   }
   bf16x8 tt[8];
@@ -537,6 +594,35 @@ bool launch_logprob_bwd_t_temp(bf16_t* logits, int64_t ld, int V, int64_t rows, 
   const dim3 grid((V + 255) / 256, static_cast<unsigned>((rows + 63) / 64));
   logprob_bwd_t_kernel<false, true><<<grid, 256, 0, st>>>(logits, ld, V, off, tgt, lse, g, outT, rows, nullptr,
                                                           nullptr, inv_temp);
+  return true;
+}
+
+// The kept-set twins (MASK instantiations) of the tempered launches: keep uint8 [M, V / 8], keep_rows
+// int64 [rows] (< 0: no mask). V % 8 == 0 and ld % 8 == 0 are the caller's to check; no vocab shard.
+void launch_logprob_fwd_keep(const bf16_t* logits, int64_t ld, int V, int64_t rows, const int64_t* tgt,
+                             float* logp, float* lse, const uint8_t* keep, const int64_t* keep_rows,
+                             float inv_temp, hipStream_t st) {
+  if (rows == 0) return;
+  logprob_fwd_kernel<true, false, true, true><<<rows, 256, 0, st>>>(logits, ld, V, 0, tgt, logp, lse, nullptr,
+                                                                    inv_temp, keep, keep_rows);
+}
+
+void launch_logprob_bwd_keep(bf16_t* logits, int64_t ld, int V, int64_t rows, const int64_t* tgt,
+                             const float* lse, const float* g, const uint8_t* keep, const int64_t* keep_rows,
+                             float inv_temp, hipStream_t st) {
+  if (rows == 0) return;
+  logprob_bwd_kernel<true, false, true, true><<<rows, 256, 0, st>>>(logits, ld, V, 0, tgt, lse, g, nullptr,
+                                                                    nullptr, inv_temp, keep, keep_rows);
+}
+
+bool launch_logprob_bwd_t_keep(bf16_t* logits, int64_t ld, int V, int64_t rows, const int64_t* tgt,
+                               const float* lse, const float* g, bf16_t* outT, const uint8_t* keep,
+                               const int64_t* keep_rows, float inv_temp, hipStream_t st) {
+  if (rows % 8 != 0 || V % 8 != 0 || ld % 8 != 0) return false;
+  if (rows == 0) return true;
+  const dim3 grid((V + 255) / 256, static_cast<unsigned>((rows + 63) / 64));
+  logprob_bwd_t_kernel<false, true, true><<<grid, 256, 0, st>>>(logits, ld, V, 0, tgt, lse, g, outT, rows,
+                                                                nullptr, nullptr, inv_temp, keep, keep_rows);
   return true;
 }
 

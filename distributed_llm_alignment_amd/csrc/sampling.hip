@@ -206,13 +206,22 @@ __device__ __forceinline__ float logp_term_z(float z) { return z == z ? __expf(z
 // engine's model log-prob of the draw). Its mass sum S1 rides the draw pass (step 4) as a second
 // per-thread accumulator over the same contiguous segments, reduced by block_sum: shuffles and a
 // fixed LDS order, so two launches give the same bits. !LOGP compiles to the kernel without it.
-template <typename T, bool VEC, bool LOGP, bool LTEMP = false>
+//
+// KEEP (with VEC, LOGP and LTEMP; never greedy): also write the set the token was drawn from,
+// keep[r] = {v : z_v >= tau} packed one bit per vocabulary entry (bit j of byte i = entry 8 i + j), with
+// the draw pass's own comparison (a NaN logit gives 0), and logp[r] = z_t - log(kept mass), the
+// log-prob under the FILTERED draw distribution; the kept mass is the scan total the draw itself
+// divides by, so no second accumulator runs. Every thread owns whole 8-entry vectors of its
+// segment and stores their bytes. A row without a finite max writes logp 0 and an all-ones mask.
+template <typename T, bool VEC, bool LOGP, bool LTEMP = false, bool KEEP = false>
 __global__ __launch_bounds__(kSampNT) void sample_kernel(const T* __restrict__ logits, int64_t ld_,
                                                           int V, float inv_temp, int top_k,
                                                           float top_p, bool greedy,
                                                           const int64_t* __restrict__ rng,
                                                           int64_t* __restrict__ out,
-                                                          float* __restrict__ logp) {
+                                                          float* __restrict__ logp,
+                                                          uint8_t* __restrict__ keep = nullptr) {
+  static_assert(!KEEP || (VEC && LOGP && LTEMP), "the keep mask rides the vectorised draw pass");
   __shared__ float sc[kSampNT / 64];
   __shared__ int amin[kSampNT / 64];
   __shared__ int hc[kBins];
@@ -325,13 +334,17 @@ __global__ __launch_bounds__(kSampNT) void sample_kernel(const T* __restrict__ l
     for (int v = s0; v < s1; v += 8) {
       float x[8];
       ld8(row, v / 8, x);
+      [[maybe_unused]] unsigned kb = 0u;
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const float z = (x[j] - gmax) * inv_temp;
         mine += z >= tau ? __expf(z) : 0.f;
-        if constexpr (LOGP && LTEMP) mine1 += logp_term_z(z);
+        if constexpr (KEEP) kb |= z >= tau ? 1u << j : 0u;
+        else if constexpr (LOGP && LTEMP) mine1 += logp_term_z(z);
         else if constexpr (LOGP) mine1 += logp_term(x[j], gmax);
       }
+      if constexpr (KEEP)
+        keep[r * (V >> 3) + (v >> 3)] = static_cast<uint8_t>(gmax - gmax == 0.f ? kb : 0xffu);
     }
   } else {
     for (int v = s0; v < s1; ++v) {
@@ -345,7 +358,7 @@ __global__ __launch_bounds__(kSampNT) void sample_kernel(const T* __restrict__ l
   [[maybe_unused]] __shared__ float dsel;  // LOGP: x_t - gmax of the picked token; LTEMP: its z
   [[maybe_unused]] float mass1 = 0.f;  // LOGP: S1
   if constexpr (LOGP) {
-    mass1 = block_sum<kSampNT>(mine1, sc);
+    if constexpr (!KEEP) mass1 = block_sum<kSampNT>(mine1, sc);
     if (tid == 0) dsel = 0.f;  // the argmax fallback below: x_t = gmax (z = 0 as well)
   }
   tm[tid] = mine;
@@ -379,7 +392,7 @@ __global__ __launch_bounds__(kSampNT) void sample_kernel(const T* __restrict__ l
   __syncthreads();
   if (tid == 0) out[r] = ans >= 0 ? ans : argmax;  // u on a rounding gap at the top: argmax
   if constexpr (LOGP) {
-    if (tid == 0) logp[r] = logp_value(dsel, mass1, gmax);
+    if (tid == 0) logp[r] = logp_value(dsel, KEEP ? total : mass1, gmax);
   }
 }
 
@@ -647,12 +660,16 @@ __global__ __launch_bounds__(kSampNT) void split_resolve_kernel(int G, int top_k
 // workspace region of its own behind the SplitWs ones); split_pick_kernel adds the G partials in
 // index order. The mass is S1, the temperature-1 sum of exp(x - gmax), or under LTEMP the tempered
 // sum of exp(z), z = (x - gmax) * inv_t, over every entry whatever tau.
-template <typename T, bool LOGP, bool LTEMP = false>
+// KEEP: this pass visits every vector with tau known, so it also stores the vector's byte of the
+// packed kept set (sample_kernel); the kept mass behind logp is the cmass sum split_pick_kernel
+// already forms, so csum is not written.
+template <typename T, bool LOGP, bool LTEMP = false, bool KEEP = false>
 __global__ __launch_bounds__(kSplitNT) void split_mass_kernel(const T* __restrict__ logits,
                                                               int64_t ld_, int V, int G,
                                                               float inv_t, bool has_tau,
                                                               SplitWs ws,
-                                                              float* __restrict__ csum) {
+                                                              float* __restrict__ csum,
+                                                              uint8_t* __restrict__ keep = nullptr) {
   __shared__ float red[kSplitNT / 64];
   const int r = blockIdx.y, g = blockIdx.x, tid = threadIdx.x;
   float gmax;
@@ -667,23 +684,28 @@ __global__ __launch_bounds__(kSplitNT) void split_mass_kernel(const T* __restric
   for (int i = v0 + tid; i < v1; i += kSplitNT) {
     float x[8];
     ld8(row, i, x);
+    [[maybe_unused]] unsigned kb = 0u;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const float z = (x[j] - gmax) * inv_t;
       acc += z >= tau ? __expf(z) : 0.f;
-      if constexpr (LOGP && LTEMP) acc1 += logp_term_z(z);
+      if constexpr (KEEP) kb |= z >= tau ? 1u << j : 0u;
+      else if constexpr (LOGP && LTEMP) acc1 += logp_term_z(z);
       else if constexpr (LOGP) acc1 += logp_term(x[j], gmax);
     }
+    if constexpr (KEEP)
+      keep[int64_t(r) * (V >> 3) + i] = static_cast<uint8_t>(gmax - gmax == 0.f ? kb : 0xffu);
   }
   const float tot = block_sum<kSplitNT>(acc, red);
   if (tid == 0) ws.cmass[r * G + g] = tot;
-  if constexpr (LOGP) {
+  if constexpr (LOGP && !KEEP) {
     const float tot1 = block_sum<kSplitNT>(acc1, red);
     if (tid == 0) csum[r * G + g] = tot1;
   }
 }
 
-template <typename T, bool LOGP, bool LTEMP = false>
+// KEEP: logp = z_t - log(total), total the index-order chunk-mass sum the draw divides by.
+template <typename T, bool LOGP, bool LTEMP = false, bool KEEP = false>
 __global__ __launch_bounds__(kSplitNT) void split_pick_kernel(const T* __restrict__ logits,
                                                               int64_t ld_, int V, int G,
                                                               float inv_t, bool has_tau,
@@ -772,10 +794,14 @@ __global__ __launch_bounds__(kSplitNT) void split_pick_kernel(const T* __restric
   if (tid == 0) out[r] = ans >= 0 ? ans : argmax;  // u on a rounding gap: argmax
   if constexpr (LOGP) {
     if (tid == 0) {
-      float s1sum = 0.f;
+      if constexpr (KEEP) {
+        logp[r] = logp_value(dsel, total, gmax);
+      } else {
+        float s1sum = 0.f;
 #pragma unroll
-      for (int g = 0; g < kSplitG; ++g) s1sum += csum[r * kSplitG + g];  // index order
-      logp[r] = logp_value(dsel, s1sum, gmax);
+        for (int g = 0; g < kSplitG; ++g) s1sum += csum[r * kSplitG + g];  // index order
+        logp[r] = logp_value(dsel, s1sum, gmax);
+      }
     }
   }
 }
@@ -803,13 +829,13 @@ size_t sample_workspace_bytes_logp(int64_t rows, int G) {
   return G > 0 ? split_ws_bytes(rows, G) + align256(size_t(rows) * G * 4) : 0;
 }
 
-template <typename T, bool LOGP, bool LTEMP = false>
+template <typename T, bool LOGP, bool LTEMP = false, bool KEEP = false>
 static void launch_split(const T* lg, int64_t ld_, int64_t rows, int V, int G, float inv_t,
                          int top_k, float top_p, const int64_t* rng, int64_t* out, float* logp,
-                         void* wsp, hipStream_t st) {
+                         void* wsp, hipStream_t st, uint8_t* keep = nullptr) {
   const SplitWs ws = split_ws(wsp, rows, G);
-  float* csum = LOGP ? reinterpret_cast<float*>(static_cast<char*>(wsp) + split_ws_bytes(rows, G))
-                     : nullptr;
+  float* csum = LOGP && !KEEP ? reinterpret_cast<float*>(static_cast<char*>(wsp) + split_ws_bytes(rows, G))
+                              : nullptr;
   const dim3 grid(G, rows);
   const bool need_k = top_k > 0 && top_k < V, need_p = top_p < 1.f;
   split_max_kernel<T><<<grid, kSplitNT, 0, st>>>(lg, ld_, V, G, ws);
@@ -819,9 +845,10 @@ static void launch_split(const T* lg, int64_t ld_, int64_t rows, int V, int G, f
     const int first_phase = p == 0 ? (need_k ? kKCoarse : kPCoarse) : kDone;
     split_resolve_kernel<<<rows, kSampNT, 0, st>>>(G, top_k, top_p, need_p, first_phase, ws);
   }
-  split_mass_kernel<T, LOGP, LTEMP><<<grid, kSplitNT, 0, st>>>(lg, ld_, V, G, inv_t, passes > 0, ws, csum);
-  split_pick_kernel<T, LOGP, LTEMP><<<rows, kSplitNT, 0, st>>>(lg, ld_, V, G, inv_t, passes > 0, rng, ws,
-                                                               out, csum, logp);
+  split_mass_kernel<T, LOGP, LTEMP, KEEP><<<grid, kSplitNT, 0, st>>>(lg, ld_, V, G, inv_t, passes > 0, ws,
+                                                                     csum, keep);
+  split_pick_kernel<T, LOGP, LTEMP, KEEP><<<rows, kSplitNT, 0, st>>>(lg, ld_, V, G, inv_t, passes > 0, rng,
+                                                                     ws, out, csum, logp);
 }
 
 template <bool LOGP, bool LTEMP = false>
@@ -859,6 +886,30 @@ void launch_sample_split_logp_tempered(const void* logits, bool is_bf16, int64_t
                                        int64_t* out, float* logp, void* ws, hipStream_t st) {
   sample_split_any<true, true>(logits, is_bf16, ld_, rows, V, G, inv_temp, top_k, top_p, rng, out, logp,
                                ws, st);
+}
+
+// The kept-set op (KEEP instantiations): tokens as the plain launches, logp under the filtered draw
+// distribution, keep uint8 [rows, V / 8]. The caller has checked V % 8 == 0, ld_ % 8 == 0, a 16-byte
+// aligned base and temperature > 0. ws (G > 0): sample_workspace_bytes(rows, G) bytes.
+void launch_sample_keep(const void* logits, bool is_bf16, int64_t ld_, int64_t rows, int V, int G,
+                        float inv_temp, int top_k, float top_p, const int64_t* rng, int64_t* out,
+                        float* logp, uint8_t* keep, void* ws, hipStream_t st) {
+  if (rows == 0) return;
+  if (G > 0) {
+    if (is_bf16)
+      launch_split<bf16_t, true, true, true>(static_cast<const bf16_t*>(logits), ld_, rows, V, G, inv_temp,
+                                             top_k, top_p, rng, out, logp, ws, st, keep);
+    else
+      launch_split<float, true, true, true>(static_cast<const float*>(logits), ld_, rows, V, G, inv_temp,
+                                            top_k, top_p, rng, out, logp, ws, st, keep);
+    return;
+  }
+  if (is_bf16)
+    sample_kernel<bf16_t, true, true, true, true><<<rows, kSampNT, 0, st>>>(
+        static_cast<const bf16_t*>(logits), ld_, V, inv_temp, top_k, top_p, false, rng, out, logp, keep);
+  else
+    sample_kernel<float, true, true, true, true><<<rows, kSampNT, 0, st>>>(
+        static_cast<const float*>(logits), ld_, V, inv_temp, top_k, top_p, false, rng, out, logp, keep);
 }
 
 template <bool LOGP, bool LTEMP = false>

@@ -200,6 +200,24 @@ def sample_next(logits: torch.Tensor, do_sample: bool, temperature: float, top_p
     return torch.multinomial(probs, 1, generator=generator).squeeze(-1)
 
 
+def filtered_logits(logits: torch.Tensor, temperature: float, top_p: float, top_k: int = 0) -> torch.Tensor:
+    """logits [B, V] fp32 -> logits / temperature with every entry outside `sample_next`'s top-k /
+    nucleus filter at -inf (the same operations in the same order): the finite entries are the set a
+    sampling `sample_next` call draws from, softmax of the result its draw distribution."""
+    logits = logits / temperature
+    if top_k and top_k > 0:
+        kth = torch.topk(logits, top_k, dim=-1).values[:, -1:]
+        logits = logits.masked_fill(logits < kth, float("-inf"))
+    if top_p < 1.0:
+        sl, si = torch.sort(logits, descending=True, dim=-1)
+        probs = torch.softmax(sl, dim=-1)
+        cum = probs.cumsum(-1)
+        remove = (cum - probs) > top_p
+        sl = sl.masked_fill(remove, float("-inf"))
+        logits = torch.full_like(logits, float("-inf")).scatter(-1, si, sl)
+    return logits
+
+
 def _graph_capable(model: CausalLM) -> bool:
     """Model-level conditions for a captured decode step: single-device, unsharded, and no host
     sync inside the forward (MoE routing still reads per-expert counts on the host unless the
@@ -215,11 +233,30 @@ def _graph_ok(model: CausalLM, cache: KVCache) -> bool:
 
 
 # which log-prob `generate(return_logprobs=True)` asks the sampler for
-_LOGP_OFF, _LOGP_PLAIN, _LOGP_TEMPERED = 0, 1, 2
+# (_LOGP_KEEP: `return_keep_mask`, the sampler op that also writes the kept set; its log-prob is the
+# one under the filtered draw distribution)
+_LOGP_OFF, _LOGP_PLAIN, _LOGP_TEMPERED, _LOGP_KEEP = 0, 1, 2, 3
 
 
 def _logp_sampler(mode: int):
+    if mode == _LOGP_KEEP:
+        return ops.decode.sample_tokens_keep
     return ops.decode.sample_tokens_logp_tempered if mode == _LOGP_TEMPERED else ops.decode.sample_tokens_logp
+
+
+def _keep_mode(model: CausalLM, return_logprobs: bool, logprob_temperature, do_sample: bool,
+               temperature: float) -> int:
+    """The conditions of `generate(return_keep_mask=True)`; raises ValueError before any work."""
+    if not (do_sample and temperature > 0):
+        raise ValueError("return_keep_mask needs do_sample and temperature > 0: a greedy call has no kept set")
+    if model.cfg.vocab_size % 8 != 0:
+        raise ValueError(f"return_keep_mask needs a vocabulary size that is a multiple of 8, got {model.cfg.vocab_size}")
+    if model.tp_size > 1:
+        raise ValueError("return_keep_mask is not supported with tensor parallelism")
+    if return_logprobs and (logprob_temperature is None or float(logprob_temperature) != float(temperature)):
+        raise ValueError(f"return_keep_mask with return_logprobs returns the kept-set log-prob at the sampling "
+                         f"temperature: logprob_temperature must be {temperature!r}, got {logprob_temperature!r}")
+    return _LOGP_KEEP
 
 
 def _logp_mode(return_logprobs: bool, logprob_temperature, do_sample: bool, temperature: float) -> int:
@@ -251,6 +288,10 @@ class _DecodeGraph:
         # temperature 1, _LOGP_TEMPERED: at the draw temperature)
         self.logp = torch.zeros((B, max_new), dtype=torch.float32, device=dev) if logprobs else None
         self.logp_op = _logp_sampler(logprobs) if logprobs else None
+        # _LOGP_KEEP: the packed set every token was drawn from; rows of finished sequences hold
+        # whatever the sampler wrote (nothing reads them)
+        self.keep = (torch.zeros((B, max_new, model.cfg.vocab_size // 8), dtype=torch.uint8, device=dev)
+                     if logprobs == _LOGP_KEEP else None)
         self.col = torch.zeros(1, dtype=torch.long, device=dev)
         self.rng = torch.tensor([seed, 0], dtype=torch.long, device=dev)
         self.eos, self.pad = eos, pad
@@ -265,7 +306,11 @@ class _DecodeGraph:
     def sample(self, logits):
         t, k, p, g = self.args
         if self.logp is not None:
-            nxt, lp = self.logp_op(logits, t, k, p, g, self.rng)
+            if self.keep is not None:
+                nxt, lp, kp = self.logp_op(logits, t, k, p, g, self.rng)
+                self.keep.index_copy_(1, self.col, kp.unsqueeze(1))
+            else:
+                nxt, lp = self.logp_op(logits, t, k, p, g, self.rng)
             self.logp.index_copy_(1, self.col, torch.where(self.finished, torch.zeros_like(lp), lp).unsqueeze(1))
         else:
             nxt = ops.decode.sample_tokens(logits, t, k, p, g, self.rng)
@@ -393,7 +438,7 @@ def generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional[
              return_mask: bool = False, use_graph: Optional[bool] = None, seed: Optional[int] = None,
              weight_dtype: str = "bf16", num_return_sequences: int = 1, share_prefill: bool = True,
              group_attention: bool = False, return_logprobs: bool = False,
-             logprob_temperature: Optional[float] = None):
+             logprob_temperature: Optional[float] = None, return_keep_mask: bool = False):
     """Left-padded prompts [B, Tp] -> sequences [B, Tp + n] (n <= max_new_tokens).
 
     `num_return_sequences=G` (group rollouts, GRPO): G samples per prompt, output [B*G, Tp + n]
@@ -422,6 +467,15 @@ def generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional[
     (`ops.decode.sample_tokens_logp_tempered`); the tokens are the same. Any other value raises
     ValueError.
 
+    With `return_keep_mask`, also returns `keep` uint8 [B, n, V / 8], last in the returned tuple
+    (`seqs[, mask][, logp], keep`): `keep[s, j]` is the set the token at position Tp + j of row s was
+    drawn from after the top-k / top-p filter, one bit per vocabulary entry (bit j' of byte i = entry
+    8 i + j', `ops.logprob.pack_keep`); rows of finished sequences hold unspecified bits. It needs
+    `do_sample`, `temperature > 0`, V % 8 == 0 and no tensor parallelism (ValueError otherwise). With
+    `return_logprobs` as well, `logprob_temperature` must be the sampling temperature and `logp` is
+    the log-prob under the FILTERED draw distribution (softmax of logits / temperature over the
+    kept set, `ops.decode.sample_tokens_keep`), the exact behaviour log-prob; the tokens are the same.
+
     On MI355X the prompt is prefilled with the flash-attention kernel, then every new token is
     ONE replay of a captured hipGraph (decode kernel + fused sampler, no host sync except an
     all-finished check every 16 tokens). `use_graph=False` forces the eager per-op loop.
@@ -440,12 +494,16 @@ def generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional[
         input_ids = input_ids.repeat_interleave(G, 0)
         attention_mask = attention_mask.repeat_interleave(G, 0) if attention_mask is not None else None
         G = 1
-    lp_mode = _logp_mode(bool(return_logprobs), logprob_temperature, do_sample, temperature)
+    if return_keep_mask:
+        lp_mode = _keep_mode(model, bool(return_logprobs), logprob_temperature, do_sample, temperature)
+    else:
+        lp_mode = _logp_mode(bool(return_logprobs), logprob_temperature, do_sample, temperature)
     f8 = weight_dtype == "fp8" or ops.decode.fp8_enabled()
     with ops.decode.fp8_weights(f8), ops.fp8_inference_scope(model, f8 and PREFILL_FP8):
         return _generate(model, input_ids, attention_mask, max_new_tokens, do_sample, temperature, top_p,
                          top_k, eos_token_id, pad_token_id, generator, return_mask, use_graph, seed, G,
-                         bool(group_attention) and G > 1, lp_mode)
+                         bool(group_attention) and G > 1, lp_mode,
+                         bool(return_logprobs) if return_keep_mask else None)
 
 
 def _generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor],
@@ -453,7 +511,9 @@ def _generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional
               eos_token_id: Optional[int], pad_token_id: Optional[int],
               generator: Optional[torch.Generator], return_mask: bool, use_graph: Optional[bool],
               seed: Optional[int], G: int = 1, group_attention: bool = False,
-              return_logprobs: int = _LOGP_OFF):
+              return_logprobs: int = _LOGP_OFF, want_logp: Optional[bool] = None):
+    # return_logprobs: the sampler mode (_LOGP_*); want_logp: whether logp is returned (None: whenever
+    # the mode produces one; the keep mode produces it also for a call that wants the mask alone)
     if DECODE_GATHER and model.layers_sharded():
         # ZeRO-3 policy: gather it once for the whole rollout (fused decode kernels + captured
         # graph) instead of an all-gather per layer per token
@@ -465,7 +525,7 @@ def _generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional
                     stack.enter_context(eng.gathered_for_inference())
                 return _generate(model, input_ids, attention_mask, max_new_tokens, do_sample, temperature,
                                  top_p, top_k, eos_token_id, pad_token_id, generator, return_mask, use_graph,
-                                 seed, G, group_attention, return_logprobs)
+                                 seed, G, group_attention, return_logprobs, want_logp)
         finally:
             # the gathered units are freed on exit: the captured graph (it reads their addresses),
             # its KV cache and the derived decode weight copies (a second full set of layer
@@ -551,16 +611,19 @@ def _generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional
         seqs = torch.cat([input_ids, dg.out[:, :n]], dim=1)
         gm = dg.gen_mask[:, :n]
         glp = dg.logp[:, :n].clone() if return_logprobs else None
+        gkeep = dg.keep[:, :n].clone() if return_logprobs == _LOGP_KEEP else None
     else:
-        out, gen_mask, logps = [input_ids], [], []
+        out, gen_mask, logps, keeps = [input_ids], [], [], []
         finished = torch.zeros(B, dtype=torch.bool, device=input_ids.device)
         rng = torch.tensor([seed, 0], dtype=torch.long, device=input_ids.device)
         for step in range(max_new_tokens):
             logits = model.logits(last)
             lp = None
             if return_logprobs:  # native on the GPU; sample_next + log_softmax off it
-                nxt, lp = _logp_sampler(return_logprobs)(logits, temperature, top_k, top_p, greedy, rng,
-                                                         generator)
+                res = _logp_sampler(return_logprobs)(logits, temperature, top_k, top_p, greedy, rng, generator)
+                nxt, lp = res[0], res[1]
+                if return_logprobs == _LOGP_KEEP:
+                    keeps.append(res[2])
                 if ops._ext.use_native(logits):
                     rng[1:].add_(1)
             elif ops._ext.use_native(logits):
@@ -587,6 +650,7 @@ def _generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional
         seqs = torch.cat(out, dim=1)
         gm = torch.stack(gen_mask, 1)
         glp = torch.stack(logps, 1) if return_logprobs else None
+        gkeep = torch.stack(keeps, 1) if return_logprobs == _LOGP_KEEP else None
     if was_training:
         model.train()
     pm = attention_mask if attention_mask is not None else torch.ones_like(input_ids)
@@ -595,6 +659,8 @@ def _generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional
     ret = (seqs,)
     if return_mask:
         ret += (torch.cat([pm.long(), gm], dim=1),)
-    if return_logprobs:
+    if return_logprobs if want_logp is None else want_logp:
         ret += (glp,)
+    if return_logprobs == _LOGP_KEEP:
+        ret += (gkeep,)
     return ret[0] if len(ret) == 1 else ret

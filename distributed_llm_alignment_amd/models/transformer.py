@@ -617,16 +617,32 @@ class CausalLM(nn.Module):
         return sp.local(sp.pad(tgt, -100)), (None if mask is None else sp.local(sp.pad(mask, 0)))
 
     def _masked_token_logprob(self, h: torch.Tensor, tgt: torch.Tensor, with_entropy: bool = False,
-                              temperature: float = 1.0):
+                              temperature: float = 1.0, keep: Optional[torch.Tensor] = None,
+                              keep_rows: Optional[torch.Tensor] = None):
         """[S, T', H] hidden + [S, T'] targets (-100 = ignore) -> [S, T'] fp32 log-probs (0 where
         ignored); the LM-head bias models (phi-2) go through full logits. `with_entropy`: also the
         entropy of each position's next-token distribution (0 where ignored). `temperature`: both of
-        softmax(logits / temperature)."""
+        softmax(logits / temperature). `keep` (uint8 [M, V / 8]) / `keep_rows` (int64 [S, T'], < 0 =
+        none): the log-prob over the kept vocabulary subset of every position (`ops.linear_logprob`)."""
         S, T, H = h.shape
+        if keep is not None or keep_rows is not None:
+            if keep is None or keep_rows is None:
+                raise ValueError("keep and keep_rows go together")
+            if with_entropy:
+                raise ValueError("the entropy under a keep mask is not implemented (with_entropy with keep)")
+            if self.vocab_parallel is not None:
+                raise ValueError("a keep mask is not supported with a vocab-parallel LM head")
+            if self.sp is not None:
+                raise ValueError("a keep mask is not supported with sequence parallelism")
+            if tuple(keep_rows.shape) != (S, T):
+                raise ValueError(f"keep_rows must be [{S}, {T}], got {tuple(keep_rows.shape)}")
         if self.lm_head_bias is not None:
             lg = self.logits(h).float()
-            if temperature != 1.0:
+            if temperature != 1.0 or keep is not None:
                 lg = lg * ops.logprob.inv_temperature(temperature)
+            if keep is not None:
+                kept = ops.logprob.keep_rows_bool(keep, keep_rows.reshape(-1)).view(S, T, -1)
+                lg = lg.masked_fill(~kept, float("-inf"))
             lsm = torch.log_softmax(lg, -1)
             lp = lsm.gather(-1, tgt.clamp(min=0).unsqueeze(-1)).squeeze(-1)
             lp = torch.where(tgt >= 0, lp, torch.zeros_like(lp))
@@ -637,6 +653,9 @@ class CausalLM(nn.Module):
         if with_entropy:
             lp, ent = self._token_logprob_entropy(h.reshape(S * T, H), tgt.reshape(-1), temperature)
             return lp.view(S, T), ent.view(S, T)
+        if keep is not None:
+            return ops.linear_logprob(h.reshape(S * T, H), self.head_weight, tgt.reshape(-1), temperature=temperature,
+                                      keep=keep, keep_rows=keep_rows.reshape(-1)).view(S, T)
         return self._token_logprob(h.reshape(S * T, H), tgt.reshape(-1), temperature).view(S, T)
 
     def sequence_logprob(self, input_ids, attention_mask=None, reduction: str = "mean"):
@@ -647,12 +666,27 @@ class CausalLM(nn.Module):
         return sp_seq_reduce(self.sp, lp, mask, reduction == "mean")
 
     def token_logprobs(self, input_ids, attention_mask=None, with_entropy: bool = False,
-                       temperature: float = 1.0):
+                       temperature: float = 1.0, keep: Optional[torch.Tensor] = None,
+                       keep_rows: Optional[torch.Tensor] = None):
         """[S, T] log p(x_{t+1} | x_<=t) at every scored position (0 elsewhere): the per-action
         grid of token-level RL objectives (PPO). `with_entropy`: returns (lp, ent), ent [S, T] the
         entropy of p(. | x_<=t) at the same positions, from the same LM-head pass. `temperature`:
         p = softmax(logits / temperature), the distribution a sampler at that temperature draws
-        from (applied in fp32 inside the LM-head row kernels)."""
+        from (applied in fp32 inside the LM-head row kernels). `keep` (uint8 [M, V / 8]) and
+        `keep_rows` (int64 [S, T], < 0 = full vocabulary): position (s, t) is scored over the
+        vocabulary subset packed in row keep_rows[s, t] of `keep`, the set a top-k / top-p sampler
+        drew x_{t+1} from (`generate(return_keep_mask=True)`, `objectives.keep_row_grid`). Not with
+        `with_entropy`, a vocab-parallel head or sequence parallelism (ValueError)."""
+        if keep is not None or keep_rows is not None:
+            if with_entropy:
+                raise ValueError("the entropy under a keep mask is not implemented (with_entropy with keep)")
+            if self.vocab_parallel is not None:
+                raise ValueError("a keep mask is not supported with a vocab-parallel LM head")
+            if self.sp is not None:
+                raise ValueError("a keep mask is not supported with sequence parallelism")
+            h = self(input_ids, attention_mask)
+            tgt = ops.shifted_targets(input_ids, attention_mask)[0]
+            return self._masked_token_logprob(h, tgt, temperature=temperature, keep=keep, keep_rows=keep_rows)
         h = self(input_ids, attention_mask)
         tgt, _ = self._sp_targets(ops.shifted_targets(input_ids, attention_mask)[0])
         if with_entropy:

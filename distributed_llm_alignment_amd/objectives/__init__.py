@@ -151,6 +151,39 @@ def rollout_logp_grid(logp: torch.Tensor, prompt_len: int, T: int) -> torch.Tens
     return grid
 
 
+def keep_row_grid(act: torch.Tensor, prompt_len: int, n: int) -> torch.Tensor:
+    """int64 [S, T]: the row of a flattened `generate(return_keep_mask=True)` mask ([S * n, V / 8])
+    that every action position reads, s * n + (t - (prompt_len - 1)) where act[s, t] == 1
+    (`rollout_logp_grid`'s alignment: grid position t scores token t + 1, generated column
+    t + 1 - prompt_len), and -1 everywhere else (prompt positions, padding, after EOS): a
+    non-action position never reads a mask row. The `keep_rows` of `token_logprobs`."""
+    S, T = act.shape
+    if prompt_len < 1 or prompt_len + n > T:
+        raise ValueError(f"keep_row_grid: prompt_len {prompt_len} + {n} generated columns do not fit T = {T}")
+    col = torch.arange(T, device=act.device) - (prompt_len - 1)
+    idx = torch.arange(S, device=act.device).unsqueeze(1) * n + col.unsqueeze(0)
+    ok = (act > 0) & (col >= 0).unsqueeze(0) & (col < n).unsqueeze(0)
+    return torch.where(ok, idx, torch.full_like(idx, -1))
+
+
+def keep_fraction(full_lp: torch.Tensor, kept_lp: torch.Tensor, act: torch.Tensor) -> torch.Tensor:
+    """`train/keep_fraction`: the mean over action tokens of exp(logp_full - logp_kept), the share of
+    the (tempered) full-vocabulary mass the kept sets hold, from two [S, T] action grids of log-probs of
+    the same tokens at the same temperature (a device tensor: no host sync)."""
+    f = torch.exp((full_lp.float() - kept_lp.float()) * act) * act
+    return f.sum() / act.sum().clamp(min=1)
+
+
+def _keep_kw(keep, keep_rows) -> dict:
+    """`token_logprobs` keywords of the step's sampling mask: none without one, so a default run makes
+    the calls (and launches the kernels) it always made."""
+    if keep is None and keep_rows is None:
+        return {}
+    if keep is None or keep_rows is None:
+        raise ValueError("keep and keep_rows go together")
+    return {"keep": keep.reshape(-1, keep.shape[-1]), "keep_rows": keep_rows}
+
+
 def rollout_mismatch(rollout_lp: torch.Tensor, trainer_lp: torch.Tensor, act: torch.Tensor):
     """How far the engine that sampled the rollouts is from the trainer's own forward, on the
     sampled tokens (both [S, T] action grids): `rollout_kl`, the mean over action tokens of
@@ -183,7 +216,8 @@ def ppo_rollout_stats(policy, ref, critic, seqs, mask, prompt_len: int, scores, 
                       gamma: float = 1.0, lam: float = 0.95, whiten: bool = True,
                       old_logp: Optional[torch.Tensor] = None, rollout_logp: Optional[torch.Tensor] = None,
                       is_cap: float = 2.0, is_floor: Optional[float] = None, is_level: str = "token",
-                      is_mode: str = "truncate", temperature: float = 1.0):
+                      is_mode: str = "truncate", temperature: float = 1.0,
+                      keep: Optional[torch.Tensor] = None, keep_rows: Optional[torch.Tensor] = None):
     """Token-level PPO targets for one batch of rollouts (actor-critic; the north-star
     "PPO RLHF (actor + critic + reward)" config). Per-token reward = -kl_coef * (logp - logp_ref)
     on every action, plus the reward-model score on the last action; GAE(gamma, lam) over the
@@ -194,8 +228,11 @@ def ppo_rollout_stats(policy, ref, critic, seqs, mask, prompt_len: int, scores, 
     adds `is_weight` / `rollout_is` (`rollout_is_stats` with the four `is_*` settings): truncated
     importance weights for `ppo_loss`, computed once per rollout batch. `temperature`: every
     log-prob here (policy, reference) is of softmax(logits / temperature); grids passed in must be
-    at the same temperature."""
-    tkw = _temp_kw(temperature)
+    at the same temperature. `keep` / `keep_rows` (`generate(return_keep_mask=True)`,
+    `keep_row_grid`): every log-prob here is over the kept set of its token; grids passed in must be
+    the engine's kept-set log-probs. `keep_rows` is returned in the stats (sliced by rows with the
+    rest; `keep` stays whole, the indices are global)."""
+    tkw = {**_temp_kw(temperature), **_keep_kw(keep, keep_rows)}
     old_lp = old_logp.float() if old_logp is not None else policy.token_logprobs(seqs, mask, **tkw)
     ref_lp = ref.token_logprobs(seqs, mask, **tkw)
     values = critic(seqs, mask)
@@ -214,6 +251,8 @@ def ppo_rollout_stats(policy, ref, critic, seqs, mask, prompt_len: int, scores, 
         adv = (adv - mu) * torch.rsqrt(var + 1e-8) * act
     out = {"old_logp": old_lp, "values": values, "advantages": adv, "returns": ret, "act": act,
            "kl": kl.sum(1) / act.sum(1).clamp(min=1), "scores": scores.float()}
+    if keep_rows is not None:
+        out["keep_rows"] = keep_rows
     if rollout_logp is not None:
         out.update(rollout_is_stats(rollout_logp, old_lp, act, is_cap, is_floor, is_level, is_mode))
     return out
@@ -239,15 +278,20 @@ def ppo_critic_stream(device: torch.device):
 
 
 def token_logprobs_entropy(policy, seqs, mask, act, entropy_coef: float = 0.0, log_entropy: bool = False,
-                           n_act: Optional[torch.Tensor] = None, temperature: float = 1.0):
+                           n_act: Optional[torch.Tensor] = None, temperature: float = 1.0,
+                           keep: Optional[torch.Tensor] = None, keep_rows: Optional[torch.Tensor] = None):
     """Token log-probs of a PPO / GRPO (micro-)batch and, when `entropy_coef != 0` or
     `log_entropy`, the policy entropy from the same LM-head pass: returns (lp, bonus, entropy).
     `bonus` = entropy_coef * sum(ent * act) / n_act (None when the coefficient is 0: the entropy is
     then detached and the plain backward kernels run); `n_act`, a device tensor (no host sync), is
     the action-token count the bonus is normalised by -- the whole minibatch's for micro-batches,
     this batch's own by default. `entropy` is this batch's detached mean over action tokens (None
-    when off). `temperature`: log-probs and entropy of softmax(logits / temperature)."""
-    tkw = _temp_kw(temperature)
+    when off). `temperature`: log-probs and entropy of softmax(logits / temperature). `keep` /
+    `keep_rows`: the log-probs over the kept sets; the entropy under a kept set does not exist yet, so
+    an entropy bonus or `log_entropy` together with them raises ValueError."""
+    tkw = {**_temp_kw(temperature), **_keep_kw(keep, keep_rows)}
+    if keep is not None and (entropy_coef != 0 or log_entropy):
+        raise ValueError("entropy_coef / log_entropy are not supported together with a keep mask")
     if entropy_coef == 0 and not log_entropy:
         return policy.token_logprobs(seqs, mask, **tkw), None, None
     lp, ent = policy.token_logprobs(seqs, mask, with_entropy=True, **tkw)
@@ -263,11 +307,13 @@ def token_logprobs_entropy(policy, seqs, mask, act, entropy_coef: float = 0.0, l
 
 def ppo_loss(policy, critic, seqs, mask, stats: Dict[str, torch.Tensor], clip_eps: float = 0.2,
              value_clip: float = 0.2, vf_coef: float = 0.1, entropy_coef: float = 0.0,
-             log_entropy: bool = False, temperature: float = 1.0):
+             log_entropy: bool = False, temperature: float = 1.0,
+             keep: Optional[torch.Tensor] = None, keep_rows: Optional[torch.Tensor] = None):
     """Clipped surrogate (HIP fused fwd+bwd) + vf_coef * clipped value loss on one minibatch,
     minus entropy_coef * the mean policy entropy over action tokens (`metrics["entropy"]`, also
     with `log_entropy` alone). `stats["is_weight"]` (optional) weights the surrogate per token.
     `temperature`: the policy's log-probs and entropy at that temperature (as in `stats`).
+    `keep` (+ `keep_rows`, default `stats["keep_rows"]`): the policy's log-probs over the kept sets.
     Run its backward through `ppo_backward` (joins the critic's stream
     afterwards)."""
     cs = ppo_critic_stream(seqs.device)
@@ -277,8 +323,10 @@ def ppo_loss(policy, critic, seqs, mask, stats: Dict[str, torch.Tensor], clip_ep
         with torch.cuda.stream(cs):
             v = critic(seqs, mask)
             vl = ops.ppo_value_loss(v, stats["values"], stats["returns"], stats["act"], value_clip)
+    if keep is not None and keep_rows is None:
+        keep_rows = stats.get("keep_rows")
     lp, bonus, entropy = token_logprobs_entropy(policy, seqs, mask, stats["act"], entropy_coef, log_entropy,
-                                                temperature=temperature)
+                                                temperature=temperature, keep=keep, keep_rows=keep_rows)
     pl, pm = ops.ppo_policy_loss(lp, stats["old_logp"], stats["advantages"], stats["act"], clip_eps,
                                  is_weight=stats.get("is_weight"))
     if cs is None:
@@ -311,7 +359,8 @@ def grpo_rollout_stats(policy, ref, seqs, mask, prompt_len: int, scores, G: int,
                        scale_std: bool = True, need_old: bool = False,
                        old_logp: Optional[torch.Tensor] = None, rollout_logp: Optional[torch.Tensor] = None,
                        is_cap: float = 2.0, is_floor: Optional[float] = None, is_level: str = "token",
-                       is_mode: str = "truncate", temperature: float = 1.0):
+                       is_mode: str = "truncate", temperature: float = 1.0,
+                       keep: Optional[torch.Tensor] = None, keep_rows: Optional[torch.Tensor] = None):
     """GRPO targets for one batch of group rollouts (rows p*G .. p*G+G-1 sample prompt p). The
     reward is the reward-model score alone (the KL lives in the loss); a rollout's advantage is its
     score standardised inside its group. The reference's token log-probs are skipped entirely
@@ -322,8 +371,9 @@ def grpo_rollout_stats(policy, ref, seqs, mask, prompt_len: int, scores, G: int,
     kind of grid) instead keeps the old-policy log-probs the trainer's own (the forward always
     runs, as with `need_old`) and adds `is_weight` / `rollout_is` (`rollout_is_stats` with the four
     `is_*` settings): truncated importance weights for `grpo_loss`, computed once per rollout batch. `temperature`:
-    every log-prob here is of softmax(logits / temperature); grids passed in must be at the same."""
-    tkw = _temp_kw(temperature)
+    every log-prob here is of softmax(logits / temperature); grids passed in must be at the same.
+    `keep` / `keep_rows`: as in `ppo_rollout_stats`."""
+    tkw = {**_temp_kw(temperature), **_keep_kw(keep, keep_rows)}
     act = action_mask(mask, prompt_len)
     adv, gm = ops.group_advantages(scores, G, scale_std)
     ref_lp = ref.token_logprobs(seqs, mask, **tkw) if beta != 0 else None
@@ -333,6 +383,8 @@ def grpo_rollout_stats(policy, ref, seqs, mask, prompt_len: int, scores, G: int,
         old_logp = policy.token_logprobs(seqs, mask, **tkw)
     out = {"act": act, "advantages": adv, "ref_logp": ref_lp, "old_logp": old_logp,
            "scores": scores.float(), "reward_std": gm["reward_std"], "frac_zero_std": gm["frac_zero_std"]}
+    if keep_rows is not None:
+        out["keep_rows"] = keep_rows
     if rollout_logp is not None:
         out.update(rollout_is_stats(rollout_logp, old_logp, act, is_cap, is_floor, is_level, is_mode))
     return out
@@ -342,14 +394,18 @@ def grpo_loss(policy, seqs, mask, stats: Dict[str, torch.Tensor], clip_low: floa
               clip_high: Optional[float] = None, beta: float = 0.04, loss_type: str = "sequence",
               max_len: Optional[int] = None, denom: Optional[torch.Tensor] = None,
               entropy_coef: float = 0.0, log_entropy: bool = False, n_act: Optional[torch.Tensor] = None,
-              temperature: float = 1.0):
+              temperature: float = 1.0, keep: Optional[torch.Tensor] = None,
+              keep_rows: Optional[torch.Tensor] = None):
     """Token-level clipped surrogate + beta * k3 KL to the reference (HIP fused fwd+bwd) on one
     (micro-)batch of rollouts; `stats` from `grpo_rollout_stats`, sliced to the same rows.
     `entropy_coef` / `log_entropy` / `n_act`: the entropy bonus and metric of
     `token_logprobs_entropy`. `stats["is_weight"]` (optional) weights the policy-gradient term per
-    token. `temperature`: the policy's log-probs and entropy at that temperature (as in `stats`)."""
+    token. `temperature`: the policy's log-probs and entropy at that temperature (as in `stats`).
+    `keep` (+ `keep_rows`, default `stats["keep_rows"]`): the policy's log-probs over the kept sets."""
+    if keep is not None and keep_rows is None:
+        keep_rows = stats.get("keep_rows")
     lp, bonus, entropy = token_logprobs_entropy(policy, seqs, mask, stats["act"], entropy_coef, log_entropy,
-                                                n_act, temperature=temperature)
+                                                n_act, temperature=temperature, keep=keep, keep_rows=keep_rows)
     loss, m = ops.grpo_loss(lp, stats.get("old_logp"), stats.get("ref_logp"), stats["advantages"],
                             stats["act"], clip_low, clip_high, beta, loss_type, max_len, denom,
                             is_weight=stats.get("is_weight"))

@@ -142,6 +142,32 @@ def sample_tokens_logp_tempered(logits: torch.Tensor, temperature: float, top_k:
     return tok, torch.log_softmax(x * inv_temperature(temperature), dim=-1).gather(-1, tok.unsqueeze(-1)).squeeze(-1)
 
 
+def sample_tokens_keep(logits: torch.Tensor, temperature: float, top_k: int, top_p: float, greedy: bool,
+                       rng: torch.Tensor, generator: Optional[torch.Generator] = None):
+    """`sample_tokens` that also returns the set every token was drawn from (the "sampling mask"):
+    (token ids [B] int64, logp [B] fp32, keep uint8 [B, V / 8]). Bit j (LSB first) of byte i of
+    `keep[r]` is set where vocabulary entry 8 i + j survived the top-k / top-p filter of row r
+    (`ops.logprob.pack_keep` format); `logp` is the log-prob under that FILTERED distribution at the
+    draw temperature, log softmax over the kept set of logits / temperature at the token: the exact
+    behaviour log-prob of the draw. The tokens are bitwise those of `sample_tokens`. `greedy`,
+    `temperature <= 0` (no kept set) and V % 8 != 0 raise ValueError. On the GPU the mask bytes and
+    the kept mass come out of the fused sampler's draw pass (`torch.ops.dla.sample_tokens_keep`)."""
+    if greedy or not temperature > 0:
+        raise ValueError("sample_tokens_keep: a greedy / temperature <= 0 call has no kept set")
+    if logits.shape[-1] % 8 != 0:
+        raise ValueError(f"sample_tokens_keep: the vocabulary size must be a multiple of 8, got {logits.shape[-1]}")
+    if _ext.use_native(logits):
+        tok, lp, keep = _ext.require().sample_tokens_keep(logits, float(temperature), int(top_k), float(top_p), rng)
+        return tok, lp, keep
+    from ..models.generation import filtered_logits
+    from .logprob import pack_keep
+
+    f = filtered_logits(logits.float(), temperature, top_p, top_k)
+    tok = torch.multinomial(torch.softmax(f, dim=-1), 1, generator=generator).squeeze(-1)
+    lp = torch.log_softmax(f, dim=-1).gather(-1, tok.unsqueeze(-1)).squeeze(-1)
+    return tok, lp, pack_keep(f > float("-inf"))
+
+
 def kv_replicate(src_k, src_v, dst_k, dst_v, G: int) -> None:
     """Shared-prefill replication for group rollouts: keys / values [0, Tp) of every layer of the
     P-row prefill cache (`src_*` [L, P, Tp, Hkv, D], or the layer-split list of [P, Tp, Hkv, D]) are

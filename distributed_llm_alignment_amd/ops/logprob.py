@@ -23,6 +23,13 @@ the distribution a sampler at that temperature draws from. The row kernels apply
 inv_temp = float(1 / temperature) in fp32 to the bf16 logits the GEMM wrote (the `*_temp` ops);
 at 1.0 the plain ops run, kernel for kernel.
 
+`linear_logprob(..., keep=, keep_rows=)` takes every row's log-prob over a KEPT subset of the
+vocabulary, the set a top-k / top-p sampler drew the row's token from ("keep sampling mask"): `keep`
+is uint8 [M, V / 8], bit j (LSB first) of byte i = vocabulary entry 8 i + j (`pack_keep`), and
+`keep_rows` int64 [N] names the mask row of every logits row (< 0: the full vocabulary). The row
+kernels read the mask byte next to each 16-byte logits vector (the `*_keep` ops), so no -inf is
+ever written into the [N, V] logits; entries outside the set get exactly zero gradient.
+
 `sequence_logprob(...)` adds the masked per-sequence reduction (length-normalised mean by default,
 exactly the reference's `/ mask.sum(1).clamp(min=1)`, or sum) as a HIP kernel pair.
 """
@@ -65,21 +72,69 @@ def _ref_linear_logprob(hidden, weight, targets, temperature: float = 1.0):
     return torch.where(targets >= 0, lp, torch.zeros_like(lp))
 
 
+def pack_keep(mask: torch.Tensor) -> torch.Tensor:
+    """bool [..., V] (V % 8 == 0) -> uint8 [..., V / 8]: bit j (LSB first) of byte i = entry 8 i + j."""
+    V = mask.shape[-1]
+    if V % 8 != 0:
+        raise ValueError(f"pack_keep: the vocabulary size must be a multiple of 8, got {V}")
+    w = torch.tensor([1, 2, 4, 8, 16, 32, 64, 128], dtype=torch.int32, device=mask.device)
+    return (mask.reshape(*mask.shape[:-1], V // 8, 8).to(torch.int32) * w).sum(-1).to(torch.uint8)
+
+
+def unpack_keep(keep: torch.Tensor) -> torch.Tensor:
+    """uint8 [..., V / 8] -> bool [..., V], the inverse of `pack_keep`."""
+    sh = torch.arange(8, dtype=torch.int32, device=keep.device)
+    bits = (keep.to(torch.int32).unsqueeze(-1) >> sh) & 1
+    return bits.bool().reshape(*keep.shape[:-1], keep.shape[-1] * 8)
+
+
+def _check_keep(keep, keep_rows, N: int, V: int):
+    if keep is None or keep_rows is None:
+        raise ValueError("keep and keep_rows go together")
+    if V % 8 != 0:
+        raise ValueError(f"a keep mask needs a vocabulary size that is a multiple of 8, got {V}")
+    if keep.dtype != torch.uint8 or keep.dim() != 2 or keep.shape[1] * 8 != V:
+        raise ValueError(f"keep must be uint8 [M, V / 8] = [M, {V // 8}], got {keep.dtype} {tuple(keep.shape)}")
+    if keep_rows.dtype != torch.int64 or tuple(keep_rows.shape) != (N,):
+        raise ValueError(f"keep_rows must be int64 [{N}], got {keep_rows.dtype} {tuple(keep_rows.shape)}")
+
+
+def keep_rows_bool(keep: torch.Tensor, keep_rows: torch.Tensor) -> torch.Tensor:
+    """bool [N, V]: the kept set of every row (all True where keep_rows < 0), in torch."""
+    m = unpack_keep(keep)[keep_rows.clamp(min=0)]
+    return m | (keep_rows < 0).unsqueeze(-1)
+
+
+def _ref_linear_logprob_keep(hidden, weight, targets, temperature, keep, keep_rows):
+    """The formula of record: log_softmax of the fp32 logits times `inv_temperature`, with the entries
+    outside the row's kept set at -inf."""
+    logits = F.linear(hidden, weight).float() * inv_temperature(temperature)
+    logits = logits.masked_fill(~keep_rows_bool(keep, keep_rows), float("-inf"))
+    # (log_softmax spelled as `_ref_linear_logprob` spells it, so an all-ones mask gives its bits)
+    lse = torch.logsumexp(logits, dim=-1)
+    lp = logits.gather(-1, targets.clamp(min=0).unsqueeze(-1)).squeeze(-1) - lse
+    return torch.where(targets >= 0, lp, torch.zeros_like(lp))
+
+
 class _LinearLogprobFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, hidden, weight, targets, inv_temp=None):
+    def forward(ctx, hidden, weight, targets, inv_temp=None, keep=None, keep_rows=None):
         # inv_temp: None = the plain ops; a float = the tempered twins (see `inv_temperature`)
+        # keep / keep_rows (with a float inv_temp): the kept-set twins of the tempered ops
         ops = _ext.require()
         need_grad = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
         N = hidden.shape[0]
         ctx.inv_temp = inv_temp
+        ctx.keep, ctx.keep_rows = keep, keep_rows
 
-        def fwd(lg, tg):
+        def fwd(lg, tg, kr=None):
+            if keep is not None:
+                return ops.logprob_fwd_keep(lg, tg, keep, kr, inv_temp)
             return ops.logprob_fwd(lg, tg) if inv_temp is None else ops.logprob_fwd_temp(lg, tg, inv_temp)
 
         if need_grad:
             logits = F.linear(hidden, weight)
-            logp, lse = fwd(logits, targets)
+            logp, lse = fwd(logits, targets, keep_rows)
             ctx.save_for_backward(hidden, targets, lse, logits)
             ctx.weight = weight  # (on ctx: see ops.linear._LinearMainGradFn)
             return logp
@@ -87,7 +142,7 @@ class _LinearLogprobFn(torch.autograd.Function):
         for s in range(0, N, _NO_GRAD_CHUNK):
             e = min(N, s + _NO_GRAD_CHUNK)
             lg = F.linear(hidden[s:e], weight)
-            lp, _ = fwd(lg, targets[s:e])
+            lp, _ = fwd(lg, targets[s:e], keep_rows[s:e] if keep is not None else None)
             logp[s:e] = lp
         return logp
 
@@ -97,6 +152,7 @@ class _LinearLogprobFn(torch.autograd.Function):
         hidden, targets, lse, logits = ctx.saved_tensors
         weight = ctx.weight
         it = ctx.inv_temp
+        keep, kr = ctx.keep, ctx.keep_rows
         from .linear import _tn_ok, accumulate_weight_grad
 
         g = g.float().contiguous()
@@ -107,12 +163,17 @@ class _LinearLogprobFn(torch.autograd.Function):
             # the LM head's weight gradient runs as a TN GEMM on dlogits^T: write it from the
             # same pass that turns the logits into dlogits (undefined when the shape is outside
             # the kernel -> in-place kernel + transpose inside accumulate_weight_grad)
-            dlt = (ops.logprob_bwd_t(logits, targets, lse, g) if it is None
-                   else ops.logprob_bwd_t_temp(logits, targets, lse, g, it))
+            if keep is not None:
+                dlt = ops.logprob_bwd_t_keep(logits, targets, lse, g, keep, kr, it)
+            else:
+                dlt = (ops.logprob_bwd_t(logits, targets, lse, g) if it is None
+                       else ops.logprob_bwd_t_temp(logits, targets, lse, g, it))
             if not dlt.numel():
                 dlt = None
         if dlt is None:
-            if it is None:
+            if keep is not None:
+                ops.logprob_bwd_keep(logits, targets, lse, g, keep, kr, it)
+            elif it is None:
                 ops.logprob_bwd(logits, targets, lse, g)
             else:
                 ops.logprob_bwd_temp(logits, targets, lse, g, it)
@@ -122,18 +183,28 @@ class _LinearLogprobFn(torch.autograd.Function):
         if ctx.needs_input_grad[1]:
             if not accumulate_weight_grad(weight, dlogits, hidden, dyt=dlt):
                 dw = dlogits.t() @ hidden
-        return dh, dw, None, None
+        return dh, dw, None, None, None, None
 
 
 def linear_logprob(hidden: torch.Tensor, weight: torch.Tensor, targets: torch.Tensor,
-                   temperature: float = 1.0) -> torch.Tensor:
+                   temperature: float = 1.0, keep: Optional[torch.Tensor] = None,
+                   keep_rows: Optional[torch.Tensor] = None) -> torch.Tensor:
     """hidden [N, H], weight [V, H], targets [N] (int64, <0 = ignore) -> logp [N] fp32, of
-    softmax(hidden @ W^T / temperature)."""
+    softmax(hidden @ W^T / temperature). With `keep` (uint8 [M, V / 8], `pack_keep`) and `keep_rows`
+    (int64 [N], < 0 = no mask; every other value must be < M) the softmax of row r runs over the
+    entries kept in row keep_rows[r] only: logp is -inf for a target outside the set, and the
+    entries outside it get exactly zero gradient."""
+    if keep is not None or keep_rows is not None:
+        _check_keep(keep, keep_rows, hidden.shape[0], weight.shape[0])
+        if _ext.use_native(hidden):
+            return _LinearLogprobFn.apply(hidden.contiguous(), weight, targets.contiguous(),
+                                          inv_temperature(temperature), keep.contiguous(), keep_rows.contiguous())
+        return _ref_linear_logprob_keep(hidden, weight, targets, temperature, keep, keep_rows)
     if _ext.use_native(hidden):
         if temperature == 1.0:
-            return _LinearLogprobFn.apply(hidden.contiguous(), weight, targets.contiguous(), None)
+            return _LinearLogprobFn.apply(hidden.contiguous(), weight, targets.contiguous(), None, None, None)
         return _LinearLogprobFn.apply(hidden.contiguous(), weight, targets.contiguous(),
-                                      inv_temperature(temperature))
+                                      inv_temperature(temperature), None, None)
     return _ref_linear_logprob(hidden, weight, targets, temperature)
 
 

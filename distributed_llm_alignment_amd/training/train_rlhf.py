@@ -76,6 +76,19 @@ the bf16 logits the GEMM wrote. With `rollout_logprobs` on, the value must be 1.
 temperature (the sampler has no other). `train/logprob_temperature` is logged once when the key is
 set. At 1.0 (or absent) a run launches exactly the kernels it launched before. The log-prob is
 over the full vocabulary: with `top_p < 1` / `top_k` it is still not the filtered draw distribution.
+
+`ppo.keep_sampling_mask: false | true` (default false), for `ppo` and `grpo`: with a top-k / top-p
+filter the rollout tokens are drawn from softmax(z / T_gen) renormalised over a kept set K per token.
+With the key on the rollouts also return K, packed one bit per vocabulary entry
+(`generate(return_keep_mask=True)`, S * n * V / 8 bytes), and EVERY trainer-side log-prob of a token
+(policy, old policy, reference) is taken over that token's K, the mask read by the LM-head row
+kernels next to the logits (`token_logprobs(keep=, keep_rows=)`): ratio, clip, k3 KL, PPO's KL
+reward live on the action space the sampler used. `rollout_logprobs: monitor|old|correct` then use
+the engine's kept-set log-probs (the exact behaviour log-probs) against the trainer's kept-set ones,
+so `logprob_temperature` must be the rollout temperature there. Not with `reinforce`, an inactive
+filter, greedy decoding, `entropy_coef` / `log_entropy` (no entropy under a kept set yet), tensor or
+sequence parallelism, or a vocabulary not divisible by 8: each raises at start-up. Absent or false,
+a run launches exactly the kernels it launched before.
 """
 from __future__ import annotations
 
@@ -84,15 +97,15 @@ import contextlib
 import math
 import random
 from pathlib import Path
-from typing import Dict, List
+from typing import Dict, List, Optional
 
 import torch
 
 from ..data import read_jsonl
 from ..models import (build_reward_model, build_value_model, generate, load_causal_lm,
                       load_reward_checkpoint)
-from ..objectives import (grpo_denominator, grpo_loss, grpo_rollout_stats, ppo_backward, ppo_loss,
-                          ppo_rollout_stats, rlhf_loss, rollout_logp_grid, rollout_mismatch)
+from ..objectives import (action_mask, grpo_denominator, grpo_loss, grpo_rollout_stats, keep_row_grid, ppo_backward,
+                          ppo_loss, ppo_rollout_stats, rlhf_loss, rollout_logp_grid, rollout_mismatch)
 from ..ops.losses import GRPO_LOSS_TYPES, ROLLOUT_IS_LEVELS, ROLLOUT_IS_MODES
 from ..parallel.dist import barrier, split_for_rank
 from ..utils.checkpoint import save_state
@@ -177,6 +190,43 @@ def logprob_temperature(ppo: Dict, algo: str) -> float:
         raise ValueError(f"ppo.rollout_logprobs needs ppo.logprob_temperature 1.0 or the rollout temperature "
                          f"({draw_temperature(gen)}): the sampler returns no other log-prob; got {t!r}")
     return t
+
+
+def keep_sampling_mask(ppo: Dict, algo: str, hardware: Optional[Dict] = None,
+                       vocab_size: Optional[int] = None) -> bool:
+    """`ppo.keep_sampling_mask` (default false); every combination it cannot honour raises.
+    `hardware` (the config's section) and `vocab_size` are checked when given."""
+    v = ppo.get("keep_sampling_mask", False)
+    if v is None or v is False:
+        return False
+    if v is not True:
+        raise ValueError(f"ppo.keep_sampling_mask must be true or false, got {v!r}")
+    if algo == "reinforce":
+        raise ValueError("ppo.keep_sampling_mask needs token-level log-probs (ppo.algorithm: ppo|grpo); "
+                         "the reinforce loop works on sequence log-probs")
+    gen = generation_params(ppo)
+    top_k, top_p = int(gen.get("top_k", 0) or 0), float(gen.get("top_p", 1.0))
+    if not (gen["do_sample"] and float(gen.get("temperature", 1.0)) > 0):
+        raise ValueError("ppo.keep_sampling_mask needs sampled rollouts (generation_params.do_sample with "
+                         "temperature > 0): greedy decoding keeps nothing")
+    if top_k <= 0 and top_p >= 1.0:
+        raise ValueError("ppo.keep_sampling_mask needs an active filter (generation_params.top_k > 0 or "
+                         "top_p < 1): without one there is nothing to keep")
+    if float(ppo.get("entropy_coef", 0.0) or 0.0) != 0 or bool(ppo.get("log_entropy", False)):
+        raise ValueError("ppo.keep_sampling_mask does not support ppo.entropy_coef / ppo.log_entropy: the "
+                         "entropy under the kept set is not implemented")
+    hw = hardware or {}
+    if int(hw.get("tp_size", 1) or 1) > 1 or int(hw.get("sp_size", 1) or 1) > 1 or hw.get("tp_sequence_parallel"):
+        raise ValueError("ppo.keep_sampling_mask does not support tensor_parallel / sequence parallel runs "
+                         "(hardware.tp_size, hardware.sp_size, hardware.tp_sequence_parallel)")
+    if vocab_size is not None and int(vocab_size) % 8 != 0:
+        raise ValueError(f"ppo.keep_sampling_mask needs a vocabulary size divisible by 8, got {vocab_size}")
+    lp_t = logprob_temperature(ppo, algo)
+    if rollout_logprobs_mode(ppo, algo) != "off" and lp_t != draw_temperature(gen):
+        raise ValueError(f"ppo.keep_sampling_mask with ppo.rollout_logprobs needs ppo.logprob_temperature to be "
+                         f"the generation temperature ({draw_temperature(gen)}; 'rollout'): the engine's kept-set "
+                         f"log-prob exists at the draw temperature only; got {lp_t!r}")
+    return True
 
 
 def rollout_is_settings(ppo: Dict) -> Dict:
@@ -269,6 +319,7 @@ def main(argv=None) -> int:
     want_logp = rollout_logprobs_mode(ppo, algo) != "off"
     rollout_is_settings(ppo)  # bad ppo.rollout_is_* values fail here, before any rollout
     lp_temp = logprob_temperature(ppo, algo)  # likewise
+    keep_on = keep_sampling_mask(ppo, algo, ctx.hw, policy.model.cfg.vocab_size)  # likewise
 
     # reward inputs built on the device when the reward tokenizer equals the policy's (no
     # decode / re-tokenise round trip through the host; training/handoff.py), else the
@@ -294,7 +345,9 @@ def main(argv=None) -> int:
                                     num_return_sequences=group, share_prefill=bool(ppo.get("share_prefill", True)),
                                     group_attention=bool(ppo.get("group_attention", False)),
                                     return_logprobs=want_logp,
-                                    logprob_temperature=lp_temp if want_logp and lp_temp != 1.0 else None)
+                                    logprob_temperature=lp_temp if want_logp and (lp_temp != 1.0 or keep_on) else None,
+                                    **({"return_keep_mask": True} if keep_on else {}))
+        keep = rlp.pop() if keep_on else None  # uint8 [S, n, V / 8], last in the returned tuple
         if group > 1:  # the reward hand-off sees one prompt row per rollout
             mine = [p for p in mine for _ in range(group)]
             ids, am = ids.repeat_interleave(group, 0), am.repeat_interleave(group, 0)
@@ -303,7 +356,7 @@ def main(argv=None) -> int:
             scores = rm(r_ids, r_mask)
         # the sampling engine's token log-probs in the trainer's [S, T] action grid, or None
         rlp = rollout_logp_grid(rlp[0], ids.shape[1], seqs.shape[1]) if want_logp else None
-        return seqs, mask, scores, ids.shape[1], rlp
+        return seqs, mask, scores, ids.shape[1], rlp, keep
 
     policy.model.train()
     if algo == "ppo":
@@ -313,7 +366,7 @@ def main(argv=None) -> int:
     micro = int(ppo.get("update_micro_batch", 0) or 0)
     pending = rollout()
     for step in range(steps):
-        seqs, mask, scores, _, _ = pending
+        seqs, mask, scores, _, _, _ = pending
         loss, m = reinforce_update(policy.model, ref.model, engine, seqs, mask, scores, kl_coef, micro)
         if ppo.get("async_rollouts", False) and step + 1 < steps:
             # the bucketed reduce-scatter launched by the backward hooks is in flight on RCCL's
@@ -378,25 +431,26 @@ def reinforce_update(policy, ref, engine, seqs, mask, scores, kl_coef: float, mi
 
 
 # the per-rollout entries of the GRPO stats that minibatches and micro-batches slice
-GRPO_ROWS = ("act", "advantages", "ref_logp", "old_logp", "is_weight")
+GRPO_ROWS = ("act", "advantages", "ref_logp", "old_logp", "is_weight", "keep_rows")
 
 
 def grpo_update(policy, engine, seqs, mask, stats, clip_low: float, clip_high, beta: float,
                 loss_type: str, max_len, micro: int = 0, entropy_coef: float = 0.0,
-                log_entropy: bool = False, temperature: float = 1.0):
+                log_entropy: bool = False, temperature: float = 1.0, keep=None):
     """Backward of the GRPO loss over one minibatch of rollouts. micro > 0
     (`ppo.update_micro_batch`): gradient-accumulated micro-batches of `micro` rollouts that share
     the whole minibatch's divisor (`denom`, a device tensor: no host sync), so their gradients sum
     to the full minibatch's; every micro-batch but the last runs under `engine.no_sync()`. The
     entropy bonus (`ppo.entropy_coef`) is likewise normalised by the whole minibatch's
     action-token count. `stats["is_weight"]` (optional) is sliced with the other per-rollout
-    entries. `temperature`: the log-prob temperature of `grpo_loss`. Returns (loss, metrics) with
+    entries. `temperature`: the log-prob temperature of `grpo_loss`. `keep`: the rollout batch's
+    whole sampling mask (`stats["keep_rows"]`, sliced with the rows, indexes it). Returns (loss, metrics) with
     token-weighted metric means."""
     n = seqs.shape[0]
     rows = GRPO_ROWS
     if micro <= 0 or micro >= n:
         loss, m = grpo_loss(policy, seqs, mask, stats, clip_low, clip_high, beta, loss_type, max_len,
-                            entropy_coef=entropy_coef, log_entropy=log_entropy, temperature=temperature)
+                            entropy_coef=entropy_coef, log_entropy=log_entropy, temperature=temperature, keep=keep)
         loss.backward()
         return loss.detach(), m
     denom = grpo_denominator(stats["act"], loss_type, max_len)
@@ -410,7 +464,8 @@ def grpo_update(policy, engine, seqs, mask, stats, clip_low: float, clip_high, b
         ctx = engine.no_sync() if i < len(bounds) - 1 else contextlib.nullcontext()
         with ctx:
             loss, m = grpo_loss(policy, seqs[s0:s1], mask[s0:s1], mb, clip_low, clip_high, beta, loss_type,
-                                max_len, denom, entropy_coef, log_entropy, tokens, temperature=temperature)
+                                max_len, denom, entropy_coef, log_entropy, tokens, temperature=temperature,
+                                keep=keep)
             loss.backward()
         tot = tot + loss.detach()
         for k in acc:
@@ -440,7 +495,10 @@ def _grpo_loop(ctx, config, ppo, policy, ref, rm, rollout, engine, steps, group,
     running = RunningLoss()
     pending = rollout()
     for step in range(steps):
-        seqs, mask, scores, tp, rlp = pending
+        seqs, mask, scores, tp, rlp, keep = pending
+        kkw = {}
+        if keep is not None:  # every log-prob of the step over the set its token was drawn from
+            kkw = {"keep": keep, "keep_rows": keep_row_grid(action_mask(mask, tp), tp, keep.shape[1])}
         # monitor: the trainer's own old-policy log-probs are computed even on-policy, to compare;
         # old: the rollout engine's ARE the old-policy log-probs (rho reflects fp8 / stale /
         # rounding mismatch, which the clip handles) and the policy forward is skipped;
@@ -450,7 +508,7 @@ def _grpo_loop(ctx, config, ppo, policy, ref, rm, rollout, engine, steps, group,
                                    need_old or lp_mode == "monitor",
                                    old_logp=rlp if lp_mode == "old" else None,
                                    rollout_logp=rlp if lp_mode == "correct" else None, **is_kw,
-                                   temperature=lp_temp)
+                                   temperature=lp_temp, **kkw)
         mism = rollout_mismatch(rlp, stats["old_logp"], stats["act"]) if lp_mode in ("monitor", "correct") else {}
         mism.update(stats.get("rollout_is", {}))
         if lp_mode in ("monitor", "correct") and not need_old:
@@ -463,7 +521,8 @@ def _grpo_loop(ctx, config, ppo, policy, ref, rm, rollout, engine, steps, group,
                     continue
                 mb = {k: (stats[k][a:b] if stats.get(k) is not None else None) for k in rows}
                 loss, m = grpo_update(policy.model, engine, seqs[a:b], mask[a:b], mb, clip_low, clip_high,
-                                      beta, loss_type, gen_len, micro, entropy_coef, log_entropy, lp_temp)
+                                      beta, loss_type, gen_len, micro, entropy_coef, log_entropy, lp_temp,
+                                      keep=keep)
                 last = ep == epochs - 1 and mi == len(bounds) - 1
                 if last and overlap and step + 1 < steps:
                     pending = rollout()  # overlaps the in-flight gradient collectives (see _ppo_loop)
@@ -519,11 +578,14 @@ def _ppo_loop(ctx, config, ppo, policy, ref, rm, rollout, engine, steps, kl_coef
     running = RunningLoss()
     pending = rollout()
     for step in range(steps):
-        seqs, mask, scores, tp, rlp = pending
+        seqs, mask, scores, tp, rlp, keep = pending
+        kkw = {}
+        if keep is not None:  # every log-prob of the step over the set its token was drawn from
+            kkw = {"keep": keep, "keep_rows": keep_row_grid(action_mask(mask, tp), tp, keep.shape[1])}
         stats = ppo_rollout_stats(policy.model, ref.model, critic, seqs, mask, tp, scores, kl_coef,
                                   gamma, lam, old_logp=rlp if lp_mode == "old" else None,
                                   rollout_logp=rlp if lp_mode == "correct" else None, **is_kw,
-                                  temperature=lp_temp)
+                                  temperature=lp_temp, **kkw)
         mism = rollout_mismatch(rlp, stats["old_logp"], stats["act"]) if lp_mode in ("monitor", "correct") else {}
         mism.update(stats.get("rollout_is", {}))
         S = seqs.shape[0]
@@ -532,9 +594,9 @@ def _ppo_loop(ctx, config, ppo, policy, ref, rm, rollout, engine, steps, kl_coef
             for mi, (a, b) in enumerate(bounds):
                 if b <= a:
                     continue
-                mb = {k: v[a:b] for k, v in stats.items() if k in ("old_logp", "values", "advantages", "returns", "act", "is_weight")}
+                mb = {k: v[a:b] for k, v in stats.items() if k in ("old_logp", "values", "advantages", "returns", "act", "is_weight", "keep_rows")}
                 loss, m = ppo_loss(policy.model, critic, seqs[a:b], mask[a:b], mb, clip, vclip, vf_coef,
-                                   entropy_coef, log_entropy, temperature=lp_temp)
+                                   entropy_coef, log_entropy, temperature=lp_temp, keep=keep)
                 ppo_backward(loss)
                 last = ep == epochs - 1 and mi == len(bounds) - 1
                 if last and overlap and step + 1 < steps:

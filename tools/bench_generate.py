@@ -29,9 +29,10 @@ def main() -> int:
                     help="samples per prompt (generate(num_return_sequences=G)); --batch counts prompts")
     ap.add_argument("--group-attention", type=int, choices=(0, 1), default=0,
                     help="decode attention reads a group's prompt K/V once (generate(group_attention=...))")
-    ap.add_argument("--logprobs", type=int, choices=(0, 1, 2), default=0,
+    ap.add_argument("--logprobs", type=int, choices=(0, 1, 2, 3), default=0,
                     help="also return the sampler's token log-probs (generate(return_logprobs=...)): 1 at "
-                         "temperature 1, 2 at the draw temperature (logprob_temperature=0.7)")
+                         "temperature 1, 2 at the draw temperature (logprob_temperature=0.7), 3 the kept-set "
+                         "log-probs and the sampling mask (return_keep_mask=True)")
     a = ap.parse_args()
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from distributed_llm_alignment_amd.models import build_model, generate, get_config
@@ -49,8 +50,8 @@ def main() -> int:
     # the sampler op alone at the decode step's shape, for its share of a token
     lg = torch.randn((a.batch * a.group, cfg.vocab_size), device=dev, generator=g).mul_(3).to(torch.bfloat16)
     rng = torch.tensor([1, 0], dtype=torch.long, device=dev)
-    op = (decode.sample_tokens, decode.sample_tokens_logp,
-          getattr(decode, "sample_tokens_logp_tempered", None))[a.logprobs]
+    op = (decode.sample_tokens, decode.sample_tokens_logp, getattr(decode, "sample_tokens_logp_tempered", None),
+          getattr(decode, "sample_tokens_keep", None))[a.logprobs]
     for _ in range(5):
         op(lg, 0.7, 0, 0.9, False, rng)
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
@@ -66,8 +67,10 @@ def main() -> int:
                   num_return_sequences=a.group, group_attention=bool(a.group_attention))
         if a.logprobs:  # (left out otherwise: the call an older build of the package takes)
             kw["return_logprobs"] = True
-        if a.logprobs == 2:
+        if a.logprobs >= 2:
             kw["logprob_temperature"] = 0.7
+        if a.logprobs == 3:
+            kw["return_keep_mask"] = True
         generate(m, ids[:, :64], am[:, :64], **{**kw, "max_new_tokens": 8})  # warm
         generate(m, ids, am, **kw)  # warm at the timed shapes (graph mode: the capture is reused)
         torch.cuda.synchronize()
@@ -85,7 +88,8 @@ def main() -> int:
         print(json.dumps({"mode": mode, "model": cfg.name, "batch": a.batch, "prompt": a.prompt,
                           "weight_dtype": a.weight_dtype, "group": a.group,
                           "group_attention": bool(a.group_attention), "logprobs": bool(a.logprobs),
-                          "logprob_temperature": 0.7 if a.logprobs == 2 else 1.0,
+                          "logprob_temperature": 0.7 if a.logprobs >= 2 else 1.0,
+                          "keep_mask": a.logprobs == 3,
                           "sampler_ms": round(sampler_ms, 4),
                           "new_tokens": n, "total_s": round(dt, 3), "prefill_s": round(tp, 3),
                           "decode_ms_per_token": round((dt - tp) / max(n - 1, 1) * 1e3, 3),

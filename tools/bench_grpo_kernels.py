@@ -16,7 +16,10 @@
                 eager torch entropy of the same logits (fp32 log_softmax), for scale. Then every
                 one of the six against its tempered twin (`*_temp`, `--temperature`, default 0.7),
                 interleaved the same way: `<kernel>_ms` / `<kernel>_temp_ms` / `<kernel>_temp_ratio`
-                under "temp". With an extension that lacks the twins (an older build through
+                under "temp". Then the kept-set twins (`logprob_fwd_keep`, `logprob_bwd_keep`,
+                `logprob_bwd_t_keep`; one mask row per logits row) against their tempered twins, with
+                the traffic ratio the mask bytes account for and the tempered twin's own spread, under
+                "keep". With an extension that lacks the twins (an older build through
                 DLA_EXT_PATH) only the plain kernels are timed.
 
   rollout_is    the truncated importance weights at S = 64, T = 768: `rollout_is_weights` (token and
@@ -124,6 +127,38 @@ def bench_logprob(dla_ops, dev, rows, V, rounds, iters, temperature=0.7):
         lp1, lse1 = dla_ops.logprob_fwd_temp(logits, tgt, 1.0)
         temp["unit_temperature_bitwise_equal"] = bool(torch.equal(lp1, lp0) and torch.equal(lse1, lse0))
         out["temp"] = temp
+    if hasattr(dla_ops, "logprob_fwd_keep") and V % 8 == 0:
+        # the kept-set twins, each against its tempered twin; one mask row per logits row (every token
+        # of a rollout has its own set), the 64 largest logits of each row kept. `*_temp_spread`: the
+        # tempered twin against itself, interleaved the same way (the run-to-run spread of the pair).
+        it = float(torch.tensor(1.0 / temperature, dtype=torch.float64).float())
+        keep = torch.zeros((rows, V // 8), device=dev, dtype=torch.uint8)
+        for s in range(0, rows, 1024):
+            m = torch.zeros((min(1024, rows - s), V), device=dev, dtype=torch.bool)
+            m.scatter_(1, logits[s:s + 1024].topk(64, dim=-1).indices, True)
+            w = torch.tensor([1, 2, 4, 8, 16, 32, 64, 128], device=dev, dtype=torch.int32)
+            keep[s:s + 1024] = (m.view(m.shape[0], V // 8, 8).int() * w).sum(-1).to(torch.uint8)
+            del m
+        kr = torch.arange(rows, device=dev)
+        lsek = dla_ops.logprob_fwd_keep(logits, tgt, keep, kr, it)[1]
+        pairs = [
+            ("fwd", 1, 1 / 16, lambda: dla_ops.logprob_fwd_temp(logits, tgt, it),
+             lambda: dla_ops.logprob_fwd_keep(logits, tgt, keep, kr, it)),
+            ("bwd", 2, 1 / 32, lambda: dla_ops.logprob_bwd_temp(work, tgt, lse, gl, it),
+             lambda: dla_ops.logprob_bwd_keep(work, tgt, lsek, gl, keep, kr, it)),
+            ("bwd_t", 3, 1 / 48, lambda: dla_ops.logprob_bwd_t_temp(work, tgt, lse, gl, it),
+             lambda: dla_ops.logprob_bwd_t_keep(work, tgt, lsek, gl, keep, kr, it)),
+        ]
+        kp = {"temperature": temperature, "keep_mib": round(keep.numel() / 2 ** 20, 1)}
+        for name, passes, extra, tempered, kept in pairs:
+            a, b = interleaved(tempered, kept, rounds, iters)
+            a1, a2 = interleaved(tempered, tempered, rounds, iters)
+            kp.update({f"{name}_temp_ms": round(a, 4), f"{name}_keep_ms": round(b, 4),
+                       f"{name}_keep_ratio": round(b / a, 4), f"{name}_traffic_ratio": round(1 + extra, 4),
+                       f"{name}_temp_spread": round(max(a1, a2) / min(a1, a2) - 1, 4),
+                       f"{name}_keep_gb_s": gbs(b, passes)})
+        out["keep"] = kp
+        del keep
     del work
 
     def eager():

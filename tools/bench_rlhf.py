@@ -81,6 +81,10 @@ def main() -> int:
                     help="ppo / grpo: ppo.logprob_temperature, a number > 0 or 'rollout' (the 0.7 the rollouts "
                          "are drawn at): the one temperature of every log-prob of the step, applied inside the "
                          "LM-head row kernels and the sampler")
+    ap.add_argument("--keep-sampling-mask", action="store_true",
+                    help="ppo / grpo: ppo.keep_sampling_mask (the rollouts return the top-p kept set of every "
+                         "token and every trainer-side log-prob is taken over it, the mask read inside the "
+                         "LM-head row kernels); with --rollout-logprobs it needs --logprob-temperature rollout")
     ap.add_argument("--rollout-is-cap", type=float, default=2.0, help="correct: ppo.rollout_is_cap")
     ap.add_argument("--rollout-is-floor", type=float, default=None, help="correct: ppo.rollout_is_floor (default 1 / cap)")
     ap.add_argument("--rollout-is-level", choices=("token", "sequence"), default="token")
@@ -111,6 +115,8 @@ def main() -> int:
         return grpo_main(a)
     if a.rollout_logprobs != "off":
         ap.error("--rollout-logprobs needs token-level log-probs: --algorithm ppo or grpo")
+    if a.keep_sampling_mask:
+        ap.error("--keep-sampling-mask needs token-level log-probs: --algorithm ppo or grpo")
     try:
         _lp_temp(a, "reinforce")  # (the reinforce loop has no log-prob temperature: only 1.0 resolves)
     except ValueError as exc:
@@ -303,13 +309,29 @@ def _lp_temp(a, algo: str) -> float:
                                 "generation_params": {"temperature": GEN_TEMPERATURE, "do_sample": True}}, algo)
 
 
+def _keep_on(a, algo: str, vocab_size: int) -> bool:
+    """--keep-sampling-mask validated as the trainer validates ppo.keep_sampling_mask."""
+    from distributed_llm_alignment_amd.training.train_rlhf import keep_sampling_mask
+
+    v = a.logprob_temperature
+    try:
+        v = float(v)
+    except ValueError:
+        pass
+    return keep_sampling_mask({"keep_sampling_mask": bool(a.keep_sampling_mask), "logprob_temperature": v,
+                               "rollout_logprobs": a.rollout_logprobs, "entropy_coef": a.entropy_coef,
+                               "log_entropy": a.log_entropy,
+                               "generation_params": {"temperature": GEN_TEMPERATURE, "do_sample": True, "top_p": 0.9}},
+                              algo, None, vocab_size)
+
+
 def ppo_main(a) -> int:
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from distributed_llm_alignment_amd.models import build_model, generate, get_config
     from distributed_llm_alignment_amd.models.reward import RewardModel, ValueModel
     from distributed_llm_alignment_amd.models.tokenizer import ByteTokenizer
-    from distributed_llm_alignment_amd.objectives import (ppo_backward, ppo_loss, ppo_rollout_stats,
-                                                          rollout_logp_grid, rollout_mismatch)
+    from distributed_llm_alignment_amd.objectives import (action_mask, keep_row_grid, ppo_backward, ppo_loss,
+                                                          ppo_rollout_stats, rollout_logp_grid, rollout_mismatch)
     from distributed_llm_alignment_amd.training.train_rlhf import rollout_is_settings, rollout_logprobs_mode
     from distributed_llm_alignment_amd.ops import _ext
     from distributed_llm_alignment_amd.parallel.data_parallel import DataParallelEngine
@@ -370,6 +392,7 @@ def ppo_main(a) -> int:
     lp_mode, mism = rollout_logprobs_mode({"rollout_logprobs": a.rollout_logprobs}, "ppo"), {}
     is_kw = _is_kw(a, rollout_is_settings) if lp_mode == "correct" else {}
     lp_temp = _lp_temp(a, "ppo")
+    keep_on = _keep_on(a, "ppo", cfg.vocab_size)
 
     def step(record):
         ids = torch.randint(3, cfg.vocab_size, (a.batch, a.prompt), device=dev, generator=g)
@@ -379,7 +402,11 @@ def ppo_main(a) -> int:
         seqs, mask, *rlp = generate(pol, ids, am, max_new_tokens=a.new, do_sample=True, temperature=GEN_TEMPERATURE,
                                     top_p=0.9, eos_token_id=-1, return_mask=True, seed=3,
                                     weight_dtype=a.rollout_dtype, return_logprobs=lp_mode != "off",
-                                    logprob_temperature=lp_temp if lp_mode != "off" and lp_temp != 1.0 else None)
+                                    logprob_temperature=lp_temp if lp_mode != "off" and lp_temp != 1.0 else None,
+                                    **({"return_keep_mask": True} if keep_on else {}))
+        keep = rlp.pop() if keep_on else None
+        kkw = {"keep": keep, "keep_rows": keep_row_grid(action_mask(mask, a.prompt), a.prompt, keep.shape[1])} \
+            if keep_on else {}
         rlp = rollout_logp_grid(rlp[0], a.prompt, seqs.shape[1]) if rlp else None
         t1 = sync()
         phase_peak("generate")
@@ -391,7 +418,7 @@ def ppo_main(a) -> int:
         stats = ppo_rollout_stats(pol, ref, critic, seqs, mask, a.prompt, scores, 0.05, 1.0, 0.95,
                                   old_logp=rlp if lp_mode == "old" else None,
                                   rollout_logp=rlp if lp_mode == "correct" else None, **is_kw,
-                                  temperature=lp_temp)
+                                  temperature=lp_temp, **kkw)
         if lp_mode in ("monitor", "correct"):
             mism.update(rollout_mismatch(rlp, stats["old_logp"], stats["act"]))
             mism.update(stats.get("rollout_is", {}))
@@ -404,9 +431,9 @@ def ppo_main(a) -> int:
         critic.train()
         for _ in range(a.ppo_epochs):
             for lo, hi in bounds:
-                mb = {k: v[lo:hi] for k, v in stats.items() if k in ("old_logp", "values", "advantages", "returns", "act", "is_weight")}
+                mb = {k: v[lo:hi] for k, v in stats.items() if k in ("old_logp", "values", "advantages", "returns", "act", "is_weight", "keep_rows")}
                 loss, m = ppo_loss(pol, critic, seqs[lo:hi], mask[lo:hi], mb, 0.2, 0.2, 0.1, a.entropy_coef,
-                                   a.log_entropy, temperature=lp_temp)
+                                   a.log_entropy, temperature=lp_temp, keep=keep)
                 ppo_backward(loss)
                 eng.step()
                 ceng.step()
@@ -433,7 +460,7 @@ def ppo_main(a) -> int:
         health["entropy"] = round(float(m["entropy"]), 5)
     health.update({k: float(v) for k, v in mism.items()})  # the last step's
     print(json.dumps({"bench": "ppo_step", "model": cfg.name, "rollouts_per_step": a.batch,
-                      "rollout_logprobs": lp_mode, "logprob_temperature": lp_temp,
+                      "rollout_logprobs": lp_mode, "logprob_temperature": lp_temp, "keep_sampling_mask": keep_on,
                       "entropy_coef": a.entropy_coef, "log_entropy": a.log_entropy,
                       "rollout_dtype": a.rollout_dtype, "frozen_fp8": a.frozen_fp8,
                       "zero_shape": a.zero_shape, "ppo_epochs": a.ppo_epochs, "minibatches": a.minibatches,
@@ -451,7 +478,8 @@ def grpo_main(a) -> int:
     from distributed_llm_alignment_amd.models import build_model, generate, get_config
     from distributed_llm_alignment_amd.models.reward import RewardModel
     from distributed_llm_alignment_amd.models.tokenizer import ByteTokenizer
-    from distributed_llm_alignment_amd.objectives import grpo_rollout_stats, rollout_logp_grid, rollout_mismatch
+    from distributed_llm_alignment_amd.objectives import (action_mask, grpo_rollout_stats, keep_fraction,
+                                                          keep_row_grid, rollout_logp_grid, rollout_mismatch)
     from distributed_llm_alignment_amd.ops import _ext
     from distributed_llm_alignment_amd.parallel.data_parallel import DataParallelEngine
     from distributed_llm_alignment_amd.training.handoff import RewardHandoff
@@ -498,6 +526,7 @@ def grpo_main(a) -> int:
     lp_mode, mism = rollout_logprobs_mode({"rollout_logprobs": a.rollout_logprobs}, "grpo"), {}
     is_kw = _is_kw(a, rollout_is_settings) if lp_mode == "correct" else {}
     lp_temp = _lp_temp(a, "grpo")
+    keep_on = _keep_on(a, "grpo", cfg.vocab_size)
 
     def sync():
         torch.cuda.synchronize()
@@ -518,7 +547,11 @@ def grpo_main(a) -> int:
                                     weight_dtype=a.rollout_dtype, num_return_sequences=G,
                                     share_prefill=bool(a.share_prefill),
                                     group_attention=bool(a.group_attention), return_logprobs=lp_mode != "off",
-                                    logprob_temperature=lp_temp if lp_mode != "off" and lp_temp != 1.0 else None)
+                                    logprob_temperature=lp_temp if lp_mode != "off" and lp_temp != 1.0 else None,
+                                    **({"return_keep_mask": True} if keep_on else {}))
+        keep = rlp.pop() if keep_on else None
+        kkw = {"keep": keep, "keep_rows": keep_row_grid(action_mask(mask, a.prompt), a.prompt, keep.shape[1])} \
+            if keep_on else {}
         rlp = rollout_logp_grid(rlp[0], a.prompt, seqs.shape[1]) if rlp else None
         t1 = sync()
         phase_peak("generate")
@@ -531,16 +564,23 @@ def grpo_main(a) -> int:
         stats = grpo_rollout_stats(pol, ref, seqs, mask, a.prompt, scores, G, a.kl_coef, True,
                                    lp_mode == "monitor", old_logp=rlp if lp_mode == "old" else None,
                                    rollout_logp=rlp if lp_mode == "correct" else None, **is_kw,
-                                   temperature=lp_temp)
+                                   temperature=lp_temp, **kkw)
         if lp_mode in ("monitor", "correct"):
             mism.update(rollout_mismatch(rlp, stats["old_logp"], stats["act"]))
             mism.update(stats.get("rollout_is", {}))
+            if keep_on and not record:
+                # warm-up steps only (never inside a timed step): the kept share of the tempered mass, from one
+                # more no-grad forward for the full-vocabulary log-probs the step itself does not form
+                with torch.no_grad():
+                    full = pol.token_logprobs(seqs, mask, temperature=lp_temp)
+                mism["keep_fraction"] = keep_fraction(full, stats["old_logp"], stats["act"])
+                del full
             stats["old_logp"] = None  # the update stays the on-policy one (correct: only w carries the gap)
         t3 = sync()
         phase_peak("stats")
         pol.train()
         loss, m = grpo_update(pol, eng, seqs, mask, stats, 0.2, None, a.kl_coef, a.loss_type, a.new, a.micro,
-                              a.entropy_coef, a.log_entropy, lp_temp)
+                              a.entropy_coef, a.log_entropy, lp_temp, keep=keep)
         eng.step()
         t4 = sync()
         phase_peak("update")
@@ -564,7 +604,7 @@ def grpo_main(a) -> int:
         health["entropy"] = round(float(m["entropy"]), 5)
     health.update({k: float(v) for k, v in mism.items()})  # the last step's
     print(json.dumps({"bench": "grpo_step", "model": cfg.name, "rollouts_per_step": a.batch, "group": G,
-                      "rollout_logprobs": lp_mode, "logprob_temperature": lp_temp,
+                      "rollout_logprobs": lp_mode, "logprob_temperature": lp_temp, "keep_sampling_mask": keep_on,
                       "share_prefill": bool(a.share_prefill), "group_attention": bool(a.group_attention),
                       "loss_type": a.loss_type, "kl_coef": a.kl_coef,
                       "entropy_coef": a.entropy_coef, "log_entropy": a.log_entropy,
