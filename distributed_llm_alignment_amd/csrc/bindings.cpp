@@ -19,6 +19,7 @@
 
 #include "attn_params.h"
 #include "bind_util.h"
+#include "gjsd_params.h"
 
 namespace dla {
 
@@ -980,6 +981,92 @@ at::Tensor ensemble_kl(at::Tensor& s_logits, const at::Tensor& t_logits, const a
   return kl;
 }
 
+// ================================= JSD(beta) distillation (GKD) ===============================
+// s [N, V] bf16, t [K, N, V] bf16 (last dim contiguous, any row strides), row_mask [N] float or
+// uint8 (0: the row is skipped and every output of it is 0). inv_temp = float(1.0 / temperature)
+// formed by the caller. See gjsd.hip for the formulas.
+static GjsdParams gjsd_params(const at::Tensor& s, const at::Tensor& t, const c10::optional<at::Tensor>& row_mask,
+                              double beta, double inv_temp) {
+  check_bf16(s, "s");
+  check_bf16(t, "t");
+  same_device(s, t);
+  TORCH_CHECK(s.dim() == 2 && t.dim() == 3 && t.size(1) == s.size(0) && t.size(2) == s.size(1),
+              "gjsd: s [N, V] and t [K, N, V] (shared vocabulary required)");
+  TORCH_CHECK(s.size(1) >= 1 && s.size(1) < (int64_t(1) << 31) && s.size(0) < (int64_t(1) << 31), "gjsd: N, V range");
+  TORCH_CHECK(t.size(0) >= 1 && t.size(0) <= kGjsdMaxTeachers, "gjsd: 1 to ", kGjsdMaxTeachers, " teachers, got ",
+              t.size(0));
+  TORCH_CHECK((s.size(1) == 1 || s.stride(1) == 1) && (t.size(2) == 1 || t.stride(2) == 1) && s.stride(0) >= s.size(1) &&
+                  t.stride(1) >= t.size(2) && t.stride(0) >= 0,
+              "gjsd: logits must be row-major with non-overlapping rows");
+  TORCH_CHECK(beta >= 0.0 && beta <= 1.0, "gjsd: beta must be in [0, 1], got ", beta);
+  GjsdParams p{};
+  p.it = static_cast<float>(inv_temp);
+  TORCH_CHECK(std::isfinite(p.it) && p.it > 0.f, "inv_temp must be finite and > 0, got ", inv_temp);
+  p.s = cbp(s);
+  p.t = cbp(t);
+  p.s_ld = s.stride(0);
+  p.t_sk = t.stride(0);
+  p.t_ld = t.stride(1);
+  p.N = s.size(0);
+  p.K = static_cast<int>(t.size(0));
+  p.V = static_cast<int>(s.size(1));
+  if (row_mask && row_mask->defined()) {
+    const at::Tensor& m = *row_mask;
+    check_cuda(m, "row_mask");
+    same_device(s, m);
+    TORCH_CHECK(m.scalar_type() == at::kFloat || m.scalar_type() == at::kByte, "row_mask must be float32 or uint8");
+    TORCH_CHECK(m.dim() == 1 && m.size(0) == p.N && m.is_contiguous(), "row_mask [N] contiguous");
+    p.mask = m.data_ptr();
+    p.mask_u8 = m.scalar_type() == at::kByte;
+  }
+  p.beta = static_cast<float>(beta);
+  p.c = beta == 1.0 ? 1.f : static_cast<float>(1.0 - beta);
+  p.lb = beta > 0.0 ? static_cast<float>(std::log(beta)) : 0.f;
+  p.l1b = beta < 1.0 ? static_cast<float>(std::log1p(-beta)) : 0.f;
+  p.logK = static_cast<float>(std::log(static_cast<double>(p.K)));
+  p.invK = static_cast<float>(1.0 / static_cast<double>(p.K));
+  return p;
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> gjsd_fwd(const at::Tensor& s, const at::Tensor& t,
+                                                                    const c10::optional<at::Tensor>& row_mask,
+                                                                    double beta, double inv_temp) {
+  GjsdParams p = gjsd_params(s, t, row_mask, beta, inv_temp);
+  c10::hip::HIPGuardMasqueradingAsCUDA g(s.device());
+  const auto f32 = s.options().dtype(at::kFloat);
+  auto loss = at::empty({p.N}, f32), aux = at::empty({p.N}, f32), s_lse = at::empty({p.N}, f32);
+  auto t_lse = at::empty({static_cast<int64_t>(p.K), p.N}, f32);
+  p.loss = loss.data_ptr<float>();
+  p.aux = aux.data_ptr<float>();
+  p.s_lse = s_lse.data_ptr<float>();
+  p.t_lse = t_lse.data_ptr<float>();
+  launch_gjsd(p, false, cur_stream(s));
+  return {loss, aux, s_lse, t_lse};
+}
+
+at::Tensor gjsd_bwd(const at::Tensor& s, const at::Tensor& t, const at::Tensor& s_lse, const at::Tensor& t_lse,
+                    const at::Tensor& aux, const c10::optional<at::Tensor>& row_mask, const at::Tensor& grad,
+                    double beta, double inv_temp) {
+  GjsdParams p = gjsd_params(s, t, row_mask, beta, inv_temp);
+  for (const at::Tensor* x : {&s_lse, &t_lse, &aux, &grad}) {
+    check_f32(*x, "s_lse / t_lse / aux / grad");
+    same_device(s, *x);
+    TORCH_CHECK(x->is_contiguous(), "gjsd_bwd: row scalars must be contiguous");
+  }
+  TORCH_CHECK(s_lse.numel() == p.N && aux.numel() == p.N && grad.numel() == p.N &&
+                  t_lse.numel() == static_cast<int64_t>(p.K) * p.N,
+              "gjsd_bwd: s_lse / aux / grad [N], t_lse [K, N]");
+  c10::hip::HIPGuardMasqueradingAsCUDA g(s.device());
+  auto ds = at::empty({p.N, static_cast<int64_t>(p.V)}, s.options());
+  p.s_lse = s_lse.data_ptr<float>();
+  p.t_lse = t_lse.data_ptr<float>();
+  p.aux = aux.data_ptr<float>();
+  p.g = grad.data_ptr<float>();
+  p.ds = bp(ds);
+  launch_gjsd(p, true, cur_stream(s));
+  return ds;
+}
+
 // ================================= sequence objectives ========================================
 std::tuple<at::Tensor, at::Tensor> seq_reduce(const at::Tensor& lp, const at::Tensor& mask) {
   check_f32(lp, "lp");
@@ -1387,6 +1474,8 @@ TORCH_LIBRARY(dla, m) {
   m.def("logprob_entropy_bwd_t_temp(Tensor(a!) logits, Tensor targets, Tensor lse, Tensor ent, Tensor grad_logp, Tensor grad_ent, float inv_temp, int vocab_offset=0) -> Tensor");
   m.def("row_lse(Tensor logits) -> Tensor");
   m.def("ensemble_kl(Tensor(a!) s_logits, Tensor t_logits, Tensor s_lse, Tensor t_lse, Tensor? grad, bool write_grad) -> Tensor");
+  m.def("gjsd_fwd(Tensor s, Tensor t, Tensor? row_mask, float beta, float inv_temp) -> (Tensor, Tensor, Tensor, Tensor)");
+  m.def("gjsd_bwd(Tensor s, Tensor t, Tensor s_lse, Tensor t_lse, Tensor aux, Tensor? row_mask, Tensor grad, float beta, float inv_temp) -> Tensor");
   m.def("seq_reduce(Tensor lp, Tensor mask) -> (Tensor, Tensor)");
   m.def("seq_expand_grad(Tensor coef, Tensor mask, Tensor cnt, bool mean) -> Tensor");
   m.def("dpo_loss(Tensor pol, Tensor ref, float beta, float label_smoothing) -> (Tensor, Tensor, Tensor, Tensor)");
@@ -1437,6 +1526,8 @@ TORCH_LIBRARY_IMPL(dla, CUDA, m) {
   m.impl("logprob_entropy_bwd_t_temp", &dla::logprob_entropy_bwd_t_temp);
   m.impl("row_lse", &dla::row_lse);
   m.impl("ensemble_kl", &dla::ensemble_kl);
+  m.impl("gjsd_fwd", &dla::gjsd_fwd);
+  m.impl("gjsd_bwd", &dla::gjsd_bwd);
   m.impl("seq_reduce", &dla::seq_reduce);
   m.impl("seq_expand_grad", &dla::seq_expand_grad);
   m.impl("dpo_loss", &dla::dpo_loss);

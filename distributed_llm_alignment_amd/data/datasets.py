@@ -194,14 +194,26 @@ class PreferenceDataset(Dataset):
 
 
 class TeacherRolloutDataset(Dataset):
-    """Teacher rollouts for distillation (reference datasets.py:155-196)."""
+    """Teacher rollouts for distillation (reference datasets.py:155-196).
+
+    `with_prompt=True` (on-policy distillation): every item also carries `index` (the record's
+    position, to look its prompt up again) and `prompt_len`, both 0-d int64 (`pad_batch` stacks
+    them). `prompt_len` is the token count of f"{prompt}\\n\\n" under the same tokenizer settings,
+    clipped to len(ids) - 1 so at least the last position stays a response position; where the
+    tokenizer merges characters across the prompt / response boundary the count is off by the merged
+    token, which is tolerated. With `False` the items are unchanged, key for key."""
 
     def __init__(self, path=None, tokenizer=None, max_length: int = 2048,
-                 records: Optional[List[Dict[str, Any]]] = None):
+                 records: Optional[List[Dict[str, Any]]] = None, with_prompt: bool = False):
         self.records = records if records is not None else read_jsonl(path)
         self.tokenizer = tokenizer
         self.max_length = max_length
         self.eos = _eos(tokenizer)
+        self.with_prompt = bool(with_prompt)
+
+    def prompt_text(self, idx: int) -> str:
+        """The text a rollout of record `idx` starts from: the prompt part of the item's text."""
+        return f"{str(self.records[idx]['prompt']).strip()}\n\n"
 
     def __len__(self) -> int:
         return len(self.records)
@@ -214,8 +226,14 @@ class TeacherRolloutDataset(Dataset):
         enc = self.tokenizer(f"{prompt}\n\n{response}{self.eos}", truncation=True,
                              max_length=self.max_length, padding=False)
         ids = _ids(enc)
-        return {"input_ids": ids, "attention_mask": torch.ones_like(ids), "labels": ids.clone(),
-                "reward": torch.tensor(reward, dtype=torch.float32)}
+        out = {"input_ids": ids, "attention_mask": torch.ones_like(ids), "labels": ids.clone(),
+               "reward": torch.tensor(reward, dtype=torch.float32)}
+        if self.with_prompt:
+            penc = self.tokenizer(self.prompt_text(idx), truncation=True, max_length=self.max_length,
+                                  padding=False)
+            out["index"] = torch.tensor(int(idx), dtype=torch.long)
+            out["prompt_len"] = torch.tensor(max(0, min(len(_ids(penc)), len(ids) - 1)), dtype=torch.long)
+        return out
 
     def collate(self, batch):
         return pad_batch(batch, _pad_id(self.tokenizer))

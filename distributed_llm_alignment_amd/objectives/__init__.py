@@ -12,6 +12,8 @@ benchmarks and tests share one implementation.
                    advantages, token-level clipped surrogate + k3 KL to the reference) for
                    `ppo.algorithm: grpo` (not in the reference)
   distill_loss     reference train_distill.py:125-147 (CE on rollouts or ensemble forward KL)
+  gkd_loss         on-policy distillation (GKD): JSD(beta) at a temperature over response positions,
+                   on dataset rows or on sequences the student sampled (not in the reference)
 """
 from __future__ import annotations
 
@@ -483,3 +485,75 @@ def distill_loss(student, teachers: Sequence, batch, use_kl: bool):
         return (kl * m).sum() / m.sum()
     m = sp.local(sp.pad(mask.float(), 0))  # sequence parallel: this rank's token slice
     return sp.reduce((kl * m).sum()) / sp.reduce(m.sum())
+
+
+# ------------------------------------------------------------ on-policy distillation (GKD)
+def _gkd_chunk(student, teachers, hs_c, ths_c, mask_c, beta, temperature):
+    s_logits = student.logits(hs_c)
+    with torch.no_grad():
+        t_logits = torch.stack([t.logits(h) for t, h in zip(teachers, ths_c)])
+    return ops.generalized_jsd(s_logits, t_logits, beta=beta, temperature=temperature, row_mask=mask_c)
+
+
+def chunked_gkd(student, teachers: Sequence, hs: torch.Tensor, ths: Sequence[torch.Tensor], beta: float,
+                temperature: float, row_mask: Optional[torch.Tensor], chunk: Optional[int] = None) -> torch.Tensor:
+    """Per-row JSD(beta) (`ops.generalized_jsd`) from final hidden rows, in `chunked_ensemble_kl`'s
+    structure: chunks of KL_CHUNK_TOKENS rows, each chunk's logits produced, reduced and dropped,
+    recomputed in the backward (activation checkpoint); the `row_mask` [N] slice travels with its
+    rows (masked rows: exactly 0, logits not read)."""
+    from torch.utils.checkpoint import checkpoint
+
+    chunk = int(chunk or KL_CHUNK_TOKENS)
+    N = hs.shape[0]
+    outs = []
+    for i in range(0, N, chunk):
+        hs_c = hs[i:i + chunk]
+        ths_c = [h[i:i + chunk] for h in ths]
+        m_c = None if row_mask is None else row_mask[i:i + chunk]
+        if torch.is_grad_enabled() and hs.requires_grad and N > chunk:
+            outs.append(checkpoint(_gkd_chunk, student, teachers, hs_c, ths_c, m_c, beta, temperature,
+                                   use_reentrant=False))
+        else:
+            outs.append(_gkd_chunk(student, teachers, hs_c, ths_c, m_c, beta, temperature))
+    return outs[0] if len(outs) == 1 else torch.cat(outs)
+
+
+def gkd_position_mask(attention_mask: torch.Tensor, prompt_len) -> torch.Tensor:
+    """[S, T] float: 1 at position t of row s when token t + 1 is a real response token, i.e.
+    first_real + prompt_len_s - 1 <= t <= last_real - 1 (first_real / last_real: the row's first and
+    last attended positions; `prompt_len`, an int or [S], counts the row's real prompt tokens). The
+    same rule serves right-padded dataset rows (first_real = 0) and left-padded generated rows. A row
+    with no response token, or with nothing attended, is all 0."""
+    am = attention_mask != 0
+    S, T = am.shape
+    idx = torch.arange(T, device=am.device).expand(S, T)
+    first = torch.where(am, idx, torch.full_like(idx, T)).min(1).values
+    last = torch.where(am, idx, torch.full_like(idx, -1)).max(1).values
+    pl = torch.as_tensor(prompt_len, device=am.device, dtype=idx.dtype)
+    lo = (first + pl - 1).clamp(min=0).unsqueeze(1)
+    return ((idx >= lo) & (idx <= (last - 1).unsqueeze(1))).float()
+
+
+def gkd_loss(student, teachers: Sequence, input_ids: torch.Tensor, attention_mask: torch.Tensor, prompt_len,
+             beta: float, temperature: float) -> torch.Tensor:
+    """Generalised knowledge distillation on one micro-batch: JSD(beta) at `temperature` between the
+    student's and the teachers' (mean) next-token distributions, over the positions that predict a
+    response token (`gkd_position_mask`): sum(mask * L) / max(sum(mask), 1)."""
+    if not teachers:
+        raise ValueError("GKD needs at least one teacher")
+    for m in (student, *teachers):
+        if getattr(m, "vocab_parallel", None) is not None:
+            raise ValueError("GKD does not support a vocab-parallel LM head (tensor parallelism)")
+        if getattr(m, "sp", None) is not None:
+            raise ValueError("GKD does not support sequence parallelism")
+    for t in teachers:
+        if t.cfg.vocab_size != student.cfg.vocab_size:
+            raise ValueError("GKD requires teacher and student to share a vocabulary")
+    hs = student(input_ids, attention_mask)
+    with torch.no_grad():
+        ths = [t(input_ids, attention_mask) for t in teachers]
+    S, T = hs.shape[0], hs.shape[1]
+    mask = gkd_position_mask(attention_mask, prompt_len)
+    L = chunked_gkd(student, teachers, hs.reshape(S * T, -1), [h.reshape(S * T, -1) for h in ths],
+                    beta, temperature, mask.reshape(-1)).view(S, T)
+    return (mask * L).sum() / mask.sum().clamp(min=1)

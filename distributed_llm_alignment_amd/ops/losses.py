@@ -156,6 +156,122 @@ def ensemble_kl(student_logits: torch.Tensor, teacher_logits: torch.Tensor) -> t
     return F.kl_div(logq, pbar, reduction="none").sum(-1)
 
 
+# ------------------------------------------------- generalised JSD(beta) distillation (GKD)
+def _inv_temp(temperature: float) -> float:
+    """float(1 / temperature): the divide in double, rounded once to fp32 (as the `*_temp` ops)."""
+    t = float(temperature)
+    if not (math.isfinite(t) and t > 0.0):
+        raise ValueError(f"temperature must be finite and > 0, got {temperature!r}")
+    return torch.tensor(1.0 / t, dtype=torch.float64).float().item()
+
+
+def _check_beta(beta: float) -> float:
+    beta = float(beta)
+    if not 0.0 <= beta <= 1.0:
+        raise ValueError(f"beta must be in [0, 1], got {beta!r}")
+    return beta
+
+
+class _GJSDFn(torch.autograd.Function):
+    """Per-row JSD(beta) on the HIP kernels: one launch forward, one backward; the gradient goes
+    into a buffer of its own (the saved logits are only read)."""
+
+    @staticmethod
+    def forward(ctx, s_logits, t_logits, row_mask, beta, inv_temp):
+        loss, aux, s_lse, t_lse = _ext.require().gjsd_fwd(s_logits, t_logits, row_mask, beta, inv_temp)
+        ctx.save_for_backward(s_logits, t_logits, s_lse, t_lse, aux, row_mask)
+        ctx.beta, ctx.inv_temp = beta, inv_temp
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        s_logits, t_logits, s_lse, t_lse, aux, row_mask = ctx.saved_tensors
+        ds = _ext.require().gjsd_bwd(s_logits, t_logits, s_lse, t_lse, aux, row_mask, g.float().contiguous(),
+                                     ctx.beta, ctx.inv_temp)
+        return ds, None, None, None, None
+
+
+def _gjsd_cpu(s: torch.Tensor, t: torch.Tensor, beta: float, inv_temp: float,
+              row_mask: Optional[torch.Tensor]) -> torch.Tensor:
+    i = torch.tensor(inv_temp, dtype=torch.float32)
+    lq = F.log_softmax(s.float() * i, dim=-1)
+    lpk = F.log_softmax(t.detach().float() * i, dim=-1)
+    K = lpk.shape[0]
+    lp = lpk[0] if K == 1 else torch.logsumexp(lpk, 0) - math.log(K)
+    q_dead, p_dead = lq == -math.inf, lp == -math.inf
+    zero = torch.zeros_like(lp)
+    inf = torch.full_like(lp, math.inf)
+    # a -inf entry is replaced BEFORE it meets a product: its term is an exact 0 and autograd never
+    # sees 0 * inf there
+    lqs, lps = torch.where(q_dead, zero, lq), torch.where(p_dead, zero, lp)
+
+    def p_sum(lm, m_dead):  # sum_v p (log p - log m); +inf where m = 0 < p
+        term = torch.where(m_dead, inf, lps.exp() * (lps - torch.where(m_dead, zero, lm)))
+        return torch.where(p_dead, zero, term).sum(-1)
+
+    def q_sum(lm, m_dead):
+        term = torch.where(m_dead, inf, lqs.exp() * (lqs - torch.where(m_dead, zero, lm)))
+        return torch.where(q_dead, zero, term).sum(-1)
+
+    if beta == 0.0:
+        loss = p_sum(lq, q_dead)
+    elif beta == 1.0:
+        loss = q_sum(lp, p_dead)
+    else:
+        both = q_dead & p_dead  # m = 0 only there, and there neither sum has a term
+        lm = torch.logaddexp(torch.where(both, zero, lp + math.log(beta)),
+                             torch.where(both, zero, lq + math.log1p(-beta)))
+        never = torch.zeros_like(both)
+        loss = beta * p_sum(lm, never) + (1.0 - beta) * q_sum(lm, never)
+    if row_mask is not None:
+        loss = torch.where(row_mask != 0, loss, torch.zeros_like(loss))
+    return loss
+
+
+def generalized_jsd(student_logits: torch.Tensor, teacher_logits: torch.Tensor, beta: float = 0.5,
+                    temperature: float = 1.0, row_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Per-row generalised Jensen-Shannon divergence JSD(beta) of GKD (Agarwal et al.):
+    student [N, V], teachers [K, N, V] (same vocabulary, K <= 8 on the GPU) -> [N] fp32.
+
+    With i = float(1 / temperature) (divided in double, rounded once to fp32), q = softmax(i s) and
+    p = (1/K) sum_k softmax(i t_k):
+
+        beta = 0      L = sum_v p (log p - log q)                  forward KL (at i = 1: `ensemble_kl`)
+        beta = 1      L = A,  A = sum_v q (log q - log p)          reverse KL
+        0 < beta < 1  m = beta p + (1 - beta) q
+                      L = beta sum_v p (log p - log m) + (1 - beta) A,   A = sum_v q (log q - log m)
+
+        dL/ds_v = i (q_v - p_v)                        beta = 0
+        dL/ds_v = i c q_v (log q_v - log m_v - A)      beta > 0; c = 1 - beta (beta = 1: c = 1, m = p)
+
+    The gradient flows through the student only; teachers are constants. Everything is formed in
+    the log domain (log p = logsumexp_k log p_k - log K, log m = logaddexp), so rows whose student
+    and teachers disagree by hundreds of nats stay finite.
+    Conventions: an entry with q_v = 0 (student logit -inf) adds exactly 0 to A and receives gradient
+    exactly 0; an entry with p_v = 0 adds exactly 0 to the p sums. The mathematically infinite cases,
+    beta = 0 with q_v = 0 < p_v and beta = 1 with p_v = 0 < q_v, return +inf (as `ensemble_kl` does),
+    and the gradient of such a row is unspecified.
+    `row_mask` [N] (fp32 or uint8 on the GPU; any dtype on the CPU): a row with mask 0 has loss and
+    gradient exactly 0 and its logits are never read into a sum (NaN there does not surface on the
+    GPU; the CPU formula masks the value, and its autograd must not be fed NaN logits).
+    GPU: `gjsd_fwd` / `gjsd_bwd` (csrc/gjsd.hip), one launch each, no host sync; the logits may be
+    row-strided views. CPU: the formula above on log_softmax(x.float() * i)."""
+    beta = _check_beta(beta)
+    it = _inv_temp(temperature)
+    if _ext.use_native(student_logits):
+        mask = None
+        if row_mask is not None:
+            mask = row_mask if row_mask.dtype == torch.uint8 else row_mask.float()
+            mask = mask.detach().contiguous()
+        if student_logits.stride(-1) != 1:
+            student_logits = student_logits.contiguous()
+        teacher_logits = teacher_logits.detach()
+        if teacher_logits.stride(-1) != 1:
+            teacher_logits = teacher_logits.contiguous()
+        return _GJSDFn.apply(student_logits, teacher_logits, mask, beta, it)
+    return _gjsd_cpu(student_logits, teacher_logits, beta, it, row_mask)
+
+
 # ------------------------------------------------------------- PPO (actor-critic) objectives
 # Token-level PPO for the north-star "PPO RLHF (actor + critic + reward)" configuration; the
 # reference's sequence-level REINFORCE (train_rlhf.py:149-153, `kl_penalty_pg` above) stays the

@@ -219,6 +219,15 @@ def move_to(batch, device):
     return batch
 
 
+def _tokenize_left(tok, texts, max_len, device):
+    """Left-padded prompt batch for `generate` (RLHF and on-policy distillation rollouts)."""
+    side = getattr(tok, "padding_side", "right")
+    tok.padding_side = "left"
+    enc = tok(texts, return_tensors="pt", padding=True, truncation=True, max_length=max_len)
+    tok.padding_side = side
+    return enc["input_ids"].to(device), enc["attention_mask"].to(device)
+
+
 def _batch_rows(batch) -> int:
     """Samples in a micro-batch: pairs for preference batches, rows otherwise."""
     if isinstance(batch, torch.Tensor):

@@ -111,7 +111,7 @@ from ..parallel.dist import barrier, split_for_rank
 from ..utils.checkpoint import save_state
 from ..utils.config import add_config_args, config_from_args
 from ..utils.logging import RunningLoss
-from .common import make_engine, parallelize, setup
+from .common import _tokenize_left, make_engine, parallelize, setup
 
 
 def parse_args(argv=None) -> argparse.Namespace:
@@ -250,14 +250,6 @@ def rollout_is_settings(ppo: Dict) -> Dict:
     if mode not in ROLLOUT_IS_MODES:
         raise ValueError(f"ppo.rollout_is_mode must be {'|'.join(ROLLOUT_IS_MODES)}, got {mode!r}")
     return {"is_cap": cap, "is_floor": floor, "is_level": level, "is_mode": mode}
-
-
-def _tokenize_left(tok, texts, max_len, device):
-    side = getattr(tok, "padding_side", "right")
-    tok.padding_side = "left"
-    enc = tok(texts, return_tensors="pt", padding=True, truncation=True, max_length=max_len)
-    tok.padding_side = side
-    return enc["input_ids"].to(device), enc["attention_mask"].to(device)
 
 
 def main(argv=None) -> int:
