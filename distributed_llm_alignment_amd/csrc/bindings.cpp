@@ -96,6 +96,9 @@ void launch_grpo_loss(const float*, const float*, const float*, const float*, co
 void launch_grpo_loss_w(const float*, const float*, const float*, const float*, const float*,
                         const float*, const float*, int, int, float, float, float, int, float,
                         float*, float*, float*, float*, hipStream_t);
+void launch_grpo_loss_seq(const float*, const float*, const float*, const float*, const float*,
+                          const float*, const float*, int, int, float, float, float, int, float,
+                          float*, float*, float*, float*, hipStream_t);
 void launch_ppo_policy_loss_w(const float*, const float*, const float*, const float*, const float*,
                               int64_t, float, float*, float*, float*, hipStream_t);
 void launch_rollout_is_weights(const float*, const float*, const float*, int, int, float, float, int,
@@ -1244,10 +1247,11 @@ std::tuple<at::Tensor, at::Tensor> group_advantages(const at::Tensor& scores, in
 // device [1] replacing the final divisor. mode: 0 sequence, 1 token, 2 constant (S * max_len).
 // Returns (loss, dloss/dlp, metrics[4]); no host read of any device value.
 // w: the importance weights of grpo_loss_w (a grid like lp), or nullptr.
+// seq: the sequence-level ratio of grpo_loss_seq (two more rows of partials).
 static std::tuple<at::Tensor, at::Tensor, at::Tensor> grpo_loss_impl(
     const at::Tensor& lp, const at::Tensor& old, const at::Tensor& ref, const at::Tensor& adv,
     const at::Tensor& mask, const at::Tensor* w, const c10::optional<at::Tensor>& denom,
-    double clip_low, double clip_high, double beta, int64_t mode, double max_len) {
+    double clip_low, double clip_high, double beta, int64_t mode, double max_len, bool seq = false) {
   check_f32(lp, "lp");
   TORCH_CHECK(lp.dim() == 2 && lp.is_contiguous(), "lp [S, T] contiguous");
   check_grid(old, lp, "old");
@@ -1276,9 +1280,16 @@ static std::tuple<at::Tensor, at::Tensor, at::Tensor> grpo_loss_impl(
   auto loss = at::empty({}, opt);
   auto dlp = at::empty_like(lp);
   auto metrics = at::empty({4}, opt);
-  auto part = at::empty({5, S}, opt);
+  auto part = at::empty({seq ? 7 : 5, S}, opt);
   const float lo = static_cast<float>(1.0 - clip_low), hi = static_cast<float>(1.0 + clip_high);
-  if (w != nullptr)
+  if (seq)
+    launch_grpo_loss_seq(lp.data_ptr<float>(), old.data_ptr<float>(), ref.data_ptr<float>(),
+                         adv.data_ptr<float>(), mask.data_ptr<float>(),
+                         w != nullptr ? w->data_ptr<float>() : nullptr, dn, S, T, lo, hi,
+                         static_cast<float>(beta), static_cast<int>(mode), static_cast<float>(max_len),
+                         part.data_ptr<float>(), loss.data_ptr<float>(), dlp.data_ptr<float>(),
+                         metrics.data_ptr<float>(), cur_stream(lp));
+  else if (w != nullptr)
     launch_grpo_loss_w(lp.data_ptr<float>(), old.data_ptr<float>(), ref.data_ptr<float>(),
                        adv.data_ptr<float>(), mask.data_ptr<float>(), w->data_ptr<float>(), dn, S, T,
                        lo, hi, static_cast<float>(beta), static_cast<int>(mode),
@@ -1308,6 +1319,15 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> grpo_loss_w(
     double clip_low, double clip_high, double beta, int64_t mode, double max_len) {
   return grpo_loss_impl(lp, old, ref, adv, mask, &w, denom, clip_low, clip_high, beta, mode,
                         max_len);
+}
+
+// grpo_loss with the length-normalised sequence-level ratio (GSPO); w as in grpo_loss_w, optional.
+std::tuple<at::Tensor, at::Tensor, at::Tensor> grpo_loss_seq(
+    const at::Tensor& lp, const at::Tensor& old, const at::Tensor& ref, const at::Tensor& adv,
+    const at::Tensor& mask, const c10::optional<at::Tensor>& w, const c10::optional<at::Tensor>& denom,
+    double clip_low, double clip_high, double beta, int64_t mode, double max_len) {
+  return grpo_loss_impl(lp, old, ref, adv, mask, w.has_value() ? &*w : nullptr, denom, clip_low,
+                        clip_high, beta, mode, max_len, true);
 }
 
 // trainer_lp / rollout_lp / mask: [S, T] fp32 grids. level: 0 token, 1 sequence (length-normalised);
@@ -1486,6 +1506,7 @@ TORCH_LIBRARY(dla, m) {
   m.def("group_advantages(Tensor scores, int G, bool scale_std, float eps) -> (Tensor, Tensor)");
   m.def("grpo_loss(Tensor lp, Tensor old, Tensor ref, Tensor adv, Tensor mask, Tensor? denom, float clip_low, float clip_high, float beta, int mode, float max_len) -> (Tensor, Tensor, Tensor)");
   m.def("grpo_loss_w(Tensor lp, Tensor old, Tensor ref, Tensor adv, Tensor mask, Tensor w, Tensor? denom, float clip_low, float clip_high, float beta, int mode, float max_len) -> (Tensor, Tensor, Tensor)");
+  m.def("grpo_loss_seq(Tensor lp, Tensor old, Tensor ref, Tensor adv, Tensor mask, Tensor? w, Tensor? denom, float clip_low, float clip_high, float beta, int mode, float max_len) -> (Tensor, Tensor, Tensor)");
   m.def("ppo_policy_loss_w(Tensor lp, Tensor old, Tensor adv, Tensor mask, Tensor w, float eps) -> (Tensor, Tensor, Tensor)");
   m.def("rollout_is_weights(Tensor trainer_lp, Tensor rollout_lp, Tensor mask, float cap, float floor, int level, int mode) -> (Tensor, Tensor)");
   m.def("kl_penalty_pg(Tensor lp, Tensor lr, Tensor reward, float kl_coef) -> (Tensor, Tensor, Tensor, Tensor)");
@@ -1539,6 +1560,7 @@ TORCH_LIBRARY_IMPL(dla, CUDA, m) {
   m.impl("group_advantages", &dla::group_advantages);
   m.impl("grpo_loss", &dla::grpo_loss);
   m.impl("grpo_loss_w", &dla::grpo_loss_w);
+  m.impl("grpo_loss_seq", &dla::grpo_loss_seq);
   m.impl("ppo_policy_loss_w", &dla::ppo_policy_loss_w);
   m.impl("rollout_is_weights", &dla::rollout_is_weights);
   m.impl("adamw_step", &dla::adamw_step);

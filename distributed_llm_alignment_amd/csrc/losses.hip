@@ -12,6 +12,7 @@
 //   group_advantages / grpo_loss : critic-free group-relative policy optimisation (below)
 //   rollout_is_weights / grpo_loss_w / ppo_policy_loss_w : truncated importance weights for the
 //                     rollout engine / trainer mismatch and the surrogates that take them (below)
+//   grpo_loss_seq   : GSPO, the GRPO loss with the length-normalised sequence-level ratio (below)
 // Batch dimensions here are small (pairs per micro-batch), so each loss is a single
 // 256-thread block; the point is fusing fwd+bwd+metrics into one launch with no host sync.
 #include "common.h"
@@ -370,7 +371,15 @@ __device__ __forceinline__ GrpoTok grpo_token(float lp, float old, float ref, fl
 
 constexpr int kGrpoThreads = 256;
 
-template <bool W>
+// SEQ (grpo_loss_seq, GSPO): the ratio is the row's length-normalised one and every action token of
+// the row carries the row's surrogate; the k3 term stays per token.
+//   l_s = sum_{t: m != 0} d / max(c_s, 1); sr_s = exp(l_s)  (c_s = 0: l_s = 0, sr_s = 1)
+//   pg_s = max(-A sr_s, -A clamp(sr_s, lo, hi)); per = w pg_s + beta * k3
+// The partials keep their meaning with rho -> sr_s (the two metric sums are c_s times the row's
+// value) and two more rows follow them: part[5 S + s] = l_s, which launch 2 reads back so that
+// both launches decide the clip on the same bits, and with W part[6 S + s] = sum m w. Entries
+// outside the mask are never read into a sum: NaN or junk there reaches no output.
+template <bool W, bool SEQ = false>
 __global__ __launch_bounds__(kGrpoThreads) void grpo_partials_kernel(
     const float* __restrict__ lp, const float* __restrict__ old, const float* __restrict__ ref,
     const float* __restrict__ adv, const float* __restrict__ m, int S, int T, float lo, float hi,
@@ -379,6 +388,50 @@ __global__ __launch_bounds__(kGrpoThreads) void grpo_partials_kernel(
   const int s = blockIdx.x;
   const int64_t base = static_cast<int64_t>(s) * T;
   const float a = adv[s];
+  if constexpr (SEQ) {
+    float dsum = 0.f, c = 0.f;
+    for (int t = threadIdx.x; t < T; t += kGrpoThreads) {
+      const float mi = m[base + t];
+      if (mi != 0.f) {
+        dsum += lp[base + t] - old[base + t];
+        c += mi;
+      }
+    }
+    dsum = block_sum<kGrpoThreads>(dsum, scratch);
+    c = block_sum<kGrpoThreads>(c, scratch);
+    const float ls = dsum / fmaxf(c, 1.f);
+    const float sr = expf(ls);
+    // A = 0 with sr = inf: l1 is NaN and fmaxf returns l2, as in grpo_token
+    const float pg = fmaxf(-a * sr, -a * fminf(fmaxf(sr, lo), hi));
+    float l = 0.f, klr = 0.f, sw = 0.f;
+    for (int t = threadIdx.x; t < T; t += kGrpoThreads) {
+      const float mi = m[base + t];
+      if (mi != 0.f) {
+        const float dr = ref[base + t] - lp[base + t];
+        const float k3 = expf(dr) - dr - 1.f;
+        float pgw = pg;
+        if constexpr (W) {
+          pgw = is_mul(w[base + t], pg);
+          sw += mi * w[base + t];
+        }
+        l += mi * fmaf(beta, k3, pgw);
+        klr += mi * k3;
+      }
+    }
+    l = block_sum<kGrpoThreads>(l, scratch);
+    klr = block_sum<kGrpoThreads>(klr, scratch);
+    if constexpr (W) sw = block_sum<kGrpoThreads>(sw, scratch);
+    if (threadIdx.x == 0) {
+      part[s] = c;
+      part[S + s] = l;
+      part[2 * S + s] = c * ((sr < lo || sr > hi) ? 1.f : 0.f);
+      part[3 * S + s] = c * ((sr - 1.f) - ls);
+      part[4 * S + s] = klr;
+      part[5 * S + s] = ls;
+      if constexpr (W) part[6 * S + s] = sw;
+    }
+    return;
+  }
   float cnt = 0.f, l = 0.f, cf = 0.f, akl = 0.f, klr = 0.f;
   for (int t = threadIdx.x; t < T; t += kGrpoThreads) {
     const float mi = m[base + t];
@@ -414,7 +467,10 @@ __global__ __launch_bounds__(kGrpoThreads) void grpo_partials_kernel(
 //   dlp = m * w_s * [(l1 >= l2 ? l1 : 0) - beta * (exp(dr) - 1)] / divisor, w_s = 1/max(c_s,1) in mode 0
 //         (W: the importance weight multiplies the (l1 >= l2 ? l1 : 0) term)
 //   metrics: [0] clipfrac, [1] approx KL, [2] k3 KL to the reference (token means), [3] tokens
-template <bool W>
+// SEQ: d sr_s / d lp_u = sr_s m_u / c_s, so with l1, l2 of the row (from part's l_s, not re-reduced)
+//   dlp = m * w_s * [g_s (l1 >= l2 ? l1 : 0) - beta * (exp(dr) - 1)] / divisor
+//   g_s = sum_t m w / max(c_s, 1) with W; without W it is the constant 1 and is not formed
+template <bool W, bool SEQ = false>
 __global__ __launch_bounds__(kGrpoThreads) void grpo_grad_kernel(
     const float* __restrict__ lp, const float* __restrict__ old, const float* __restrict__ ref,
     const float* __restrict__ adv, const float* __restrict__ m, const float* __restrict__ part,
@@ -454,6 +510,20 @@ __global__ __launch_bounds__(kGrpoThreads) void grpo_grad_kernel(
   const int64_t base = static_cast<int64_t>(s) * T;
   const float a = adv[s];
   const float scale = (mode == 0 ? 1.f / fmaxf(part[s], 1.f) : 1.f) / div;
+  if constexpr (SEQ) {
+    const float sr = expf(part[5 * S + s]);
+    const float l1 = -a * sr, l2 = -a * fminf(fmaxf(sr, lo), hi);
+    float pg = l1 >= l2 ? l1 : 0.f;
+    // g_s pg as fma(g_s, pg, 0), rounded on its own: g_s = c_s / c_s = 1 with w = 1 leaves pg exact
+    if constexpr (W) pg = fmaf(part[6 * S + s] / fmaxf(part[s], 1.f), pg, 0.f);
+    for (int t = threadIdx.x; t < T; t += kGrpoThreads) {
+      const float mi = m[base + t];
+      float g = 0.f;
+      if (mi != 0.f) g = mi * scale * (pg - beta * (expf(ref[base + t] - lp[base + t]) - 1.f));
+      dlp[base + t] = g;
+    }
+    return;
+  }
   for (int t = threadIdx.x; t < T; t += kGrpoThreads) {
     const GrpoTok k = grpo_token<W>(lp[base + t], old[base + t], ref[base + t], a, lo, hi, beta, 1.f);
     const float pg = k.l1 >= k.l2 ? k.l1 : 0.f;
@@ -586,6 +656,24 @@ void launch_grpo_loss_w(const float* lp, const float* old, const float* ref, con
                                                           part, w);
   grpo_grad_kernel<true><<<S, kGrpoThreads, 0, st>>>(lp, old, ref, adv, m, part, denom, S, T, lo, hi,
                                                      beta, mode, max_len, loss, dlp, metrics, w);
+}
+// part holds 7 * S floats here (rows 5 and 6: see grpo_partials_kernel); w may be nullptr
+void launch_grpo_loss_seq(const float* lp, const float* old, const float* ref, const float* adv,
+                          const float* m, const float* w, const float* denom, int S, int T, float lo,
+                          float hi, float beta, int mode, float max_len, float* part, float* loss,
+                          float* dlp, float* metrics, hipStream_t st) {
+  if (w != nullptr) {
+    grpo_partials_kernel<true, true><<<S, kGrpoThreads, 0, st>>>(lp, old, ref, adv, m, S, T, lo, hi,
+                                                                  beta, part, w);
+    grpo_grad_kernel<true, true><<<S, kGrpoThreads, 0, st>>>(lp, old, ref, adv, m, part, denom, S, T, lo,
+                                                              hi, beta, mode, max_len, loss, dlp, metrics, w);
+  } else {
+    grpo_partials_kernel<false, true><<<S, kGrpoThreads, 0, st>>>(lp, old, ref, adv, m, S, T, lo, hi,
+                                                                   beta, part, nullptr);
+    grpo_grad_kernel<false, true><<<S, kGrpoThreads, 0, st>>>(lp, old, ref, adv, m, part, denom, S, T, lo,
+                                                               hi, beta, mode, max_len, loss, dlp, metrics,
+                                                               nullptr);
+  }
 }
 void launch_rollout_is_weights(const float* tlp, const float* rlp, const float* m, int S, int T,
                                float cap, float floor_, int level, int mode, float* part, float* w,

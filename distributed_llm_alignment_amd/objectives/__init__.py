@@ -397,20 +397,22 @@ def grpo_loss(policy, seqs, mask, stats: Dict[str, torch.Tensor], clip_low: floa
               max_len: Optional[int] = None, denom: Optional[torch.Tensor] = None,
               entropy_coef: float = 0.0, log_entropy: bool = False, n_act: Optional[torch.Tensor] = None,
               temperature: float = 1.0, keep: Optional[torch.Tensor] = None,
-              keep_rows: Optional[torch.Tensor] = None):
+              keep_rows: Optional[torch.Tensor] = None, importance_level: str = "token"):
     """Token-level clipped surrogate + beta * k3 KL to the reference (HIP fused fwd+bwd) on one
     (micro-)batch of rollouts; `stats` from `grpo_rollout_stats`, sliced to the same rows.
     `entropy_coef` / `log_entropy` / `n_act`: the entropy bonus and metric of
     `token_logprobs_entropy`. `stats["is_weight"]` (optional) weights the policy-gradient term per
     token. `temperature`: the policy's log-probs and entropy at that temperature (as in `stats`).
-    `keep` (+ `keep_rows`, default `stats["keep_rows"]`): the policy's log-probs over the kept sets."""
+    `keep` (+ `keep_rows`, default `stats["keep_rows"]`): the policy's log-probs over the kept sets.
+    `importance_level`: "token", or "sequence" for one length-normalised ratio per rollout (GSPO;
+    `ops.grpo_loss`)."""
     if keep is not None and keep_rows is None:
         keep_rows = stats.get("keep_rows")
     lp, bonus, entropy = token_logprobs_entropy(policy, seqs, mask, stats["act"], entropy_coef, log_entropy,
                                                 n_act, temperature=temperature, keep=keep, keep_rows=keep_rows)
     loss, m = ops.grpo_loss(lp, stats.get("old_logp"), stats.get("ref_logp"), stats["advantages"],
                             stats["act"], clip_low, clip_high, beta, loss_type, max_len, denom,
-                            is_weight=stats.get("is_weight"))
+                            is_weight=stats.get("is_weight"), importance_level=importance_level)
     if bonus is not None:
         loss = loss - bonus
     if entropy is not None:

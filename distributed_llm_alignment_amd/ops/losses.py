@@ -9,7 +9,7 @@ host sync); CPU paths are the literal reference formulas:
   * gae / ppo_policy_loss / ppo_value_loss: token-level actor-critic PPO (north-star config; the
     reference's REINFORCE above stays the default RLHF algorithm)
   * group_advantages / grpo_loss: critic-free group-relative policy optimisation (GRPO and its
-    DAPO / Dr. GRPO normalisations; not in the reference)
+    DAPO / Dr. GRPO normalisations, and GSPO's sequence-level ratio; not in the reference)
   * rollout_is_weights: truncated importance weights for the rollout engine / trainer mismatch,
     taken by grpo_loss / ppo_policy_loss as `is_weight` (not in the reference)
 """
@@ -393,6 +393,9 @@ def ppo_value_loss(values: torch.Tensor, old_values: torch.Tensor, returns: torc
 # plus a k3 KL term to the frozen reference. `loss_type` picks the normalisation: "sequence"
 # (GRPO), "token" (DAPO), "constant" (Dr. GRPO).
 GRPO_LOSS_TYPES = ("sequence", "token", "constant")
+# the importance ratio of the clipped surrogate: per token (GRPO), or one length-normalised ratio
+# per rollout (GSPO, Group Sequence Policy Optimization)
+GRPO_IMPORTANCE_LEVELS = ("token", "sequence")
 
 
 def _ref_group_advantages(scores: torch.Tensor, G: int, scale_std: bool = True, eps: float = 1e-4):
@@ -427,13 +430,19 @@ def group_advantages(scores: torch.Tensor, G: int, scale_std: bool = True, eps: 
 def _ref_grpo_loss(logp, old_logp, ref_logp, adv, mask, clip_low: float = 0.2,
                    clip_high: Optional[float] = None, beta: float = 0.04, loss_type: str = "sequence",
                    max_len: Optional[int] = None, denom: Optional[torch.Tensor] = None,
-                   is_weight: Optional[torch.Tensor] = None):
+                   is_weight: Optional[torch.Tensor] = None, importance_level: str = "token"):
     """The torch formula of `grpo_loss` (any device, differentiable in `logp` through autograd)."""
+    if importance_level not in GRPO_IMPORTANCE_LEVELS:
+        raise ValueError(f"grpo_loss: importance_level must be one of {'|'.join(GRPO_IMPORTANCE_LEVELS)}, "
+                         f"got {importance_level!r}")
     clip_high = clip_low if clip_high is None else clip_high
     lp = logp.float()
     m = mask.detach().float()
     a = adv.detach().float().view(-1, 1)
     old = lp.detach() if old_logp is None else old_logp.detach().float()
+    if importance_level == "sequence":
+        return _ref_gspo_loss(lp, old, ref_logp, a, m, clip_low, clip_high, beta, loss_type, max_len, denom,
+                              is_weight)
     d = lp - old
     rho = torch.exp(d)
     per = torch.maximum(-a * rho, -a * rho.clamp(1 - clip_low, 1 + clip_high))
@@ -460,6 +469,45 @@ def _ref_grpo_loss(logp, old_logp, ref_logp, adv, mask, clip_low: float = 0.2,
         inv = 1.0 / n.clamp(min=1)
         out = ((rho < 1 - clip_low) | (rho > 1 + clip_high)).float()
         metrics = {"clipfrac": (out * m).sum() * inv, "approx_kl": (((rho - 1) - d) * m).sum() * inv,
+                   "kl_ref": (kl * m).sum() * inv, "tokens": n}
+    return loss, metrics
+
+
+def _ref_gspo_loss(lp, old, ref_logp, a, m, clip_low, clip_high, beta, loss_type, max_len, denom, is_weight):
+    """`_ref_grpo_loss` at `importance_level="sequence"` (its prepared operands: fp32 `lp`, detached
+    `old` and `m`, `a` [S, 1]). Entries outside the mask are selected away before any sum, so NaN
+    or junk there reaches neither an output nor the gradient. Precondition: exp(l_s) finite (with
+    A = 0 an infinite ratio would give NaN here; the kernel returns the clamped branch)."""
+    on = m != 0
+    zero = torch.zeros_like(lp)
+    c = m.sum(1, keepdim=True)
+    ls = torch.where(on, lp - old, zero).sum(1, keepdim=True) / c.clamp(min=1)
+    sr = torch.exp(ls)
+    pg = torch.maximum(-a * sr, -a * sr.clamp(1 - clip_low, 1 + clip_high))  # [S, 1]: the row's surrogate
+    per = pg.expand_as(lp)
+    if is_weight is not None:
+        per = torch.where(on, is_weight.detach().float(), zero) * per
+    kl = zero
+    if ref_logp is not None:
+        dr = torch.where(on, ref_logp.detach().float() - lp, zero)
+        kl = torch.exp(dr) - dr - 1
+        per = per + beta * kl
+    per = torch.where(on, per, zero)
+    S = lp.shape[0]
+    if loss_type == "sequence":
+        num, div = ((per * m).sum(1) / c.view(-1).clamp(min=1)).sum(), float(S)
+    elif loss_type == "token":
+        num, div = (per * m).sum(), m.sum().clamp(min=1)
+    else:
+        num, div = (per * m).sum(), float(S) * float(max_len if max_len is not None else 0)
+    if denom is not None:
+        div = denom.detach().float().reshape(())
+    loss = num / div
+    with torch.no_grad():
+        n = m.sum()
+        inv = 1.0 / n.clamp(min=1)
+        out = ((sr < 1 - clip_low) | (sr > 1 + clip_high)).float()
+        metrics = {"clipfrac": (out * c).sum() * inv, "approx_kl": (((sr - 1) - ls) * c).sum() * inv,
                    "kl_ref": (kl * m).sum() * inv, "tokens": n}
     return loss, metrics
 
@@ -494,11 +542,28 @@ class _GRPOWFn(torch.autograd.Function):
         return (dlp * gloss,) + (None,) * 11
 
 
+class _GRPOSeqFn(torch.autograd.Function):
+    """`grpo_loss_seq`: the sequence-level ratio (GSPO); `w` may be None."""
+
+    @staticmethod
+    def forward(ctx, lp, old, ref, adv, mask, w, denom, clip_low, clip_high, beta, mode, max_len):
+        loss, dlp, metrics = _ext.require().grpo_loss_seq(lp, old, ref, adv, mask, w, denom, clip_low,
+                                                          clip_high, beta, mode, max_len)
+        ctx.save_for_backward(dlp)
+        ctx.mark_non_differentiable(metrics)
+        return loss, metrics
+
+    @staticmethod
+    def backward(ctx, gloss, _gm):
+        (dlp,) = ctx.saved_tensors
+        return (dlp * gloss,) + (None,) * 11
+
+
 def grpo_loss(logp: torch.Tensor, old_logp: Optional[torch.Tensor], ref_logp: Optional[torch.Tensor],
               adv: torch.Tensor, mask: torch.Tensor, clip_low: float = 0.2,
               clip_high: Optional[float] = None, beta: float = 0.04, loss_type: str = "sequence",
               max_len: Optional[int] = None, denom: Optional[torch.Tensor] = None, *,
-              is_weight: Optional[torch.Tensor] = None
+              is_weight: Optional[torch.Tensor] = None, importance_level: str = "token"
               ) -> Tuple[torch.Tensor, Dict[str, torch.Tensor]]:
     """GRPO objective on [S, T] fp32 grids (`mask`: action tokens), `adv` [S] one value per rollout.
 
@@ -513,7 +578,23 @@ def grpo_loss(logp: torch.Tensor, old_logp: Optional[torch.Tensor], ref_logp: Op
     (sequence mode: the full batch's S). `is_weight` ([S, T], detached, e.g. from
     `rollout_is_weights`) multiplies pg only: per = w pg + beta kl; the divisors stay the
     action-token counts and the metrics stay unweighted. Returns (loss, metrics) with device
-    tensors `clipfrac`, `approx_kl`, `kl_ref` (token means over the mask) and `tokens`."""
+    tensors `clipfrac`, `approx_kl`, `kl_ref` (token means over the mask) and `tokens`.
+
+    `importance_level="sequence"` (GSPO): one length-normalised ratio per rollout replaces rho, and
+    every action token of the row carries the row's surrogate; kl, the normalisations, `denom` and
+    the unweighted divisors keep their meaning:
+
+        l_s = sum_{t: m != 0} d / max(c_s, 1); sr_s = exp(l_s)        (c_s = 0: l_s = 0, sr_s = 1)
+        pg_s = max(-A sr_s, -A clamp(sr_s, 1 - clip_low, 1 + clip_high)); per = w pg_s + beta kl
+        dloss/dlogp_u = m_u scale_s [g_s (l1 >= l2 ? l1 : 0) - beta (exp(dr_u) - 1)],
+        g_s = sum_t m w / max(c_s, 1) (1 without `is_weight`), scale_s the token-level scale
+        clipfrac = sum_s c_s [sr_s outside the clip range] / n; approx_kl = sum_s c_s ((sr_s - 1) - l_s) / n
+
+    Entries outside the mask are never read into a sum there: NaN or junk in them reaches no
+    output. A fully masked row contributes 0 and takes a zero gradient row."""
+    if importance_level not in GRPO_IMPORTANCE_LEVELS:
+        raise ValueError(f"grpo_loss: importance_level must be one of {'|'.join(GRPO_IMPORTANCE_LEVELS)}, "
+                         f"got {importance_level!r}")
     if loss_type not in GRPO_LOSS_TYPES:
         raise ValueError(f"grpo_loss: loss_type must be one of {'|'.join(GRPO_LOSS_TYPES)}, got {loss_type!r}")
     if loss_type == "constant" and max_len is None and denom is None:
@@ -529,7 +610,7 @@ def grpo_loss(logp: torch.Tensor, old_logp: Optional[torch.Tensor], ref_logp: Op
             raise ValueError(f"grpo_loss: is_weight {tuple(w.shape)} must have logp's shape {tuple(lp.shape)}")
     if not _ext.use_native(lp):
         return _ref_grpo_loss(lp, old_logp, ref_logp, adv, mask, clip_low, clip_high,
-                              beta, loss_type, max_len, denom, w)
+                              beta, loss_type, max_len, denom, w, importance_level)
     # absent operands alias logp: d = 0 (rho = 1) on-policy, dr = 0 (kl = 0) without a reference
     old = lp.detach() if old_logp is None else old_logp.detach().float().contiguous()
     ref = lp.detach() if ref_logp is None else ref_logp.detach().float().contiguous()
@@ -538,7 +619,9 @@ def grpo_loss(logp: torch.Tensor, old_logp: Optional[torch.Tensor], ref_logp: Op
     dn = denom.detach().float().reshape(1) if denom is not None else None
     tail = (dn, float(clip_low), float(clip_high), float(beta), GRPO_LOSS_TYPES.index(loss_type),
             float(max_len or 0))
-    if w is None:
+    if importance_level == "sequence":
+        loss, met = _GRPOSeqFn.apply(lp, old, ref, a, m, w, *tail)
+    elif w is None:
         loss, met = _GRPOFn.apply(lp, old, ref, a, m, *tail)
     else:
         loss, met = _GRPOWFn.apply(lp, old, ref, a, m, w, *tail)

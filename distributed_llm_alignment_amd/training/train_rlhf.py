@@ -89,6 +89,21 @@ so `logprob_temperature` must be the rollout temperature there. Not with `reinfo
 filter, greedy decoding, `entropy_coef` / `log_entropy` (no entropy under a kept set yet), tensor or
 sequence parallelism, or a vocabulary not divisible by 8: each raises at start-up. Absent or false,
 a run launches exactly the kernels it launched before.
+
+`ppo.importance_sampling_level: token | sequence` (default token), for `grpo` only: `sequence` is
+GSPO (Group Sequence Policy Optimization). The reward and the advantage are per rollout, so the
+ratio becomes per rollout too: sr_s = exp(mean over the row's action tokens of logp - logp_old),
+the length-normalised ratio (not the product), clipped once per rollout, and every action token of
+the row carries the row's surrogate max(-A sr_s, -A clamp(sr_s, 1 - clip_range, 1 + clip_range_high));
+the gradient flows through sr_s to every action token (fused HIP fwd+bwd kernels, two launches, no
+host sync). The k3 KL term stays per token; `loss_type`, the shared micro-batch divisor (micro-batches
+slice whole rows), `rollout_logprobs`, `logprob_temperature` and `keep_sampling_mask` keep their
+meaning, and the importance weights of `correct` stay per token. `train/clipfrac` and
+`train/approx_kl` are token-weighted means of the per-rollout values. A length-normalised ratio
+moves far less than a token ratio, so the clip ranges are orders of magnitude below GRPO's 0.2
+(config/rlhf_gspo_llama3_8b.yaml). `ppo` (per-token advantages) and `reinforce` raise at start-up.
+`train/importance_sampling_level` is logged once (1 = sequence). At `token` (or absent) a run
+launches exactly the kernels it launched before.
 """
 from __future__ import annotations
 
@@ -106,7 +121,7 @@ from ..models import (build_reward_model, build_value_model, generate, load_caus
                       load_reward_checkpoint)
 from ..objectives import (action_mask, grpo_denominator, grpo_loss, grpo_rollout_stats, keep_row_grid, ppo_backward,
                           ppo_loss, ppo_rollout_stats, rlhf_loss, rollout_logp_grid, rollout_mismatch)
-from ..ops.losses import GRPO_LOSS_TYPES, ROLLOUT_IS_LEVELS, ROLLOUT_IS_MODES
+from ..ops.losses import GRPO_IMPORTANCE_LEVELS, GRPO_LOSS_TYPES, ROLLOUT_IS_LEVELS, ROLLOUT_IS_MODES
 from ..parallel.dist import barrier, split_for_rank
 from ..utils.checkpoint import save_state
 from ..utils.config import add_config_args, config_from_args
@@ -252,6 +267,19 @@ def rollout_is_settings(ppo: Dict) -> Dict:
     return {"is_cap": cap, "is_floor": floor, "is_level": level, "is_mode": mode}
 
 
+def importance_sampling_level(ppo: Dict, algo: str) -> str:
+    """`ppo.importance_sampling_level` (default token); an unknown value raises, and so does
+    `sequence` outside `ppo.algorithm: grpo` (GSPO is defined for per-rollout advantages)."""
+    v = ppo.get("importance_sampling_level", "token")
+    level = str(v).lower()
+    if level not in GRPO_IMPORTANCE_LEVELS:
+        raise ValueError(f"ppo.importance_sampling_level must be {'|'.join(GRPO_IMPORTANCE_LEVELS)}, got {v!r}")
+    if level == "sequence" and algo != "grpo":
+        raise ValueError("ppo.importance_sampling_level: sequence needs per-rollout advantages "
+                         f"(ppo.algorithm: grpo), got ppo.algorithm: {algo}")
+    return level
+
+
 def main(argv=None) -> int:
     args = parse_args(argv)
     config = config_from_args(args)
@@ -267,6 +295,7 @@ def main(argv=None) -> int:
                              f"ppo.group_size ({group})")
         if str(ppo.get("loss_type", "sequence")).lower() not in GRPO_LOSS_TYPES:
             raise ValueError(f"ppo.loss_type must be {'|'.join(GRPO_LOSS_TYPES)}, got {ppo.get('loss_type')!r}")
+    is_level = importance_sampling_level(ppo, str(ppo.get("algorithm", "reinforce")).lower())
     policy = load_causal_lm(model_cfg["policy_model_name_or_path"],
                             gradient_checkpointing=model_cfg.get("gradient_checkpointing", True),
                             device=ctx.device, seed=ctx.seed)
@@ -354,7 +383,7 @@ def main(argv=None) -> int:
     if algo == "ppo":
         return _ppo_loop(ctx, config, ppo, policy, ref, rm, rollout, engine, steps, kl_coef, log_every)
     if algo == "grpo":
-        return _grpo_loop(ctx, config, ppo, policy, ref, rm, rollout, engine, steps, group, log_every)
+        return _grpo_loop(ctx, config, ppo, policy, ref, rm, rollout, engine, steps, group, log_every, is_level)
     micro = int(ppo.get("update_micro_batch", 0) or 0)
     pending = rollout()
     for step in range(steps):
@@ -428,7 +457,8 @@ GRPO_ROWS = ("act", "advantages", "ref_logp", "old_logp", "is_weight", "keep_row
 
 def grpo_update(policy, engine, seqs, mask, stats, clip_low: float, clip_high, beta: float,
                 loss_type: str, max_len, micro: int = 0, entropy_coef: float = 0.0,
-                log_entropy: bool = False, temperature: float = 1.0, keep=None):
+                log_entropy: bool = False, temperature: float = 1.0, keep=None,
+                importance_level: str = "token"):
     """Backward of the GRPO loss over one minibatch of rollouts. micro > 0
     (`ppo.update_micro_batch`): gradient-accumulated micro-batches of `micro` rollouts that share
     the whole minibatch's divisor (`denom`, a device tensor: no host sync), so their gradients sum
@@ -436,13 +466,15 @@ def grpo_update(policy, engine, seqs, mask, stats, clip_low: float, clip_high, b
     entropy bonus (`ppo.entropy_coef`) is likewise normalised by the whole minibatch's
     action-token count. `stats["is_weight"]` (optional) is sliced with the other per-rollout
     entries. `temperature`: the log-prob temperature of `grpo_loss`. `keep`: the rollout batch's
-    whole sampling mask (`stats["keep_rows"]`, sliced with the rows, indexes it). Returns (loss, metrics) with
-    token-weighted metric means."""
+    whole sampling mask (`stats["keep_rows"]`, sliced with the rows, indexes it). `importance_level`:
+    `ppo.importance_sampling_level`; micro-batches slice whole rows, so a row's sequence-level ratio
+    never straddles two of them. Returns (loss, metrics) with token-weighted metric means."""
     n = seqs.shape[0]
     rows = GRPO_ROWS
     if micro <= 0 or micro >= n:
         loss, m = grpo_loss(policy, seqs, mask, stats, clip_low, clip_high, beta, loss_type, max_len,
-                            entropy_coef=entropy_coef, log_entropy=log_entropy, temperature=temperature, keep=keep)
+                            entropy_coef=entropy_coef, log_entropy=log_entropy, temperature=temperature, keep=keep,
+                            importance_level=importance_level)
         loss.backward()
         return loss.detach(), m
     denom = grpo_denominator(stats["act"], loss_type, max_len)
@@ -457,7 +489,7 @@ def grpo_update(policy, engine, seqs, mask, stats, clip_low: float, clip_high, b
         with ctx:
             loss, m = grpo_loss(policy, seqs[s0:s1], mask[s0:s1], mb, clip_low, clip_high, beta, loss_type,
                                 max_len, denom, entropy_coef, log_entropy, tokens, temperature=temperature,
-                                keep=keep)
+                                keep=keep, importance_level=importance_level)
             loss.backward()
         tot = tot + loss.detach()
         for k in acc:
@@ -465,7 +497,8 @@ def grpo_update(policy, engine, seqs, mask, stats, clip_low: float, clip_high, b
     return tot, {"kl": acc["kl_ref"], "tokens": tokens, **acc}
 
 
-def _grpo_loop(ctx, config, ppo, policy, ref, rm, rollout, engine, steps, group, log_every) -> int:
+def _grpo_loop(ctx, config, ppo, policy, ref, rm, rollout, engine, steps, group, log_every,
+               importance_level: str = "token") -> int:
     """Critic-free group-relative policy optimisation (`ppo.algorithm: grpo`)."""
     clip_low = float(ppo.get("clip_range", 0.2))
     clip_high = ppo.get("clip_range_high")
@@ -483,6 +516,7 @@ def _grpo_loop(ctx, config, ppo, policy, ref, rm, rollout, engine, steps, group,
     is_kw = rollout_is_settings(ppo) if lp_mode == "correct" else {}
     lp_temp = logprob_temperature(ppo, "grpo")
     log_temp = "logprob_temperature" in ppo  # logged once, and only when the key is set
+    log_level = importance_level == "sequence"  # logged once
     rows = GRPO_ROWS
     running = RunningLoss()
     pending = rollout()
@@ -514,7 +548,7 @@ def _grpo_loop(ctx, config, ppo, policy, ref, rm, rollout, engine, steps, group,
                 mb = {k: (stats[k][a:b] if stats.get(k) is not None else None) for k in rows}
                 loss, m = grpo_update(policy.model, engine, seqs[a:b], mask[a:b], mb, clip_low, clip_high,
                                       beta, loss_type, gen_len, micro, entropy_coef, log_entropy, lp_temp,
-                                      keep=keep)
+                                      keep=keep, importance_level=importance_level)
                 last = ep == epochs - 1 and mi == len(bounds) - 1
                 if last and overlap and step + 1 < steps:
                     pending = rollout()  # overlaps the in-flight gradient collectives (see _ppo_loop)
@@ -531,9 +565,11 @@ def _grpo_loop(ctx, config, ppo, policy, ref, rm, rollout, engine, steps, group,
                             **({"train/entropy": m["entropy"]} if "entropy" in m else {}),
                             **{f"train/{k}": v for k, v in mism.items()},
                             **({"train/logprob_temperature": lp_temp} if log_temp else {}),
+                            **({"train/importance_sampling_level":
+                                GRPO_IMPORTANCE_LEVELS.index(importance_level)} if log_level else {}),
                             "train/grad_norm": engine.last_grad_norm,
                             "train/comm_exposed_ms": engine.comm_timer.last_step_ms()}, step + 1)
-            running, log_temp = RunningLoss(), False
+            running, log_temp, log_level = RunningLoss(), False, False
     barrier()
     save_state(config["logging"]["output_dir"], [policy.model, ref.model, rm], engine, None, steps,
                policy.tokenizer)

@@ -28,6 +28,13 @@
                 the composed torch formulas on the GPU. With an extension that lacks the new ops
                 (an older build through DLA_EXT_PATH) only the unweighted loss is timed.
 
+  gspo          the raw `grpo_loss` op (token-level ratio) against `grpo_loss_seq` (sequence-level ratio,
+                GSPO), unweighted and weighted, at `--rollouts` x `--tokens`: the arms interleaved round
+                by round, median / min / max of the rounds per arm, the bytes each moves (10 grid passes against the
+                token op's 9: the row pass reads the mask, lp and old, the later loops no longer read old), and the op against the composed torch
+                formula. With an extension that lacks the op (an older build through DLA_EXT_PATH)
+                only the token op is timed, in the same harness.
+
 Prints one JSON line per kernel (per shape for `logprob`). `--bench` selects one of them."""
 from __future__ import annotations
 
@@ -175,7 +182,8 @@ def bench_logprob(dla_ops, dev, rows, V, rounds, iters, temperature=0.7):
 
 def main() -> int:
     ap = argparse.ArgumentParser()
-    ap.add_argument("--bench", choices=("all", "kv_replicate", "grpo_loss", "logprob", "rollout_is"), default="all")
+    ap.add_argument("--bench", choices=("all", "kv_replicate", "grpo_loss", "logprob", "rollout_is", "gspo"),
+                    default="all")
     ap.add_argument("--vocab", type=int, default=128256)
     ap.add_argument("--logprob-rows", type=int, nargs="+", default=[6144, 8192])
     ap.add_argument("--rounds", type=int, default=5, help="logprob: interleaved rounds per pair")
@@ -208,6 +216,8 @@ def main() -> int:
             bench_logprob(dla_ops, dev, rows, a.vocab, a.rounds, a.iters, a.temperature)
     if a.bench in ("all", "rollout_is"):
         bench_rollout_is(a, dla_ops, dev)
+    if a.bench in ("all", "gspo"):
+        bench_gspo(a, dla_ops, dev)
     return 0
 
 
@@ -358,6 +368,53 @@ def bench_rollout_is(a, dla_ops, dev):
     out["step_grad_max_diff"] = float((g1 - g2).abs().max())
     tf, tc = interleaved(fused_step, composed_step, a.rounds, a.iters)
     out.update(step_fused_ms=round(tf, 4), step_composed_ms=round(tc, 4))
+    print(json.dumps(out), flush=True)
+
+
+def bench_gspo(a, dla_ops, dev):
+    from distributed_llm_alignment_amd.ops import losses
+
+    S, T = a.rollouts, a.tokens
+    g = torch.Generator(device=dev).manual_seed(0)
+    lp = -torch.rand(S, T, device=dev, generator=g) * 3
+    old = lp + 0.3 * torch.randn(S, T, device=dev, generator=g)
+    ref = lp + 0.2 * torch.randn(S, T, device=dev, generator=g)
+    mask = (torch.rand(S, T, device=dev, generator=g) > 0.3).float()
+    adv = torch.randn(S, device=dev, generator=g)
+    w = 2.0 * torch.rand(S, T, device=dev, generator=g)
+    grid = S * T * 4
+    tail = (None, 0.2, 0.28, 0.04, 0, float(T))
+    arms = {"grpo_loss": lambda: dla_ops.grpo_loss(lp, old, ref, adv, mask, *tail)}
+    # passes over one [S, T] fp32 grid: the token op reads lp, old, ref, m in both launches and writes dlp
+    # (4 + 4 + 1). The sequence op reads m, lp, old in the row pass, m, lp, ref (+ w) in the second loop
+    # and m, lp, ref in the gradient launch, and writes dlp: 3 + 3 + 3 + 1, and one more with the weights
+    nbytes = {"grpo_loss": 9 * grid, "grpo_loss_seq": 10 * grid, "grpo_loss_seq_w": 11 * grid}
+    try:
+        dla_ops.grpo_loss_seq
+        arms["grpo_loss_seq"] = lambda: dla_ops.grpo_loss_seq(lp, old, ref, adv, mask, None, *tail)
+        arms["grpo_loss_seq_w"] = lambda: dla_ops.grpo_loss_seq(lp, old, ref, adv, mask, w, *tail)
+    except (AttributeError, RuntimeError):
+        pass  # an older extension: the token op alone
+    out = {"bench": "gspo", "S": S, "T": T, "grid_bytes": grid, "rounds": a.rounds, "iters": a.iters}
+    ts = {k: [] for k in arms}
+    for _ in range(a.rounds):
+        for k, fn in arms.items():
+            ts[k].append(timed(fn, a.iters, warmup=1))
+    for k, v in ts.items():
+        v.sort()
+        out[f"{k}_ms"] = {"median": round(v[len(v) // 2], 4), "min": round(v[0], 4), "max": round(v[-1], 4)}
+        out[f"{k}_gb_s"] = round(nbytes[k] / v[len(v) // 2] / 1e6, 1)
+    if "grpo_loss_seq" in arms:
+        out["seq_ratio"] = round(out["grpo_loss_seq_ms"]["median"] / out["grpo_loss_ms"]["median"], 4)
+        x = lp.detach().requires_grad_(True)
+        l1, _ = losses.grpo_loss(x, old, ref, adv, mask, 0.2, 0.28, 0.04, "sequence", T, importance_level="sequence")
+        l1.backward()
+        y = lp.detach().requires_grad_(True)
+        l2, _ = losses._ref_grpo_loss(y, old, ref, adv, mask, 0.2, 0.28, 0.04, "sequence", T,
+                                      importance_level="sequence")
+        l2.backward()
+        out["seq_loss_diff"] = float((l1 - l2).detach().abs())
+        out["seq_grad_max_diff"] = float((x.grad - y.grad).abs().max())
     print(json.dumps(out), flush=True)
 
 

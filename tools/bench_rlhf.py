@@ -67,6 +67,12 @@ def main() -> int:
                          "(ppo.group_attention)")
     ap.add_argument("--loss-type", choices=("sequence", "token", "constant"), default="sequence")
     ap.add_argument("--kl-coef", type=float, default=0.04, help="grpo: beta of the k3 KL term")
+    ap.add_argument("--importance-sampling-level", choices=("token", "sequence"), default="token",
+                    help="grpo: ppo.importance_sampling_level (sequence = GSPO: one length-normalised ratio "
+                         "per rollout inside the clipped surrogate)")
+    ap.add_argument("--clip-range", type=float, default=0.2, help="grpo: ppo.clip_range")
+    ap.add_argument("--clip-range-high", type=float, default=None,
+                    help="grpo: ppo.clip_range_high (default: --clip-range)")
     ap.add_argument("--entropy-coef", type=float, default=0.0,
                     help="ppo / grpo: entropy bonus (ppo.entropy_coef); the entropy comes out of the LM-head kernels")
     ap.add_argument("--log-entropy", action="store_true",
@@ -105,6 +111,8 @@ def main() -> int:
         ap.error("--batch must be a multiple of --micro")
     if a.micro and (a.overlap or a.algorithm == "ppo"):
         ap.error("--micro applies to the synchronous reinforce and grpo updates only")
+    if a.algorithm != "grpo" and a.importance_sampling_level != "token":
+        ap.error("--importance-sampling-level sequence needs per-rollout advantages: --algorithm grpo")
     if a.algorithm == "ppo":
         return ppo_main(a)
     if a.algorithm == "grpo":
@@ -579,8 +587,9 @@ def grpo_main(a) -> int:
         t3 = sync()
         phase_peak("stats")
         pol.train()
-        loss, m = grpo_update(pol, eng, seqs, mask, stats, 0.2, None, a.kl_coef, a.loss_type, a.new, a.micro,
-                              a.entropy_coef, a.log_entropy, lp_temp, keep=keep)
+        loss, m = grpo_update(pol, eng, seqs, mask, stats, a.clip_range, a.clip_range_high, a.kl_coef, a.loss_type,
+                              a.new, a.micro, a.entropy_coef, a.log_entropy, lp_temp, keep=keep,
+                              importance_level=a.importance_sampling_level)
         eng.step()
         t4 = sync()
         phase_peak("update")
@@ -598,7 +607,8 @@ def grpo_main(a) -> int:
         loss, m, stats = step(True)
     dt = sync() - t
     health = {"loss": round(float(loss), 6), "policy_grad_norm": round(float(eng.last_grad_norm), 5),
-              "kl_ref": round(float(m["kl"]), 6), "reward_std": round(float(stats["reward_std"]), 4),
+              "kl_ref": round(float(m["kl"]), 6), "clipfrac": round(float(m["clipfrac"]), 6),
+              "approx_kl": round(float(m["approx_kl"]), 8), "reward_std": round(float(stats["reward_std"]), 4),
               "frac_zero_std": round(float(stats["frac_zero_std"]), 4)}
     if "entropy" in m:
         health["entropy"] = round(float(m["entropy"]), 5)
@@ -607,6 +617,8 @@ def grpo_main(a) -> int:
                       "rollout_logprobs": lp_mode, "logprob_temperature": lp_temp, "keep_sampling_mask": keep_on,
                       "share_prefill": bool(a.share_prefill), "group_attention": bool(a.group_attention),
                       "loss_type": a.loss_type, "kl_coef": a.kl_coef,
+                      "importance_sampling_level": a.importance_sampling_level,
+                      "clip_range": a.clip_range, "clip_range_high": a.clip_range_high,
                       "entropy_coef": a.entropy_coef, "log_entropy": a.log_entropy,
                       "rollout_dtype": a.rollout_dtype, "frozen_fp8": a.frozen_fp8, "zero_shape": a.zero_shape,
                       "update_micro": a.micro or a.batch, "grad_ckpt": a.grad_ckpt or "none",
