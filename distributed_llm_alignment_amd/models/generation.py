@@ -487,6 +487,12 @@ def generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional[
     scales, hipBLASLt fp8). Attention, norms and the KV cache stay bf16."""
     if weight_dtype not in ("bf16", "fp8"):
         raise ValueError(f"weight_dtype must be 'bf16' or 'fp8', got {weight_dtype!r}")
+    from .lora import has_active_lora
+
+    if has_active_lora(model):
+        # the decode fast paths (decode_fused, the skinny GEMMs) read the base weights directly
+        raise ValueError("generate() does not run LoRA adapters: merge_lora(model) first, or generate "
+                         "inside lora_disabled(model) for the base model's samples")
     G = int(num_return_sequences)
     if G < 1:
         raise ValueError(f"num_return_sequences must be >= 1, got {num_return_sequences!r}")

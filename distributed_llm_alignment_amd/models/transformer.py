@@ -81,6 +81,8 @@ class Attention(nn.Module):
         self.tp_seq = None  # Megatron sequence parallel over the TP group (token-sharded stream)
         self.sp = None  # Ulysses sequence parallel (parallel.sequence.apply_sequence_parallel)
         self.h_local, self.kv_local = cfg.num_heads, cfg.num_kv_heads
+        self.lora_qkv = None  # LoRA adapters (models.lora.apply_lora)
+        self.lora_o = None
 
     def forward(self, h, rope, kv_start, kv_end, positions, cache=None, layer_idx=0, segs=None,
                 resid=None):
@@ -103,7 +105,8 @@ class Attention(nn.Module):
 
             qkv = col_parallel_linear(h, self.qkv_proj, self.qkv_bias, self.tp)
         else:  # (no autograd: the TP input copy is the identity; decode keeps the skinny GEMMs)
-            qkv = _lin(h, self.qkv_proj, self.qkv_bias)
+            lq = _lora(self.lora_qkv)
+            qkv = _lin(h, self.qkv_proj, self.qkv_bias) if lq is None else lq(h, self.qkv_proj, self.qkv_bias)
         window = cfg.sliding_window if cfg.sliding_window else 0
         if cache is None and self.sp is not None:
             # Ulysses: all-to-all to (all tokens, 1/P of the heads), attention, all-to-all back
@@ -119,10 +122,13 @@ class Attention(nn.Module):
         else:
             a = cache.attend(layer_idx, qkv, rope, window)
         if self.tp is None:
+            lo = _lora(self.lora_o)
             if resid is not None:
                 assert self.o_bias is None
+                if lo is not None:
+                    return lo(a, self.o_proj, resid=resid)
                 return ops.linear_add(a, self.o_proj, resid)
-            return _lin(a, self.o_proj, self.o_bias)
+            return _lin(a, self.o_proj, self.o_bias) if lo is None else lo(a, self.o_proj, self.o_bias)
         assert resid is None
         from ..parallel.tensor_parallel import sp_reduce_scatter, tp_grad_sum, tp_reduce
 
@@ -152,10 +158,28 @@ class MLP(nn.Module):
         self.down_bias = _param(H, device=device, dtype=dtype) if cfg.mlp_bias else None
         self.tp = None
         self.tp_seq = None
+        self.lora_up = None  # LoRA adapters (models.lora.apply_lora)
+        self.lora_down = None
+
+    def _forward_lora(self, h, resid, lu, ld):
+        """The unfused up / activation / down chain with an adapter on either projection (the
+        base weights are frozen, so the fused SwiGLU node does not apply; no TP)."""
+        assert self.tp is None and self.tp_seq is None
+        u = ops.linear(h, self.up_proj, self.up_bias) if lu is None else lu(h, self.up_proj, self.up_bias)
+        m = ops.swiglu(u) if self.cfg.activation == "swiglu" else ops.gelu_new(u)
+        if resid is not None and self.down_bias is None:
+            if ld is None:
+                return ops.linear_add(m, self.down_proj, resid)
+            return ld(m, self.down_proj, resid=resid)
+        out = ops.linear(m, self.down_proj, self.down_bias) if ld is None else ld(m, self.down_proj, self.down_bias)
+        return out if resid is None else out + resid
 
     def forward(self, h, resid=None):
         """`resid` (no TP): return resid + MLP(h); on the fused SwiGLU node the add runs inside
         the down GEMM (its C input), elsewhere as a plain add."""
+        lu, ld = _lora(self.lora_up), _lora(self.lora_down)
+        if lu is not None or ld is not None:
+            return self._forward_lora(h, resid, lu, ld)
         if resid is not None:
             if (self.cfg.activation == "swiglu" and self.up_bias is None and self.down_bias is None
                     and self.tp is None and self.tp_seq is None
@@ -296,6 +320,8 @@ class DecoderLayer(nn.Module):
                 and cfg.activation == "swiglu" and mlp.up_bias is None and mlp.down_bias is None
                 and at.qkv_bias is None and at.o_bias is None and at.tp is None and mlp.tp is None
                 and at.sp is None and self.ln1_b is None and self.ln2_b is None
+                and _lora(at.lora_qkv) is None and _lora(at.lora_o) is None
+                and _lora(mlp.lora_up) is None and _lora(mlp.lora_down) is None
                 and ops.decode.fused_layer_ok(x, cfg.hidden_size, at.qkv_proj, at.o_proj,
                                               mlp.up_proj, mlp.down_proj))
 
@@ -360,6 +386,11 @@ class DecoderLayer(nn.Module):
 
 def _ident(w, _seq=None):
     return w
+
+
+def _lora(adapter):
+    """The projection's LoRA adapter if one is attached and switched on, else None."""
+    return adapter if (adapter is not None and adapter.enabled) else None
 
 
 class CausalLM(nn.Module):

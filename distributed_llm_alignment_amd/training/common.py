@@ -69,6 +69,9 @@ class TrainContext:
 
 
 def setup(cfg: Dict[str, Any], stage: str, default_seed: int = 0) -> TrainContext:
+    from ..models.lora import lora_config
+
+    lora_config(cfg.get("model"))  # bad values / unknown keys in model.lora fail at start-up
     hw_cfg = cfg.get("hardware", {}) or {}
     st = init_distributed(timeout_s=int(hw_cfg.get("collective_timeout_s", 1800)))
     if st.device.type == "cuda":
@@ -130,6 +133,42 @@ def parallelize(ctx: TrainContext, model):
         # at a time; a trainable FSDP model is materialised unit by unit by its engine instead
         materialize(model, ctx.device)
     return model
+
+
+def lora_enabled(cfg) -> bool:
+    """`model.lora.enabled` of a config dict (or of a TrainContext's), validated."""
+    from ..models.lora import lora_config
+
+    cfg = cfg.cfg if isinstance(cfg, TrainContext) else cfg
+    return lora_config(cfg.get("model"))["enabled"]
+
+
+def maybe_apply_lora(ctx: TrainContext, model, base_path: Optional[str] = None) -> Optional[Dict[str, Any]]:
+    """`model.lora.enabled`: freeze `model` and attach the adapters (models.lora.apply_lora). Call
+    it after `parallelize` and before `make_engine`. Returns the validated block, or None when
+    LoRA is off (then nothing is touched: every trainer is the one it was)."""
+    from ..models.lora import apply_lora, lora_config
+
+    lc = lora_config(ctx.cfg.get("model"))
+    if not lc["enabled"]:
+        return None
+    m = ctx.mesh
+    if m is not None and (m.tp > 1 or m.sp > 1 or m.ep > 1):
+        raise ValueError("model.lora is not supported with tensor, sequence or expert parallelism "
+                         "(hardware.tp_size / sp_size / ep_size must be 1)")
+    if use_fsdp(ctx):
+        raise ValueError("model.lora is not supported with ZeRO-3 / FSDP (use zero_stage <= 1)")
+    from ..models.materialize import has_meta_params, materialize
+
+    if has_meta_params(model):
+        materialize(model, ctx.device)
+    stats = apply_lora(model, r=lc["r"], alpha=lc["alpha"], dropout=lc["dropout"],
+                       target_modules=lc["target_modules"], seed=ctx.seed, save_merged=lc["save_merged"],
+                       base_model=base_path)
+    ctx.log(f"LoRA r={lc['r']} alpha={lc['alpha']} dropout={lc['dropout']} targets={lc['target_modules']}: "
+            f"{stats['trainable_params']:,} trainable of {stats['total_params']:,} parameters "
+            f"({100.0 * stats['trainable_ratio']:.3f} %)")
+    return lc
 
 
 def meta_init(ctx: TrainContext) -> bool:

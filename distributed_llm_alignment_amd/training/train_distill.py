@@ -28,8 +28,8 @@ from ..data import TeacherRolloutDataset, build_dataloader
 from ..models import generate, load_causal_lm
 from ..objectives import distill_loss, gkd_loss
 from ..utils.config import add_config_args, config_from_args, hardware_parallel
-from .common import (_tokenize_left, effective_batch_msg, make_engine, meta_init, parallelize, setup,
-                     train_loop)
+from .common import (_tokenize_left, effective_batch_msg, lora_enabled, make_engine, maybe_apply_lora, meta_init,
+                     parallelize, setup, train_loop)
 
 # GKD's usual settings in the literature; config defaults, not something tuned here
 GKD_DEFAULTS = {"enabled": False, "beta": 0.5, "lmbda": 0.5, "temperature": 0.9, "max_new_tokens": 128,
@@ -92,6 +92,9 @@ def main(argv=None) -> int:
     args = parse_args(argv)
     config = config_from_args(args)
     gkd = gkd_settings(config)
+    if lora_enabled(config) and gkd and gkd["lmbda"] > 0.0:
+        raise ValueError("model.lora with distill.gkd.lmbda > 0: student rollouts need generate(), which does "
+                         "not run live adapters; use lmbda: 0 or disable model.lora")
     ctx = setup(config, "distill", default_seed=0)
     model_cfg: Dict = config["model"]
     dcfg: Dict = config.get("distill", {}) or {}
@@ -110,6 +113,7 @@ def main(argv=None) -> int:
             tb.model.eval().requires_grad_(False)
             teachers.append(tb.model)
     parallelize(ctx, student.model)
+    maybe_apply_lora(ctx, student.model, model_cfg["student_model_name_or_path"])  # student only
     for t in teachers:
         parallelize(ctx, t)
     tok = student.tokenizer

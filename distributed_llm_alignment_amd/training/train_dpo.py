@@ -27,7 +27,7 @@ from ..models import load_causal_lm
 from ..objectives import dpo_step_loss
 from ..optim.scheduler import LRSchedule
 from ..utils.config import add_config_args, config_from_args
-from .common import meta_init, effective_batch_msg, make_engine, parallelize, setup, train_loop
+from .common import lora_enabled, maybe_apply_lora, meta_init, effective_batch_msg, make_engine, parallelize, setup, train_loop
 
 
 def parse_args(argv=None) -> argparse.Namespace:
@@ -42,16 +42,38 @@ def main(argv=None) -> int:
     policy = load_causal_lm(model_cfg["policy_model_name_or_path"],
                             gradient_checkpointing=model_cfg.get("gradient_checkpointing", True),
                             device=ctx.device, seed=ctx.seed, meta_init=meta_init(ctx))
-    ref = load_causal_lm(model_cfg["reference_model_name_or_path"], gradient_checkpointing=False,
-                         device=ctx.device, seed=ctx.seed, meta_init=meta_init(ctx))
-    ref.model.eval()
-    ref.model.requires_grad_(False)
-    if model_cfg.get("reference_fp8", False):  # frozen reference on the fp8 inference GEMMs (opt-in)
-        from ..ops import enable_fp8_inference
+    ref_path = model_cfg.get("reference_model_name_or_path")
+    # model.lora with no reference path, or the policy's own: the frozen reference is the policy
+    # with its adapters switched off -- no second model is loaded
+    shared_ref = lora_enabled(ctx) and (not ref_path or str(ref_path) == str(model_cfg["policy_model_name_or_path"]))
+    if shared_ref and model_cfg.get("reference_fp8", False):
+        raise ValueError("model.reference_fp8 with the shared LoRA reference: the reference runs the policy's "
+                         "own bf16 base weights; give a separate reference_model_name_or_path or drop reference_fp8")
+    if not shared_ref and not ref_path:
+        raise ValueError("model.reference_model_name_or_path is required (only model.lora can take the "
+                         "reference from the policy itself)")
+    ref = None
+    if not shared_ref:
+        ref = load_causal_lm(ref_path, gradient_checkpointing=False,
+                             device=ctx.device, seed=ctx.seed, meta_init=meta_init(ctx))
+        ref.model.eval()
+        ref.model.requires_grad_(False)
+        if model_cfg.get("reference_fp8", False):  # frozen reference on the fp8 inference GEMMs (opt-in)
+            from ..ops import enable_fp8_inference
 
-        enable_fp8_inference(ref.model)
+            enable_fp8_inference(ref.model)
     parallelize(ctx, policy.model)
-    parallelize(ctx, ref.model)
+    if ref is not None:
+        parallelize(ctx, ref.model)
+    maybe_apply_lora(ctx, policy.model, model_cfg["policy_model_name_or_path"])
+    if shared_ref:
+        from ..models.lora import LoRAReference
+
+        ref_model = LoRAReference(policy.model)
+        ctx.log("DPO reference: the policy with its LoRA adapters switched off (no second model)")
+    else:
+        ref_model = ref.model
+    saved_models = [policy.model] if shared_ref else [policy.model, ref.model]
     tok = policy.tokenizer
     data_cfg = dict(config["data"])
     data_cfg["preference_path"] = data_cfg.get("preference_path")
@@ -78,7 +100,7 @@ def main(argv=None) -> int:
     policy.model.train()
 
     def step_fn(batch):
-        return dpo_step_loss(policy.model, ref.model, batch, beta=beta, label_smoothing=ls,
+        return dpo_step_loss(policy.model, ref_model, batch, beta=beta, label_smoothing=ls,
                              reduction=reduction, pad_id=pad_id)
 
     def extra(step, m):
@@ -87,7 +109,7 @@ def main(argv=None) -> int:
             out["train/preference_rate"] = (m["policy_chosen_logps"] > m["policy_rejected_logps"]).float().mean()
         return out
 
-    train_loop(ctx, loader, sampler, engine, step_fn, opt["max_train_steps"], [policy.model, ref.model],
+    train_loop(ctx, loader, sampler, engine, step_fn, opt["max_train_steps"], saved_models,
                tok, scheduler=sched, log_every=lg.get("log_every_steps", 10), save_every=lg.get("save_every_steps", 200),
                extra_log_fn=extra, resume=args.resume, keep_last=lg.get("keep_last"))
     ctx.log("DPO training complete")

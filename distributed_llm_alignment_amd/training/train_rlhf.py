@@ -126,7 +126,7 @@ from ..parallel.dist import barrier, split_for_rank
 from ..utils.checkpoint import save_state
 from ..utils.config import add_config_args, config_from_args
 from ..utils.logging import RunningLoss
-from .common import _tokenize_left, make_engine, parallelize, setup
+from .common import lora_enabled, _tokenize_left, make_engine, parallelize, setup
 
 
 def parse_args(argv=None) -> argparse.Namespace:
@@ -283,6 +283,9 @@ def importance_sampling_level(ppo: Dict, algo: str) -> str:
 def main(argv=None) -> int:
     args = parse_args(argv)
     config = config_from_args(args)
+    if lora_enabled(config):
+        raise ValueError("model.lora is not supported by the RLHF trainer: rollouts need generate(), which "
+                         "does not run live adapters")
     ctx = setup(config, "rlhf", default_seed=0)
     model_cfg: Dict = config["model"]
     ppo = config["ppo"]

@@ -19,7 +19,7 @@ from ..objectives import sft_loss
 from ..optim.scheduler import LRSchedule
 from ..parallel.dist import all_gather_tensor
 from ..utils.config import add_config_args, config_from_args
-from .common import meta_init, effective_batch_msg, make_engine, move_to, parallelize, setup, train_loop
+from .common import maybe_apply_lora, meta_init, effective_batch_msg, make_engine, move_to, parallelize, setup, train_loop
 
 
 def parse_args(argv=None) -> argparse.Namespace:
@@ -54,6 +54,7 @@ def main(argv=None) -> int:
                             device=ctx.device, seed=ctx.seed, meta_init=meta_init(ctx))
     model, tok = bundle.model, bundle.tokenizer
     parallelize(ctx, model)
+    maybe_apply_lora(ctx, model, model_cfg["model_name_or_path"])
     data_cfg = dict(config["data"])
     max_len = model_cfg.get("max_seq_length", 2048)
     opt = config["optimization"]

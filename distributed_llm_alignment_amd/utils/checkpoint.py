@@ -5,6 +5,14 @@
   model.safetensors, model_1.safetensors, ...   HF key names, in `prepare` order
                                                  (DPO: policy, ref; RLHF: policy, ref, reward;
                                                  distill: student, teachers...)
+  adapter.safetensors, adapter_config.json       a model with LoRA adapters: A and B, and every other
+                                                 parameter it trains (the reward model's score
+                                                 head), under their module names, and r / alpha /
+                                                 targets / base path
+                                                 (`adapter_{i}` for model i > 0); its
+                                                 model*.safetensors and hf/ then hold MERGED
+                                                 weights, or are not written (save_merged: false);
+                                                 resume restores the adapters only
   optimizer.bin                                  torch AdamW-format state dict (consolidated)
   scheduler.bin                                  only when a scheduler is given
   random_states_{rank}.pkl                       step + python / numpy / torch / cuda RNG
@@ -92,6 +100,8 @@ def save_state(output_dir, models: Sequence, engine=None, scheduler=None, step: 
     tp = any(is_tensor_parallel(m) for m in models)
     mode = weights or os.environ.get("DLA_CKPT_WEIGHTS") or "auto"
     for i, m in enumerate(models):
+        if _save_adapters(m, out, i, st.is_main):
+            continue  # model.lora.save_merged: false -- the adapter files are the checkpoint
         m_mode = mode if mode != "auto" else ("both" if _is_sharded(m) else "full")
         if m_mode in ("sharded", "both"):
             sharded_io.save_rank_shards(m, out, _stem(i))
@@ -150,6 +160,42 @@ def save_state(output_dir, models: Sequence, engine=None, scheduler=None, step: 
             _rotate(out.parent, keep_last)
     pdist.barrier()
     return out
+
+
+def _adapter_stem(i: int) -> str:
+    return "adapter" if i == 0 else f"adapter_{i}"
+
+
+def _save_adapters(model, out: Path, index: int, is_main: bool) -> bool:
+    """A model with LoRA adapters: write `adapter[_i].safetensors` (A and B and every other trainable
+    parameter, e.g. the reward model's score head, under their module names) and `adapter[_i]_config.json`. Returns True when the model's own weight files are to
+    be skipped (`save_merged: false`); otherwise they follow and hold the MERGED weights
+    (sharded_io.iter_hf_groups merges per tensor while streaming; the live weights stay)."""
+    from ..models import lora
+
+    if not lora.has_lora(model):
+        return False
+    info = dict(getattr(lora._causal_lm(model), "_dla_lora", {}) or {})
+    if is_main:
+        from safetensors.torch import save_file
+
+        sd = {k: v.to("cpu", copy=True).contiguous() for k, v in lora.adapter_state_dict(model).items()}
+        stem = _adapter_stem(index)
+        save_file(sd, str(out / f"{stem}.safetensors"), metadata={"format": "pt"})
+        cfg = {k: info.get(k) for k in ("r", "alpha", "dropout", "target_modules", "base_model_name_or_path")}
+        (out / f"{stem}_config.json").write_text(json.dumps(cfg, indent=2))
+    return not info.get("save_merged", True)
+
+
+def _load_adapters(model, d: Path, index: int) -> None:
+    from safetensors.torch import load_file
+
+    from ..models import lora
+
+    f = d / f"{_adapter_stem(index)}.safetensors"
+    if not f.exists():
+        raise FileNotFoundError(f"{f}: the model has LoRA adapters but the checkpoint has no adapter file")
+    lora.load_adapter_state_dict(model, load_file(str(f)))
 
 
 def _link_or_copy(src: Path, dst: Path) -> None:
@@ -228,8 +274,14 @@ def load_state(ckpt_dir, models: Sequence, engine=None, scheduler=None, load_mod
         raise FileNotFoundError(ckpt_dir)
     st = pdist.state()
     if load_models:
+        from ..models.lora import has_lora
+
         for i, m in enumerate(models):
-            if _weights_present(d, i):
+            if has_lora(m):
+                # the frozen base came from the configured model path, as on a fresh start; the
+                # checkpoint's model files hold MERGED weights and are not loaded into it
+                _load_adapters(m, d, i)
+            elif _weights_present(d, i):
                 load_model_weights(m, d, i, strict=True)
     if engine is not None:
         shard = d / f"optimizer_shard_{st.rank}.safetensors"

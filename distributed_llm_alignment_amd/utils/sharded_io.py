@@ -135,13 +135,23 @@ def _hf_subset(model, only):
 
 def iter_hf_groups(model, keep: bool = True):
     """Yield {hf_key: cpu tensor} per unit (None on ranks with keep=False). Collective."""
+    from ..models.lora import merged_overrides, merged_weight
+
     names = {id(p): n for n, p in model.named_parameters()}
+    adapters = merged_overrides(model)  # LoRA: the files hold W + scale * B A, merged per tensor
     for eng, u, ps in unit_groups(model):
         with full_params(model, eng, u, ps):
             out = None
             if keep:
-                sd = _hf_subset(model, {names[id(p)] for p in ps})
-                out = {k: v.detach().to("cpu", copy=True).contiguous() for k, v in sd.items()}
+                swapped = [(p, p.data) for p in ps if id(p) in adapters]
+                try:
+                    for p, live in swapped:  # the live weights are not written to
+                        p.data = merged_weight(live, adapters[id(p)])
+                    sd = _hf_subset(model, {names[id(p)] for p in ps})
+                    out = {k: v.detach().to("cpu", copy=True).contiguous() for k, v in sd.items()}
+                finally:
+                    for p, live in swapped:
+                        p.data = live
         yield out
 
 
