@@ -11,6 +11,11 @@ void launch_lora_shrink(const bf16_t*, int64_t, const bf16_t*, int64_t, bf16_t*,
                         int, float, hipStream_t);
 void launch_lora_expand_add(bf16_t*, int64_t, const bf16_t*, int64_t, const bf16_t*, int64_t, bool,
                             int64_t, int, int, float, hipStream_t);
+void launch_lora_tile_weight(const bf16_t*, int64_t, const bf16_t*, const bf16_t*, int64_t, int, float,
+                             const bf16_t*, bf16_t*, int, int, bool, hipStream_t);
+void launch_lora_quant_tile_f8(const bf16_t*, int64_t, const bf16_t*, const bf16_t*, int64_t, int, float,
+                               const bf16_t*, uint8_t*, float*, int, int, bool, hipStream_t);
+void launch_transpose_bf16(const bf16_t*, int64_t, int64_t, int64_t, bf16_t*, int64_t, hipStream_t);
 
 static bool lora_rank_ok(int64_t r) { return r == 8 || r == 16 || r == 32 || r == 64; }
 
@@ -64,9 +69,84 @@ void lora_expand_add_(at::Tensor& y, const at::Tensor& t, const at::Tensor& b, d
                          (int)N, (int)R, static_cast<float>(scale), cur_stream(y));
 }
 
+// ---- decode weight copies from W + scale B A in one pass (kernels in skinny64.hip) ----
+// Shared checks; returns A^T [K, R] contiguous (r K elements per refresh; the refresh never runs
+// inside a graph capture, ops/decode.py _cached).
+static at::Tensor merged_operands(const at::Tensor& w, const at::Tensor& a, const at::Tensor& b,
+                                  const c10::optional<at::Tensor>& nw, bool glu_il, int64_t kmult,
+                                  const bf16_t** nwp) {
+  check_bf16(w, "w");
+  TORCH_CHECK(w.dim() == 2 && w.stride(1) == 1 && w.stride(0) % 8 == 0 && w.stride(0) >= w.size(1),
+              "w [N, K], unit inner stride, row stride % 8 == 0");
+  check_aligned16(w, "w");
+  check_rows16(a, "a");
+  check_rows16(b, "b");
+  same_device(w, a);
+  same_device(w, b);
+  const int64_t N = w.size(0), K = w.size(1), R = a.size(0);
+  TORCH_CHECK(lora_rank_ok(R), "rank must be 8, 16, 32 or 64");
+  TORCH_CHECK(a.size(1) == K && b.size(0) == N && b.size(1) == R, "w [N, K], a [R, K], b [N, R]");
+  TORCH_CHECK(N > 0 && N % 16 == 0 && K > 0 && K % kmult == 0 && N < (1ll << 30) && K < (1ll << 30),
+              "N % 16 == 0, K % ", kmult, " == 0");
+  TORCH_CHECK(!glu_il || (N / 2) % 8 == 0, "glu_il: N = 2F, F % 8 == 0");
+  *nwp = nullptr;
+  if (nw.has_value() && nw->defined()) {
+    check_bf16(*nw, "nw");
+    TORCH_CHECK(nw->dim() == 1 && nw->size(0) == K && nw->is_contiguous(), "nw [K] contiguous");
+    check_aligned16(*nw, "nw");
+    same_device(w, *nw);
+    *nwp = cbp(*nw);
+  }
+  c10::hip::HIPGuardMasqueradingAsCUDA g(w.device());
+  auto at_ = at::empty({K, R}, a.options());
+  launch_transpose_bf16(cbp(a), R, K, a.stride(0), bp(at_), R, cur_stream(w));
+  return at_;
+}
+
+void lora_tile_weight(const at::Tensor& w, const at::Tensor& a, const at::Tensor& b, double scale,
+                      const c10::optional<at::Tensor>& nw, at::Tensor& out, bool glu_il) {
+  const bf16_t* np = nullptr;
+  const at::Tensor at_ = merged_operands(w, a, b, nw, glu_il, 32, &np);
+  const int64_t N = w.size(0), K = w.size(1);
+  check_bf16(out, "out");
+  TORCH_CHECK(out.dim() == 5 && out.size(0) == N / 16 && out.size(1) == K / 32 && out.size(2) == 4 &&
+                  out.size(3) == 16 && out.size(4) == 8 && out.is_contiguous(),
+              "out [N/16, K/32, 4, 16, 8] contiguous");
+  check_aligned16(out, "out");
+  same_device(w, out);
+  c10::hip::HIPGuardMasqueradingAsCUDA g(w.device());
+  launch_lora_tile_weight(cbp(w), w.stride(0), cbp(at_), cbp(b), b.stride(0), (int)a.size(0),
+                          static_cast<float>(scale), np, bp(out), (int)N, (int)K, glu_il, cur_stream(w));
+}
+
+void lora_quant_tile_f8(const at::Tensor& w, const at::Tensor& a, const at::Tensor& b, double scale,
+                        const c10::optional<at::Tensor>& nw, at::Tensor& out8, at::Tensor& scale_out,
+                        bool glu_il) {
+  const bf16_t* np = nullptr;
+  const at::Tensor at_ = merged_operands(w, a, b, nw, glu_il, 64, &np);
+  const int64_t N = w.size(0), K = w.size(1);
+  check_cuda(out8, "out8");
+  TORCH_CHECK(out8.scalar_type() == at::kByte && out8.is_contiguous() && out8.dim() == 4 &&
+                  out8.size(0) == N / 16 && out8.size(1) == K / 64 && out8.size(2) == 64 && out8.size(3) == 16,
+              "out8 uint8 [N/16, K/64, 64, 16] contiguous");
+  check_f32(scale_out, "scale_out");
+  TORCH_CHECK(scale_out.is_contiguous() && scale_out.dim() == 1 && scale_out.size(0) == N, "scale_out fp32 [N]");
+  check_aligned16(out8, "out8");
+  same_device(w, out8);
+  same_device(w, scale_out);
+  c10::hip::HIPGuardMasqueradingAsCUDA g(w.device());
+  launch_lora_quant_tile_f8(cbp(w), w.stride(0), cbp(at_), cbp(b), b.stride(0), (int)a.size(0),
+                            static_cast<float>(scale), np, out8.data_ptr<uint8_t>(), scale_out.data_ptr<float>(),
+                            (int)N, (int)K, glu_il, cur_stream(w));
+}
+
 }  // namespace dla
 
 TORCH_LIBRARY_FRAGMENT(dla, m) {
+  m.def("lora_tile_weight(Tensor w, Tensor a, Tensor b, float scale, Tensor? nw, Tensor(a!) out, "
+        "bool glu_il=False) -> ()");
+  m.def("lora_quant_tile_f8(Tensor w, Tensor a, Tensor b, float scale, Tensor? nw, Tensor(a!) out8, "
+        "Tensor(b!) scale_out, bool glu_il=False) -> ()");
   m.def("lora_shrink(Tensor x, Tensor a, float scale) -> Tensor");
   m.def("lora_expand_add_(Tensor(a!) y, Tensor t, Tensor b, float scale, bool transposed=False) -> ()");
 }
@@ -74,4 +154,6 @@ TORCH_LIBRARY_FRAGMENT(dla, m) {
 TORCH_LIBRARY_IMPL(dla, CUDA, m) {
   m.impl("lora_shrink", &dla::lora_shrink);
   m.impl("lora_expand_add_", &dla::lora_expand_add_);
+  m.impl("lora_tile_weight", &dla::lora_tile_weight);
+  m.impl("lora_quant_tile_f8", &dla::lora_quant_tile_f8);
 }

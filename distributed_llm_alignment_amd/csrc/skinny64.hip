@@ -385,6 +385,41 @@ void launch_m64(const SkinnyParams& p, hipStream_t st) {
   else splits(m64_int<0>{});
 }
 
+// Shared by the weight-copy kernels below (tile_weight / quant_tile_f8 and their LoRA-merged forms).
+// Row r of 16-row tile t -> weight row. glu_f > 0 (gate|up, F = glu_f): rows r < 8 are gate rows
+// 8t + r, rows r >= 8 up rows F + 8t + r - 8.
+__device__ __forceinline__ int64_t tile_row_of(int64_t t, int r, int glu_f) {
+  return glu_f > 0 ? (r < 8 ? 8 * t + r : glu_f + 8 * t + r - 8) : t * 16 + r;
+}
+
+// bf16(v * nw) on 8 columns (torch.mul's rounding); nw_col == nullptr: v
+__device__ __forceinline__ bf16x8 fold_norm8(bf16x8 v, const bf16_t* nw_col) {
+  if (nw_col != nullptr) {
+    const bf16x8 g = load_bf16x8(nw_col);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = f2bf(bf2f(v[e]) * bf2f(g[e]));
+  }
+  return v;
+}
+
+// One 16-byte lane piece of the F8 tiled layout: e4m3(clamp(v / sc, +-448)) of lo (k = 8 qd ..) then
+// hi (k = 32 + 8 qd ..), round to nearest even; bytes 4j .. 4j+3 hold elements 4j .. 4j+3
+__device__ __forceinline__ uint4 pack_f8_piece(const bf16x8& lo, const bf16x8& hi, float sc) {
+  auto q8 = [&](bf16_t x) { return fminf(fmaxf(bf2f(x) / sc, -448.f), 448.f); };
+  uint32_t wv[4];
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const bf16x8& v = h ? hi : lo;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      uint32_t wd = __builtin_amdgcn_cvt_pk_fp8_f32(q8(v[4 * j]), q8(v[4 * j + 1]), 0u, false);
+      wd = __builtin_amdgcn_cvt_pk_fp8_f32(q8(v[4 * j + 2]), q8(v[4 * j + 3]), wd, true);
+      wv[2 * h + j] = wd;
+    }
+  }
+  return make_uint4(wv[0], wv[1], wv[2], wv[3]);
+}
+
 // W [N, K] (row stride ldw) -> the tiled layout [N/16, K/32, 4, 16, 8] (see TW above; glu_il: gate /
 // up rows interleaved 8 + 8 per tile, skinny.hip skinny_glu_il_kernel), with nw
 // the RMSNorm weight folded in (bf16(W * nw), torch.mul's rounding). One 16-byte output piece per
@@ -402,15 +437,8 @@ __global__ __launch_bounds__(256) void tile_weight_kernel(const bf16_t* __restri
   const int64_t t = blk / kb;
   const int kk = static_cast<int>(blk - t * kb);
   const int col = kk * 32 + (lane >> 4) * 8;
-  // glu_f > 0 (gate|up, F = glu_f): tile t row r < 8 is gate row 8t + r, r >= 8 up row F + 8t + r - 8
-  const int r = lane & 15;
-  const int64_t row = glu_f > 0 ? (r < 8 ? 8 * t + r : glu_f + 8 * t + r - 8) : t * 16 + r;
-  bf16x8 v = load_bf16x8(W + row * ldw + col);
-  if (nw != nullptr) {
-    const bf16x8 g = load_bf16x8(nw + col);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = f2bf(bf2f(v[e]) * bf2f(g[e]));
-  }
+  const int64_t row = tile_row_of(t, lane & 15, glu_f);
+  const bf16x8 v = fold_norm8(load_bf16x8(W + row * ldw + col), nw != nullptr ? nw + col : nullptr);
   store_bf16x8(out + i * 8, v);
 }
 
@@ -434,18 +462,9 @@ __global__ __launch_bounds__(256) void quant_tile_f8_kernel(const bf16_t* __rest
                                                             int K, int glu_f) {
   __shared__ float inv_s[16];
   const int t = blockIdx.x, tid = threadIdx.x;
-  auto row_of = [&](int r) -> int64_t {
-    return glu_f > 0 ? (r < 8 ? 8 * static_cast<int64_t>(t) + r : glu_f + 8 * static_cast<int64_t>(t) + r - 8)
-                     : static_cast<int64_t>(t) * 16 + r;
-  };
+  auto row_of = [&](int r) -> int64_t { return tile_row_of(t, r, glu_f); };
   auto fetch = [&](int64_t row, int col) {
-    bf16x8 v = load_bf16x8(W + row * ldw + col);
-    if (nw != nullptr) {
-      const bf16x8 g = load_bf16x8(nw + col);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) v[e] = f2bf(bf2f(v[e]) * bf2f(g[e]));
-    }
-    return v;
+    return fold_norm8(load_bf16x8(W + row * ldw + col), nw != nullptr ? nw + col : nullptr);
   };
   {
     const int r = tid >> 4, sub = tid & 15;
@@ -472,26 +491,178 @@ __global__ __launch_bounds__(256) void quant_tile_f8_kernel(const bf16_t* __rest
     const int64_t row = row_of(r);
     const float sc = inv_s[r];
     const bf16x8 lo = fetch(row, 64 * kt + 8 * qd), hi = fetch(row, 64 * kt + 32 + 8 * qd);
-    auto q8 = [&](bf16_t x) { return fminf(fmaxf(bf2f(x) / sc, -448.f), 448.f); };
-    uint32_t wv[4];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const bf16x8& v = h ? hi : lo;
-      // bytes 4j .. 4j+3 of the piece: e4m3 of elements 4j .. 4j+3 (low half first)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        uint32_t wd = __builtin_amdgcn_cvt_pk_fp8_f32(q8(v[4 * j]), q8(v[4 * j + 1]), 0u, false);
-        wd = __builtin_amdgcn_cvt_pk_fp8_f32(q8(v[4 * j + 2]), q8(v[4 * j + 3]), wd, true);
-        wv[2 * h + j] = wd;
-      }
-    }
-    *reinterpret_cast<uint4*>(otile + static_cast<int64_t>(p) * 16) = make_uint4(wv[0], wv[1], wv[2], wv[3]);
+    *reinterpret_cast<uint4*>(otile + static_cast<int64_t>(p) * 16) = pack_f8_piece(lo, hi, sc);
   }
 }
 
 void launch_quant_tile_f8(const bf16_t* W, int64_t ldw, const bf16_t* nw, uint8_t* out, float* scale, int N,
                           int K, bool glu_il, hipStream_t st) {
   quant_tile_f8_kernel<<<N / 16, 256, 0, st>>>(W, ldw, nw, out, scale, K, glu_il ? N / 2 : 0);
+}
+
+// ---- LoRA-merged forms: the same copies built from W + s B A in one pass (ops/decode.py `lora=`) ----
+//   m[n, k] = bf16(float(w[n, k]) + s * sum_j b[n, j] a[j, k])      sum in fp32 (MFMA), one fma
+//   v       = nw ? bf16(float(m) * float(nw[k])) : m                then the layout of the op above
+// mfma_f32_16x16x32_bf16 on the transposed 16 x 32 block (fragment maps: lora.hip): the A operand's
+// rows are k, the B operand's columns the tile's 16 weight rows. Two MFMAs h = 0, 1 take their A
+// rows interleaved (row r' of h holds k = 8 (r' / 4) + 4 h + r' % 4), so lane (fr, fq) ends up
+// with k = 8 fq .. 8 fq + 7 of tile row fr: exactly the tiled layout's 16-byte piece, and the w
+// load, the nw load and the store are those of tile_weight_kernel. B operand: 8 consecutive j of
+// one b row, invariant along K, held in registers. A operand: 8 consecutive j of one column of a,
+// read from a contiguous A^T [K, R] copy (both 16-byte loads). R = 8, 16: lanes with j >= R load a
+// clamped address and are zeroed with a select; R = 64: KS = 2 k-steps. No atomics.
+__device__ __forceinline__ s16x8 frag_or_zero(const bf16_t* p, bool ok) {
+  const s16x8 v = *reinterpret_cast<const s16x8*>(p);
+  const s16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
+  return ok ? v : z;
+}
+
+template <int KS>
+__device__ __forceinline__ void lora_b_frags(const bf16_t* __restrict__ b, int64_t ldb, int64_t row, int R,
+                                             int fq, s16x8 (&bf)[KS]) {
+#pragma unroll
+  for (int s = 0; s < KS; ++s) {
+    const int j0 = 32 * s + 8 * fq;
+    const bool ok = j0 < R;
+    bf[s] = frag_or_zero(b + row * ldb + (ok ? j0 : 0), ok);
+  }
+}
+
+template <int KS>
+__device__ __forceinline__ void lora_at_frags(const bf16_t* __restrict__ at, int R, int col0, int fr, int fq,
+                                              s16x8 (&af)[2][KS]) {
+#pragma unroll
+  for (int h = 0; h < 2; ++h)
+#pragma unroll
+    for (int s = 0; s < KS; ++s) {
+      const int k = col0 + 8 * (fr >> 2) + 4 * h + (fr & 3);
+      const int j0 = 32 * s + 8 * fq;
+      const bool ok = j0 < R;
+      af[h][s] = frag_or_zero(at + static_cast<int64_t>(k) * R + (ok ? j0 : 0), ok);
+    }
+}
+
+// the lane's piece of v: columns col .. col + 7 of weight row `wrow`
+template <int KS>
+__device__ __forceinline__ bf16x8 lora_merged_piece(const bf16_t* __restrict__ wrow, const bf16_t* __restrict__ nw,
+                                                    int col, const s16x8 (&af)[2][KS], const s16x8 (&bf)[KS],
+                                                    float scale) {
+  f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+  for (int s = 0; s < KS; ++s)
+#pragma unroll
+    for (int h = 0; h < 2; ++h) acc[h] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[h][s], bf[s], acc[h], 0, 0, 0);
+  const bf16x8 wv = load_bf16x8(wrow + col);
+  float o[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) o[e] = fmaf(scale, acc[e >> 2][e & 3], bf2f(wv[e]));
+  return fold_norm8(pack_bf16x8(o), nw != nullptr ? nw + col : nullptr);
+}
+
+constexpr int kLoraMT = 4;  // 16-row tiles per workgroup: one A^T fragment feeds all of them
+
+// grid (ceil(ntiles / kLoraMT), ksplit), 4 waves: wave (blockIdx.y, w) walks the 32-column blocks
+// kk = 4 blockIdx.y + w, + 4 gridDim.y, ... of its tiles (neighbouring waves write neighbouring KBs)
+template <int KS>
+__global__ __launch_bounds__(256) void lora_tile_weight_kernel(
+    const bf16_t* __restrict__ W, int64_t ldw, const bf16_t* __restrict__ at, const bf16_t* __restrict__ b,
+    int64_t ldb, int R, float scale, const bf16_t* __restrict__ nw, bf16_t* __restrict__ out, int K,
+    int64_t ntiles, int glu_f) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int fr = lane & 15, fq = lane >> 4;
+  const int kb = K >> 5;
+  const int64_t t0 = static_cast<int64_t>(blockIdx.x) * kLoraMT;
+  s16x8 bf[kLoraMT][KS];
+  const bf16_t* wrow[kLoraMT];
+#pragma unroll
+  for (int i = 0; i < kLoraMT; ++i) {
+    const int64_t t = t0 + i < ntiles ? t0 + i : ntiles - 1;  // (a tail tile is computed, not stored)
+    const int64_t row = tile_row_of(t, fr, glu_f);
+    wrow[i] = W + row * ldw;
+    lora_b_frags<KS>(b, ldb, row, R, fq, bf[i]);
+  }
+  const int step = 4 * static_cast<int>(gridDim.y);
+  for (int kk = 4 * static_cast<int>(blockIdx.y) + w; kk < kb; kk += step) {
+    s16x8 af[2][KS];
+    lora_at_frags<KS>(at, R, kk * 32, fr, fq, af);
+#pragma unroll
+    for (int i = 0; i < kLoraMT; ++i) {
+      const bf16x8 v = lora_merged_piece<KS>(wrow[i], nw, kk * 32 + 8 * fq, af, bf[i], scale);
+      if (t0 + i < ntiles) store_bf16x8(out + (((t0 + i) * kb + kk) * 64 + lane) * 8, v);
+    }
+  }
+}
+
+void launch_lora_tile_weight(const bf16_t* W, int64_t ldw, const bf16_t* at, const bf16_t* b, int64_t ldb, int R,
+                             float scale, const bf16_t* nw, bf16_t* out, int N, int K, bool glu_il,
+                             hipStream_t st) {
+  const int64_t ntiles = N / 16;
+  const int kb = K / 32;
+  dim3 grid(static_cast<unsigned>((ntiles + kLoraMT - 1) / kLoraMT),
+            static_cast<unsigned>(kb >= 32 ? (kb / 16 < 64 ? kb / 16 : 64) : 1));
+  const int glu_f = glu_il ? N / 2 : 0;
+  if (R <= 32)
+    lora_tile_weight_kernel<1><<<grid, 256, 0, st>>>(W, ldw, at, b, ldb, R, scale, nw, out, K, ntiles, glu_f);
+  else
+    lora_tile_weight_kernel<2><<<grid, 256, 0, st>>>(W, ldw, at, b, ldb, R, scale, nw, out, K, ntiles, glu_f);
+}
+
+// quant_tile_f8_kernel on the merged weight: one workgroup per 16-row tile, pass 1 the row amax of
+// v (wave w takes the 32-column blocks w, w + 4, ...; lanes, then waves, meet through fmaxf: order
+// free), pass 2 recomputes v (a K = 14336 tile row does not fit LDS) and writes the e4m3 pieces.
+template <int KS>
+__global__ __launch_bounds__(256) void lora_quant_tile_f8_kernel(
+    const bf16_t* __restrict__ W, int64_t ldw, const bf16_t* __restrict__ at, const bf16_t* __restrict__ b,
+    int64_t ldb, int R, float scale, const bf16_t* __restrict__ nw, uint8_t* __restrict__ out,
+    float* __restrict__ scale_out, int K, int glu_f) {
+  __shared__ float am_s[4][16];
+  __shared__ float sc_s[16];
+  const int64_t t = blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int fr = lane & 15, fq = lane >> 4;
+  const int64_t row = tile_row_of(t, fr, glu_f);
+  const bf16_t* wrow = W + row * ldw;
+  s16x8 bf[KS];
+  lora_b_frags<KS>(b, ldb, row, R, fq, bf);
+  auto piece = [&](int kk) {
+    s16x8 af[2][KS];
+    lora_at_frags<KS>(at, R, kk * 32, fr, fq, af);
+    return lora_merged_piece<KS>(wrow, nw, kk * 32 + 8 * fq, af, bf, scale);
+  };
+  const int kb = K >> 5;
+  float am = 0.f;
+  for (int kk = w; kk < kb; kk += 4) {
+    const bf16x8 v = piece(kk);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) am = fmaxf(am, fabsf(bf2f(v[e])));
+  }
+  am = fmaxf(am, __shfl_xor(am, 16, 64));
+  am = fmaxf(am, __shfl_xor(am, 32, 64));
+  if (fq == 0) am_s[w][fr] = am;
+  __syncthreads();
+  if (tid < 16) {
+    const float a4 = fmaxf(fmaxf(am_s[0][tid], am_s[1][tid]), fmaxf(am_s[2][tid], am_s[3][tid]));
+    const float sc = fmaxf(a4 / 448.f, 1e-12f);
+    scale_out[16 * t + tid] = sc;
+    sc_s[tid] = sc;
+  }
+  __syncthreads();
+  const float sc = sc_s[fr];
+  uint8_t* otile = out + t * 16 * K;
+  for (int kt = w; kt < (K >> 6); kt += 4) {
+    const bf16x8 lo = piece(2 * kt), hi = piece(2 * kt + 1);
+    *reinterpret_cast<uint4*>(otile + (static_cast<int64_t>(kt) * 64 + lane) * 16) = pack_f8_piece(lo, hi, sc);
+  }
+}
+
+void launch_lora_quant_tile_f8(const bf16_t* W, int64_t ldw, const bf16_t* at, const bf16_t* b, int64_t ldb, int R,
+                               float scale, const bf16_t* nw, uint8_t* out, float* scale_out, int N, int K,
+                               bool glu_il, hipStream_t st) {
+  const int glu_f = glu_il ? N / 2 : 0;
+  if (R <= 32)
+    lora_quant_tile_f8_kernel<1><<<N / 16, 256, 0, st>>>(W, ldw, at, b, ldb, R, scale, nw, out, scale_out, K, glu_f);
+  else
+    lora_quant_tile_f8_kernel<2><<<N / 16, 256, 0, st>>>(W, ldw, at, b, ldb, R, scale, nw, out, scale_out, K, glu_f);
 }
 
 }  // namespace dla

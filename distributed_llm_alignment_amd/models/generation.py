@@ -395,6 +395,12 @@ def _remember(model: CausalLM, key, cache, dg) -> None:
     _GRAPH_SLOT[mid] = (weakref.ref(model, lambda _r, mid=mid: _GRAPH_SLOT.pop(mid, None)), key, cache, dg)
 
 
+def _live_adapters(model: CausalLM) -> bool:
+    from .lora import has_active_lora
+
+    return has_active_lora(model)
+
+
 def _weights_key(model: CausalLM) -> tuple:
     return tuple(t.data_ptr() for t in model.parameters()) + tuple(t.data_ptr() for t in model.buffers())
 
@@ -438,7 +444,8 @@ def generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional[
              return_mask: bool = False, use_graph: Optional[bool] = None, seed: Optional[int] = None,
              weight_dtype: str = "bf16", num_return_sequences: int = 1, share_prefill: bool = True,
              group_attention: bool = False, return_logprobs: bool = False,
-             logprob_temperature: Optional[float] = None, return_keep_mask: bool = False):
+             logprob_temperature: Optional[float] = None, return_keep_mask: bool = False,
+             adapters: Optional[str] = None):
     """Left-padded prompts [B, Tp] -> sequences [B, Tp + n] (n <= max_new_tokens).
 
     `num_return_sequences=G` (group rollouts, GRPO): G samples per prompt, output [B*G, Tp + n]
@@ -484,12 +491,27 @@ def generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional[
     stream an e4m3 copy of the weights with per-row scales (ops.decode.fp8_weights; half the
     bytes of the dominant weight streams), and the prompt prefill runs those projections on the
     fp8 inference GEMMs (ops.fp8_inference_scope: e4m3 weights and activations, row
-    scales, hipBLASLt fp8). Attention, norms and the KV cache stay bf16."""
+    scales, hipBLASLt fp8). Attention, norms and the KV cache stay bf16.
+
+    `adapters`: None (default) refuses a model with live LoRA adapters (ValueError). "merged"
+    runs them: the fused decode layer (decode rows <= 64 on the GPU, captured or eager) reads
+    derived weight copies built from m = bf16(W + (alpha / r) B A) (one HIP pass per projection
+    per refresh, `ops.decode.lora_merged`; bf16 or e4m3 per `weight_dtype`), so adapters cost
+    nothing per token. Everything else -- the prompt prefill, `prefill_shared`, layers the fused
+    decode layer does not take, more than 64 rows, the CPU -- runs the live-adapter forward that
+    training runs, y = x W^T + s (x A^T) B^T. A rollout therefore mixes two roundings of the same
+    function (merged: rounded once after the sum; live: base product, t and the sum rounded
+    separately), the same kind of gap as prefill GEMM against skinny decode without adapters;
+    `ppo.rollout_logprobs` measures and corrects it. With no adapter attached or active the call
+    is the default call, kernel for kernel. Any other value raises ValueError."""
     if weight_dtype not in ("bf16", "fp8"):
         raise ValueError(f"weight_dtype must be 'bf16' or 'fp8', got {weight_dtype!r}")
+    if adapters not in (None, "merged"):
+        raise ValueError(f"adapters must be None or 'merged', got {adapters!r}")
     from .lora import has_active_lora
 
-    if has_active_lora(model):
+    live = has_active_lora(model)
+    if live and adapters is None:
         # the decode fast paths (decode_fused, the skinny GEMMs) read the base weights directly
         raise ValueError("generate() does not run LoRA adapters: merge_lora(model) first, or generate "
                          "inside lora_disabled(model) for the base model's samples")
@@ -505,7 +527,8 @@ def generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional[
     else:
         lp_mode = _logp_mode(bool(return_logprobs), logprob_temperature, do_sample, temperature)
     f8 = weight_dtype == "fp8" or ops.decode.fp8_enabled()
-    with ops.decode.fp8_weights(f8), ops.fp8_inference_scope(model, f8 and PREFILL_FP8):
+    with ops.decode.fp8_weights(f8), ops.fp8_inference_scope(model, f8 and PREFILL_FP8), \
+            ops.decode.lora_merged(live and adapters == "merged"):
         return _generate(model, input_ids, attention_mask, max_new_tokens, do_sample, temperature, top_p,
                          top_k, eos_token_id, pad_token_id, generator, return_mask, use_graph, seed, G,
                          bool(group_attention) and G > 1, lp_mode,
@@ -569,7 +592,10 @@ def _generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional
         reuse_key = (B, Tp, max_new_tokens, kv_start is None, greedy, float(temperature), int(top_k),
                      float(top_p), eos, pad, input_ids.device, _weights_key(model), ops.decode.fp8_enabled(),
                      G if group_attention else 0,  # the grouped ops capture G (and Tp) as host constants
-                     return_logprobs)  # the captured step holds one sampler op or the other
+                     return_logprobs,  # the captured step holds one sampler op or the other
+                     # adapter mode: the captured step of a model with live adapters holds the first
+                     # layer's adapter launches
+                     (_live_adapters(model), ops.decode.lora_merged_enabled()))
         hit = _GRAPH_SLOT.get(id(model))
         if hit is not None and hit[0]() is model and hit[1] == reuse_key:
             cache, dg = hit[2], hit[3]

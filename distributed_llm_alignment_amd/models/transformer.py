@@ -314,14 +314,19 @@ class DecoderLayer(nn.Module):
         self.recompute = None  # selective activation recompute: None | "attention" | "mlp"
 
     def decode_fused_ok(self, x) -> bool:
-        """This layer's decode step can run on the fused residual/norm kernels."""
+        """This layer's decode step can run on the fused residual/norm kernels. Active LoRA
+        adapters are accepted only inside `ops.decode.lora_merged` (the kernels then read copies
+        built from W + s B A) and with the tiled weight layouts; elsewhere such a layer takes the
+        generic path."""
         cfg, at, mlp = self.cfg, self.attn, self.mlp
+        live = any(_lora(a) is not None for a in (at.lora_qkv, at.lora_o, getattr(mlp, "lora_up", None),
+                                                   getattr(mlp, "lora_down", None)))
+        if live and not ops.decode.lora_merged_ok():
+            return False
         return (cfg.norm_type == "rms" and not cfg.parallel_block and isinstance(mlp, MLP)
                 and cfg.activation == "swiglu" and mlp.up_bias is None and mlp.down_bias is None
                 and at.qkv_bias is None and at.o_bias is None and at.tp is None and mlp.tp is None
                 and at.sp is None and self.ln1_b is None and self.ln2_b is None
-                and _lora(at.lora_qkv) is None and _lora(at.lora_o) is None
-                and _lora(mlp.lora_up) is None and _lora(mlp.lora_down) is None
                 and ops.decode.fused_layer_ok(x, cfg.hidden_size, at.qkv_proj, at.o_proj,
                                               mlp.up_proj, mlp.down_proj))
 
@@ -330,17 +335,27 @@ class DecoderLayer(nn.Module):
         residual stream after the previous layer and `ssq` its row-norm partials (None for the
         first layer). Returns the next (s, ssq)."""
         cfg, at, mlp = self.cfg, self.attn, self.mlp
+        # active adapters (only inside ops.decode.lora_merged, see decode_fused_ok): each projection
+        # reads its merged derived copy; the first layer's un-fused qkv runs the live adapter
+        lq, lo, lu, ld = _lora(at.lora_qkv), _lora(at.lora_o), _lora(mlp.lora_up), _lora(mlp.lora_down)
         if ssq is None:
             h, _ = ops.add_norm(s, None, self.ln1_w, None, cfg.norm_eps, True)
             qkv = _lin(h, at.qkv_proj, None)
+            if lq is not None:
+                # the adapter's two rank-r products on top of the same base product as without
+                # adapters (the skinny GEMM), rounded where `ops.lora.lora_linear` rounds
+                from ..ops import lora as lora_ops
+
+                t = lora_ops.lora_shrink(h.reshape(-1, h.shape[-1]), lq.A, lq.scale)
+                lora_ops.lora_expand_add_(qkv.view(-1, qkv.shape[-1]), t, lq.B)
             a = cache.attend(layer_idx, qkv, rope, cfg.sliding_window if cfg.sliding_window else 0)
         else:
             window = cfg.sliding_window if cfg.sliding_window else 0
-            qkv = ops.decode.skinny_normed(s, ssq, self.ln1_w, cfg.norm_eps, at.qkv_proj)
+            qkv = ops.decode.skinny_normed(s, ssq, self.ln1_w, cfg.norm_eps, at.qkv_proj, lora=lq)
             a = cache.attend(layer_idx, qkv, rope, window)
-        s2, ssq2 = ops.decode.skinny_residual(a, at.o_proj, s)
-        m = ops.decode.skinny_normed(s2, ssq2, self.ln2_w, cfg.norm_eps, mlp.up_proj, glu=True)
-        return ops.decode.skinny_residual(m, mlp.down_proj, s2)
+        s2, ssq2 = ops.decode.skinny_residual(a, at.o_proj, s, lora=lo)
+        m = ops.decode.skinny_normed(s2, ssq2, self.ln2_w, cfg.norm_eps, mlp.up_proj, glu=True, lora=lu)
+        return ops.decode.skinny_residual(m, mlp.down_proj, s2, lora=ld)
 
     def fused_residual_ok(self, x, cache, seq) -> bool:
         at, mlp = self.attn, self.mlp

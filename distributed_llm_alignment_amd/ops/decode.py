@@ -394,11 +394,97 @@ def _glu_interleave(w: torch.Tensor) -> torch.Tensor:
     return torch.stack((w[:F].reshape(F // 8, 8, -1), w[F:].reshape(F // 8, 8, -1)), 1).reshape(2 * F, -1)
 
 
-def _tile_into(t: torch.Tensor, w: torch.Tensor, norm_w: Optional[torch.Tensor] = None,
-               glu_il: bool = False) -> None:
-    """t <- w (with norm_w: bf16(w * norm_w); glu_il: gate / up rows interleaved 8 + 8 per tile) in
-    the tiled layout: one HIP pass on the GPU."""
+# ---------------------------------------------------------------------------------------------
+# LoRA-merged derived weights. The fused decode layer never reads W itself, only the copies below,
+# so a live adapter costs nothing per token when the copies are built from
+#
+#     m = bf16(float(W) + scale * (B.float() @ A.float()))      (models.lora.merged_weight)
+#
+# instead of W: `lora=` on folded_weight / tiled_weight / fp8_tiled_weight (an adapter object with
+# .A / .B / .scale, or the triple). The copy lands in the SAME attribute and storage as the
+# adapter-free one (a captured graph keeps reading it); the cache key gains the adapter's tensors'
+# keys and its scale, so switching adapters off / on, or an optimizer step on A or B, refreshes in
+# place. On the GPU the merge, the norm fold and the tiling (or the e4m3 quantisation) are ONE HIP
+# pass per projection (csrc/skinny64.hip lora_tile_weight_kernel / lora_quant_tile_f8_kernel) at
+# r in MERGE_KERNEL_RANKS; anything else runs `merged()` into a temporary and then the adapter-free
+# path (also the CPU formula of record). The e4m3 kernel is the default at r <= MERGE_F8_KERNEL_MAX_RANK
+# only: its two passes re-read A^T from L2 per 16-row tile, and at r = 64 it measured 1.07-1.18x the
+# three-launch composition (clone, lora_expand_add_, quant_tile_f8) at three of Llama-3-8B's four
+# projections (profiles/lora_rollout.md); above the gate an eligible GPU call runs that composition.
+# DLA_LORA_MERGE_KERNELS=0 forces the compositions everywhere, =1 lifts the gate (A/B switch).
+_MERGE_MODE = os.environ.get("DLA_LORA_MERGE_KERNELS", "auto")
+MERGE_KERNELS = _MERGE_MODE != "0"
+MERGE_KERNEL_RANKS = (8, 16, 32, 64)
+MERGE_F8_KERNEL_MAX_RANK = 64 if _MERGE_MODE == "1" else 32
+MERGE_CALLS = {"kernel": 0, "composition": 0}  # which path built each merged copy (tests, benches)
+
+
+def lora_triple(lora):
+    """(A [r, K], B [N, r], scale) of an adapter object or a triple; None stays None. The tensors
+    are handed on as they are, NOT detached: the cache key reads the engine's weight epoch off the
+    parameter object itself (`_wkey`; a detached view would not carry it, and the fused optimizer
+    step moves no version counter)."""
+    if lora is None:
+        return None
+    if isinstance(lora, (tuple, list)):
+        A, B, scale = lora
+    else:
+        A, B, scale = lora.A, lora.B, lora.scale
+    return A, B, float(scale)
+
+
+def _lora_key(lora):
+    A, B, scale = lora
+    return (_wkey(A), _wkey(B), scale)
+
+
+def merged(w: torch.Tensor, lora) -> torch.Tensor:
+    """W + scale * B A as a new tensor: product and sum in fp32, one rounding (on the GPU at the
+    expand kernel's ranks: a clone and one `lora_expand_add_` launch, W as the [N, K] "activation",
+    B as t and A as the [r, K] small operand: one fma where the formula has a product and a sum,
+    an fp32 difference far below the bf16 rounding that follows)."""
+    A, B, scale = lora_triple(lora)
+    if A.dim() != 2 or B.dim() != 2 or A.shape[1] != w.shape[1] or B.shape != (w.shape[0], A.shape[0]):
+        raise ValueError(f"merged: W {tuple(w.shape)} A {tuple(A.shape)} B {tuple(B.shape)} do not fit W + s B A")
+    if _ext.use_native(w) and w.dtype == torch.bfloat16 and A.device == w.device and B.device == w.device:
+        from . import lora as lora_ops
+
+        m = w.detach().clone(memory_format=torch.contiguous_format)
+        if lora_ops.expand_ok(m, B, A, transposed=True):
+            torch.ops.dla.lora_expand_add_(m, B.detach(), A.detach(), scale, True)
+            return m
+    return (w.detach().float() + scale * (B.detach().float() @ A.detach().float()).to(w.device)).to(w.dtype)
+
+
+def merge_kernel_ok(w: torch.Tensor, lora, glu_il: bool = False, f8: bool = False) -> bool:
+    """The one-pass merge kernels take this call (else: `merged()` + the adapter-free path)."""
+    A, B, _ = lora
     N, K = w.shape
+
+    def rows16(t):
+        return (t.dim() == 2 and t.is_cuda and t.dtype == torch.bfloat16 and t.stride(1) == 1
+                and t.stride(0) % 8 == 0 and t.stride(0) >= t.shape[1] and t.data_ptr() % 16 == 0)
+
+    return (MERGE_KERNELS and _ext.use_native(w) and w.dtype == torch.bfloat16 and rows16(w) and rows16(A)
+            and rows16(B) and A.shape[0] in MERGE_KERNEL_RANKS and A.shape[1] == K
+            and (not f8 or A.shape[0] <= MERGE_F8_KERNEL_MAX_RANK)
+            and tuple(B.shape) == (N, A.shape[0]) and N % 16 == 0 and K % (64 if f8 else 32) == 0
+            and (not glu_il or (N // 2) % 8 == 0) and A.device == w.device and B.device == w.device)
+
+
+def _tile_into(t: torch.Tensor, w: torch.Tensor, norm_w: Optional[torch.Tensor] = None,
+               glu_il: bool = False, lora=None) -> None:
+    """t <- w (with norm_w: bf16(w * norm_w); glu_il: gate / up rows interleaved 8 + 8 per tile) in
+    the tiled layout: one HIP pass on the GPU. `lora` (a triple): from W + s B A, still one pass."""
+    N, K = w.shape
+    if lora is not None:
+        if merge_kernel_ok(w, lora, glu_il):
+            MERGE_CALLS["kernel"] += 1
+            _ext.require().lora_tile_weight(w, lora[0].detach(), lora[1].detach(), lora[2],
+                                            norm_w.contiguous() if norm_w is not None else None, t, bool(glu_il))
+            return
+        MERGE_CALLS["composition"] += 1
+        w = merged(w, lora)
     if _ext.use_native(w) and w.stride(-1) == 1 and w.stride(0) % 8 == 0:
         _ext.require().tile_weight(w, norm_w.contiguous() if norm_w is not None else None, t, bool(glu_il))
         return
@@ -426,11 +512,15 @@ def _cached(w: torch.Tensor, attr: str, key, make) -> torch.Tensor:
 
 
 def folded_weight(w: torch.Tensor, norm_w: torch.Tensor, tiled: bool = False,
-                  glu_il: bool = False) -> torch.Tensor:
+                  glu_il: bool = False, lora=None) -> torch.Tensor:
     """Cached W o norm_w (the RMSNorm weight folded into W's input columns; `tiled`: in the
     skinny64 tiled layout, `glu_il`: tiled with gate / up rows interleaved), refreshed in place
-    when either tensor changed (version counter / engine weight epoch)."""
+    when either tensor changed (version counter / engine weight epoch). `lora`: the copy of
+    W + s B A instead (tiled forms only), keyed on the adapter as well."""
     N, K = w.shape
+    lora = lora_triple(lora)
+    if lora is not None and not tiled:
+        raise ValueError("folded_weight: the row-major copy has no LoRA-merged form (DLA_DECODE_TILED >= 1)")
 
     def make(t):
         if not tiled:
@@ -438,23 +528,26 @@ def folded_weight(w: torch.Tensor, norm_w: torch.Tensor, tiled: bool = False,
             torch.mul(w.detach(), norm_w.detach().view(1, -1), out=t)
             return t
         t = t if t is not None else torch.empty((N // 16, K // 32, 4, 16, 8), dtype=w.dtype, device=w.device)
-        _tile_into(t, w.detach(), norm_w.detach(), glu_il)
+        _tile_into(t, w.detach(), norm_w.detach(), glu_il, lora)
         return t
 
     attr = "_dla_fold_g" if glu_il else ("_dla_fold_t" if tiled else "_dla_fold")
-    return _cached(w, attr, (_wkey(w), _wkey(norm_w)), make)
+    key = (_wkey(w), _wkey(norm_w))
+    return _cached(w, attr, key if lora is None else key + (_lora_key(lora),), make)
 
 
-def tiled_weight(w: torch.Tensor) -> torch.Tensor:
-    """Cached copy of W in the skinny64 tiled layout (refreshed like `folded_weight`)."""
+def tiled_weight(w: torch.Tensor, lora=None) -> torch.Tensor:
+    """Cached copy of W (`lora`: of W + s B A) in the skinny64 tiled layout (refreshed like
+    `folded_weight`)."""
     N, K = w.shape
+    lora = lora_triple(lora)
 
     def make(t):
         t = t if t is not None else torch.empty((N // 16, K // 32, 4, 16, 8), dtype=w.dtype, device=w.device)
-        _tile_into(t, w.detach())
+        _tile_into(t, w.detach(), lora=lora)
         return t
 
-    return _cached(w, "_dla_tile", _wkey(w), make)
+    return _cached(w, "_dla_tile", _wkey(w) if lora is None else (_wkey(w), _lora_key(lora)), make)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -488,6 +581,38 @@ def fp8_enabled() -> bool:
     return _FP8[0]
 
 
+# Merged-adapter decode (`generate(..., adapters="merged")`): only inside this scope does the fused
+# decode layer accept a layer with live LoRA adapters, reading copies built from W + s B A.
+_MERGED = [False]
+
+
+class lora_merged:
+    """Context manager: inside the block the fused decode layer runs layers with active LoRA
+    adapters on merged derived weights (outside it such layers take the generic path)."""
+
+    def __init__(self, enabled: bool = True):
+        self.enabled = bool(enabled)
+
+    def __enter__(self):
+        self.prev = _MERGED[0]
+        _MERGED[0] = self.enabled
+        return self
+
+    def __exit__(self, *exc):
+        _MERGED[0] = self.prev
+        return False
+
+
+def lora_merged_enabled() -> bool:
+    return _MERGED[0]
+
+
+def lora_merged_ok() -> bool:
+    """Merged scope on and a layout with a merged form: the row-major variants (`_dla_fold`, raw W
+    at DLA_DECODE_TILED < 2) have none."""
+    return _MERGED[0] and DECODE_TILED >= 2
+
+
 F8_MAX = 448.0  # largest finite e4m3 (OCP e4m3fn) value
 
 
@@ -507,12 +632,28 @@ def tile_f8(q: torch.Tensor) -> torch.Tensor:
             .reshape(N // 16, K // 64, 64, 16).contiguous())
 
 
-def fp8_tiled_weight(w: torch.Tensor, norm_w: Optional[torch.Tensor] = None, glu_il: bool = False):
+def fp8_tiled_weight(w: torch.Tensor, norm_w: Optional[torch.Tensor] = None, glu_il: bool = False, lora=None):
     """Cached (e4m3 tiled copy, per-row scales) of W (o norm_w folded in; glu_il: gate / up rows
-    interleaved 8 + 8 per 16-row tile), refreshed when W or norm_w moved (as folded_weight)."""
+    interleaved 8 + 8 per 16-row tile), refreshed when W or norm_w moved (as folded_weight).
+    `lora`: of W + s B A instead, quantised after the merge (and the fold)."""
     N, K = w.shape
+    lora = lora_triple(lora)
+    w0 = w
 
     def make(prev):
+        w = w0
+        if lora is not None:
+            if merge_kernel_ok(w, lora, glu_il, f8=True):
+                MERGE_CALLS["kernel"] += 1
+                t, sc = prev if prev is not None else (
+                    torch.empty((N // 16, K // 64, 64, 16), dtype=torch.uint8, device=w.device),
+                    torch.empty(N, dtype=torch.float32, device=w.device))
+                _ext.require().lora_quant_tile_f8(w.detach(), lora[0].detach(), lora[1].detach(), lora[2],
+                                                  norm_w.detach().contiguous() if norm_w is not None else None,
+                                                  t, sc, bool(glu_il))
+                return (t, sc)
+            MERGE_CALLS["composition"] += 1
+            w = merged(w, lora)
         if _ext.use_native(w) and w.stride(-1) == 1 and w.stride(0) % 8 == 0:
             # one HIP pass (csrc/skinny64.hip quant_tile_f8_kernel), in place when refreshing: a
             # captured decode graph keeps reading the same storage
@@ -535,7 +676,7 @@ def fp8_tiled_weight(w: torch.Tensor, norm_w: Optional[torch.Tensor] = None, glu
 
     attr = "_dla_f8_g" if glu_il else ("_dla_f8_n" if norm_w is not None else "_dla_f8")
     key = (_wkey(w), _wkey(norm_w) if norm_w is not None else None)
-    return _cached(w, attr, key, make)
+    return _cached(w, attr, key if lora is None else key + (_lora_key(lora),), make)
 
 
 def _f8_ok(rows: int, w: torch.Tensor) -> bool:
@@ -594,39 +735,49 @@ def refresh_folded_weights(model) -> None:
     hw = getattr(model, "head_weight", None)
     if isinstance(hw, torch.Tensor) and getattr(hw, "_dla_f8", None) is not None:
         fp8_tiled_weight(hw)
+    def active(owner, name):  # the projection's adapter if attached and switched on
+        ad = getattr(owner, name, None)
+        return ad if (ad is not None and ad.enabled) else None
+
     for layer in getattr(model, "layers", []):
-        for w, nw in ((getattr(layer.attn, "qkv_proj", None), getattr(layer, "ln1_w", None)),
-                      (getattr(layer.mlp, "up_proj", None), getattr(layer, "ln2_w", None))):
+        for w, nw, ad in ((getattr(layer.attn, "qkv_proj", None), getattr(layer, "ln1_w", None),
+                           active(layer.attn, "lora_qkv")),
+                          (getattr(layer.mlp, "up_proj", None), getattr(layer, "ln2_w", None),
+                           active(layer.mlp, "lora_up"))):
             if w is None or nw is None:
                 continue
-            if getattr(w, "_dla_fold", None) is not None:
+            if getattr(w, "_dla_fold", None) is not None and ad is None:  # (row-major: no merged form)
                 folded_weight(w, nw)
             if getattr(w, "_dla_fold_t", None) is not None:
-                folded_weight(w, nw, tiled=True)
+                folded_weight(w, nw, tiled=True, lora=ad)
             if getattr(w, "_dla_fold_g", None) is not None:
-                folded_weight(w, nw, tiled=True, glu_il=True)
+                folded_weight(w, nw, tiled=True, glu_il=True, lora=ad)
             if getattr(w, "_dla_f8_n", None) is not None:
-                fp8_tiled_weight(w, nw)
+                fp8_tiled_weight(w, nw, lora=ad)
             if getattr(w, "_dla_f8_g", None) is not None:
-                fp8_tiled_weight(w, nw, glu_il=True)
-        for w in (getattr(layer.attn, "o_proj", None), getattr(layer.mlp, "down_proj", None)):
+                fp8_tiled_weight(w, nw, glu_il=True, lora=ad)
+        for w, ad in ((getattr(layer.attn, "o_proj", None), active(layer.attn, "lora_o")),
+                      (getattr(layer.mlp, "down_proj", None), active(layer.mlp, "lora_down"))):
             if w is not None and getattr(w, "_dla_tile", None) is not None:
-                tiled_weight(w)
+                tiled_weight(w, lora=ad)
             if w is not None and getattr(w, "_dla_f8", None) is not None:
-                fp8_tiled_weight(w)
+                fp8_tiled_weight(w, lora=ad)
 
 
-def skinny_residual(x: torch.Tensor, w: torch.Tensor, res: torch.Tensor):
-    """s = res + x @ w^T (bf16 rounding as linear + add), plus the row-norm partials of s."""
+def skinny_residual(x: torch.Tensor, w: torch.Tensor, res: torch.Tensor, lora=None):
+    """s = res + x @ w^T (bf16 rounding as linear + add), plus the row-norm partials of s.
+    `lora`: on the merged copy of W + s B A (tiled layouts only)."""
     x2 = _rows(x)
+    if lora is not None and DECODE_TILED < 2:
+        raise RuntimeError("merged LoRA decode needs the tiled weight copies (DLA_DECODE_TILED=2)")
     if _f8_ok(x2.shape[0], w):
-        w8, sc = fp8_tiled_weight(w)
+        w8, sc = fp8_tiled_weight(w, lora=lora)
         if x2.shape[0] > 16:
             s, ssq = _ext.require().skinny64_f8(x2, w8, sc, _rows(res), None, 0.0, False)
         else:
             s, ssq = _ext.require().skinny_fused_f8(x2, w8, sc, _rows(res), None, 0.0)
         return s.view(*res.shape[:-1], w.shape[0]), ssq
-    wk = tiled_weight(w) if DECODE_TILED >= 2 else w
+    wk = tiled_weight(w, lora=lora) if DECODE_TILED >= 2 else w
     if x2.shape[0] > 16:
         s, ssq = _ext.require().skinny64(x2, wk, _rows(res), None, 0.0, False)
     else:
@@ -635,27 +786,30 @@ def skinny_residual(x: torch.Tensor, w: torch.Tensor, res: torch.Tensor):
 
 
 def skinny_normed(s: torch.Tensor, ssq: torch.Tensor, norm_w: torch.Tensor, eps: float,
-                  w: torch.Tensor, glu: bool = False) -> torch.Tensor:
-    """RMSNorm(s) * norm_w @ w^T from the producer's partials (glu: gate|up + SwiGLU epilogue)."""
+                  w: torch.Tensor, glu: bool = False, lora=None) -> torch.Tensor:
+    """RMSNorm(s) * norm_w @ w^T from the producer's partials (glu: gate|up + SwiGLU epilogue).
+    `lora`: on the merged copy of W + s B A (tiled layouts only)."""
     s2 = _rows(s)
+    if lora is not None and DECODE_TILED < 1:
+        raise RuntimeError("merged LoRA decode needs the tiled weight copies (DLA_DECODE_TILED=2)")
     if _f8_ok(s2.shape[0], w) and s2.shape[0] > 16:
         # 17..64 rows: gate|up in the plain [gate; up] row order (the m64 GLU epilogue pairs them)
-        w8, sc = fp8_tiled_weight(w, norm_w)
+        w8, sc = fp8_tiled_weight(w, norm_w, lora=lora)
         y, _ = _ext.require().skinny64_f8(s2, w8, sc, None, ssq, float(eps), bool(glu))
         return y.view(*s.shape[:-1], y.shape[-1])
     if _f8_ok(s2.shape[0], w):
         if glu:
-            w8, sc = fp8_tiled_weight(w, norm_w, glu_il=True)
+            w8, sc = fp8_tiled_weight(w, norm_w, glu_il=True, lora=lora)
             m = _ext.require().skinny_glu_il_f8(s2, w8, sc, ssq, float(eps))
             return m.view(*s.shape[:-1], m.shape[-1])
-        w8, sc = fp8_tiled_weight(w, norm_w)
+        w8, sc = fp8_tiled_weight(w, norm_w, lora=lora)
         y, _ = _ext.require().skinny_fused_f8(s2, w8, sc, None, ssq, float(eps))
         return y.view(*s.shape[:-1], y.shape[-1])
     if (glu and DECODE_GLU_IL and DECODE_TILED >= 1 and s2.shape[0] <= 16 and w.shape[0] % 32 == 0
             and w.shape[1] % 512 == 0):
-        m = _ext.require().skinny_glu_il(s2, folded_weight(w, norm_w, tiled=True, glu_il=True), ssq, float(eps))
+        m = _ext.require().skinny_glu_il(s2, folded_weight(w, norm_w, tiled=True, glu_il=True, lora=lora), ssq, float(eps))
         return m.view(*s.shape[:-1], m.shape[-1])
-    wf = folded_weight(w, norm_w, tiled=DECODE_TILED >= 1)
+    wf = folded_weight(w, norm_w, tiled=DECODE_TILED >= 1, lora=lora)
     if s2.shape[0] > 16:
         y, _ = _ext.require().skinny64(s2, wf, None, ssq, float(eps), bool(glu))
     else:

@@ -39,7 +39,8 @@ import torch
 import torch.nn.functional as F
 
 from . import _ext
-from .linear import accumulate_weight_grad, add_gemm, input_grad, transposed_weight
+from .linear import (accumulate_weight_grad, add_gemm, fp8_inference_ok, fp8_linear_frozen, input_grad,
+                     transposed_weight)
 
 _MODE = os.environ.get("DLA_LORA_KERNELS", "auto")
 KERNELS = _MODE != "0"
@@ -176,7 +177,13 @@ class _LoRALinearFn(torch.autograd.Function):
         K, N = x.shape[-1], weight.shape[0]
         x2 = x.reshape(-1, K)
         # both base paths return a fresh tensor, so the in-place expand is safe
-        if resid is not None:
+        if fp8_inference_ok(x2, weight, bias):
+            # the no-grad prefill of an fp8 rollout (ops.linear.fp8_inference_scope): the base
+            # product on the fp8 inference GEMM, as `ops.linear` / `linear_add` run it without adapters
+            y = fp8_linear_frozen(x2, weight)
+            if resid is not None:
+                y.add_(resid.reshape(-1, N))
+        elif resid is not None:
             y = add_gemm(x2, weight, resid.reshape(-1, N))
         else:
             y = F.linear(x2, weight, bias)

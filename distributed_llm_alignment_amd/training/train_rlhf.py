@@ -104,6 +104,18 @@ moves far less than a token ratio, so the clip ranges are orders of magnitude be
 (config/rlhf_gspo_llama3_8b.yaml). `ppo` (per-token advantages) and `reinforce` raise at start-up.
 `train/importance_sampling_level` is logged once (1 = sequence). At `token` (or absent) a run
 launches exactly the kernels it launched before.
+
+`model.lora.enabled` (`ppo.algorithm: grpo | ppo`; config/rlhf_grpo_lora_llama3_8b.yaml): the
+policy is frozen and trains LoRA adapters only (attached after `parallelize`, before the engine: no
+Adam state for the base). Rollouts run `generate(adapters="merged")`: the captured decode graph
+reads weight copies built from W + (alpha / r) B A, refreshed in one HIP pass per projection once
+per step, while the prompt prefill runs the live-adapter forward the update runs; the gap between
+the two roundings is what `ppo.rollout_logprobs` measures and corrects. With no
+`model.reference_model_name_or_path` (or the policy's own path) no second policy is loaded: the
+reference is `LoRAReference(policy)`, the policy with its adapters switched off, and the checkpoint
+holds the policy (`adapter.safetensors` + merged weights) and the reward model. The PPO critic stays
+fully fine-tuned. `reinforce` with `model.lora`, and `ppo.frozen_fp8` with the shared reference,
+raise at start-up. Without `model.lora` a run launches what it launched before.
 """
 from __future__ import annotations
 
@@ -126,7 +138,7 @@ from ..parallel.dist import barrier, split_for_rank
 from ..utils.checkpoint import save_state
 from ..utils.config import add_config_args, config_from_args
 from ..utils.logging import RunningLoss
-from .common import lora_enabled, _tokenize_left, make_engine, parallelize, setup
+from .common import lora_enabled, maybe_apply_lora, _tokenize_left, make_engine, parallelize, setup
 
 
 def parse_args(argv=None) -> argparse.Namespace:
@@ -283,12 +295,22 @@ def importance_sampling_level(ppo: Dict, algo: str) -> str:
 def main(argv=None) -> int:
     args = parse_args(argv)
     config = config_from_args(args)
-    if lora_enabled(config):
-        raise ValueError("model.lora is not supported by the RLHF trainer: rollouts need generate(), which "
-                         "does not run live adapters")
-    ctx = setup(config, "rlhf", default_seed=0)
+    lora_on = lora_enabled(config)
     model_cfg: Dict = config["model"]
     ppo = config["ppo"]
+    ref_path = model_cfg.get("reference_model_name_or_path")
+    # model.lora with no reference path, or the policy's own: the frozen reference of the k3 KL term
+    # is the policy with its adapters switched off -- no second copy of the policy is loaded
+    shared_ref = lora_on and (not ref_path or str(ref_path) == str(model_cfg["policy_model_name_or_path"]))
+    if lora_on and str(ppo.get("algorithm", "reinforce")).lower() not in ("grpo", "ppo"):
+        raise ValueError("model.lora in the RLHF trainer is supported for ppo.algorithm: grpo and ppo; the "
+                         "reinforce loop works on sequence log-probs and has none of the rollout-mismatch "
+                         "tooling (ppo.rollout_logprobs) that merged-adapter rollouts rely on")
+    if shared_ref and ppo.get("frozen_fp8", False):
+        raise ValueError("ppo.frozen_fp8 with the shared LoRA reference: the reference runs the policy's own "
+                         "bf16 base weights; give a separate model.reference_model_name_or_path or drop "
+                         "frozen_fp8 (the reward model keeps its own fp8 option only with a separate reference)")
+    ctx = setup(config, "rlhf", default_seed=0)
     group = 1
     if str(ppo.get("algorithm", "reinforce")).lower() == "grpo":
         # ppo.batch_size stays the number of rollouts per step: whole groups of one prompt each
@@ -302,9 +324,11 @@ def main(argv=None) -> int:
     policy = load_causal_lm(model_cfg["policy_model_name_or_path"],
                             gradient_checkpointing=model_cfg.get("gradient_checkpointing", True),
                             device=ctx.device, seed=ctx.seed)
-    ref = load_causal_lm(model_cfg["reference_model_name_or_path"], gradient_checkpointing=False,
-                         device=ctx.device, seed=ctx.seed)
-    ref.model.eval().requires_grad_(False)
+    ref = None
+    if not shared_ref:
+        ref = load_causal_lm(model_cfg["reference_model_name_or_path"], gradient_checkpointing=False,
+                             device=ctx.device, seed=ctx.seed)
+        ref.model.eval().requires_grad_(False)
     rcfg = config.get("reward_model", {}) or {}
     rbase = rcfg.get("base_model_name_or_path", model_cfg["policy_model_name_or_path"])
     rpath = rcfg.get("path")
@@ -319,8 +343,19 @@ def main(argv=None) -> int:
 
         enable_fp8_inference(ref.model)
         enable_fp8_inference(rm.backbone)
-    for m in (policy.model, ref.model, rm):
+    for m in (policy.model, rm) if shared_ref else (policy.model, ref.model, rm):
         parallelize(ctx, m)
+    maybe_apply_lora(ctx, policy.model, model_cfg["policy_model_name_or_path"])
+    if shared_ref:
+        import types
+
+        from ..models.lora import LoRAReference
+
+        # (`ref.model` is what the loops read; `ref.saved` what they checkpoint next to the policy)
+        ref = types.SimpleNamespace(model=LoRAReference(policy.model), saved=[])
+        ctx.log("RLHF reference: the policy with its LoRA adapters switched off (no second model)")
+    else:
+        ref.saved = [ref.model]
 
     prompts = load_prompts(config["sampling"])
     gen = generation_params(ppo)
@@ -369,6 +404,9 @@ def main(argv=None) -> int:
                                     num_return_sequences=group, share_prefill=bool(ppo.get("share_prefill", True)),
                                     group_attention=bool(ppo.get("group_attention", False)),
                                     return_logprobs=want_logp,
+                                    # live adapters: the decode graph reads weight copies built from
+                                    # W + s B A, refreshed once per step (models.generation.generate)
+                                    adapters="merged" if lora_on else None,
                                     logprob_temperature=lp_temp if want_logp and (lp_temp != 1.0 or keep_on) else None,
                                     **({"return_keep_mask": True} if keep_on else {}))
         keep = rlp.pop() if keep_on else None  # uint8 [S, n, V / 8], last in the returned tuple
@@ -409,7 +447,7 @@ def main(argv=None) -> int:
                            step + 1)
             running = RunningLoss()
     barrier()
-    save_state(config["logging"]["output_dir"], [policy.model, ref.model, rm], engine, None, steps, tok)
+    save_state(config["logging"]["output_dir"], [policy.model, *ref.saved, rm], engine, None, steps, tok)
     ctx.log("RLHF PPO loop complete")
     ctx.logger.close()
     return 0
@@ -574,7 +612,7 @@ def _grpo_loop(ctx, config, ppo, policy, ref, rm, rollout, engine, steps, group,
                             "train/comm_exposed_ms": engine.comm_timer.last_step_ms()}, step + 1)
             running, log_temp, log_level = RunningLoss(), False, False
     barrier()
-    save_state(config["logging"]["output_dir"], [policy.model, ref.model, rm], engine, None, steps,
+    save_state(config["logging"]["output_dir"], [policy.model, *ref.saved, rm], engine, None, steps,
                policy.tokenizer)
     ctx.log("RLHF GRPO loop complete")
     ctx.logger.close()
@@ -652,7 +690,7 @@ def _ppo_loop(ctx, config, ppo, policy, ref, rm, rollout, engine, steps, kl_coef
                             "train/comm_exposed_ms": engine.comm_timer.last_step_ms()}, step + 1)
             running, log_temp = RunningLoss(), False
     barrier()
-    out = save_state(config["logging"]["output_dir"], [policy.model, ref.model, rm, critic], engine, None,
+    out = save_state(config["logging"]["output_dir"], [policy.model, *ref.saved, rm, critic], engine, None,
                      steps, policy.tokenizer)
     from ..utils.stream_st import save_streamed
 

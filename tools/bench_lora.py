@@ -2,6 +2,8 @@
 
     python tools/bench_lora.py kernels [--rounds 7] [--iters 20]
     python tools/bench_lora.py step --mode full|lora|lora-shared [--steps 5] [--warmup 2]
+    python tools/bench_lora.py refresh [--rounds 7] [--iters 10]          (results: profiles/lora_rollout.md)
+    python tools/bench_lora.py decode [--rows 8 64] [--rounds 5]           (likewise)
 
 kernels: lora_shrink and lora_expand_add_ against the torch composition of the same step
 (the library GEMMs with the rounding of the formula of record, `ops.lora.shrink_library` = mm with
@@ -19,6 +21,17 @@ of 4 pairs, one GPU, ZeRO-1 engine as bench.py). `full` = full fine-tuning with 
 reference (the default trainer), `lora` = r = 16 adapters (`--r`) with a separate reference model,
 `lora-shared` = adapters with the reference taken from the policy (LoRAReference). Prints pairs/s
 per step with its spread and the peak allocated memory. One mode per process: a fresh allocator.
+
+refresh: building one decode weight copy from W + s B A at Llama-3-8B's four projections (qkv
+6144 x 4096 and gate|up 28672 x 4096 with the norm weight folded, o 4096 x 4096, down 4096 x 14336),
+r in {16, 64}, bf16 tiled and e4m3 tiled: (a) the one-pass op (`lora_tile_weight` /
+`lora_quant_tile_f8`, its A^T copy included), (b) the three-launch composition on the same tensors
+(clone, `lora_expand_add_(transposed=True)`, the existing `tile_weight` / `quant_tile_f8`), (c) the
+existing op on W alone, the floor: a refresh without adapters. Interleaved rounds as `kernels`.
+
+decode: graph decode ms/token of `generate(adapters="merged")` against the same model under
+`lora_disabled` (the adapter-free kernels), from the difference of two generation lengths so the
+prefill cancels; interleaved rounds, median and spread.
 """
 from __future__ import annotations
 
@@ -182,6 +195,96 @@ def bench_step(args):
                       "trainable": stats, "loss": float(loss.detach())}))
 
 
+REFRESH_SHAPES = [("qkv", 6144, 4096, True), ("o", 4096, 4096, False), ("gate|up", 28672, 4096, True),
+                  ("down", 4096, 14336, False)]
+
+
+def bench_refresh(args):
+    dev = _need_gpu()
+    k = torch.ops.dla
+    gen = torch.Generator(device=dev).manual_seed(0)
+    rows = []
+    for name, N, K, fold in REFRESH_SHAPES:
+        w = _rand((N, K), dev, gen, K ** -0.5)
+        nw = (1.0 + 0.1 * _rand((K,), dev, gen).float()).to(torch.bfloat16) if fold else None
+        out = torch.empty((N // 16, K // 32, 4, 16, 8), dtype=torch.bfloat16, device=dev)
+        o8 = torch.empty((N // 16, K // 64, 64, 16), dtype=torch.uint8, device=dev)
+        sc = torch.empty(N, dtype=torch.float32, device=dev)
+        for r in args.ranks:
+            a = _rand((r, K), dev, gen, K ** -0.5)
+            b = _rand((N, r), dev, gen, r ** -0.5)
+
+            def comp(f8):
+                tmp = w.clone()
+                k.lora_expand_add_(tmp, b, a, 2.0, True)
+                if f8:
+                    k.quant_tile_f8(tmp, nw, o8, sc, False)
+                else:
+                    k.tile_weight(tmp, nw, out, False)
+
+            for f8 in (False, True):
+                if f8:
+                    arms = {"fused": lambda: k.lora_quant_tile_f8(w, a, b, 2.0, nw, o8, sc, False),
+                            "comp": lambda: comp(True), "floor": lambda: k.quant_tile_f8(w, nw, o8, sc, False)}
+                else:
+                    arms = {"fused": lambda: k.lora_tile_weight(w, a, b, 2.0, nw, out, False),
+                            "comp": lambda: comp(False), "floor": lambda: k.tile_weight(w, nw, out, False)}
+                rows.append((name, N, K, r, "fp8" if f8 else "bf16", _ab(arms, args.rounds, args.iters)))
+        del w, out, o8
+    print("| projection | N | K | r | copy | (a) one pass us (min..max) | (b) clone + expand + tile us | "
+          "(c) existing op on W us | (a)/(b) | (a)/(c) |")
+    print("|---|---|---|---|---|---|---|---|---|---|")
+    for name, N, K, r, dt, res in rows:
+        fm, cm, fl = (statistics.median(res[x]) for x in ("fused", "comp", "floor"))
+        print(f"| {name} | {N} | {K} | {r} | {dt} | {_fmt(res['fused'])} | {_fmt(res['comp'])} | {_fmt(res['floor'])} | "
+              f"{fm / cm:.2f} | {fm / fl:.2f} |")
+    print(json.dumps({"bench": "lora_refresh", "rows": [
+        {"proj": name, "N": N, "K": K, "r": r, "copy": dt, **{f"{x}_us": res[x] for x in res}}
+        for name, N, K, r, dt, res in rows]}))
+
+
+def bench_decode(args):
+    dev = _need_gpu()
+    from distributed_llm_alignment_amd.models import build_model, generate, get_config
+    from distributed_llm_alignment_amd.models.lora import apply_lora, lora_adapters, lora_disabled
+
+    overrides = {"num_layers": args.layers} if args.layers else {}
+    cfg = get_config(args.model, **overrides)
+    m = build_model(cfg, device=dev, dtype=torch.bfloat16, seed=1234).eval()
+    apply_lora(m, r=args.r, alpha=2 * args.r, seed=0)
+    for ad in lora_adapters(m):
+        ad.B.data.normal_(0.0, 0.01)
+    n1, n2 = args.new_tokens
+    out = []
+    for rows in args.rows:
+        ids = torch.randint(3, cfg.vocab_size, (rows, args.prompt), device=dev,
+                            generator=torch.Generator(device=dev).manual_seed(rows))
+
+        def run(n, merged):
+            kw = dict(max_new_tokens=n, do_sample=True, temperature=0.7, top_p=0.9, eos_token_id=-1, seed=1,
+                      weight_dtype=args.weight_dtype)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            if merged:
+                generate(m, ids, None, adapters="merged", **kw)
+            else:
+                with lora_disabled(m):
+                    generate(m, ids, None, **kw)
+            torch.cuda.synchronize()
+            return time.perf_counter() - t0
+
+        res = {"merged": [], "base": []}
+        for merged in (True, False):  # warm: captures, derived copies, library picks
+            run(n1, merged), run(n2, merged)
+        for _ in range(args.rounds):
+            for name, merged in (("merged", True), ("base", False)):
+                res[name].append((run(n2, merged) - run(n1, merged)) / (n2 - n1) * 1e3)
+        out.append({"rows": rows, **{f"{k}_ms_per_token": v for k, v in res.items()}})
+        print(f"rows {rows}: merged {_fmt(res['merged'])} ms/token, adapter-free {_fmt(res['base'])} ms/token")
+    print(json.dumps({"bench": "lora_decode", "model": args.model, "layers": cfg.num_layers, "r": args.r,
+                      "weight_dtype": args.weight_dtype, "prompt": args.prompt, "results": out}))
+
+
 class _Null:
     def __enter__(self):
         return self
@@ -206,8 +309,21 @@ def main(argv=None) -> int:
     ps.add_argument("--accum", type=int, default=4)
     ps.add_argument("--steps", type=int, default=5)
     ps.add_argument("--warmup", type=int, default=2)
+    pr = sub.add_parser("refresh")
+    pr.add_argument("--rounds", type=int, default=7)
+    pr.add_argument("--iters", type=int, default=10)
+    pr.add_argument("--ranks", type=int, nargs="+", default=[16, 64])
+    pd = sub.add_parser("decode")
+    pd.add_argument("--model", default="llama3-8b")
+    pd.add_argument("--layers", type=int, default=None, help="debug only: override the layer count")
+    pd.add_argument("--r", type=int, default=16)
+    pd.add_argument("--rows", type=int, nargs="+", default=[8, 64])
+    pd.add_argument("--prompt", type=int, default=512)
+    pd.add_argument("--new-tokens", type=int, nargs=2, default=[64, 192])
+    pd.add_argument("--weight-dtype", default="bf16", choices=("bf16", "fp8"))
+    pd.add_argument("--rounds", type=int, default=5)
     args = ap.parse_args(argv)
-    (bench_kernels if args.cmd == "kernels" else bench_step)(args)
+    {"kernels": bench_kernels, "step": bench_step, "refresh": bench_refresh, "decode": bench_decode}[args.cmd](args)
     return 0
 
 

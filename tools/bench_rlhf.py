@@ -103,6 +103,12 @@ def main() -> int:
                          "--overlap runs generation beside real collectives")
     ap.add_argument("--zero-shape", type=int, default=1,
                     help="engines laid out as rank 0 of an N-rank ZeRO-1 job (1/N optimizer state)")
+    ap.add_argument("--lora-r", type=int, default=0,
+                    help="grpo: LoRA adapters of this rank on the policy (model.lora; 0 = full fine-tuning); the "
+                         "rollouts run generate(adapters='merged')")
+    ap.add_argument("--lora-shared-ref", type=int, choices=(0, 1), default=0,
+                    help="grpo with --lora-r: 1 = the reference is the policy with its adapters off "
+                         "(LoRAReference, no second model), 0 = a separate reference model")
     ap.add_argument("--ppo-epochs", type=int, default=2)
     ap.add_argument("--minibatches", type=int, default=2)
     a = ap.parse_args()
@@ -113,6 +119,8 @@ def main() -> int:
         ap.error("--micro applies to the synchronous reinforce and grpo updates only")
     if a.algorithm != "grpo" and a.importance_sampling_level != "token":
         ap.error("--importance-sampling-level sequence needs per-rollout advantages: --algorithm grpo")
+    if a.lora_r and a.algorithm != "grpo":
+        ap.error("--lora-r is measured on the grpo step only: --algorithm grpo")
     if a.algorithm == "ppo":
         return ppo_main(a)
     if a.algorithm == "grpo":
@@ -509,7 +517,12 @@ def grpo_main(a) -> int:
     note("start")
     pol = build_model(cfg, device=dev, dtype=torch.bfloat16, seed=1)
     note("policy")
-    ref = build_model(cfg, device=dev, dtype=torch.bfloat16, seed=1).requires_grad_(False).eval()
+    shared_ref = bool(a.lora_r) and bool(a.lora_shared_ref)
+    if shared_ref and a.frozen_fp8:
+        raise SystemExit("--frozen-fp8 with --lora-shared-ref 1: the reference runs the policy's bf16 base weights")
+    ref = None
+    if not shared_ref:
+        ref = build_model(cfg, device=dev, dtype=torch.bfloat16, seed=1).requires_grad_(False).eval()
     note("reference")
     rm = RewardModel(build_model(cfg, device=dev, dtype=torch.bfloat16, seed=2, headless=True)).to(dev, torch.bfloat16)
     if a.frozen_fp8:
@@ -521,6 +534,14 @@ def grpo_main(a) -> int:
     note("reward")
     if a.grad_ckpt:
         pol.gradient_checkpointing_enable(a.grad_ckpt)
+    if a.lora_r:
+        from distributed_llm_alignment_amd.models.lora import LoRAReference, apply_lora, lora_adapters
+
+        apply_lora(pol, r=a.lora_r, alpha=2 * a.lora_r, seed=0)
+        for ad in lora_adapters(pol):  # B != 0: the merge and the adapter products run on real data
+            ad.B.data.normal_(0.0, 0.01)
+        if shared_ref:
+            ref = LoRAReference(pol)
     eng = DataParallelEngine(pol, lr=1e-6, betas=(0.9, 0.95), weight_decay=0.01, max_grad_norm=1.0,
                              shape_world=a.zero_shape)
     note("policy_engine")
@@ -556,6 +577,7 @@ def grpo_main(a) -> int:
                                     share_prefill=bool(a.share_prefill),
                                     group_attention=bool(a.group_attention), return_logprobs=lp_mode != "off",
                                     logprob_temperature=lp_temp if lp_mode != "off" and lp_temp != 1.0 else None,
+                                    adapters="merged" if a.lora_r else None,
                                     **({"return_keep_mask": True} if keep_on else {}))
         keep = rlp.pop() if keep_on else None
         kkw = {"keep": keep, "keep_rows": keep_row_grid(action_mask(mask, a.prompt), a.prompt, keep.shape[1])} \
@@ -621,11 +643,13 @@ def grpo_main(a) -> int:
                       "clip_range": a.clip_range, "clip_range_high": a.clip_range_high,
                       "entropy_coef": a.entropy_coef, "log_entropy": a.log_entropy,
                       "rollout_dtype": a.rollout_dtype, "frozen_fp8": a.frozen_fp8, "zero_shape": a.zero_shape,
+                      "lora_r": a.lora_r, "lora_shared_ref": shared_ref,
                       "update_micro": a.micro or a.batch, "grad_ckpt": a.grad_ckpt or "none",
                       "prompt": a.prompt, "new_tokens": a.new,
                       "s_per_step": round(dt / a.steps, 3), "rollouts_per_s": round(a.batch * a.steps / dt, 3),
                       **{f"{k}_s": round(v / a.steps, 3) for k, v in phases.items()},
                       "mem_after_gib": mem, "peak_gib_by_phase": peaks,
+                      "peak_gib": max(peaks.values()) if peaks else None,
                       "device_total_gib": round(torch.cuda.get_device_properties(dev).total_memory / gib, 1),
                       **health}), flush=True)
     return 0
