@@ -136,6 +136,8 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> norm_fwd(
   // forward kernels cover H <= 8192 (wave per row, 16 x 8 columns per lane)
   TORCH_CHECK(H % 8 == 0 && H <= 8192, "norm_fwd: hidden size must be a multiple of 8 and <= 8192");
   TORCH_CHECK(w.numel() == H && w.is_contiguous(), "w shape");
+  // the RMS kernels are instantiated without a bias (no model has one): reject, never drop it
+  TORCH_CHECK(!(rms && b && b->defined()), "norm_fwd: RMSNorm takes no bias");
   const int64_t rows = x.numel() / H;
   TORCH_CHECK(rows < (1ll << 31), "too many rows");
   c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
@@ -179,6 +181,8 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> norm_bwd(const at::Tensor& dy, co
   const int64_t H = s.size(-1);
   const int64_t rows = s.numel() / H;
   TORCH_CHECK(H % 8 == 0 && H <= 16384, "hidden size");
+  // no RMS kernel writes db partials: folding them would return uninitialised memory as db
+  TORCH_CHECK(!(has_bias && rms), "norm_bwd: RMSNorm takes no bias");
   TORCH_CHECK(rstd.numel() == rows, "rstd shape");
   const float* mptr = nullptr;
   if (!rms) {
@@ -285,7 +289,7 @@ at::Tensor gelu_bwd(const at::Tensor& x, const at::Tensor& dy) {
 // ================================= rope =======================================================
 static void check_rope_common(const at::Tensor& cos_t, const at::Tensor& sin_t,
                               const c10::optional<at::Tensor>& pos, int64_t tokens, int64_t D,
-                              int64_t rot) {
+                              int64_t rot, int64_t T, int64_t pos_offset) {
   check_f32(cos_t, "cos");
   check_f32(sin_t, "sin");
   TORCH_CHECK(cos_t.is_contiguous() && sin_t.is_contiguous() && cos_t.dim() == 2 &&
@@ -295,6 +299,10 @@ static void check_rope_common(const at::Tensor& cos_t, const at::Tensor& sin_t,
   if (pos && pos->defined()) {
     TORCH_CHECK(pos->scalar_type() == at::kInt && pos->is_contiguous() && pos->numel() == tokens,
                 "pos must be int32 [tokens]");
+  } else {
+    // implicit positions t + pos_offset, t < T, must stay inside the table (as attn_fwd checks)
+    TORCH_CHECK(pos_offset >= 0 && T + pos_offset <= cos_t.size(0),
+                "rope: T + pos_offset exceeds the cos/sin table length");
   }
 }
 
@@ -309,7 +317,7 @@ std::tuple<at::Tensor, at::Tensor> rope_fwd(const at::Tensor& qkv, const at::Ten
   TORCH_CHECK(qkv.stride(0) % 8 == 0, "qkv row stride must be a multiple of 8");
   const int64_t tokens = qkv.size(0);
   TORCH_CHECK(T > 0 && tokens % T == 0, "tokens must be a multiple of T");
-  check_rope_common(cos_t, sin_t, pos, tokens, D, rot);
+  check_rope_common(cos_t, sin_t, pos, tokens, D, rot, T, pos_offset);
   c10::hip::HIPGuardMasqueradingAsCUDA g(qkv.device());
   auto q = at::empty({tokens, Hq * D}, qkv.options());
   auto k = at::empty({tokens, Hkv * D}, qkv.options());
@@ -337,7 +345,7 @@ void rope_bwd(const at::Tensor& dq, const at::Tensor& dk, at::Tensor& dqkv,
                   dqkv.size(1) >= (Hq + 2 * Hkv) * D,
               "dqkv layout");
   TORCH_CHECK(T > 0 && tokens % T == 0, "tokens must be a multiple of T");
-  check_rope_common(cos_t, sin_t, pos, tokens, D, rot);
+  check_rope_common(cos_t, sin_t, pos, tokens, D, rot, T, pos_offset);
   c10::hip::HIPGuardMasqueradingAsCUDA g(dqkv.device());
   launch_rope_bwd(cbp(dq), cbp(dk), bp(dqkv), dqkv.stride(0), cos_t.data_ptr<float>(),
                   sin_t.data_ptr<float>(),

@@ -66,7 +66,12 @@ def add_norm(x: torch.Tensor, residual: Optional[torch.Tensor], weight: torch.Te
              bias: Optional[torch.Tensor] = None, eps: float = 1e-5,
              rms: bool = True, keep_stream: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
     """`keep_stream`: return the stream s as an output of the norm node even without a
-    residual (see _NormFn), for a caller that feeds s to ops.linear.linear_add."""
+    residual (see _NormFn), for a caller that feeds s to ops.linear.linear_add.
+
+    RMSNorm takes no bias: the RMS kernels are built without one (no model has it), so the
+    combination is rejected here, on the native and on the CPU path alike."""
+    if rms and bias is not None:
+        raise ValueError("add_norm: RMSNorm (rms=True) takes no bias")
     if _ext.use_native(x):
         y, s = _NormFn.apply(x.contiguous(), residual.contiguous() if residual is not None else None,
                              weight, bias, eps, rms, keep_stream)
