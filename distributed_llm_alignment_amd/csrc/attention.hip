@@ -197,7 +197,12 @@ __device__ __forceinline__ int fwd_persist_logical(int i, int g, int G, int nblk
 // per workgroup (HP = 2: waves 0..NW/2-1 take head 2p, the rest head 2p+1): every K/V tile staged
 // in LDS still feeds 32 NW query rows, but a head's query block is only BQ = 32 NW / HP rows, so
 // the causal diagonal (whose tiles run with part of the waves idle) is HP times narrower.
-template <int D, bool CAUSAL, int NW, int HP, bool MSUB = false>
+// PFX (shared prefix, p.prefix = (ps, pe, qe) per batch row): queries pe <= i < qe also see the
+// keys [ps, pe) below their segment start. A query block that begins at or past pe walks the
+// tiles covering [ps, pe) first, then jumps to the tile of its segment start; the tiles in
+// between are never loaded. Tile index t maps to key offset tile_kt(t), which the staging of
+// tile t+1 and the prefetch of tile t+2 go through as well, so the double buffering is unchanged.
+template <int D, bool CAUSAL, int NW, int HP, bool MSUB = false, bool PFX = false>
 __global__ __launch_bounds__(64 * NW) void attn_fwd_kernel(AttnParams p) {
   constexpr int NT = 64 * NW, BQ = 32 * NW / HP, BK = kFwdKeys;
   constexpr int WPH = NW / HP;  // waves per head
@@ -255,8 +260,31 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_kernel(AttnParams p) {
     wseg_hi = __builtin_amdgcn_readfirstlane(ss[min(q0 + 31, p.Tq - 1)]);
     qseg = ss[min(qi, p.Tq - 1)];
   }
-  const int tile0 = (max(kmin, 0) / BK) * BK;
-  const int ntiles = kmax > tile0 ? (kmax - tile0 + BK - 1) / BK : 0;
+  // shared prefix: per-row scalars (b is workgroup-uniform, so these are scalar loads); pfx_nt
+  // tiles cover the prefix, then the walk skips pfx_jump keys to the segment's first tile (0 when
+  // one tile holds both the prefix end and the segment start: that tile is staged once)
+  int pfx_ps = 0, pfx_pe = 0, pfx_qe = 0, pfx_nt = 0, pfx_jump = 0, pfx_first = 0, pfx_ntiles = 0;
+  if constexpr (PFX) {
+    pfx_ps = p.prefix[3 * b];
+    pfx_pe = p.prefix[3 * b + 1];
+    pfx_qe = p.prefix[3 * b + 2];
+    const int a_lo = max(max(pfx_ps, kbeg), 0), a_hi = min(pfx_pe, kmax);
+    if (qb * BQ >= pfx_pe && qb * BQ < pfx_qe && a_hi > a_lo && kmin > a_lo) {
+      const int first = (a_lo / BK) * BK;
+      const int end_a = first + (a_hi - first + BK - 1) / BK * BK;
+      const int start_b = max((kmin / BK) * BK, end_a);
+      pfx_nt = (end_a - first) / BK;
+      pfx_jump = start_b - end_a;
+      pfx_ntiles = pfx_nt + (kmax > start_b ? (kmax - start_b + BK - 1) / BK : 0);
+      pfx_first = first;
+    }
+  }
+  const int tile0 = (PFX && pfx_nt > 0) ? pfx_first : (max(kmin, 0) / BK) * BK;
+  const int ntiles = (PFX && pfx_nt > 0) ? pfx_ntiles : (kmax > tile0 ? (kmax - tile0 + BK - 1) / BK : 0);
+  auto tile_kt = [&](int t) {
+    if constexpr (PFX) return tile0 + t * BK + (t >= pfx_nt ? pfx_jump : 0);
+    else return tile0 + t * BK;
+  };
 
   bf16x8 kreg[CPT], vreg[CPT];
   // whole tiles load from a wave-uniform (SGPR) tile base + a per-lane 32-bit byte offset fixed for
@@ -402,7 +430,7 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_kernel(AttnParams p) {
     if (ntiles > 0) {
       if constexpr (!EARLY) gload(tile0);
       lwrite(0, tile0);
-      if (ntiles > 1) gload(tile0 + BK);
+      if (ntiles > 1) gload(tile_kt(1));
     }
   };
   {
@@ -432,10 +460,15 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_kernel(AttnParams p) {
   // base plus an immediate: no per-tile buffer select in the VALU stream
   auto step = [&](auto bufc, int t) {
     constexpr int BUF = decltype(bufc)::value;
-    const int kt = tile0 + t * BK;
+    const int kt = tile_kt(t);
     const bf16_t* Ks = Kb[BUF];
     const bf16_t* Vs = Vb[BUF];
     bool active = q0 < p.Tq && kt + BK > wseg_lo;
+    // a tile below the wave's segments is still live when it overlaps the prefix and one of the
+    // wave's 32 queries lies in [pe, qe)
+    if constexpr (PFX)
+      active = q0 < p.Tq && (kt + BK > wseg_lo ||
+                             (kt < pfx_pe && kt + BK > pfx_ps && q0 + 31 >= pfx_pe && q0 < pfx_qe));
     if (CAUSAL) {
       active = active && (kt <= q0 + 31 + p.causal_off);
       if (p.window > 0) active = active && (kt + BK - 1 > q0 + p.causal_off - p.window);
@@ -468,6 +501,10 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_kernel(AttnParams p) {
       if (p.fwd_prio == 1) __builtin_amdgcn_s_setprio(0);
       // mask only tiles that touch a boundary (kv range, causal diagonal, window edge)
       bool need_mask = kt < kbeg || kt + BK > kend || kt < wseg_hi;
+      // interior prefix tiles run unmasked: every key a prefix key, every query in [pe, qe)
+      if constexpr (PFX)
+        need_mask = kt < kbeg || kt + BK > kend ||
+                    (kt < wseg_hi && !(kt >= pfx_ps && kt + BK <= pfx_pe && q0 >= pfx_pe && q0 + 32 <= pfx_qe));
       if (CAUSAL) {
         need_mask = need_mask || (kt + BK - 1 > q0 + p.causal_off);
         if (p.window > 0) need_mask = need_mask || (kt <= q0 + 31 + p.causal_off - p.window);
@@ -483,12 +520,29 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_kernel(AttnParams p) {
           if (p.window > 0) lo = max(lo, qi + p.causal_off - p.window + 1 - base);
         }
         const unsigned span = hi > lo ? static_cast<unsigned>(hi - lo) : 0u;
+        if constexpr (PFX) {
+          // second interval: the prefix keys, for this lane's query if it lies in [pe, qe)
+          const int lo2 = max(kbeg, pfx_ps) - base;
+          const int hi2 = min(min(pfx_pe, kend), qi + p.causal_off + 1) - base;
+          const unsigned span2 =
+              (qi >= pfx_pe && qi < pfx_qe && hi2 > lo2) ? static_cast<unsigned>(hi2 - lo2) : 0u;
 #pragma unroll
-        for (int st = 0; st < 2; ++st) {
+          for (int st = 0; st < 2; ++st) {
 #pragma unroll
-          for (int i = 0; i < 16; ++i) {
-            const int r = 32 * st + (i & 3) + 8 * (i >> 2);
-            sacc[st][i] = static_cast<unsigned>(r - lo) < span ? sacc[st][i] : -INFINITY;
+            for (int i = 0; i < 16; ++i) {
+              const int r = 32 * st + (i & 3) + 8 * (i >> 2);
+              const bool vis = static_cast<unsigned>(r - lo) < span || static_cast<unsigned>(r - lo2) < span2;
+              sacc[st][i] = vis ? sacc[st][i] : -INFINITY;
+            }
+          }
+        } else {
+#pragma unroll
+          for (int st = 0; st < 2; ++st) {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+              const int r = 32 * st + (i & 3) + 8 * (i >> 2);
+              sacc[st][i] = static_cast<unsigned>(r - lo) < span ? sacc[st][i] : -INFINITY;
+            }
           }
         }
       }
@@ -575,8 +629,8 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_kernel(AttnParams p) {
       if (p.fwd_prio == 1) __builtin_amdgcn_s_setprio(0);
     }
     if (t + 1 < ntiles) {  // stage tile t+1 into the other buffer, prefetch tile t+2
-      lwrite(BUF ^ 1, kt + BK);
-      if (t + 2 < ntiles) gload(kt + 2 * BK);
+      lwrite(BUF ^ 1, PFX ? tile_kt(t + 1) : kt + BK);
+      if (t + 2 < ntiles) gload(PFX ? tile_kt(t + 2) : kt + 2 * BK);
     }
     __syncthreads();
   };
@@ -1067,6 +1121,19 @@ __global__ __launch_bounds__(256) void attn_bwd_delta_kernel(const bf16_t* __res
 // Query tiles [qt0, qend) swept by the workgroup that owns keys [k0, k0 + 256): every query
 // that can see one of its keys. Shared by the main kernel and the dQ reduce pass (which must
 // know exactly which slab rows a key block wrote).
+// minimum / maximum of v over the 32 keys of a sub-tile (lanes l and l + 32 hold the same key's
+// value), wave-uniform; once per key block, outside the query loop
+__device__ __forceinline__ void wave_minmax32(int v, int& lo, int& hi) {
+  int a = v, b = v;
+#pragma unroll
+  for (int d = 1; d < 32; d <<= 1) {
+    a = min(a, __shfl_xor(a, d));
+    b = max(b, __shfl_xor(b, d));
+  }
+  lo = __builtin_amdgcn_readfirstlane(a);
+  hi = __builtin_amdgcn_readfirstlane(b);
+}
+
 template <bool CAUSAL>
 __device__ __forceinline__ void bwd_q_range(int k0, int Tq, int causal_off, int window, int& qt0,
                                             int& qend) {
@@ -1233,8 +1300,9 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_kernel(AttnBwdParams p) {
 #pragma unroll
   for (int g = 0; g < 4; ++g) woff[g] = ds_off(l32, 2 * g + h);
 
-  // packed sequences: key kj is seen only by queries < seg_end[kj] (non-decreasing in kj); per
-  // sub-tile j: this lane's bound and the wave-uniform bounds of its first / last key
+  // packed sequences: key kj is seen only by queries < seg_end[kj]; per sub-tile j: this lane's
+  // bound and the wave-uniform minimum / maximum over its 32 keys (the first / last key's while
+  // seg_end is non-decreasing; a shared prefix makes it drop at the prefix end)
   const int* se = p.seg_end ? p.seg_end + static_cast<int64_t>(b) * p.Tk : nullptr;
   int kse[2], kse_lo[2], kse_hi[2];
 #pragma unroll
@@ -1243,8 +1311,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_kernel(AttnBwdParams p) {
     if (se) {
       const int kj0 = kw + 32 * j;
       kse[j] = se[min(kj0 + l32, p.Tk - 1)];
-      kse_lo[j] = __builtin_amdgcn_readfirstlane(se[min(kj0, p.Tk - 1)]);
-      kse_hi[j] = __builtin_amdgcn_readfirstlane(se[min(kj0 + 31, p.Tk - 1)]);
+      wave_minmax32(kse[j], kse_lo[j], kse_hi[j]);
     }
   }
 
@@ -1717,8 +1784,7 @@ __global__ __launch_bounds__(512) void attn_bwd8_kernel(AttnBwdParams p) {
   int kse = 0x7fffffff, kse_lo = 0x7fffffff, kse_hi = 0x7fffffff;
   if (se) {
     kse = se[min(kw + l32, p.Tk - 1)];
-    kse_lo = __builtin_amdgcn_readfirstlane(se[min(kw, p.Tk - 1)]);
-    kse_hi = __builtin_amdgcn_readfirstlane(se[min(kw + 31, p.Tk - 1)]);
+    wave_minmax32(kse, kse_lo, kse_hi);
   }
 
   f32x16 dk[DT], dv[DT];
@@ -2318,6 +2384,18 @@ static void fwd_launch(const AttnParams& p0, bool causal, hipStream_t st) {
   }
   const int nqb = (p.Tq + BQ - 1) / BQ;
   const int64_t nblk = static_cast<int64_t>(nqb) * (p.Hq / HP) * p.B;
+  const dim3 grid(static_cast<unsigned>(nblk));
+  if (p.prefix != nullptr) {  // shared prefix: this kernel only (the persistent one has no second range)
+    if (!causal || p.seg_start == nullptr) throw std::invalid_argument("attn_fwd: prefix needs causal segs");
+    if constexpr (D == 128) {
+      if (p.fwd_msub) {
+        attn_fwd_kernel<D, true, NW, HP, true, true><<<grid, 64 * NW, 0, st>>>(p);
+        return;
+      }
+    }
+    attn_fwd_kernel<D, true, NW, HP, false, true><<<grid, 64 * NW, 0, st>>>(p);
+    return;
+  }
   if (fwd_persist(p.Tk) && nblk < (int64_t(1) << 30)) {
     // one 8-wave workgroup per CU (230 VGPRs: two waves per SIMD), never more than the blocks
     const int grid = static_cast<int>(std::min<int64_t>(nblk, device_cus()));
@@ -2325,7 +2403,6 @@ static void fwd_launch(const AttnParams& p0, bool causal, hipStream_t st) {
     else attn_fwd_persist_kernel<D, false, NW, HP><<<grid, 64 * NW, 0, st>>>(p, static_cast<int>(nblk));
     return;
   }
-  const dim3 grid(static_cast<unsigned>(nblk));
   if constexpr (D == 128) {
     if (p.fwd_msub) {
       if (causal) attn_fwd_kernel<D, true, NW, HP, true><<<grid, 64 * NW, 0, st>>>(p);

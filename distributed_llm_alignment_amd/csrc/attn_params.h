@@ -23,6 +23,9 @@ struct AttnParams {
   const int* kv_start;  // [B] or null
   const int* kv_end;    // [B] or null
   const int* seg_start;  // [B, Tq] or null: packed sequences, query i sees keys >= seg_start[i]
+  // shared prefix [B, 3] = (ps, pe, qe) or null (needs seg_start, causal self-attention, no
+  // window): queries pe <= i < qe also see the keys ps <= j < pe below their segment start
+  const int* prefix;
   // RoPE on load (full rotary, self-attention): q / k are the un-rotated projections; the kernel
   // rotates Q in registers and every K row as it is staged into LDS; null = inputs pre-rotated
   const float* rope_cos;  // [max_pos, D/2] fp32

@@ -437,7 +437,8 @@ std::tuple<at::Tensor, at::Tensor> attn_fwd(const at::Tensor& q, const at::Tenso
                                             const c10::optional<at::Tensor>& rope_cos,
                                             const c10::optional<at::Tensor>& rope_sin,
                                             const c10::optional<at::Tensor>& rope_pos,
-                                            const c10::optional<at::Tensor>& q_rot, bool rope_k) {
+                                            const c10::optional<at::Tensor>& q_rot, bool rope_k,
+                                            const c10::optional<at::Tensor>& prefix) {
   check_bthd(q, "q");
   check_bthd(k, "k");
   check_bthd(v, "v");
@@ -472,6 +473,15 @@ std::tuple<at::Tensor, at::Tensor> attn_fwd(const at::Tensor& q, const at::Tenso
   p.kv_start = (kv_start && kv_start->defined()) ? kv_start->data_ptr<int>() : nullptr;
   p.kv_end = (kv_end && kv_end->defined()) ? kv_end->data_ptr<int>() : nullptr;
   p.seg_start = seg_ptr(segs, B, Tq, Tk, causal, causal_off, q, 0);
+  if (prefix && prefix->defined()) {  // shared prefix (ps, pe, qe) per batch row
+    TORCH_CHECK(prefix->scalar_type() == at::kInt && prefix->is_contiguous() && prefix->dim() == 2 &&
+                    prefix->size(0) == B && prefix->size(1) == 3,
+                "prefix must be contiguous int32 [B, 3]");
+    TORCH_CHECK(p.seg_start != nullptr && causal && causal_off == 0 && Tq == Tk && window <= 0,
+                "prefix needs segs and causal self-attention without a window");
+    same_device(q, *prefix);
+    p.prefix = prefix->data_ptr<int>();
+  }
   rope_args(rope_cos, rope_sin, rope_pos, q, B, Tq, Tk, D, causal_off, &p.rope_cos, &p.rope_sin,
             &p.rope_pos);
   TORCH_CHECK(p.rope_cos == nullptr || D != 80, "RoPE on load: full-rotary head dims 64 / 128 only");
@@ -1480,7 +1490,7 @@ TORCH_LIBRARY(dla, m) {
   m.def("gelu_bwd(Tensor x, Tensor dy) -> Tensor");
   m.def("rope_fwd(Tensor qkv, Tensor cos, Tensor sin, Tensor? pos, int Hq, int Hkv, int D, int rot, int T, int pos_offset) -> (Tensor, Tensor)");
   m.def("rope_bwd(Tensor dq, Tensor dk, Tensor(a!) dqkv, Tensor cos, Tensor sin, Tensor? pos, int Hq, int Hkv, int D, int rot, int T, int pos_offset) -> ()");
-  m.def("attn_fwd(Tensor q, Tensor k, Tensor v, float scale, bool causal, int causal_off, int window, Tensor? kv_start, Tensor? kv_end, Tensor? segs=None, Tensor? rope_cos=None, Tensor? rope_sin=None, Tensor? rope_pos=None, Tensor(a!)? q_rot=None, bool rope_k=True) -> (Tensor, Tensor)");
+  m.def("attn_fwd(Tensor q, Tensor k, Tensor v, float scale, bool causal, int causal_off, int window, Tensor? kv_start, Tensor? kv_end, Tensor? segs=None, Tensor? rope_cos=None, Tensor? rope_sin=None, Tensor? rope_pos=None, Tensor(a!)? q_rot=None, bool rope_k=True, Tensor? prefix=None) -> (Tensor, Tensor)");
   m.def("attn_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse2, Tensor(a!) dq, Tensor(b!) dk, Tensor(c!) dv, float scale, bool causal, int causal_off, int window, Tensor? kv_start, Tensor? kv_end, Tensor? segs=None, Tensor? rope_cos=None, Tensor? rope_sin=None, Tensor? rope_pos=None, bool rope_inputs=False) -> ()");
   m.def("attn_stamps(Tensor like) -> Tensor");
   m.def("attn_fwd_switch(str name, int value) -> int", &dla::attn_fwd_switch);

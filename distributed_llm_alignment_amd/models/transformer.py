@@ -67,6 +67,71 @@ def packed_layout(segment_ids: torch.Tensor):
     return pos, torch.stack([start, end]).to(torch.int32).contiguous()
 
 
+def shared_prefix_pack(seqs: torch.Tensor, mask: Optional[torch.Tensor], prompt_len: int, G: int):
+    """Pack each group of `G` rollouts of one prompt into one row that holds the prompt once.
+    `seqs` / `mask` [S, T]: rows bG .. bG+G-1 have equal columns 0:prompt_len (what
+    `generate(num_return_sequences=G)` returns; not checked). With Lp = prompt_len - 1 and
+    n1 = T - Lp, packed row b of length L = Lp + G * n1 is
+
+        [ seqs[bG, 0:Lp] | seqs[bG, Lp:T] | seqs[bG+1, Lp:T] | ... | seqs[bG+G-1, Lp:T] ]
+
+    so the last prompt token opens every response segment and each rollout's first action has a
+    row of its own. Returns (ids [S/G, L], positions [S/G, L] int32, segs [2, S/G, L] int32,
+    prefix [S/G, 3] int32, slot_map [S/G, L] int64), on device, no host sync:
+      * positions: the slot's grid column minus the row's first real column, clamped at 0 (what
+        `attention_layout` gives the unshared run);
+      * segs / prefix = (ps, pe, qe) = (first real column, Lp, L): a segment slot sees its
+        segment causally plus the prefix slots [ps, pe) (`ops.attention` forward form). Prefix
+        slots carry (seg_start, seg_end) = (ps, L), segment slots their own bounds, and the
+        left-padding slots below ps (ps, 0): no query sees them in either form of the mask;
+      * slot_map: the flat index row * T + column of the grid cell a segment slot holds, -1 on
+        prefix slots (`shared_prefix_unpack`)."""
+    S, T = seqs.shape
+    if G < 1 or S % G != 0:
+        raise ValueError(f"shared prefix: {S} rows do not split into groups of {G}")
+    if not 2 <= prompt_len <= T - 1:
+        raise ValueError(f"shared prefix: prompt_len {prompt_len} outside [2, {T - 1}]")
+    dev = seqs.device
+    B, Lp = S // G, prompt_len - 1
+    n1 = T - Lp
+    L = Lp + G * n1
+    slot = torch.arange(L, device=dev)
+    g = (slot - Lp).clamp(min=0) // n1  # segment of a slot (0 on the prefix)
+    col = torch.where(slot < Lp, slot, Lp + (slot - Lp).clamp(min=0) % n1)
+    rows = torch.arange(B, device=dev).unsqueeze(1) * G + g.unsqueeze(0)  # [B, L] grid row
+    flat = rows * T + col.unsqueeze(0)
+    ids = seqs.reshape(-1)[flat]
+    is_seg = (slot >= Lp).unsqueeze(0).expand(B, L)
+    if mask is None:
+        first = torch.zeros(S, dtype=torch.int32, device=dev)
+        pos_grid = torch.arange(T, device=dev, dtype=torch.int32).expand(S, T)
+    else:
+        first, _, pos_grid = attention_layout(mask)
+    positions = pos_grid.reshape(-1)[flat].contiguous()
+    ps = first[::G].to(torch.int32).clamp(max=Lp)  # [B]
+    seg_lo = (Lp + g * n1).to(torch.int32).unsqueeze(0).expand(B, L)
+    slot32 = slot.to(torch.int32).unsqueeze(0)
+    start = torch.where(is_seg, seg_lo, ps.unsqueeze(1).expand(B, L))
+    end = torch.where(is_seg, seg_lo + n1,
+                      torch.where(slot32 >= ps.unsqueeze(1), torch.full_like(seg_lo, L), torch.zeros_like(seg_lo)))
+    segs = torch.stack([start, end]).to(torch.int32).contiguous()
+    prefix = torch.stack([ps, torch.full_like(ps, Lp), torch.full_like(ps, L)], dim=1).contiguous()
+    slot_map = torch.where(is_seg, flat, torch.full_like(flat, -1))
+    return ids, positions, segs, prefix, slot_map
+
+
+def shared_prefix_unpack(x_packed: torch.Tensor, slot_map: torch.Tensor, S: int, T: int) -> torch.Tensor:
+    """Scatter per-slot values [S/G, L, ...] back into the [S, T, ...] grid: a segment slot's value
+    lands in its grid cell; columns below prompt_len - 1 (held only by prefix slots) are exactly 0."""
+    seg = slot_map >= 0
+    tail = x_packed.shape[2:]
+    m = seg.view(*seg.shape, *([1] * len(tail)))
+    src = torch.where(m, x_packed, torch.zeros_like(x_packed)).reshape(-1, *tail)
+    out = x_packed.new_zeros((S * T, *tail))
+    # every grid cell is the target of at most one segment slot; prefix slots add 0 to cell 0
+    return out.index_add(0, slot_map.clamp(min=0).reshape(-1), src).view(S, T, *tail)
+
+
 class Attention(nn.Module):
     def __init__(self, cfg: ModelConfig, device=None, dtype=None):
         super().__init__()
@@ -85,7 +150,7 @@ class Attention(nn.Module):
         self.lora_o = None
 
     def forward(self, h, rope, kv_start, kv_end, positions, cache=None, layer_idx=0, segs=None,
-                resid=None):
+                resid=None, prefix=None):
         """`resid` (no TP, no o bias): return resid + o_proj(attention), the add inside the o GEMM."""
         cfg = self.cfg
         seq = self.tp_seq if (h.dim() == 2 and cache is None) else None
@@ -114,11 +179,11 @@ class Attention(nn.Module):
                 qkv, self.h_local, self.kv_local, cfg.head_dim,
                 lambda full, hq, hkv: ops.qkv_attention(full, hq, hkv, cfg.head_dim, rope, causal=True,
                                                         window=window, kv_start=kv_start, kv_end=kv_end,
-                                                        positions=positions, segs=segs))
+                                                        positions=positions, segs=segs, prefix=prefix))
         elif cache is None:
             a = ops.qkv_attention(qkv, self.h_local, self.kv_local, cfg.head_dim, rope,
                                   causal=True, window=window, kv_start=kv_start, kv_end=kv_end,
-                                  positions=positions, segs=segs)
+                                  positions=positions, segs=segs, prefix=prefix)
         else:
             a = cache.attend(layer_idx, qkv, rope, window)
         if self.tp is None:
@@ -363,7 +428,8 @@ class DecoderLayer(nn.Module):
                 and isinstance(mlp, MLP) and at.tp is None and mlp.tp is None and at.o_bias is None
                 and mlp.down_bias is None)
 
-    def forward(self, x, resid, rope, kv_start, kv_end, positions, cache=None, layer_idx=0, segs=None):
+    def forward(self, x, resid, rope, kv_start, kv_end, positions, cache=None, layer_idx=0, segs=None,
+                prefix=None):
         cfg = self.cfg
         rms = cfg.norm_type == "rms"
         seq = self.tp_seq if x.dim() == 2 else None
@@ -379,9 +445,10 @@ class DecoderLayer(nn.Module):
             h, s = ops.add_norm(x, resid, self.ln1_w, self.ln1_b, cfg.norm_eps, rms, keep_stream=True)
             if rc == "attention":
                 s = checkpoint(self.attn, h, rope, kv_start, kv_end, positions, None, layer_idx, segs, s,
-                               use_reentrant=False)
+                               prefix, use_reentrant=False)
             else:
-                s = self.attn(h, rope, kv_start, kv_end, positions, None, layer_idx, segs, resid=s)
+                s = self.attn(h, rope, kv_start, kv_end, positions, None, layer_idx, segs, resid=s,
+                              prefix=prefix)
             h, s = ops.add_norm(s, None, self.ln2_w, self.ln2_b, cfg.norm_eps, rms, keep_stream=True)
             if rc == "mlp":
                 return checkpoint(self.mlp, h, s, use_reentrant=False), None
@@ -389,9 +456,9 @@ class DecoderLayer(nn.Module):
         h, resid = ops.add_norm(x, resid, w_(self.ln1_w, seq), w_(self.ln1_b, seq), cfg.norm_eps, rms)
         if rc == "attention":  # keep h; drop q/k/v, O and the LSE; recompute them in backward
             a = checkpoint(self.attn, h, rope, kv_start, kv_end, positions, None, layer_idx, segs,
-                           use_reentrant=False)
+                           None, prefix, use_reentrant=False)
         else:
-            a = self.attn(h, rope, kv_start, kv_end, positions, cache, layer_idx, segs)
+            a = self.attn(h, rope, kv_start, kv_end, positions, cache, layer_idx, segs, prefix=prefix)
         mlp = (lambda t: checkpoint(self.mlp, t, use_reentrant=False)) if rc == "mlp" else self.mlp
         if cfg.parallel_block:
             return a + mlp(h), resid
@@ -528,10 +595,14 @@ class CausalLM(nn.Module):
         return x
 
     def forward(self, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
-                cache=None, segment_ids: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """`segment_ids` (optional, [B, T]): several sequences packed per row (see packed_layout)."""
+                cache=None, segment_ids: Optional[torch.Tensor] = None, packed=None) -> torch.Tensor:
+        """`segment_ids` (optional, [B, T]): several sequences packed per row (see packed_layout).
+        `packed` (optional): a prepared `(positions, segs, prefix)` layout for `input_ids`, as
+        `shared_prefix_pack` returns it; `attention_mask` and `segment_ids` are then not used."""
         if cache is not None:
             return self._forward_cached(input_ids, attention_mask, cache)
+        if packed is not None and (self.sp is not None or self.tp_seq is not None):
+            raise ValueError("a packed (shared-prefix) layout is not supported with sequence parallelism")
         sp = self.sp
         if sp is not None:  # full (padded) masks / positions drive attention; tokens are sliced
             from ..parallel.sequence import sp_shard_inputs
@@ -542,6 +613,10 @@ class CausalLM(nn.Module):
         segs = None
         if segment_ids is not None:
             positions, segs = packed_layout(segment_ids)
+        prefix = None
+        if packed is not None:
+            kv_start = kv_end = None
+            positions, segs, prefix = packed
         tp_seq = self.tp_seq if (sp is None and self.tp_seq is not None
                                  and input_ids.numel() % self.tp_seq.tp == 0) else None
         if sp is not None or tp_seq is not None:
@@ -557,13 +632,13 @@ class CausalLM(nn.Module):
         resid = None
         for i, layer in enumerate(self.layers):
             if self.layer_devices is not None:
-                x, resid, kv_start, kv_end, positions, segs = _hop(self.layer_devices[i], x, resid,
-                                                                   kv_start, kv_end, positions, segs)
+                x, resid, kv_start, kv_end, positions, segs, prefix = _hop(
+                    self.layer_devices[i], x, resid, kv_start, kv_end, positions, segs, prefix)
             if self.gradient_checkpointing and self.training and torch.is_grad_enabled():
                 x, resid = checkpoint(layer, x, resid, self.rope, kv_start, kv_end, positions, None, 0,
-                                      segs, use_reentrant=False)
+                                      segs, prefix, use_reentrant=False)
             else:
-                x, resid = layer(x, resid, self.rope, kv_start, kv_end, positions, segs=segs)
+                x, resid = layer(x, resid, self.rope, kv_start, kv_end, positions, segs=segs, prefix=prefix)
         if self.layer_devices is not None:
             x, resid = _hop(self.norm_w.device, x, resid)
         if tp_seq is not None:
@@ -713,7 +788,7 @@ class CausalLM(nn.Module):
 
     def token_logprobs(self, input_ids, attention_mask=None, with_entropy: bool = False,
                        temperature: float = 1.0, keep: Optional[torch.Tensor] = None,
-                       keep_rows: Optional[torch.Tensor] = None):
+                       keep_rows: Optional[torch.Tensor] = None, shared_prefix=None):
         """[S, T] log p(x_{t+1} | x_<=t) at every scored position (0 elsewhere): the per-action
         grid of token-level RL objectives (PPO). `with_entropy`: returns (lp, ent), ent [S, T] the
         entropy of p(. | x_<=t) at the same positions, from the same LM-head pass. `temperature`:
@@ -722,7 +797,13 @@ class CausalLM(nn.Module):
         `keep_rows` (int64 [S, T], < 0 = full vocabulary): position (s, t) is scored over the
         vocabulary subset packed in row keep_rows[s, t] of `keep`, the set a top-k / top-p sampler
         drew x_{t+1} from (`generate(return_keep_mask=True)`, `objectives.keep_row_grid`). Not with
-        `with_entropy`, a vocab-parallel head or sequence parallelism (ValueError)."""
+        `with_entropy`, a vocab-parallel head or sequence parallelism (ValueError).
+        `shared_prefix=(G, prompt_len)`: the rows are groups of G rollouts of one prompt (equal
+        columns 0:prompt_len); the model runs once on the `shared_prefix_pack` layout, each group's
+        prompt computed once, and only columns >= prompt_len - 1 are scored (0 below)."""
+        if shared_prefix is not None:
+            return self._token_logprobs_shared(input_ids, attention_mask, shared_prefix, with_entropy,
+                                               temperature, keep, keep_rows)
         if keep is not None or keep_rows is not None:
             if with_entropy:
                 raise ValueError("the entropy under a keep mask is not implemented (with_entropy with keep)")
@@ -745,6 +826,33 @@ class CausalLM(nn.Module):
         if self.sp is not None:
             lp = self.sp.gather(lp, dim=1)[:, :input_ids.shape[1]]
         return lp
+
+    def _token_logprobs_shared(self, input_ids, attention_mask, shared_prefix, with_entropy, temperature,
+                               keep, keep_rows):
+        G, prompt_len = shared_prefix
+        if self.vocab_parallel is not None:
+            raise ValueError("shared_prefix is not supported with a vocab-parallel LM head")
+        if self.sp is not None or self.tp_seq is not None:
+            raise ValueError("shared_prefix is not supported with sequence parallelism")
+        S, T = input_ids.shape
+        ids, positions, segs, prefix, slot_map = shared_prefix_pack(input_ids, attention_mask, prompt_len, G)
+        h = self(ids, None, packed=(positions, segs, prefix))
+        # targets of the grid, gathered into the packed slots: prefix slots are not scored, and a
+        # segment's last slot is the grid's last column, which shifted_targets already ignores
+        seg = slot_map >= 0
+        src = slot_map.clamp(min=0)
+        tgt = ops.shifted_targets(input_ids, attention_mask)[0].reshape(-1)[src]
+        tgt = torch.where(seg, tgt, torch.full_like(tgt, -100))
+        if keep is not None or keep_rows is not None:
+            if keep_rows is not None:
+                kr = keep_rows.reshape(-1)[src]
+                keep_rows = torch.where(seg, kr, torch.full_like(kr, -1))
+            lp = self._masked_token_logprob(h, tgt, with_entropy, temperature, keep, keep_rows)
+            return shared_prefix_unpack(lp, slot_map, S, T)
+        if with_entropy:
+            lp, ent = self._masked_token_logprob(h, tgt, True, temperature)
+            return shared_prefix_unpack(lp, slot_map, S, T), shared_prefix_unpack(ent, slot_map, S, T)
+        return shared_prefix_unpack(self._masked_token_logprob(h, tgt, temperature=temperature), slot_map, S, T)
 
     def causal_lm_loss(self, input_ids, labels, attention_mask=None, segment_ids=None):
         """HF ForCausalLMLoss (train_sft.py:145-146): mean token NLL over labels != -100.

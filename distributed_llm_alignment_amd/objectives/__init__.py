@@ -207,6 +207,16 @@ def rollout_is_stats(rollout_logp: torch.Tensor, trainer_lp: torch.Tensor, act: 
     return {"is_weight": w, "rollout_is": {f"rollout_{k}": v for k, v in met.items() if k != "tokens"}}
 
 
+def _share_kw(shared_prefix) -> dict:
+    """`token_logprobs` keyword of prefix sharing (`shared_prefix=(G, prompt_len)`: every group's
+    prompt computed once, `models.transformer.shared_prefix_pack`): none when off, so a default run
+    makes the calls (and launches the kernels) it always made."""
+    if shared_prefix is None:
+        return {}
+    G, prompt_len = shared_prefix
+    return {"shared_prefix": (int(G), int(prompt_len))}
+
+
 def _temp_kw(temperature: float) -> dict:
     """`token_logprobs` keywords for the step's log-prob temperature: none at 1.0, so a default
     run makes the calls (and launches the kernels) it always made."""
@@ -281,7 +291,8 @@ def ppo_critic_stream(device: torch.device):
 
 def token_logprobs_entropy(policy, seqs, mask, act, entropy_coef: float = 0.0, log_entropy: bool = False,
                            n_act: Optional[torch.Tensor] = None, temperature: float = 1.0,
-                           keep: Optional[torch.Tensor] = None, keep_rows: Optional[torch.Tensor] = None):
+                           keep: Optional[torch.Tensor] = None, keep_rows: Optional[torch.Tensor] = None,
+                           shared_prefix=None):
     """Token log-probs of a PPO / GRPO (micro-)batch and, when `entropy_coef != 0` or
     `log_entropy`, the policy entropy from the same LM-head pass: returns (lp, bonus, entropy).
     `bonus` = entropy_coef * sum(ent * act) / n_act (None when the coefficient is 0: the entropy is
@@ -290,8 +301,9 @@ def token_logprobs_entropy(policy, seqs, mask, act, entropy_coef: float = 0.0, l
     this batch's own by default. `entropy` is this batch's detached mean over action tokens (None
     when off). `temperature`: log-probs and entropy of softmax(logits / temperature). `keep` /
     `keep_rows`: the log-probs over the kept sets; the entropy under a kept set does not exist yet, so
-    an entropy bonus or `log_entropy` together with them raises ValueError."""
-    tkw = {**_temp_kw(temperature), **_keep_kw(keep, keep_rows)}
+    an entropy bonus or `log_entropy` together with them raises ValueError. `shared_prefix`
+    (`(G, prompt_len)`, whole groups of G rows): the forward shares each group's prompt."""
+    tkw = {**_temp_kw(temperature), **_keep_kw(keep, keep_rows), **_share_kw(shared_prefix)}
     if keep is not None and (entropy_coef != 0 or log_entropy):
         raise ValueError("entropy_coef / log_entropy are not supported together with a keep mask")
     if entropy_coef == 0 and not log_entropy:
@@ -362,7 +374,8 @@ def grpo_rollout_stats(policy, ref, seqs, mask, prompt_len: int, scores, G: int,
                        old_logp: Optional[torch.Tensor] = None, rollout_logp: Optional[torch.Tensor] = None,
                        is_cap: float = 2.0, is_floor: Optional[float] = None, is_level: str = "token",
                        is_mode: str = "truncate", temperature: float = 1.0,
-                       keep: Optional[torch.Tensor] = None, keep_rows: Optional[torch.Tensor] = None):
+                       keep: Optional[torch.Tensor] = None, keep_rows: Optional[torch.Tensor] = None,
+                       shared_prefix=None):
     """GRPO targets for one batch of group rollouts (rows p*G .. p*G+G-1 sample prompt p). The
     reward is the reward-model score alone (the KL lives in the loss); a rollout's advantage is its
     score standardised inside its group. The reference's token log-probs are skipped entirely
@@ -374,8 +387,12 @@ def grpo_rollout_stats(policy, ref, seqs, mask, prompt_len: int, scores, G: int,
     runs, as with `need_old`) and adds `is_weight` / `rollout_is` (`rollout_is_stats` with the four
     `is_*` settings): truncated importance weights for `grpo_loss`, computed once per rollout batch. `temperature`:
     every log-prob here is of softmax(logits / temperature); grids passed in must be at the same.
-    `keep` / `keep_rows`: as in `ppo_rollout_stats`."""
-    tkw = {**_temp_kw(temperature), **_keep_kw(keep, keep_rows)}
+    `keep` / `keep_rows`: as in `ppo_rollout_stats`. `shared_prefix=(G, prompt_len)`, the same
+    keyword as `grpo_loss` takes (it must repeat this call's `G` and `prompt_len`: ValueError): the
+    reference and old-policy forwards run on the prefix-shared layout, each group's prompt once."""
+    if shared_prefix is not None and tuple(int(x) for x in shared_prefix) != (int(G), int(prompt_len)):
+        raise ValueError(f"shared_prefix {tuple(shared_prefix)} differs from (G, prompt_len) = ({G}, {prompt_len})")
+    tkw = {**_temp_kw(temperature), **_keep_kw(keep, keep_rows), **_share_kw(shared_prefix)}
     act = action_mask(mask, prompt_len)
     adv, gm = ops.group_advantages(scores, G, scale_std)
     ref_lp = ref.token_logprobs(seqs, mask, **tkw) if beta != 0 else None
@@ -397,7 +414,8 @@ def grpo_loss(policy, seqs, mask, stats: Dict[str, torch.Tensor], clip_low: floa
               max_len: Optional[int] = None, denom: Optional[torch.Tensor] = None,
               entropy_coef: float = 0.0, log_entropy: bool = False, n_act: Optional[torch.Tensor] = None,
               temperature: float = 1.0, keep: Optional[torch.Tensor] = None,
-              keep_rows: Optional[torch.Tensor] = None, importance_level: str = "token"):
+              keep_rows: Optional[torch.Tensor] = None, importance_level: str = "token",
+              shared_prefix=None):
     """Token-level clipped surrogate + beta * k3 KL to the reference (HIP fused fwd+bwd) on one
     (micro-)batch of rollouts; `stats` from `grpo_rollout_stats`, sliced to the same rows.
     `entropy_coef` / `log_entropy` / `n_act`: the entropy bonus and metric of
@@ -405,11 +423,13 @@ def grpo_loss(policy, seqs, mask, stats: Dict[str, torch.Tensor], clip_low: floa
     token. `temperature`: the policy's log-probs and entropy at that temperature (as in `stats`).
     `keep` (+ `keep_rows`, default `stats["keep_rows"]`): the policy's log-probs over the kept sets.
     `importance_level`: "token", or "sequence" for one length-normalised ratio per rollout (GSPO;
-    `ops.grpo_loss`)."""
+    `ops.grpo_loss`). `shared_prefix=(G, prompt_len)`: the rows are whole groups of G rollouts and
+    the policy forward and backward run on the prefix-shared layout (each prompt once)."""
     if keep is not None and keep_rows is None:
         keep_rows = stats.get("keep_rows")
     lp, bonus, entropy = token_logprobs_entropy(policy, seqs, mask, stats["act"], entropy_coef, log_entropy,
-                                                n_act, temperature=temperature, keep=keep, keep_rows=keep_rows)
+                                                n_act, temperature=temperature, keep=keep, keep_rows=keep_rows,
+                                                shared_prefix=shared_prefix)
     loss, m = ops.grpo_loss(lp, stats.get("old_logp"), stats.get("ref_logp"), stats["advantages"],
                             stats["act"], clip_low, clip_high, beta, loss_type, max_len, denom,
                             is_weight=stats.get("is_weight"), importance_level=importance_level)

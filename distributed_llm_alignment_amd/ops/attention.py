@@ -81,12 +81,21 @@ def _ref_rope(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: torch.
     return torch.cat([o1, o2, rest], dim=-1).to(x.dtype)
 
 
-def _visibility(B, Tq, Tk, causal, causal_off, window, kv_start, kv_end, device, segs=None):
+def _visibility(B, Tq, Tk, causal, causal_off, window, kv_start, kv_end, device, segs=None,
+                prefix=None):
     qi = torch.arange(Tq, device=device).view(1, Tq, 1)
     kj = torch.arange(Tk, device=device).view(1, 1, Tk)
     ok = torch.ones(B, Tq, Tk, dtype=torch.bool, device=device)
     if segs is not None:  # packed sequences: query i sees keys >= seg_start[i] (block diagonal)
         ok = ok & (kj >= segs[0].view(B, Tq, 1).to(device))
+    if prefix is not None:
+        # shared prefix (ps, pe, qe): queries pe <= i < qe also see the keys ps <= j < pe that lie
+        # below their segment start (the forward form of the mask)
+        if segs is None or not causal or causal_off != 0 or Tq != Tk or (window and window > 0):
+            raise ValueError("prefix needs segs and causal self-attention without a window")
+        pf = prefix.to(device).view(B, 3, 1, 1)
+        ps, pe, qe = pf[:, 0], pf[:, 1], pf[:, 2]
+        ok = ok | ((kj >= ps) & (kj < pe) & (qi >= pe) & (qi < qe))
     if kv_start is not None:
         ok = ok & (kj >= kv_start.view(B, 1, 1).to(device))
     if kv_end is not None:
@@ -99,7 +108,7 @@ def _visibility(B, Tq, Tk, causal, causal_off, window, kv_start, kv_end, device,
 
 
 def ref_attention(q, k, v, scale, causal=True, causal_off=0, window=0, kv_start=None,
-                  kv_end=None, segs=None) -> torch.Tensor:
+                  kv_end=None, segs=None, prefix=None) -> torch.Tensor:
     """q [B, Tq, Hq, D], k/v [B, Tk, Hkv, D] -> [B, Tq, Hq, D] (fp32 math)."""
     B, Tq, Hq, D = q.shape
     Tk, Hkv = k.shape[1], k.shape[2]
@@ -108,7 +117,7 @@ def ref_attention(q, k, v, scale, causal=True, causal_off=0, window=0, kv_start=
     kf = k.float().transpose(1, 2).repeat_interleave(rep, dim=1)
     vf = v.float().transpose(1, 2).repeat_interleave(rep, dim=1)
     s = torch.matmul(qf, kf.transpose(-1, -2)) * scale
-    ok = _visibility(B, Tq, Tk, causal, causal_off, window, kv_start, kv_end, q.device, segs)
+    ok = _visibility(B, Tq, Tk, causal, causal_off, window, kv_start, kv_end, q.device, segs, prefix)
     s = s.masked_fill(~ok.unsqueeze(1), float("-inf"))
     p = torch.softmax(s, dim=-1)
     p = torch.nan_to_num(p, nan=0.0)
@@ -145,7 +154,7 @@ class _FusedQKVAttnFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, qkv, cos, sin, pos, Hq, Hkv, D, rot, scale, causal, window, kv_start, kv_end,
-                segs=None):
+                segs=None, prefix=None):
         ops = _ext.require()
         B, T, C = qkv.shape
         q2 = qkv.reshape(B * T, C)
@@ -161,7 +170,7 @@ class _FusedQKVAttnFn(torch.autograd.Function):
             q_rot = torch.empty((B, T, Hq, D), dtype=qkv.dtype, device=qkv.device) \
                 if ctx.needs_input_grad[0] else None
             o, lse2 = ops.attn_fwd(q4, k4, v4, float(scale), bool(causal), 0, int(window), kv_start,
-                                   kv_end, segs, cos, sin, pos, q_rot, False)
+                                   kv_end, segs, cos, sin, pos, q_rot, False, prefix)
             ctx.save_for_backward(qkv, q_rot, k4, o, lse2, cos, sin, pos, kv_start, kv_end, segs)
         elif on_load:
             # RoPE on load: the kernel rotates Q in registers and K as it stages it; the rotated
@@ -171,7 +180,7 @@ class _FusedQKVAttnFn(torch.autograd.Function):
             q_rot = torch.empty((B, T, Hq, D), dtype=qkv.dtype, device=qkv.device) \
                 if ctx.needs_input_grad[0] else None
             o, lse2 = ops.attn_fwd(q4, k4, v4, float(scale), bool(causal), 0, int(window), kv_start,
-                                   kv_end, segs, cos, sin, pos, q_rot)
+                                   kv_end, segs, cos, sin, pos, q_rot, True, prefix)
             ctx.save_for_backward(qkv, q_rot, None, o, lse2, cos, sin, pos, kv_start, kv_end, segs)
         else:
             if rot > 0:
@@ -182,7 +191,7 @@ class _FusedQKVAttnFn(torch.autograd.Function):
                 q4 = qkv.as_strided((B, T, Hq, D), (T * C, C, D, 1), off)
                 k4 = qkv.as_strided((B, T, Hkv, D), (T * C, C, D, 1), off + Hq * D)
             o, lse2 = ops.attn_fwd(q4, k4, v4, float(scale), bool(causal), 0, int(window), kv_start,
-                                   kv_end, segs)
+                                   kv_end, segs, prefix=prefix)
             ctx.save_for_backward(qkv, q4 if rot > 0 else None, k4 if rot > 0 else None, o, lse2,
                                   cos, sin, pos, kv_start, kv_end, segs)
         ctx.on_load = on_load
@@ -223,17 +232,18 @@ class _FusedQKVAttnFn(torch.autograd.Function):
         if rot > 0 and not fused_rope:
             ops.rope_bwd(dq.view(B * T, Hq * D), dk.view(B * T, Hkv * D), dqkv.view(B * T, C),
                          cos, sin, pos, Hq, Hkv, D, rot, T, 0)
-        return dqkv, None, None, None, None, None, None, None, None, None, None, None, None, None
+        return (dqkv,) + (None,) * 14
 
 
 class _AttnCoreFn(torch.autograd.Function):
     """[B, T, H, D] q/k/v -> o. Used for KV-cache decode and padded head dims."""
 
     @staticmethod
-    def forward(ctx, q, k, v, scale, causal, causal_off, window, kv_start, kv_end, segs=None):
+    def forward(ctx, q, k, v, scale, causal, causal_off, window, kv_start, kv_end, segs=None,
+                prefix=None):
         ops = _ext.require()
         o, lse2 = ops.attn_fwd(q, k, v, float(scale), bool(causal), int(causal_off), int(window),
-                               kv_start, kv_end, segs)
+                               kv_start, kv_end, segs, prefix=prefix)
         ctx.save_for_backward(q, k, v, o, lse2, kv_start, kv_end, segs)
         ctx.cfg = (scale, causal, causal_off, window)
         return o
@@ -248,7 +258,7 @@ class _AttnCoreFn(torch.autograd.Function):
         dv = torch.empty_like(v, memory_format=torch.contiguous_format)
         ops.attn_bwd(do.contiguous(), q, k, v, o, lse2, dq, dk, dv, float(scale), bool(causal),
                      int(causal_off), int(window), kv_start, kv_end, segs)
-        return dq, dk, dv, None, None, None, None, None, None, None
+        return dq, dk, dv, None, None, None, None, None, None, None, None
 
 
 # head dims with a native kernel tile: 64 / 128, and 80 (phi-2: Q.K^T over exactly 5 MFMA k-steps,
@@ -262,21 +272,34 @@ def _pad_d(x: torch.Tensor, Dp: int) -> torch.Tensor:
 
 
 def attention_core(q, k, v, scale=None, causal=True, causal_off=None, window=0, kv_start=None,
-                   kv_end=None, segs=None) -> torch.Tensor:
-    """q [B, Tq, Hq, D], k/v [B, Tk, Hkv, D] (unit stride on D) -> [B, Tq, Hq, D]."""
+                   kv_end=None, segs=None, prefix=None) -> torch.Tensor:
+    """q [B, Tq, Hq, D], k/v [B, Tk, Hkv, D] (unit stride on D) -> [B, Tq, Hq, D].
+    `prefix` int32 [B, 3] = (ps, pe, qe), with `segs`: queries pe <= i < qe also see keys [ps, pe)."""
     D = q.shape[-1]
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
     if causal_off is None:
         causal_off = k.shape[1] - q.shape[1]
     if not _ext.use_native(q):
-        return ref_attention(q, k, v, scale, causal, causal_off, window, kv_start, kv_end, segs)
-    ks, ke, sg = _i32(kv_start), _i32(kv_end), _i32(segs)
+        return ref_attention(q, k, v, scale, causal, causal_off, window, kv_start, kv_end, segs, prefix)
+    ks, ke, sg, pf = _i32(kv_start), _i32(kv_end), _i32(segs), _i32(prefix)
     if D in NATIVE_HEAD_DIMS:
-        return _AttnCoreFn.apply(q, k, v, scale, causal, causal_off, window, ks, ke, sg)
+        return _AttnCoreFn.apply(q, k, v, scale, causal, causal_off, window, ks, ke, sg, pf)
     Dp = 64 if D < 64 else 128
     o = _AttnCoreFn.apply(_pad_d(q, Dp), _pad_d(k, Dp), _pad_d(v, Dp), scale, causal, causal_off,
-                          window, ks, ke, sg)
+                          window, ks, ke, sg, pf)
     return o[..., :D]
+
+
+def prefix_masks_agree(segs: torch.Tensor, prefix: torch.Tensor) -> bool:
+    """True when the forward form of the shared-prefix mask (`_visibility`: seg_start + prefix)
+    and the backward form the kernels evaluate per element (j <= i < seg_end[b, j]) are the same
+    set. Builds both [B, T, T] masks and syncs: tests and debugging only."""
+    _, B, T = segs.shape
+    fwd = _visibility(B, T, T, True, 0, 0, None, None, segs.device, segs, prefix)
+    qi = torch.arange(T, device=segs.device).view(1, T, 1)
+    kj = torch.arange(T, device=segs.device).view(1, 1, T)
+    bwd = (kj <= qi) & (qi < segs[1].view(B, 1, T))
+    return bool(torch.equal(fwd, bwd))
 
 
 def apply_rope(x: torch.Tensor, rope: RotaryCache, positions: torch.Tensor) -> torch.Tensor:
@@ -288,9 +311,12 @@ def apply_rope(x: torch.Tensor, rope: RotaryCache, positions: torch.Tensor) -> t
 def qkv_attention(qkv: torch.Tensor, Hq: int, Hkv: int, D: int, rope: Optional[RotaryCache],
                   causal: bool = True, window: int = 0, kv_start=None, kv_end=None,
                   positions: Optional[torch.Tensor] = None, scale: Optional[float] = None,
-                  segs: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  segs: Optional[torch.Tensor] = None,
+                  prefix: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Fused QKV -> (RoPE) -> attention. qkv [B, T, (Hq+2Hkv)*D] -> [B, T, Hq*D].
-    `segs` [2, B, T] int32 (seg_start; seg_end): packed sequences, block-diagonal causal mask."""
+    `segs` [2, B, T] int32 (seg_start; seg_end): packed sequences, block-diagonal causal mask.
+    `prefix` [B, 3] int32 (ps, pe, qe), with `segs`: queries pe <= i < qe also see keys [ps, pe)
+    (a group's responses sharing one copy of their prompt; `prefix_masks_agree`)."""
     B, T, C = qkv.shape
     assert C == (Hq + 2 * Hkv) * D, "qkv width mismatch"
     if rope is not None and T > rope.max_pos:
@@ -305,9 +331,9 @@ def qkv_attention(qkv: torch.Tensor, Hq: int, Hkv: int, D: int, rope: Optional[R
             pos = positions if positions is not None else torch.arange(T, device=qkv.device).expand(B, T)
             q = apply_rope(q, rope, pos)
             k = apply_rope(k, rope, pos)
-        o = ref_attention(q, k, v, scale, causal, 0, window, kv_start, kv_end, segs)
+        o = ref_attention(q, k, v, scale, causal, 0, window, kv_start, kv_end, segs, prefix)
         return o.reshape(B, T, Hq * D)
-    ks, ke, sg = _i32(kv_start), _i32(kv_end), _i32(segs)
+    ks, ke, sg, pf = _i32(kv_start), _i32(kv_end), _i32(segs), _i32(prefix)
     pos32 = _i32(positions.reshape(-1)) if positions is not None else None
     if D in NATIVE_HEAD_DIMS:
         if rope is not None:
@@ -315,7 +341,7 @@ def qkv_attention(qkv: torch.Tensor, Hq: int, Hkv: int, D: int, rope: Optional[R
         else:
             cos = sin = torch.empty(0, device=qkv.device)
         return _FusedQKVAttnFn.apply(qkv.contiguous(), cos, sin, pos32, Hq, Hkv, D, rot, scale,
-                                     causal, window, ks, ke, sg)
+                                     causal, window, ks, ke, sg, pf)
     # other head dims (e.g. 96, 256): HIP RoPE forward/backward on the fused
     # qkv buffer (the kernels take any D % 8 == 0), then the native attention core on head dims
     # zero-padded to the next supported size
@@ -330,7 +356,7 @@ def qkv_attention(qkv: torch.Tensor, Hq: int, Hkv: int, D: int, rope: Optional[R
             pos = positions if positions is not None else torch.arange(T, device=qkv.device).expand(B, T)
             q = apply_rope(q, rope, pos)
             k = apply_rope(k, rope, pos)
-    o = attention_core(q, k, v, scale, causal, 0, window, kv_start, kv_end, segs)
+    o = attention_core(q, k, v, scale, causal, 0, window, kv_start, kv_end, segs, prefix)
     return o.reshape(B, T, Hq * D)
 
 

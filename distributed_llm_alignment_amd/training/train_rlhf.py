@@ -256,6 +256,39 @@ def keep_sampling_mask(ppo: Dict, algo: str, hardware: Optional[Dict] = None,
     return True
 
 
+def share_prefix_update(ppo: Dict, algo: str, hardware: Optional[Dict] = None, world: int = 1) -> bool:
+    """`ppo.share_prefix_update` (default false): the GRPO update and stats forwards run on the
+    prefix-shared layout, every group's prompt computed once (`shared_prefix_pack`). Every
+    combination it cannot honour raises: another algorithm, tensor / sequence parallelism, and a
+    minibatch or `update_micro_batch` that does not slice whole groups. `world`: the number of
+    data-parallel replicas; the `batch_size / group_size` prompts of a step are split between them
+    (`split_for_rank`) and each replica cuts its own rollouts into `num_minibatches`."""
+    v = ppo.get("share_prefix_update", False)
+    if v is None or v is False:
+        return False
+    if v is not True:
+        raise ValueError(f"ppo.share_prefix_update must be true or false, got {v!r}")
+    if algo != "grpo":
+        raise ValueError(f"ppo.share_prefix_update needs group rollouts (ppo.algorithm: grpo), got ppo.algorithm: {algo}")
+    hw = hardware or {}
+    if int(hw.get("tp_size", 1) or 1) > 1 or int(hw.get("sp_size", 1) or 1) > 1 or hw.get("tp_sequence_parallel"):
+        raise ValueError("ppo.share_prefix_update does not support tensor_parallel / sequence parallel runs "
+                         "(hardware.tp_size, hardware.sp_size, hardware.tp_sequence_parallel)")
+    group = int(ppo.get("group_size", 8))
+    batch, nmb = int(ppo.get("batch_size", 64)), max(1, int(ppo.get("num_minibatches", 1)))
+    micro = int(ppo.get("update_micro_batch", 0) or 0)
+    world = max(1, int(world))
+    per, extra = divmod(batch // max(group, 1), world)  # prompts per replica: per, or per + 1 on `extra` of them
+    if group < 1 or batch % group or per % nmb or (extra and (per + 1) % nmb):
+        raise ValueError(f"ppo.share_prefix_update: minibatches must hold whole groups; the ppo.batch_size ({batch}) "
+                         f"/ ppo.group_size ({group}) prompts of a step, split over {world} data-parallel "
+                         f"replica(s), do not divide into ppo.num_minibatches ({nmb}) on every replica")
+    if micro and micro % group:
+        raise ValueError(f"ppo.share_prefix_update: ppo.update_micro_batch ({micro}) must be a multiple of "
+                         f"ppo.group_size ({group}): micro-batches slice whole groups")
+    return True
+
+
 def rollout_is_settings(ppo: Dict) -> Dict:
     """`ppo.rollout_is_cap / _floor / _level / _mode` (for `rollout_logprobs: correct`) as the
     `is_*` keyword arguments of `ppo_rollout_stats` / `grpo_rollout_stats`; bad values raise."""
@@ -379,6 +412,7 @@ def main(argv=None) -> int:
     rollout_is_settings(ppo)  # bad ppo.rollout_is_* values fail here, before any rollout
     lp_temp = logprob_temperature(ppo, algo)  # likewise
     keep_on = keep_sampling_mask(ppo, algo, ctx.hw, policy.model.cfg.vocab_size)  # likewise
+    share_prefix_update(ppo, algo, ctx.hw, ctx.dp_size)  # likewise
 
     # reward inputs built on the device when the reward tokenizer equals the policy's (no
     # decode / re-tokenise round trip through the host; training/handoff.py), else the
@@ -499,7 +533,7 @@ GRPO_ROWS = ("act", "advantages", "ref_logp", "old_logp", "is_weight", "keep_row
 def grpo_update(policy, engine, seqs, mask, stats, clip_low: float, clip_high, beta: float,
                 loss_type: str, max_len, micro: int = 0, entropy_coef: float = 0.0,
                 log_entropy: bool = False, temperature: float = 1.0, keep=None,
-                importance_level: str = "token"):
+                importance_level: str = "token", shared_prefix=None):
     """Backward of the GRPO loss over one minibatch of rollouts. micro > 0
     (`ppo.update_micro_batch`): gradient-accumulated micro-batches of `micro` rollouts that share
     the whole minibatch's divisor (`denom`, a device tensor: no host sync), so their gradients sum
@@ -509,13 +543,18 @@ def grpo_update(policy, engine, seqs, mask, stats, clip_low: float, clip_high, b
     entries. `temperature`: the log-prob temperature of `grpo_loss`. `keep`: the rollout batch's
     whole sampling mask (`stats["keep_rows"]`, sliced with the rows, indexes it). `importance_level`:
     `ppo.importance_sampling_level`; micro-batches slice whole rows, so a row's sequence-level ratio
-    never straddles two of them. Returns (loss, metrics) with token-weighted metric means."""
+    never straddles two of them. `shared_prefix=(G, prompt_len)` (`ppo.share_prefix_update`): the
+    policy runs on the prefix-shared layout; the minibatch and every micro-batch must then hold
+    whole groups (ValueError). Returns (loss, metrics) with token-weighted metric means."""
     n = seqs.shape[0]
     rows = GRPO_ROWS
+    if shared_prefix is not None and (n % shared_prefix[0] or (0 < micro < n and micro % shared_prefix[0])):
+        raise ValueError(f"share_prefix_update: a minibatch of {n} rollouts in micro-batches of {micro} does not "
+                         f"slice whole groups of {shared_prefix[0]}")
     if micro <= 0 or micro >= n:
         loss, m = grpo_loss(policy, seqs, mask, stats, clip_low, clip_high, beta, loss_type, max_len,
                             entropy_coef=entropy_coef, log_entropy=log_entropy, temperature=temperature, keep=keep,
-                            importance_level=importance_level)
+                            importance_level=importance_level, shared_prefix=shared_prefix)
         loss.backward()
         return loss.detach(), m
     denom = grpo_denominator(stats["act"], loss_type, max_len)
@@ -530,7 +569,7 @@ def grpo_update(policy, engine, seqs, mask, stats, clip_low: float, clip_high, b
         with ctx:
             loss, m = grpo_loss(policy, seqs[s0:s1], mask[s0:s1], mb, clip_low, clip_high, beta, loss_type,
                                 max_len, denom, entropy_coef, log_entropy, tokens, temperature=temperature,
-                                keep=keep, importance_level=importance_level)
+                                keep=keep, importance_level=importance_level, shared_prefix=shared_prefix)
             loss.backward()
         tot = tot + loss.detach()
         for k in acc:
@@ -558,6 +597,8 @@ def _grpo_loop(ctx, config, ppo, policy, ref, rm, rollout, engine, steps, group,
     lp_temp = logprob_temperature(ppo, "grpo")
     log_temp = "logprob_temperature" in ppo  # logged once, and only when the key is set
     log_level = importance_level == "sequence"  # logged once
+    share = share_prefix_update(ppo, "grpo", ctx.hw, ctx.dp_size)
+    log_share = share  # logged once
     rows = GRPO_ROWS
     running = RunningLoss()
     pending = rollout()
@@ -575,7 +616,7 @@ def _grpo_loop(ctx, config, ppo, policy, ref, rm, rollout, engine, steps, group,
                                    need_old or lp_mode == "monitor",
                                    old_logp=rlp if lp_mode == "old" else None,
                                    rollout_logp=rlp if lp_mode == "correct" else None, **is_kw,
-                                   temperature=lp_temp, **kkw)
+                                   temperature=lp_temp, **kkw, **({"shared_prefix": (group, tp)} if share else {}))
         mism = rollout_mismatch(rlp, stats["old_logp"], stats["act"]) if lp_mode in ("monitor", "correct") else {}
         mism.update(stats.get("rollout_is", {}))
         if lp_mode in ("monitor", "correct") and not need_old:
@@ -589,7 +630,8 @@ def _grpo_loop(ctx, config, ppo, policy, ref, rm, rollout, engine, steps, group,
                 mb = {k: (stats[k][a:b] if stats.get(k) is not None else None) for k in rows}
                 loss, m = grpo_update(policy.model, engine, seqs[a:b], mask[a:b], mb, clip_low, clip_high,
                                       beta, loss_type, gen_len, micro, entropy_coef, log_entropy, lp_temp,
-                                      keep=keep, importance_level=importance_level)
+                                      keep=keep, importance_level=importance_level,
+                                      **({"shared_prefix": (group, tp)} if share else {}))
                 last = ep == epochs - 1 and mi == len(bounds) - 1
                 if last and overlap and step + 1 < steps:
                     pending = rollout()  # overlaps the in-flight gradient collectives (see _ppo_loop)
@@ -608,9 +650,10 @@ def _grpo_loop(ctx, config, ppo, policy, ref, rm, rollout, engine, steps, group,
                             **({"train/logprob_temperature": lp_temp} if log_temp else {}),
                             **({"train/importance_sampling_level":
                                 GRPO_IMPORTANCE_LEVELS.index(importance_level)} if log_level else {}),
+                            **({"train/share_prefix_update": 1} if log_share else {}),
                             "train/grad_norm": engine.last_grad_norm,
                             "train/comm_exposed_ms": engine.comm_timer.last_step_ms()}, step + 1)
-            running, log_temp, log_level = RunningLoss(), False, False
+            running, log_temp, log_level, log_share = RunningLoss(), False, False, False
     barrier()
     save_state(config["logging"]["output_dir"], [policy.model, *ref.saved, rm], engine, None, steps,
                policy.tokenizer)

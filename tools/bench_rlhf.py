@@ -91,6 +91,10 @@ def main() -> int:
                     help="ppo / grpo: ppo.keep_sampling_mask (the rollouts return the top-p kept set of every "
                          "token and every trainer-side log-prob is taken over it, the mask read inside the "
                          "LM-head row kernels); with --rollout-logprobs it needs --logprob-temperature rollout")
+    ap.add_argument("--share-prefix-update", action="store_true",
+                    help="grpo: ppo.share_prefix_update (the stats and update forwards run on the prefix-shared "
+                         "layout: each group's prompt computed once, prefix-shared attention); --micro must "
+                         "then be a multiple of --group")
     ap.add_argument("--rollout-is-cap", type=float, default=2.0, help="correct: ppo.rollout_is_cap")
     ap.add_argument("--rollout-is-floor", type=float, default=None, help="correct: ppo.rollout_is_floor (default 1 / cap)")
     ap.add_argument("--rollout-is-level", choices=("token", "sequence"), default="token")
@@ -121,9 +125,13 @@ def main() -> int:
         ap.error("--importance-sampling-level sequence needs per-rollout advantages: --algorithm grpo")
     if a.lora_r and a.algorithm != "grpo":
         ap.error("--lora-r is measured on the grpo step only: --algorithm grpo")
+    if a.share_prefix_update and a.algorithm != "grpo":
+        ap.error("--share-prefix-update needs group rollouts: --algorithm grpo")
     if a.algorithm == "ppo":
         return ppo_main(a)
     if a.algorithm == "grpo":
+        if a.share_prefix_update and a.micro % a.group:
+            ap.error("--share-prefix-update: --micro must be a multiple of --group")
         if a.batch % a.group:
             ap.error("--batch must be a multiple of --group")
         if a.overlap:
@@ -594,7 +602,8 @@ def grpo_main(a) -> int:
         stats = grpo_rollout_stats(pol, ref, seqs, mask, a.prompt, scores, G, a.kl_coef, True,
                                    lp_mode == "monitor", old_logp=rlp if lp_mode == "old" else None,
                                    rollout_logp=rlp if lp_mode == "correct" else None, **is_kw,
-                                   temperature=lp_temp, **kkw)
+                                   temperature=lp_temp, **kkw,
+                                   **({"shared_prefix": (G, a.prompt)} if a.share_prefix_update else {}))
         if lp_mode in ("monitor", "correct"):
             mism.update(rollout_mismatch(rlp, stats["old_logp"], stats["act"]))
             mism.update(stats.get("rollout_is", {}))
@@ -611,7 +620,8 @@ def grpo_main(a) -> int:
         pol.train()
         loss, m = grpo_update(pol, eng, seqs, mask, stats, a.clip_range, a.clip_range_high, a.kl_coef, a.loss_type,
                               a.new, a.micro, a.entropy_coef, a.log_entropy, lp_temp, keep=keep,
-                              importance_level=a.importance_sampling_level)
+                              importance_level=a.importance_sampling_level,
+                              **({"shared_prefix": (G, a.prompt)} if a.share_prefix_update else {}))
         eng.step()
         t4 = sync()
         phase_peak("update")
@@ -638,6 +648,7 @@ def grpo_main(a) -> int:
     print(json.dumps({"bench": "grpo_step", "model": cfg.name, "rollouts_per_step": a.batch, "group": G,
                       "rollout_logprobs": lp_mode, "logprob_temperature": lp_temp, "keep_sampling_mask": keep_on,
                       "share_prefill": bool(a.share_prefill), "group_attention": bool(a.group_attention),
+                      "share_prefix_update": bool(a.share_prefix_update),
                       "loss_type": a.loss_type, "kl_coef": a.kl_coef,
                       "importance_sampling_level": a.importance_sampling_level,
                       "clip_range": a.clip_range, "clip_range_high": a.clip_range_high,
