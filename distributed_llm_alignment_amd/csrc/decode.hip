@@ -20,29 +20,12 @@
 #include "common.h"
 #include "decode_geom.h"
 #include "decode_params.h"
+#include "decode_rope.h"
 
 namespace dla {
 
 // Lanes cooperate on rows: LPK = D/8 lanes x 16 B cover one K/V row (coalesced 256-byte rows
 // for D = 128), KPI = 64/LPK rows per wave instruction.
-
-// 8 rotated dims [d0, d0 + 8) of one head (rotate-half over the first `rot` dims), rounded to bf16
-__device__ __forceinline__ bf16x8 dec_rope8(const bf16_t* src, int d0, int rot, const float* cs,
-                                            const float* sn) {
-  const bf16x8 x = load_bf16x8(src + d0);
-  if (d0 >= rot) return x;
-  const int half = rot >> 1;
-  const bool lo = d0 < half;
-  const bf16x8 y = load_bf16x8(src + (lo ? d0 + half : d0 - half));
-  const int c0 = lo ? d0 : d0 - half;
-  bf16x8 o;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const float c = cs[c0 + j], s = sn[c0 + j], a = bf2f(x[j]), bb = bf2f(y[j]);
-    o[j] = f2bf(lo ? a * c - bb * s : a * c + bb * s);
-  }
-  return o;
-}
 
 // Element offset of 16-byte chunk `ch` of key row `row` in a wave's [32 keys][D] bf16 V image;
 // the XOR keeps the ds_read_b64_tr_b16 column reads of the P.V MFMA spread over banks (cdna
@@ -1153,6 +1136,13 @@ static void launch_decode_group(const DecodeParams& p, hipStream_t st) {
       p.q, p.q_sb, p.q_sh, p.kc, p.vc, p.c_sb, p.c_st, p.c_sh, p.kv_len, p.kv_start, p.window,
       p.scale_log2, ntot, g.cpb_s, p.part_o, p.part_ml, p.Hq, p.rope, fin, p.o_sb, p.o_sh, cn, p.Tmax, gp);
   if (fin == nullptr) launch_decode_combine<D>(p, ntot, st);
+}
+
+// the combine launch on its own: for other producers of (m, l, o) partials in this layout (decode_f8.hip)
+void launch_decode_combine_parts(const float* part_o, const float* part_ml, int nsplit, bf16_t* out,
+                                 int64_t o_sb, int64_t o_sh, int B, int Hq, int D, hipStream_t st) {
+  if (D == 128) decode_combine_kernel<128><<<B * Hq, 64, 0, st>>>(part_o, part_ml, nsplit, out, o_sb, o_sh, Hq);
+  else decode_combine_kernel<64><<<B * Hq, 64, 0, st>>>(part_o, part_ml, nsplit, out, o_sb, o_sh, Hq);
 }
 
 // partial slots per (row, q head); a group-structured step: prefix splits, then suffix splits

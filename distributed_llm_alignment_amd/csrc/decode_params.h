@@ -51,6 +51,11 @@ struct DecodeParams {
 int decode_splits(const DecodeParams& p);
 void launch_decode(const DecodeParams& p, hipStream_t st);
 
+// merge `nsplit` partials per (row, q head) (part_o [B, Hq, nsplit, D], part_ml [B, Hq, nsplit, 2])
+// into the normalised bf16 output: the combine launch of launch_decode on its own
+void launch_decode_combine_parts(const float* part_o, const float* part_ml, int nsplit, bf16_t* out,
+                                 int64_t o_sb, int64_t o_sh, int B, int Hq, int D, hipStream_t st);
+
 // qkv rows of the newest token -> rotated q_out [B, Hq, D], rotated k / plain v into cache row *slot
 void launch_rope_cache(const bf16_t* qkv, int64_t ld, bf16_t* q_out, bf16_t* kc, bf16_t* vc,
                        int64_t c_sb, int64_t c_st, int64_t c_sh, const int64_t* slot,

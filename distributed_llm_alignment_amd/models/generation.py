@@ -22,6 +22,12 @@ from .. import ops
 from .transformer import CausalLM, attention_layout
 
 
+def _check_kv_dtype(kv_dtype: str) -> str:
+    if kv_dtype not in ("bf16", "fp8"):
+        raise ValueError(f"kv_dtype must be 'bf16' or 'fp8', got {kv_dtype!r}")
+    return kv_dtype
+
+
 class KVCache:
     """Contiguous per-layer K/V cache [L, B, T_max, Hkv, D] sized once for prompt + new tokens.
 
@@ -29,14 +35,32 @@ class KVCache:
     `kv_len`, `pos`), so a single-token decode step touches no host value: it can be captured
     in a hipGraph and replayed (`advance_device`)."""
 
-    def __init__(self, model: CausalLM, batch: int, max_len: int, kv_start: Optional[torch.Tensor]):
+    def __init__(self, model: CausalLM, batch: int, max_len: int, kv_start: Optional[torch.Tensor],
+                 kv_dtype: str = "bf16"):
         cfg = model.cfg
         dev, dt = model.embed.device, model.embed.dtype
         L, Hkv, D = cfg.num_layers, model.layers[0].attn.kv_local, cfg.head_dim
         self.h_local, self.kv_local = model.layers[0].attn.h_local, Hkv
         self.cfg = cfg
         self.split = model.layer_devices is not None
-        if self.split:  # layer-split model: each layer's K/V on that layer's device
+        self.kv_dtype = _check_kv_dtype(kv_dtype)
+        self.k_scale = self.v_scale = None
+        if self.kv_dtype == "fp8":
+            # e4m3 codes (`k` / `v`, uint8, the layouts below) + one fp32 scale per (row, token, kv
+            # head) for K and for V (`k_scale` / `v_scale` [L, B, T_max, Hkv], head-major alike):
+            # ops.decode.quantize_kv_f8 is the format of record
+            if self.split:
+                raise ValueError("kv_dtype='fp8' does not support a layer-split model")
+            if D % 16 != 0:
+                raise ValueError(f"kv_dtype='fp8' needs head_dim % 16 == 0, got {D}")
+            shape, sshape = ((L, batch, Hkv, max_len, D), (L, batch, Hkv, max_len)) if KV_HEAD_MAJOR \
+                else ((L, batch, max_len, Hkv, D), (L, batch, max_len, Hkv))
+            self.k, self.v = (torch.empty(shape, device=dev, dtype=torch.uint8) for _ in range(2))
+            self.k_scale, self.v_scale = (torch.empty(sshape, device=dev, dtype=torch.float32) for _ in range(2))
+            if KV_HEAD_MAJOR:
+                self.k, self.v = self.k.transpose(2, 3), self.v.transpose(2, 3)
+                self.k_scale, self.v_scale = self.k_scale.transpose(2, 3), self.v_scale.transpose(2, 3)
+        elif self.split:  # layer-split model: each layer's K/V on that layer's device
             self.k = [torch.empty((batch, max_len, Hkv, D), device=d, dtype=dt) for d in model.layer_devices]
             self.v = [torch.empty((batch, max_len, Hkv, D), device=d, dtype=dt) for d in model.layer_devices]
         elif KV_HEAD_MAJOR:
@@ -65,6 +89,8 @@ class KVCache:
 
     def nbytes(self) -> int:
         ks = self.k if isinstance(self.k, list) else [self.k]
+        if self.k_scale is not None:
+            ks = ks + [self.k_scale]
         return 2 * sum(t.numel() * t.element_size() for t in ks)
 
     def reset(self, kv_start: Optional[torch.Tensor]):
@@ -92,6 +118,8 @@ class KVCache:
         B, T, _ = qkv.shape
         if self.len + T > self.max_len:
             raise RuntimeError("KV cache overflow")
+        if self.kv_dtype == "fp8":
+            return self._attend_f8(layer, qkv, rope, window)
         if T == 1 and self.len > 0 and self.fast_decode:
             # device-indexed cache write + split-KV decode kernel (graph-capturable)
             D = cfg.head_dim
@@ -144,6 +172,51 @@ class KVCache:
                                causal=True, causal_off=self.len, window=window,
                                kv_start=kv_start, kv_end=None)
         return o.reshape(B, T, self.h_local * cfg.head_dim)
+
+    def _attend_f8(self, layer: int, qkv: torch.Tensor, rope, window: int) -> torch.Tensor:
+        """`attend` over the e4m3 cache. Decode step on the GPU: the quantising prologue
+        (rope_cache_write_f8) and decode attention over codes (decode_attn_f8), two launches
+        whatever DLA_FUSED_DECODE_ROPE says; a model without a rotary table (or rot_dim % 16 != 0)
+        ropes on the torch path and copies the quantised rows to the device slot, so every
+        fast-decode step is device-indexed and graph-capturable. Prefill into an empty cache: attention on the prompt's
+        own bf16 K / V as with the bf16 cache, then one quantising fill per K and V. Everything
+        else (and the CPU): the new rows are quantised into the cache and the existing attention
+        runs over the dequantised rows."""
+        cfg, D = self.cfg, self.cfg.head_dim
+        B, T, _ = qkv.shape
+        kc, vc, ksc, vsc = self.k[layer], self.v[layer], self.k_scale[layer], self.v_scale[layer]
+        if (T == 1 and self.len > 0 and self.fast_decode and rope is not None and rope.rot_dim % 16 == 0
+                and self.group is None):
+            cos, sin = rope.tables(qkv.device)
+            q = ops._ext.require().rope_cache_write_f8(qkv, cos, sin, self.pos.view(-1), kc, vc, ksc, vsc,
+                                                       self.slot, self.h_local, self.kv_local, D, rope.rot_dim)
+            o = ops.decode.decode_attention_f8(q, kc, vc, ksc, vsc, self.kv_len, self.kv_start, window)
+            return o.reshape(B, 1, self.h_local * D)
+        if self.group is not None:
+            raise RuntimeError("a group-structured cache (group_attention) has no e4m3 form")
+        q, k, v = ops.attention.rope_qk(qkv, rope, self.h_local, self.kv_local, D, positions=self._pos)
+        if T == 1 and self.len > 0 and self.fast_decode:
+            # no rotary table (learned positions) or rot_dim % 16 != 0: still device-indexed, as the
+            # bf16 cache's branch for these models, so the step stays graph-capturable: the new rows
+            # are quantised into one-token buffers and copied to row `slot` (a device value)
+            for src, codes, scales in ((k, kc, ksc), (v, vc, vsc)):
+                c1 = torch.empty(src.shape, dtype=torch.uint8, device=src.device)
+                s1 = torch.empty(src.shape[:-1], dtype=torch.float32, device=src.device)
+                ops.decode.kv_quant_f8(src, c1, s1, 0)
+                codes.index_copy_(1, self.slot, c1)
+                scales.index_copy_(1, self.slot, s1)
+            o = ops.decode.decode_attention_f8(q.reshape(B, self.h_local, D), kc, vc, ksc, vsc, self.kv_len,
+                                               self.kv_start, window)
+            return o.reshape(B, 1, self.h_local * D)
+        ops.decode.kv_quant_f8(k, kc, ksc, self.len)
+        ops.decode.kv_quant_f8(v, vc, vsc, self.len)
+        end = self.len + T
+        if self.len > 0 or T == 1:
+            k = ops.decode.dequantize_kv_f8(kc[:, :end], ksc[:, :end], k.dtype)
+            v = ops.decode.dequantize_kv_f8(vc[:, :end], vsc[:, :end], v.dtype)
+        o = ops.attention_core(q.contiguous(), k, v, causal=True, causal_off=self.len, window=window,
+                               kv_start=self.kv_start, kv_end=None)
+        return o.reshape(B, T, self.h_local * D)
 
     def advance(self, T: int):
         """Host-driven advance (prefill / eager decode) keeping the device state in step."""
@@ -411,7 +484,8 @@ PREFILL_FP8 = os.environ.get("DLA_PREFILL_FP8", "1") != "0"
 
 @torch.no_grad()
 def prefill_shared(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor],
-                   G: int, max_len: int, cache: Optional[KVCache] = None, group_attention: bool = False):
+                   G: int, max_len: int, cache: Optional[KVCache] = None, group_attention: bool = False,
+                   kv_dtype: str = "bf16"):
     """Prefill P left-padded prompts ONCE for G samples each: the prompts run through a P-row
     cache of length Tp, and their keys / values [0, Tp) of every layer are replicated into rows
     p*G .. p*G+G-1 of a P*G-row cache of length `max_len` (`ops.decode.kv_replicate`, one HIP
@@ -420,17 +494,33 @@ def prefill_shared(model: CausalLM, input_ids: torch.Tensor, attention_mask: Opt
     `repeat_interleave` order: what a prefill of the G-times repeated prompts leaves behind, for
     1/G of the prompt forward. `group_attention`: mark the cache as group-structured
     (`cache.group = (G, Tp)`), so its fast-decode steps read the prompt keys / values once per
-    group instead of once per row (ops.decode.decode_attention `group_size`)."""
+    group instead of once per row (ops.decode.decode_attention `group_size`). `kv_dtype`: the
+    format of a new cache (a given `cache` brings its own); "fp8" prefills an e4m3 P-row cache and
+    replicates codes and scales, and refuses `group_attention`."""
     P, Tp = input_ids.shape
     kv_start = attention_layout(attention_mask)[0] if attention_mask is not None else None
-    small = KVCache(model, P, Tp, kv_start)
+    kv_dtype = _check_kv_dtype(kv_dtype if cache is None else cache.kv_dtype)
+    if kv_dtype == "fp8" and group_attention and G > 1:
+        raise ValueError("prefill_shared: group_attention has no e4m3 KV cache form")
+    small = KVCache(model, P, Tp, kv_start, kv_dtype=kv_dtype)
     h = model(input_ids, cache=small)
     if cache is None:
         cache = KVCache(model, P * G, max_len,
-                        kv_start.repeat_interleave(G) if kv_start is not None else None)
+                        kv_start.repeat_interleave(G) if kv_start is not None else None, kv_dtype=kv_dtype)
     if cache.batch != P * G or cache.max_len < Tp or cache.len != 0:
         raise ValueError("prefill_shared: cache must be an empty P*G-row cache of at least Tp keys")
-    ops.decode.kv_replicate(small.k, small.v, cache.k, cache.v, G)
+    if kv_dtype == "fp8":
+        # codes: a byte copy through the bf16 replication kernel (2-byte view, D / 2 "elements" per
+        # row); scales (4 / D of the bytes): one strided copy each
+        if ops._ext.use_native(cache.k):
+            ops.decode.kv_replicate(small.k.view(torch.bfloat16), small.v.view(torch.bfloat16),
+                                    cache.k.view(torch.bfloat16), cache.v.view(torch.bfloat16), G)
+        else:
+            ops.decode.kv_replicate(small.k, small.v, cache.k, cache.v, G)
+        for src, dst in ((small.k_scale, cache.k_scale), (small.v_scale, cache.v_scale)):
+            dst[:, :, :Tp].unflatten(1, (P, G)).copy_(src.unsqueeze(2).expand(-1, -1, G, -1, -1))
+    else:
+        ops.decode.kv_replicate(small.k, small.v, cache.k, cache.v, G)
     cache.advance(Tp)
     cache.group = (int(G), int(Tp)) if group_attention and G > 1 else None
     return cache, h[:, -1].repeat_interleave(G, 0)
@@ -445,7 +535,7 @@ def generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional[
              weight_dtype: str = "bf16", num_return_sequences: int = 1, share_prefill: bool = True,
              group_attention: bool = False, return_logprobs: bool = False,
              logprob_temperature: Optional[float] = None, return_keep_mask: bool = False,
-             adapters: Optional[str] = None):
+             adapters: Optional[str] = None, kv_dtype: str = "bf16"):
     """Left-padded prompts [B, Tp] -> sequences [B, Tp + n] (n <= max_new_tokens).
 
     `num_return_sequences=G` (group rollouts, GRPO): G samples per prompt, output [B*G, Tp + n]
@@ -503,9 +593,24 @@ def generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional[
     function (merged: rounded once after the sum; live: base product, t and the sum rounded
     separately), the same kind of gap as prefill GEMM against skinny decode without adapters;
     `ppo.rollout_logprobs` measures and corrects it. With no adapter attached or active the call
-    is the default call, kernel for kernel. Any other value raises ValueError."""
+    is the default call, kernel for kernel. Any other value raises ValueError.
+
+    `kv_dtype="fp8"`: the KV cache holds e4m3 codes with one fp32 scale per (row, token, kv head)
+    for K and for V (`KVCache(kv_dtype="fp8")`, csrc/decode_f8.hip), 1 + 4/D bytes per element
+    against 2. The prompt attends to its own bf16 K / V and one quantising launch per layer fills the
+    cache; every decode step quantises the newest token in its prologue and attends over the codes
+    (q, softmax and both MFMAs stay bf16 / fp32). It composes with `weight_dtype`, `adapters`,
+    `return_logprobs`, `return_keep_mask`, `num_return_sequences` / `share_prefill` and MoE models;
+    with `group_attention=True` or a layer-split model it raises ValueError. The cache changes
+    which tokens are sampled (`ppo.rollout_logprobs` measures and corrects that gap). "bf16" is
+    the default call, kernel for kernel; any other value raises ValueError."""
     if weight_dtype not in ("bf16", "fp8"):
         raise ValueError(f"weight_dtype must be 'bf16' or 'fp8', got {weight_dtype!r}")
+    _check_kv_dtype(kv_dtype)
+    if kv_dtype == "fp8" and group_attention:
+        raise ValueError("kv_dtype='fp8' does not support group_attention=True")
+    if kv_dtype == "fp8" and model.layer_devices is not None:
+        raise ValueError("kv_dtype='fp8' does not support a layer-split model")
     if adapters not in (None, "merged"):
         raise ValueError(f"adapters must be None or 'merged', got {adapters!r}")
     from .lora import has_active_lora
@@ -532,7 +637,7 @@ def generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional[
         return _generate(model, input_ids, attention_mask, max_new_tokens, do_sample, temperature, top_p,
                          top_k, eos_token_id, pad_token_id, generator, return_mask, use_graph, seed, G,
                          bool(group_attention) and G > 1, lp_mode,
-                         bool(return_logprobs) if return_keep_mask else None)
+                         bool(return_logprobs) if return_keep_mask else None, kv_dtype)
 
 
 def _generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor],
@@ -540,7 +645,7 @@ def _generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional
               eos_token_id: Optional[int], pad_token_id: Optional[int],
               generator: Optional[torch.Generator], return_mask: bool, use_graph: Optional[bool],
               seed: Optional[int], G: int = 1, group_attention: bool = False,
-              return_logprobs: int = _LOGP_OFF, want_logp: Optional[bool] = None):
+              return_logprobs: int = _LOGP_OFF, want_logp: Optional[bool] = None, kv_dtype: str = "bf16"):
     # return_logprobs: the sampler mode (_LOGP_*); want_logp: whether logp is returned (None: whenever
     # the mode produces one; the keep mode produces it also for a call that wants the mask alone)
     if DECODE_GATHER and model.layers_sharded():
@@ -554,7 +659,7 @@ def _generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional
                     stack.enter_context(eng.gathered_for_inference())
                 return _generate(model, input_ids, attention_mask, max_new_tokens, do_sample, temperature,
                                  top_p, top_k, eos_token_id, pad_token_id, generator, return_mask, use_graph,
-                                 seed, G, group_attention, return_logprobs, want_logp)
+                                 seed, G, group_attention, return_logprobs, want_logp, kv_dtype)
         finally:
             # the gathered units are freed on exit: the captured graph (it reads their addresses),
             # its KV cache and the derived decode weight copies (a second full set of layer
@@ -595,7 +700,8 @@ def _generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional
                      return_logprobs,  # the captured step holds one sampler op or the other
                      # adapter mode: the captured step of a model with live adapters holds the first
                      # layer's adapter launches
-                     (_live_adapters(model), ops.decode.lora_merged_enabled()))
+                     (_live_adapters(model), ops.decode.lora_merged_enabled()),
+                     kv_dtype)  # the captured step holds the bf16 or the e4m3 cache ops and buffers
         hit = _GRAPH_SLOT.get(id(model))
         if hit is not None and hit[0]() is model and hit[1] == reuse_key:
             cache, dg = hit[2], hit[3]
@@ -603,7 +709,7 @@ def _generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional
         else:
             _GRAPH_SLOT.pop(id(model), None)  # free the old cache before sizing a new one
     if dg is None:
-        cache = KVCache(model, B, Tp + max_new_tokens, kv_start)
+        cache = KVCache(model, B, Tp + max_new_tokens, kv_start, kv_dtype=kv_dtype)
     # folded RMSNorm weights of the fused decode layer are refreshed in place (never inside the
     # captured step): a cached graph replays the same buffers with the current weights
     ops.decode.refresh_folded_weights(model)

@@ -89,6 +89,67 @@ def ref_decode_attention(q, k_cache, v_cache, L: int, kv_start=None, window: int
     return torch.einsum("bhl,blhd->bhd", p, v).to(q.dtype)
 
 
+# ------------------------------------------------------------------- e4m3 KV cache (opt-in)
+# `KVCache(kv_dtype="fp8")`, `generate(kv_dtype="fp8")`, `ppo.rollout_kv_dtype`: K (after RoPE) and V
+# are stored as e4m3 codes with one fp32 scale per (cache row, token, kv head) for K and one for V,
+# 1 + 4/D bytes per element against 2 (csrc/decode_f8.hip). q, the softmax and both MFMAs stay
+# bf16 / fp32; the cache changes which tokens are sampled, which `ppo.rollout_logprobs` measures
+# and corrects.
+KV_F8_MAX = 448.0  # largest finite e4m3 (OCP e4m3fn) value
+
+
+def quantize_kv_f8(x: torch.Tensor):
+    """x [..., D] (the bf16 head rows: K after RoPE, V plain) -> (codes uint8 [..., D], scale fp32
+    [...]). The formula of record of the e4m3 KV cache, every step one correctly rounded fp32
+    operation; the GPU quantisers (kv_quant_f8, rope_cache_write_f8) give these bits:
+
+        sc   = max(amax_d |x| / 448, 1e-12)
+        code = e4m3fn_rne(clamp(float(x) * (1 / sc), -448, 448))"""
+    a = x.float()
+    sc = (a.abs().amax(dim=-1) / KV_F8_MAX).clamp_min(1e-12)
+    inv = torch.ones_like(sc) / sc
+    q = (a * inv.unsqueeze(-1)).clamp_(-KV_F8_MAX, KV_F8_MAX).to(torch.float8_e4m3fn)
+    return q.view(torch.uint8), sc
+
+
+def dequantize_kv_f8(codes: torch.Tensor, scale: torch.Tensor, dtype=torch.float32) -> torch.Tensor:
+    """deq = float(code) * scale (fp32), cast to `dtype`."""
+    return (codes.view(torch.float8_e4m3fn).float() * scale.unsqueeze(-1)).to(dtype)
+
+
+def kv_quant_f8(src: torch.Tensor, dst_codes: torch.Tensor, dst_scale: torch.Tensor, t0: int = 0) -> None:
+    """Quantise a layer's K (rotated) or V slab src [B, T, Hkv, D] into tokens [t0, t0 + T) of
+    dst_codes uint8 [B, Tmax, Hkv, D] / dst_scale fp32 [B, Tmax, Hkv] (strided views). bf16 GPU
+    tensors run `torch.ops.dla.kv_quant_f8` (one streaming launch); anything else the torch formula."""
+    T = src.shape[1]
+    if _ext.use_native(src) and src.dtype == torch.bfloat16 and src.shape[-1] in (64, 128):
+        if src.stride(-1) != 1 or any(s % 8 for s in src.stride()[:-1]) or src.data_ptr() % 16:
+            src = src.contiguous()
+        _ext.require().kv_quant_f8(src, dst_codes, dst_scale, int(t0))
+        return
+    q, sc = quantize_kv_f8(src)
+    dst_codes[:, t0:t0 + T] = q
+    dst_scale[:, t0:t0 + T] = sc
+
+
+def decode_attention_f8(q: torch.Tensor, k8: torch.Tensor, v8: torch.Tensor, k_scale: torch.Tensor,
+                        v_scale: torch.Tensor, kv_len: torch.Tensor, kv_start: Optional[torch.Tensor] = None,
+                        window: int = 0, scale: Optional[float] = None) -> torch.Tensor:
+    """`decode_attention` over an e4m3 cache: q [B, Hq, D] bf16, codes uint8 [B, Tmax, Hkv, D],
+    scales fp32 [B, Tmax, Hkv]; keys [kv_start, kv_len) are attended. On the GPU
+    `torch.ops.dla.decode_attn_f8` (csrc/decode_f8.hip); elsewhere, and as the formula of record,
+    `ref_decode_attention` over `dequantize_kv_f8`."""
+    D = q.shape[-1]
+    scale = scale if scale is not None else 1.0 / math.sqrt(D)
+    if _ext.use_native(q):
+        ks = kv_start.to(torch.int32) if kv_start is not None else None
+        return _ext.require().decode_attn_f8(q, k8, v8, k_scale, v_scale, kv_len.to(torch.int32), ks,
+                                             int(window), float(scale))
+    L = int(kv_len.reshape(-1)[0])
+    return ref_decode_attention(q, dequantize_kv_f8(k8[:, :L], k_scale[:, :L]),
+                                dequantize_kv_f8(v8[:, :L], v_scale[:, :L]), L, kv_start, window, scale)
+
+
 def sample_tokens(logits: torch.Tensor, temperature: float, top_k: int, top_p: float, greedy: bool,
                   rng: torch.Tensor, generator: Optional[torch.Generator] = None) -> torch.Tensor:
     """logits [B, V] -> token ids [B] (int64). rng: int64 [2] device tensor (seed, counter) for

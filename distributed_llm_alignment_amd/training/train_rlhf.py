@@ -256,6 +256,20 @@ def keep_sampling_mask(ppo: Dict, algo: str, hardware: Optional[Dict] = None,
     return True
 
 
+def rollout_kv_dtype(ppo: Dict) -> str:
+    """`ppo.rollout_kv_dtype: bf16 | fp8` (default bf16): the KV cache of the rollout generation
+    (`generate(kv_dtype=)`; fp8 = e4m3 codes with per-(token, kv head) scales). The e4m3 cache
+    changes the policy that samples: `ppo.rollout_logprobs` measures and corrects that gap. A
+    bad value, or fp8 with `ppo.group_attention`, raises."""
+    v = ppo.get("rollout_kv_dtype", "bf16")
+    if v not in ("bf16", "fp8"):
+        raise ValueError(f"ppo.rollout_kv_dtype must be bf16|fp8, got {v!r}")
+    if v == "fp8" and bool(ppo.get("group_attention", False)):
+        raise ValueError("ppo.rollout_kv_dtype: fp8 does not support ppo.group_attention (the grouped decode "
+                         "attention has no e4m3 cache form)")
+    return v
+
+
 def share_prefix_update(ppo: Dict, algo: str, hardware: Optional[Dict] = None, world: int = 1) -> bool:
     """`ppo.share_prefix_update` (default false): the GRPO update and stats forwards run on the
     prefix-shared layout, every group's prompt computed once (`shared_prefix_pack`). Every
@@ -413,6 +427,7 @@ def main(argv=None) -> int:
     lp_temp = logprob_temperature(ppo, algo)  # likewise
     keep_on = keep_sampling_mask(ppo, algo, ctx.hw, policy.model.cfg.vocab_size)  # likewise
     share_prefix_update(ppo, algo, ctx.hw, ctx.dp_size)  # likewise
+    kv_dtype = rollout_kv_dtype(ppo)  # likewise
 
     # reward inputs built on the device when the reward tokenizer equals the policy's (no
     # decode / re-tokenise round trip through the host; training/handoff.py), else the
@@ -434,7 +449,7 @@ def main(argv=None) -> int:
                                     top_p=gen.get("top_p", 1.0), top_k=gen.get("top_k", 0),
                                     pad_token_id=tok.pad_token_id, eos_token_id=getattr(tok, "eos_token_id", None),
                                     generator=gen_g, return_mask=True,
-                                    weight_dtype=ppo.get("rollout_weight_dtype", "bf16"),
+                                    weight_dtype=ppo.get("rollout_weight_dtype", "bf16"), kv_dtype=kv_dtype,
                                     num_return_sequences=group, share_prefill=bool(ppo.get("share_prefill", True)),
                                     group_attention=bool(ppo.get("group_attention", False)),
                                     return_logprobs=want_logp,

@@ -25,6 +25,8 @@ def main() -> int:
     ap.add_argument("--modes", default="eager,graph")
     ap.add_argument("--weight-dtype", choices=("bf16", "fp8"), default="bf16",
                     help="decode weight streams (generate(weight_dtype=...))")
+    ap.add_argument("--kv-dtype", choices=("bf16", "fp8"), default="bf16",
+                    help="KV cache format (generate(kv_dtype=...); fp8 = e4m3 codes + row scales)")
     ap.add_argument("--group", type=int, default=1,
                     help="samples per prompt (generate(num_return_sequences=G)); --batch counts prompts")
     ap.add_argument("--group-attention", type=int, choices=(0, 1), default=0,
@@ -65,6 +67,8 @@ def main() -> int:
         kw = dict(max_new_tokens=a.new, do_sample=True, temperature=0.7, top_p=0.9, eos_token_id=-1,
                   use_graph=(mode == "graph"), seed=1, weight_dtype=a.weight_dtype,
                   num_return_sequences=a.group, group_attention=bool(a.group_attention))
+        if a.kv_dtype != "bf16":  # (left out otherwise: the call an older build of the package takes)
+            kw["kv_dtype"] = a.kv_dtype
         if a.logprobs:  # (left out otherwise: the call an older build of the package takes)
             kw["return_logprobs"] = True
         if a.logprobs >= 2:
@@ -86,7 +90,7 @@ def main() -> int:
         torch.cuda.synchronize()
         tp = time.perf_counter() - t1
         print(json.dumps({"mode": mode, "model": cfg.name, "batch": a.batch, "prompt": a.prompt,
-                          "weight_dtype": a.weight_dtype, "group": a.group,
+                          "weight_dtype": a.weight_dtype, "kv_dtype": a.kv_dtype, "group": a.group,
                           "group_attention": bool(a.group_attention), "logprobs": bool(a.logprobs),
                           "logprob_temperature": 0.7 if a.logprobs >= 2 else 1.0,
                           "keep_mask": a.logprobs == 3,

@@ -79,6 +79,8 @@ def main() -> int:
                     help="ppo / grpo: compute and report the policy entropy without a bonus (ppo.log_entropy)")
     ap.add_argument("--rollout-dtype", choices=("bf16", "fp8"), default="bf16",
                     help="decode weight streams of the rollout generation (ppo.rollout_weight_dtype)")
+    ap.add_argument("--kv-dtype", choices=("bf16", "fp8"), default="bf16",
+                    help="KV cache of the rollout generation (ppo.rollout_kv_dtype; fp8 = e4m3 codes + row scales)")
     ap.add_argument("--rollout-logprobs", choices=("off", "monitor", "old", "correct"), default="off",
                     help="ppo / grpo: ppo.rollout_logprobs (the sampler's token log-probs: monitor = log "
                          "rollout_kl / rollout_logp_absdiff_max against the trainer's, old = use them as old_logp, "
@@ -200,7 +202,7 @@ def main() -> int:
         t0 = sync()
         seqs, mask = generate(pol, ids, am, max_new_tokens=a.new, do_sample=True, temperature=0.7,
                               top_p=0.9, eos_token_id=-1, return_mask=True, seed=3,
-                              weight_dtype=a.rollout_dtype)
+                              weight_dtype=a.rollout_dtype, kv_dtype=a.kv_dtype)
         t1 = sync()
         with torch.no_grad():
             if a.handoff == "none":
@@ -237,7 +239,7 @@ def main() -> int:
             am = torch.ones_like(ids)
             seqs, mask = generate(snap, ids, am, max_new_tokens=a.new, do_sample=True, temperature=0.7,
                                   top_p=0.9, eos_token_id=-1, return_mask=True, seed=3,
-                              weight_dtype=a.rollout_dtype)
+                              weight_dtype=a.rollout_dtype, kv_dtype=a.kv_dtype)
             with torch.no_grad():
                 if a.handoff == "none":
                     scores = rm(seqs, mask)
@@ -425,7 +427,7 @@ def ppo_main(a) -> int:
         t0 = sync()
         seqs, mask, *rlp = generate(pol, ids, am, max_new_tokens=a.new, do_sample=True, temperature=GEN_TEMPERATURE,
                                     top_p=0.9, eos_token_id=-1, return_mask=True, seed=3,
-                                    weight_dtype=a.rollout_dtype, return_logprobs=lp_mode != "off",
+                                    weight_dtype=a.rollout_dtype, kv_dtype=a.kv_dtype, return_logprobs=lp_mode != "off",
                                     logprob_temperature=lp_temp if lp_mode != "off" and lp_temp != 1.0 else None,
                                     **({"return_keep_mask": True} if keep_on else {}))
         keep = rlp.pop() if keep_on else None
@@ -581,7 +583,7 @@ def grpo_main(a) -> int:
         t0 = sync()
         seqs, mask, *rlp = generate(pol, ids, am, max_new_tokens=a.new, do_sample=True, temperature=GEN_TEMPERATURE,
                                     top_p=0.9, eos_token_id=-1, return_mask=True, seed=3,
-                                    weight_dtype=a.rollout_dtype, num_return_sequences=G,
+                                    weight_dtype=a.rollout_dtype, kv_dtype=a.kv_dtype, num_return_sequences=G,
                                     share_prefill=bool(a.share_prefill),
                                     group_attention=bool(a.group_attention), return_logprobs=lp_mode != "off",
                                     logprob_temperature=lp_temp if lp_mode != "off" and lp_temp != 1.0 else None,
