@@ -41,39 +41,6 @@ void launch_rope_fwd(const bf16_t*, int64_t, bf16_t*, bf16_t*, const float*, con
                      const int*, int64_t, int, int, int, int, int, int, hipStream_t);
 void launch_rope_bwd(const bf16_t*, const bf16_t*, bf16_t*, int64_t, const float*, const float*,
                      const int*, int64_t, int, int, int, int, int, int, hipStream_t);
-void launch_logprob_fwd(const bf16_t*, int64_t, int, int64_t, int64_t, const int64_t*, float*,
-                        float*, hipStream_t);
-void launch_logprob_bwd(bf16_t*, int64_t, int, int64_t, int64_t, const int64_t*, const float*,
-                        const float*, hipStream_t);
-void launch_row_lse(const bf16_t*, int64_t, int, int64_t, float*, hipStream_t);
-void launch_logprob_fwd_temp(const bf16_t*, int64_t, int, int64_t, int64_t, const int64_t*, float*, float*,
-                             float, hipStream_t);
-void launch_logprob_bwd_temp(bf16_t*, int64_t, int, int64_t, int64_t, const int64_t*, const float*,
-                             const float*, float, hipStream_t);
-bool launch_logprob_bwd_t_temp(bf16_t*, int64_t, int, int64_t, int64_t, const int64_t*, const float*,
-                               const float*, bf16_t*, float, hipStream_t);
-void launch_logprob_entropy_fwd_temp(const bf16_t*, int64_t, int, int64_t, int64_t, const int64_t*, float*,
-                                     float*, float*, float, hipStream_t);
-void launch_logprob_entropy_bwd_temp(bf16_t*, int64_t, int, int64_t, int64_t, const int64_t*, const float*,
-                                     const float*, const float*, const float*, float, hipStream_t);
-bool launch_logprob_entropy_bwd_t_temp(bf16_t*, int64_t, int, int64_t, int64_t, const int64_t*, const float*,
-                                       const float*, const float*, const float*, bf16_t*, float, hipStream_t);
-void launch_logprob_fwd_keep(const bf16_t*, int64_t, int, int64_t, const int64_t*, float*, float*,
-                             const uint8_t*, const int64_t*, float, hipStream_t);
-void launch_logprob_bwd_keep(bf16_t*, int64_t, int, int64_t, const int64_t*, const float*, const float*,
-                             const uint8_t*, const int64_t*, float, hipStream_t);
-bool launch_logprob_bwd_t_keep(bf16_t*, int64_t, int, int64_t, const int64_t*, const float*, const float*,
-                               bf16_t*, const uint8_t*, const int64_t*, float, hipStream_t);
-bool launch_logprob_bwd_t(bf16_t*, int64_t, int, int64_t, int64_t, const int64_t*, const float*,
-                          const float*, bf16_t*, hipStream_t);
-void launch_logprob_entropy_fwd(const bf16_t*, int64_t, int, int64_t, int64_t, const int64_t*, float*,
-                                float*, float*, hipStream_t);
-void launch_logprob_entropy_bwd(bf16_t*, int64_t, int, int64_t, int64_t, const int64_t*, const float*,
-                                const float*, const float*, const float*, hipStream_t);
-bool launch_logprob_entropy_bwd_t(bf16_t*, int64_t, int, int64_t, int64_t, const int64_t*, const float*,
-                                  const float*, const float*, const float*, bf16_t*, hipStream_t);
-void launch_ensemble_kl(bf16_t*, const bf16_t*, int64_t, int64_t, int, int, const float*,
-                        const float*, int64_t, const float*, float*, bool, hipStream_t);
 void launch_seq_reduce(const float*, const float*, int, int, float*, float*, hipStream_t);
 void launch_seq_expand_grad(const float*, const float*, const float*, int, int, bool, float*,
                             hipStream_t);
@@ -642,366 +609,6 @@ void transpose_bf16(const at::Tensor& in, at::Tensor& out) {
                         cur_stream(in));
 }
 
-// ================================= vocab reductions ===========================================
-static void check_logits(const at::Tensor& logits) {
-  check_bf16(logits, "logits");
-  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1, "logits must be [N, V] row-major");
-}
-
-// The *_temp ops are the same ops on softmax(inv_temp * logits), inv_temp = float(1.0 / temperature)
-// formed by the caller (the divide in double, rounded once); `inv` below is null for the plain ops,
-// which launch the kernels they always launched.
-static float checked_inv_temp(double inv_temp) {
-  const float i = static_cast<float>(inv_temp);
-  TORCH_CHECK(std::isfinite(i) && i > 0.f, "inv_temp must be finite and > 0, got ", inv_temp);
-  return i;
-}
-
-static std::tuple<at::Tensor, at::Tensor> logprob_fwd_impl(const at::Tensor& logits, const at::Tensor& tgt,
-                                                           int64_t vocab_offset, const float* inv) {
-  check_logits(logits);
-  TORCH_CHECK(tgt.scalar_type() == at::kLong && tgt.is_contiguous() && tgt.numel() == logits.size(0),
-              "targets int64 [N]");
-  same_device(logits, tgt);
-  c10::hip::HIPGuardMasqueradingAsCUDA g(logits.device());
-  auto opt = logits.options().dtype(at::kFloat);
-  auto logp = at::empty({logits.size(0)}, opt);
-  auto lse = at::empty({logits.size(0)}, opt);
-  if (inv)
-    launch_logprob_fwd_temp(cbp(logits), logits.stride(0), static_cast<int>(logits.size(1)), vocab_offset,
-                            logits.size(0), tgt.data_ptr<int64_t>(), logp.data_ptr<float>(),
-                            lse.data_ptr<float>(), *inv, cur_stream(logits));
-  else
-    launch_logprob_fwd(cbp(logits), logits.stride(0), static_cast<int>(logits.size(1)),
-                       vocab_offset, logits.size(0), tgt.data_ptr<int64_t>(), logp.data_ptr<float>(),
-                       lse.data_ptr<float>(), cur_stream(logits));
-  return {logp, lse};
-}
-
-std::tuple<at::Tensor, at::Tensor> logprob_fwd(const at::Tensor& logits, const at::Tensor& tgt,
-                                               int64_t vocab_offset) {
-  return logprob_fwd_impl(logits, tgt, vocab_offset, nullptr);
-}
-
-std::tuple<at::Tensor, at::Tensor> logprob_fwd_temp(const at::Tensor& logits, const at::Tensor& tgt,
-                                                    double inv_temp, int64_t vocab_offset) {
-  const float i = checked_inv_temp(inv_temp);
-  return logprob_fwd_impl(logits, tgt, vocab_offset, &i);
-}
-
-static void logprob_bwd_impl(at::Tensor& logits, const at::Tensor& tgt, const at::Tensor& lse,
-                             const at::Tensor& grad, int64_t vocab_offset, const float* inv) {
-  check_logits(logits);
-  check_f32(lse, "lse");
-  check_f32(grad, "grad");
-  const int64_t N = logits.size(0);
-  TORCH_CHECK(tgt.scalar_type() == at::kLong && tgt.numel() == N && tgt.is_contiguous(), "targets");
-  TORCH_CHECK(lse.numel() == N && grad.numel() == N && grad.is_contiguous(), "lse/grad shape");
-  c10::hip::HIPGuardMasqueradingAsCUDA g(logits.device());
-  if (inv)
-    launch_logprob_bwd_temp(bp(logits), logits.stride(0), static_cast<int>(logits.size(1)), vocab_offset, N,
-                            tgt.data_ptr<int64_t>(), lse.data_ptr<float>(), grad.data_ptr<float>(), *inv,
-                            cur_stream(logits));
-  else
-    launch_logprob_bwd(bp(logits), logits.stride(0), static_cast<int>(logits.size(1)), vocab_offset,
-                       N, tgt.data_ptr<int64_t>(), lse.data_ptr<float>(), grad.data_ptr<float>(),
-                       cur_stream(logits));
-}
-
-void logprob_bwd(at::Tensor& logits, const at::Tensor& tgt, const at::Tensor& lse,
-                 const at::Tensor& grad, int64_t vocab_offset) {
-  logprob_bwd_impl(logits, tgt, lse, grad, vocab_offset, nullptr);
-}
-
-void logprob_bwd_temp(at::Tensor& logits, const at::Tensor& tgt, const at::Tensor& lse,
-                      const at::Tensor& grad, double inv_temp, int64_t vocab_offset) {
-  const float i = checked_inv_temp(inv_temp);
-  logprob_bwd_impl(logits, tgt, lse, grad, vocab_offset, &i);
-}
-
-// logprob_bwd with the transposed gradient as a second output: logits <- dlogits (in place) and
-// returns dlogitsT [V, N] (the LM head's TN weight-gradient operand). An empty tensor when the
-// shape is outside the kernel (N, V or the row stride not a multiple of 8): run logprob_bwd.
-static at::Tensor logprob_bwd_t_impl(at::Tensor& logits, const at::Tensor& tgt, const at::Tensor& lse,
-                                     const at::Tensor& grad, int64_t vocab_offset, const float* inv) {
-  check_logits(logits);
-  check_f32(lse, "lse");
-  check_f32(grad, "grad");
-  const int64_t N = logits.size(0), V = logits.size(1);
-  TORCH_CHECK(tgt.scalar_type() == at::kLong && tgt.numel() == N && tgt.is_contiguous(), "targets");
-  TORCH_CHECK(lse.numel() == N && grad.numel() == N && grad.is_contiguous() && lse.is_contiguous(),
-              "lse/grad shape");
-  if (N == 0 || N % 8 != 0 || V % 8 != 0 || logits.stride(0) % 8 != 0) return at::empty({0}, logits.options());
-  c10::hip::HIPGuardMasqueradingAsCUDA g(logits.device());
-  auto outT = at::empty({V, N}, logits.options());
-  const bool ok =
-      inv ? launch_logprob_bwd_t_temp(bp(logits), logits.stride(0), static_cast<int>(V), N, vocab_offset,
-                                      tgt.data_ptr<int64_t>(), lse.data_ptr<float>(), grad.data_ptr<float>(),
-                                      bp(outT), *inv, cur_stream(logits))
-          : launch_logprob_bwd_t(bp(logits), logits.stride(0), static_cast<int>(V), N, vocab_offset,
-                                 tgt.data_ptr<int64_t>(), lse.data_ptr<float>(), grad.data_ptr<float>(),
-                                 bp(outT), cur_stream(logits));
-  TORCH_CHECK(ok, "logprob_bwd_t: shape");
-  return outT;
-}
-
-at::Tensor logprob_bwd_t(at::Tensor& logits, const at::Tensor& tgt, const at::Tensor& lse,
-                         const at::Tensor& grad, int64_t vocab_offset) {
-  return logprob_bwd_t_impl(logits, tgt, lse, grad, vocab_offset, nullptr);
-}
-
-at::Tensor logprob_bwd_t_temp(at::Tensor& logits, const at::Tensor& tgt, const at::Tensor& lse,
-                              const at::Tensor& grad, double inv_temp, int64_t vocab_offset) {
-  const float i = checked_inv_temp(inv_temp);
-  return logprob_bwd_t_impl(logits, tgt, lse, grad, vocab_offset, &i);
-}
-
-// The kept-set twins of the *_temp ops: row r is taken over the vocabulary entries whose bit is set
-// in row keep_rows[r] of keep (uint8 [M, V / 8], bit j of byte i = entry 8 i + j; keep_rows[r] < 0 =
-// the full vocabulary). Equal, bit for bit, to the *_temp ops on logits with the dropped entries
-// written as -inf, without that write. keep_rows[r] < keep.size(0) is the caller's precondition (a
-// check would need a sync). No vocab shard.
-static void check_keep(const at::Tensor& logits, const at::Tensor& keep, const at::Tensor& keep_rows) {
-  const int64_t N = logits.size(0), V = logits.size(1);
-  TORCH_CHECK(V % 8 == 0, "keep mask: the vocabulary size must be a multiple of 8 (V % 8 == 0), got ", V);
-  TORCH_CHECK(logits.stride(0) % 8 == 0, "keep mask: the logits row stride must be a multiple of 8 (ld % 8 == 0)");
-  check_aligned16(logits, "logits");
-  TORCH_CHECK(keep.is_cuda() && keep.scalar_type() == at::kByte && keep.dim() == 2 && keep.is_contiguous(),
-              "keep must be a contiguous uint8 [M, V / 8] tensor on the GPU");
-  TORCH_CHECK(keep.size(1) * 8 == V, "keep.size(1) * 8 must equal V");
-  TORCH_CHECK(keep_rows.is_cuda() && keep_rows.scalar_type() == at::kLong && keep_rows.dim() == 1 &&
-                  keep_rows.size(0) == N && keep_rows.is_contiguous(),
-              "keep_rows must be int64 [N]");
-  same_device(logits, keep);
-  same_device(logits, keep_rows);
-}
-
-std::tuple<at::Tensor, at::Tensor> logprob_fwd_keep(const at::Tensor& logits, const at::Tensor& tgt,
-                                                    const at::Tensor& keep, const at::Tensor& keep_rows,
-                                                    double inv_temp) {
-  const float i = checked_inv_temp(inv_temp);
-  check_logits(logits);
-  check_keep(logits, keep, keep_rows);
-  TORCH_CHECK(tgt.scalar_type() == at::kLong && tgt.is_contiguous() && tgt.numel() == logits.size(0),
-              "targets int64 [N]");
-  same_device(logits, tgt);
-  c10::hip::HIPGuardMasqueradingAsCUDA g(logits.device());
-  auto opt = logits.options().dtype(at::kFloat);
-  auto logp = at::empty({logits.size(0)}, opt);
-  auto lse = at::empty({logits.size(0)}, opt);
-  launch_logprob_fwd_keep(cbp(logits), logits.stride(0), static_cast<int>(logits.size(1)), logits.size(0),
-                          tgt.data_ptr<int64_t>(), logp.data_ptr<float>(), lse.data_ptr<float>(),
-                          keep.data_ptr<uint8_t>(), keep_rows.data_ptr<int64_t>(), i, cur_stream(logits));
-  return {logp, lse};
-}
-
-void logprob_bwd_keep(at::Tensor& logits, const at::Tensor& tgt, const at::Tensor& lse, const at::Tensor& grad,
-                      const at::Tensor& keep, const at::Tensor& keep_rows, double inv_temp) {
-  const float i = checked_inv_temp(inv_temp);
-  check_logits(logits);
-  check_keep(logits, keep, keep_rows);
-  check_f32(lse, "lse");
-  check_f32(grad, "grad");
-  const int64_t N = logits.size(0);
-  TORCH_CHECK(tgt.scalar_type() == at::kLong && tgt.numel() == N && tgt.is_contiguous(), "targets");
-  TORCH_CHECK(lse.numel() == N && grad.numel() == N && grad.is_contiguous() && lse.is_contiguous(),
-              "lse/grad shape");
-  c10::hip::HIPGuardMasqueradingAsCUDA g(logits.device());
-  launch_logprob_bwd_keep(bp(logits), logits.stride(0), static_cast<int>(logits.size(1)), N,
-                          tgt.data_ptr<int64_t>(), lse.data_ptr<float>(), grad.data_ptr<float>(),
-                          keep.data_ptr<uint8_t>(), keep_rows.data_ptr<int64_t>(), i, cur_stream(logits));
-}
-
-// Empty outside the transposing kernel's shapes (N % 8 != 0), as logprob_bwd_t: run logprob_bwd_keep.
-at::Tensor logprob_bwd_t_keep(at::Tensor& logits, const at::Tensor& tgt, const at::Tensor& lse,
-                              const at::Tensor& grad, const at::Tensor& keep, const at::Tensor& keep_rows,
-                              double inv_temp) {
-  const float i = checked_inv_temp(inv_temp);
-  check_logits(logits);
-  check_keep(logits, keep, keep_rows);
-  check_f32(lse, "lse");
-  check_f32(grad, "grad");
-  const int64_t N = logits.size(0), V = logits.size(1);
-  TORCH_CHECK(tgt.scalar_type() == at::kLong && tgt.numel() == N && tgt.is_contiguous(), "targets");
-  TORCH_CHECK(lse.numel() == N && grad.numel() == N && grad.is_contiguous() && lse.is_contiguous(),
-              "lse/grad shape");
-  if (N == 0 || N % 8 != 0) return at::empty({0}, logits.options());
-  c10::hip::HIPGuardMasqueradingAsCUDA g(logits.device());
-  auto outT = at::empty({V, N}, logits.options());
-  const bool ok = launch_logprob_bwd_t_keep(bp(logits), logits.stride(0), static_cast<int>(V), N,
-                                            tgt.data_ptr<int64_t>(), lse.data_ptr<float>(),
-                                            grad.data_ptr<float>(), bp(outT), keep.data_ptr<uint8_t>(),
-                                            keep_rows.data_ptr<int64_t>(), i, cur_stream(logits));
-  TORCH_CHECK(ok, "logprob_bwd_t_keep: shape");
-  return outT;
-}
-
-// The entropy twins: the forward also emits the local shard's softmax entropy per row (every row,
-// whatever its target) from the same read; the backwards add grad_ent's term given the GLOBAL lse
-// and entropy. logp and lse are bitwise logprob_fwd's.
-static std::tuple<at::Tensor, at::Tensor, at::Tensor> logprob_entropy_fwd_impl(const at::Tensor& logits,
-                                                                               const at::Tensor& tgt,
-                                                                               int64_t vocab_offset,
-                                                                               const float* inv) {
-  check_logits(logits);
-  TORCH_CHECK(tgt.scalar_type() == at::kLong && tgt.is_contiguous() && tgt.numel() == logits.size(0),
-              "targets int64 [N]");
-  same_device(logits, tgt);
-  c10::hip::HIPGuardMasqueradingAsCUDA g(logits.device());
-  auto opt = logits.options().dtype(at::kFloat);
-  auto logp = at::empty({logits.size(0)}, opt);
-  auto lse = at::empty({logits.size(0)}, opt);
-  auto ent = at::empty({logits.size(0)}, opt);
-  if (inv)
-    launch_logprob_entropy_fwd_temp(cbp(logits), logits.stride(0), static_cast<int>(logits.size(1)),
-                                    vocab_offset, logits.size(0), tgt.data_ptr<int64_t>(),
-                                    logp.data_ptr<float>(), lse.data_ptr<float>(), ent.data_ptr<float>(), *inv,
-                                    cur_stream(logits));
-  else
-    launch_logprob_entropy_fwd(cbp(logits), logits.stride(0), static_cast<int>(logits.size(1)),
-                               vocab_offset, logits.size(0), tgt.data_ptr<int64_t>(),
-                               logp.data_ptr<float>(), lse.data_ptr<float>(), ent.data_ptr<float>(),
-                               cur_stream(logits));
-  return {logp, lse, ent};
-}
-
-std::tuple<at::Tensor, at::Tensor, at::Tensor> logprob_entropy_fwd(const at::Tensor& logits,
-                                                                   const at::Tensor& tgt,
-                                                                   int64_t vocab_offset) {
-  return logprob_entropy_fwd_impl(logits, tgt, vocab_offset, nullptr);
-}
-
-std::tuple<at::Tensor, at::Tensor, at::Tensor> logprob_entropy_fwd_temp(const at::Tensor& logits,
-                                                                        const at::Tensor& tgt, double inv_temp,
-                                                                        int64_t vocab_offset) {
-  const float i = checked_inv_temp(inv_temp);
-  return logprob_entropy_fwd_impl(logits, tgt, vocab_offset, &i);
-}
-
-static void check_entropy_bwd(const at::Tensor& logits, const at::Tensor& tgt, const at::Tensor& lse,
-                              const at::Tensor& ent, const at::Tensor& grad_logp,
-                              const at::Tensor& grad_ent) {
-  check_logits(logits);
-  check_f32(lse, "lse");
-  check_f32(ent, "ent");
-  check_f32(grad_logp, "grad_logp");
-  check_f32(grad_ent, "grad_ent");
-  const int64_t N = logits.size(0);
-  TORCH_CHECK(tgt.scalar_type() == at::kLong && tgt.numel() == N && tgt.is_contiguous(), "targets");
-  TORCH_CHECK(lse.numel() == N && ent.numel() == N && grad_logp.numel() == N && grad_ent.numel() == N &&
-                  lse.is_contiguous() && ent.is_contiguous() && grad_logp.is_contiguous() &&
-                  grad_ent.is_contiguous(),
-              "lse/ent/grad shape");
-  same_device(logits, tgt);
-  same_device(logits, lse);
-  same_device(logits, ent);
-  same_device(logits, grad_logp);
-  same_device(logits, grad_ent);
-}
-
-static void logprob_entropy_bwd_impl(at::Tensor& logits, const at::Tensor& tgt, const at::Tensor& lse,
-                                     const at::Tensor& ent, const at::Tensor& grad_logp,
-                                     const at::Tensor& grad_ent, int64_t vocab_offset, const float* inv) {
-  check_entropy_bwd(logits, tgt, lse, ent, grad_logp, grad_ent);
-  c10::hip::HIPGuardMasqueradingAsCUDA g(logits.device());
-  if (inv)
-    launch_logprob_entropy_bwd_temp(bp(logits), logits.stride(0), static_cast<int>(logits.size(1)), vocab_offset,
-                                    logits.size(0), tgt.data_ptr<int64_t>(), lse.data_ptr<float>(),
-                                    ent.data_ptr<float>(), grad_logp.data_ptr<float>(),
-                                    grad_ent.data_ptr<float>(), *inv, cur_stream(logits));
-  else
-    launch_logprob_entropy_bwd(bp(logits), logits.stride(0), static_cast<int>(logits.size(1)), vocab_offset,
-                               logits.size(0), tgt.data_ptr<int64_t>(), lse.data_ptr<float>(),
-                               ent.data_ptr<float>(), grad_logp.data_ptr<float>(),
-                               grad_ent.data_ptr<float>(), cur_stream(logits));
-}
-
-void logprob_entropy_bwd(at::Tensor& logits, const at::Tensor& tgt, const at::Tensor& lse,
-                         const at::Tensor& ent, const at::Tensor& grad_logp, const at::Tensor& grad_ent,
-                         int64_t vocab_offset) {
-  logprob_entropy_bwd_impl(logits, tgt, lse, ent, grad_logp, grad_ent, vocab_offset, nullptr);
-}
-
-void logprob_entropy_bwd_temp(at::Tensor& logits, const at::Tensor& tgt, const at::Tensor& lse,
-                              const at::Tensor& ent, const at::Tensor& grad_logp, const at::Tensor& grad_ent,
-                              double inv_temp, int64_t vocab_offset) {
-  const float i = checked_inv_temp(inv_temp);
-  logprob_entropy_bwd_impl(logits, tgt, lse, ent, grad_logp, grad_ent, vocab_offset, &i);
-}
-
-static at::Tensor logprob_entropy_bwd_t_impl(at::Tensor& logits, const at::Tensor& tgt, const at::Tensor& lse,
-                                             const at::Tensor& ent, const at::Tensor& grad_logp,
-                                             const at::Tensor& grad_ent, int64_t vocab_offset,
-                                             const float* inv) {
-  check_entropy_bwd(logits, tgt, lse, ent, grad_logp, grad_ent);
-  const int64_t N = logits.size(0), V = logits.size(1);
-  if (N == 0 || N % 8 != 0 || V % 8 != 0 || logits.stride(0) % 8 != 0) return at::empty({0}, logits.options());
-  c10::hip::HIPGuardMasqueradingAsCUDA g(logits.device());
-  auto outT = at::empty({V, N}, logits.options());
-  const bool ok =
-      inv ? launch_logprob_entropy_bwd_t_temp(bp(logits), logits.stride(0), static_cast<int>(V), N, vocab_offset,
-                                              tgt.data_ptr<int64_t>(), lse.data_ptr<float>(),
-                                              ent.data_ptr<float>(), grad_logp.data_ptr<float>(),
-                                              grad_ent.data_ptr<float>(), bp(outT), *inv, cur_stream(logits))
-          : launch_logprob_entropy_bwd_t(bp(logits), logits.stride(0), static_cast<int>(V), N, vocab_offset,
-                                         tgt.data_ptr<int64_t>(), lse.data_ptr<float>(), ent.data_ptr<float>(),
-                                         grad_logp.data_ptr<float>(), grad_ent.data_ptr<float>(), bp(outT),
-                                         cur_stream(logits));
-  TORCH_CHECK(ok, "logprob_entropy_bwd_t: shape");
-  return outT;
-}
-
-at::Tensor logprob_entropy_bwd_t(at::Tensor& logits, const at::Tensor& tgt, const at::Tensor& lse,
-                                 const at::Tensor& ent, const at::Tensor& grad_logp,
-                                 const at::Tensor& grad_ent, int64_t vocab_offset) {
-  return logprob_entropy_bwd_t_impl(logits, tgt, lse, ent, grad_logp, grad_ent, vocab_offset, nullptr);
-}
-
-at::Tensor logprob_entropy_bwd_t_temp(at::Tensor& logits, const at::Tensor& tgt, const at::Tensor& lse,
-                                      const at::Tensor& ent, const at::Tensor& grad_logp,
-                                      const at::Tensor& grad_ent, double inv_temp, int64_t vocab_offset) {
-  const float i = checked_inv_temp(inv_temp);
-  return logprob_entropy_bwd_t_impl(logits, tgt, lse, ent, grad_logp, grad_ent, vocab_offset, &i);
-}
-
-at::Tensor row_lse(const at::Tensor& logits) {
-  check_logits(logits);
-  c10::hip::HIPGuardMasqueradingAsCUDA g(logits.device());
-  auto lse = at::empty({logits.size(0)}, logits.options().dtype(at::kFloat));
-  launch_row_lse(cbp(logits), logits.stride(0), static_cast<int>(logits.size(1)), logits.size(0),
-                 lse.data_ptr<float>(), cur_stream(logits));
-  return lse;
-}
-
-// s_logits [N, V] (overwritten with dKL/dz * g when write_grad), t_logits [K, N, V] contiguous
-at::Tensor ensemble_kl(at::Tensor& s_logits, const at::Tensor& t_logits, const at::Tensor& s_lse,
-                       const at::Tensor& t_lse, const c10::optional<at::Tensor>& grad,
-                       bool write_grad) {
-  check_bf16(s_logits, "s_logits");
-  check_bf16(t_logits, "t_logits");
-  TORCH_CHECK(s_logits.is_contiguous() && t_logits.is_contiguous() && s_logits.dim() == 2 &&
-                  t_logits.dim() == 3 && t_logits.size(1) == s_logits.size(0) &&
-                  t_logits.size(2) == s_logits.size(1),
-              "ensemble_kl shapes (shared vocab required)");
-  const int64_t N = s_logits.size(0), K = t_logits.size(0);
-  check_f32(s_lse, "s_lse");
-  check_f32(t_lse, "t_lse");
-  TORCH_CHECK(s_lse.numel() == N && t_lse.numel() == K * N && t_lse.is_contiguous(), "lse shapes");
-  const float* gp = nullptr;
-  if (write_grad) {
-    TORCH_CHECK(grad && grad->defined() && grad->numel() == N, "grad required");
-    check_f32(*grad, "grad");
-    gp = grad->data_ptr<float>();
-  }
-  c10::hip::HIPGuardMasqueradingAsCUDA g(s_logits.device());
-  auto kl = at::empty({N}, s_logits.options().dtype(at::kFloat));
-  launch_ensemble_kl(bp(s_logits), cbp(t_logits), s_logits.size(1), N * s_logits.size(1),
-                     static_cast<int>(K), static_cast<int>(s_logits.size(1)),
-                     s_lse.data_ptr<float>(), t_lse.data_ptr<float>(), N, gp,
-                     kl.data_ptr<float>(), write_grad, cur_stream(s_logits));
-  return kl;
-}
-
 // ================================= JSD(beta) distillation (GKD) ===============================
 // s [N, V] bf16, t [K, N, V] bf16 (last dim contiguous, any row strides), row_mask [N] float or
 // uint8 (0: the row is skipped and every output of it is 0). inv_temp = float(1.0 / temperature)
@@ -1495,23 +1102,6 @@ TORCH_LIBRARY(dla, m) {
   m.def("attn_stamps(Tensor like) -> Tensor");
   m.def("attn_fwd_switch(str name, int value) -> int", &dla::attn_fwd_switch);
   m.def("transpose_bf16(Tensor input, Tensor(a!) out) -> ()");
-  m.def("logprob_fwd(Tensor logits, Tensor targets, int vocab_offset=0) -> (Tensor, Tensor)");
-  m.def("logprob_bwd(Tensor(a!) logits, Tensor targets, Tensor lse, Tensor grad, int vocab_offset=0) -> ()");
-  m.def("logprob_bwd_t(Tensor(a!) logits, Tensor targets, Tensor lse, Tensor grad, int vocab_offset=0) -> Tensor");
-  m.def("logprob_entropy_fwd(Tensor logits, Tensor targets, int vocab_offset=0) -> (Tensor, Tensor, Tensor)");
-  m.def("logprob_entropy_bwd(Tensor(a!) logits, Tensor targets, Tensor lse, Tensor ent, Tensor grad_logp, Tensor grad_ent, int vocab_offset=0) -> ()");
-  m.def("logprob_entropy_bwd_t(Tensor(a!) logits, Tensor targets, Tensor lse, Tensor ent, Tensor grad_logp, Tensor grad_ent, int vocab_offset=0) -> Tensor");
-  m.def("logprob_fwd_temp(Tensor logits, Tensor targets, float inv_temp, int vocab_offset=0) -> (Tensor, Tensor)");
-  m.def("logprob_bwd_temp(Tensor(a!) logits, Tensor targets, Tensor lse, Tensor grad, float inv_temp, int vocab_offset=0) -> ()");
-  m.def("logprob_bwd_t_temp(Tensor(a!) logits, Tensor targets, Tensor lse, Tensor grad, float inv_temp, int vocab_offset=0) -> Tensor");
-  m.def("logprob_fwd_keep(Tensor logits, Tensor targets, Tensor keep, Tensor keep_rows, float inv_temp) -> (Tensor, Tensor)");
-  m.def("logprob_bwd_keep(Tensor(a!) logits, Tensor targets, Tensor lse, Tensor grad, Tensor keep, Tensor keep_rows, float inv_temp) -> ()");
-  m.def("logprob_bwd_t_keep(Tensor(a!) logits, Tensor targets, Tensor lse, Tensor grad, Tensor keep, Tensor keep_rows, float inv_temp) -> Tensor");
-  m.def("logprob_entropy_fwd_temp(Tensor logits, Tensor targets, float inv_temp, int vocab_offset=0) -> (Tensor, Tensor, Tensor)");
-  m.def("logprob_entropy_bwd_temp(Tensor(a!) logits, Tensor targets, Tensor lse, Tensor ent, Tensor grad_logp, Tensor grad_ent, float inv_temp, int vocab_offset=0) -> ()");
-  m.def("logprob_entropy_bwd_t_temp(Tensor(a!) logits, Tensor targets, Tensor lse, Tensor ent, Tensor grad_logp, Tensor grad_ent, float inv_temp, int vocab_offset=0) -> Tensor");
-  m.def("row_lse(Tensor logits) -> Tensor");
-  m.def("ensemble_kl(Tensor(a!) s_logits, Tensor t_logits, Tensor s_lse, Tensor t_lse, Tensor? grad, bool write_grad) -> Tensor");
   m.def("gjsd_fwd(Tensor s, Tensor t, Tensor? row_mask, float beta, float inv_temp) -> (Tensor, Tensor, Tensor, Tensor)");
   m.def("gjsd_bwd(Tensor s, Tensor t, Tensor s_lse, Tensor t_lse, Tensor aux, Tensor? row_mask, Tensor grad, float beta, float inv_temp) -> Tensor");
   m.def("seq_reduce(Tensor lp, Tensor mask) -> (Tensor, Tensor)");
@@ -1548,23 +1138,6 @@ TORCH_LIBRARY_IMPL(dla, CUDA, m) {
   m.impl("attn_bwd", &dla::attn_bwd);
   m.impl("attn_stamps", &dla::attn_stamps);
   m.impl("transpose_bf16", &dla::transpose_bf16);
-  m.impl("logprob_fwd", &dla::logprob_fwd);
-  m.impl("logprob_bwd", &dla::logprob_bwd);
-  m.impl("logprob_bwd_t", &dla::logprob_bwd_t);
-  m.impl("logprob_entropy_fwd", &dla::logprob_entropy_fwd);
-  m.impl("logprob_entropy_bwd", &dla::logprob_entropy_bwd);
-  m.impl("logprob_entropy_bwd_t", &dla::logprob_entropy_bwd_t);
-  m.impl("logprob_fwd_temp", &dla::logprob_fwd_temp);
-  m.impl("logprob_bwd_temp", &dla::logprob_bwd_temp);
-  m.impl("logprob_bwd_t_temp", &dla::logprob_bwd_t_temp);
-  m.impl("logprob_fwd_keep", &dla::logprob_fwd_keep);
-  m.impl("logprob_bwd_keep", &dla::logprob_bwd_keep);
-  m.impl("logprob_bwd_t_keep", &dla::logprob_bwd_t_keep);
-  m.impl("logprob_entropy_fwd_temp", &dla::logprob_entropy_fwd_temp);
-  m.impl("logprob_entropy_bwd_temp", &dla::logprob_entropy_bwd_temp);
-  m.impl("logprob_entropy_bwd_t_temp", &dla::logprob_entropy_bwd_t_temp);
-  m.impl("row_lse", &dla::row_lse);
-  m.impl("ensemble_kl", &dla::ensemble_kl);
   m.impl("gjsd_fwd", &dla::gjsd_fwd);
   m.impl("gjsd_bwd", &dla::gjsd_bwd);
   m.impl("seq_reduce", &dla::seq_reduce);

@@ -9,7 +9,11 @@
 // V=128256). Here one 256-thread block streams a bf16 logits row once (16 B per lane,
 // online max/sum in fp32), emitting only per-row scalars; the backward rewrites the SAME
 // buffer in place as bf16 dlogits, which feeds the dH / dW GEMMs directly.
+#include <stdexcept>
+#include <type_traits>
+
 #include "common.h"
+#include "logprob_params.h"
 
 namespace dla {
 
@@ -473,156 +477,89 @@ __global__ __launch_bounds__(256) void row_lse_kernel(const bf16_t* __restrict__
 }
 
 // ----------------------------------------------------------------------------------------------
-void launch_logprob_fwd(const bf16_t* logits, int64_t ld, int V, int64_t off, int64_t rows,
-                        const int64_t* tgt, float* logp, float* lse, hipStream_t st) {
-  if (rows == 0) return;
-  const bool vec = (V % 8 == 0) && (ld % 8 == 0);
-  if (vec) logprob_fwd_kernel<true><<<rows, 256, 0, st>>>(logits, ld, V, off, tgt, logp, lse);
-  else logprob_fwd_kernel<false><<<rows, 256, 0, st>>>(logits, ld, V, off, tgt, logp, lse);
+// Host launchers (logprob_params.h): one per kernel, the instantiation picked from the struct.
+
+// f(std::true_type / std::false_type): a run-time flag as a template argument
+template <class F>
+static void with_flag(bool b, F&& f) {
+  if (b) f(std::true_type{});
+  else f(std::false_type{});
 }
 
-void launch_logprob_bwd(bf16_t* logits, int64_t ld, int V, int64_t off, int64_t rows,
-                        const int64_t* tgt, const float* lse, const float* g, hipStream_t st) {
-  if (rows == 0) return;
-  const bool vec = (V % 8 == 0) && (ld % 8 == 0);
-  if (vec) logprob_bwd_kernel<true><<<rows, 256, 0, st>>>(logits, ld, V, off, tgt, lse, g);
-  else logprob_bwd_kernel<false><<<rows, 256, 0, st>>>(logits, ld, V, off, tgt, lse, g);
+static bool vec_ok(const LogprobParams& p) { return (p.V % 8 == 0) && (p.ld % 8 == 0); }
+
+// The one place that rejects the combinations without a kernel (the MASK static_asserts above):
+// never a quiet fall-back to another instantiation.
+static void check_combo(const LogprobParams& p, bool ent) {
+  if ((p.keep == nullptr) != (p.keep_rows == nullptr))
+    throw std::invalid_argument("logprob: keep and keep_rows go together");
+  if (!p.keep) return;
+  if (!p.temp) throw std::invalid_argument("logprob: the keep mask exists for the tempered kernels only");
+  if (ent) throw std::invalid_argument("logprob: no kernel takes a keep mask and the entropy");
+  if (!vec_ok(p)) throw std::invalid_argument("logprob: the keep mask needs V % 8 == 0 and ld % 8 == 0");
+  if (p.off != 0) throw std::invalid_argument("logprob: the keep mask takes no vocab shard");
 }
 
-void launch_logprob_entropy_fwd(const bf16_t* logits, int64_t ld, int V, int64_t off, int64_t rows,
-                                const int64_t* tgt, float* logp, float* lse, float* ent, hipStream_t st) {
-  if (rows == 0) return;
-  const bool vec = (V % 8 == 0) && (ld % 8 == 0);
-  if (vec) logprob_fwd_kernel<true, true><<<rows, 256, 0, st>>>(logits, ld, V, off, tgt, logp, lse, ent);
-  else logprob_fwd_kernel<false, true><<<rows, 256, 0, st>>>(logits, ld, V, off, tgt, logp, lse, ent);
+// (the non-TEMP kernels get the 1.f their argument defaults to)
+static float inv_temp_arg(const LogprobParams& p) { return p.temp ? p.inv_temp : 1.f; }
+
+template <bool VEC, bool ENT, bool TEMP, bool MASK = false>
+static void fwd_rows(const LogprobParams& p, hipStream_t st) {
+  logprob_fwd_kernel<VEC, ENT, TEMP, MASK><<<p.rows, 256, 0, st>>>(
+      p.logits, p.ld, p.V, p.off, p.tgt, p.logp, p.lse, p.ent, inv_temp_arg(p), p.keep, p.keep_rows);
 }
 
-void launch_logprob_entropy_bwd(bf16_t* logits, int64_t ld, int V, int64_t off, int64_t rows,
-                                const int64_t* tgt, const float* lse, const float* ent, const float* g,
-                                const float* ge, hipStream_t st) {
-  if (rows == 0) return;
-  const bool vec = (V % 8 == 0) && (ld % 8 == 0);
-  if (vec) logprob_bwd_kernel<true, true><<<rows, 256, 0, st>>>(logits, ld, V, off, tgt, lse, g, ent, ge);
-  else logprob_bwd_kernel<false, true><<<rows, 256, 0, st>>>(logits, ld, V, off, tgt, lse, g, ent, ge);
+void launch_logprob_fwd(const LogprobParams& p, hipStream_t st) {
+  const bool ent = p.ent != nullptr;
+  check_combo(p, ent);
+  if (p.rows == 0) return;
+  if (p.keep) return fwd_rows<true, false, true, true>(p, st);
+  with_flag(vec_ok(p), [&](auto VEC) {
+    with_flag(ent, [&](auto ENT) {
+      with_flag(p.temp, [&](auto TEMP) { fwd_rows<VEC(), ENT(), TEMP()>(p, st); });
+    });
+  });
 }
 
-bool launch_logprob_entropy_bwd_t(bf16_t* logits, int64_t ld, int V, int64_t rows, int64_t off,
-                                  const int64_t* tgt, const float* lse, const float* ent, const float* g,
-                                  const float* ge, bf16_t* outT, hipStream_t st) {
-  if (rows % 8 != 0 || V % 8 != 0 || ld % 8 != 0) return false;
-  if (rows == 0) return true;
-  const dim3 grid((V + 255) / 256, static_cast<unsigned>((rows + 63) / 64));
-  logprob_bwd_t_kernel<true><<<grid, 256, 0, st>>>(logits, ld, V, off, tgt, lse, g, outT, rows, ent, ge);
-  return true;
+template <bool VEC, bool ENT, bool TEMP, bool MASK = false>
+static void bwd_rows(const LogprobParams& p, hipStream_t st) {
+  logprob_bwd_kernel<VEC, ENT, TEMP, MASK><<<p.rows, 256, 0, st>>>(
+      p.logits, p.ld, p.V, p.off, p.tgt, p.lse, p.g, ENT ? p.ent : nullptr, p.ge, inv_temp_arg(p), p.keep,
+      p.keep_rows);
 }
 
-bool launch_logprob_bwd_t(bf16_t* logits, int64_t ld, int V, int64_t rows, int64_t off, const int64_t* tgt,
-                          const float* lse, const float* g, bf16_t* outT, hipStream_t st) {
-  if (rows % 8 != 0 || V % 8 != 0 || ld % 8 != 0) return false;
-  if (rows == 0) return true;
-  const dim3 grid((V + 255) / 256, static_cast<unsigned>((rows + 63) / 64));
-  logprob_bwd_t_kernel<false><<<grid, 256, 0, st>>>(logits, ld, V, off, tgt, lse, g, outT, rows);
-  return true;
+void launch_logprob_bwd(const LogprobParams& p, hipStream_t st) {
+  const bool ent = p.ge != nullptr;
+  check_combo(p, ent);
+  if (p.rows == 0) return;
+  if (p.keep) return bwd_rows<true, false, true, true>(p, st);
+  with_flag(vec_ok(p), [&](auto VEC) {
+    with_flag(ent, [&](auto ENT) {
+      with_flag(p.temp, [&](auto TEMP) { bwd_rows<VEC(), ENT(), TEMP()>(p, st); });
+    });
+  });
 }
 
-// The tempered twins (TEMP instantiations): the same launches with inv_temp = 1 / temperature.
-void launch_logprob_fwd_temp(const bf16_t* logits, int64_t ld, int V, int64_t off, int64_t rows,
-                             const int64_t* tgt, float* logp, float* lse, float inv_temp, hipStream_t st) {
-  if (rows == 0) return;
-  const bool vec = (V % 8 == 0) && (ld % 8 == 0);
-  if (vec)
-    logprob_fwd_kernel<true, false, true><<<rows, 256, 0, st>>>(logits, ld, V, off, tgt, logp, lse, nullptr,
-                                                                inv_temp);
-  else
-    logprob_fwd_kernel<false, false, true><<<rows, 256, 0, st>>>(logits, ld, V, off, tgt, logp, lse, nullptr,
-                                                                 inv_temp);
+template <bool ENT, bool TEMP, bool MASK = false>
+static void bwd_t_tiles(const LogprobParams& p, hipStream_t st) {
+  const dim3 grid((p.V + 255) / 256, static_cast<unsigned>((p.rows + 63) / 64));
+  logprob_bwd_t_kernel<ENT, TEMP, MASK><<<grid, 256, 0, st>>>(
+      p.logits, p.ld, p.V, p.off, p.tgt, p.lse, p.g, p.outT, p.rows, ENT ? p.ent : nullptr, p.ge,
+      inv_temp_arg(p), p.keep, p.keep_rows);
 }
 
-void launch_logprob_bwd_temp(bf16_t* logits, int64_t ld, int V, int64_t off, int64_t rows, const int64_t* tgt,
-                             const float* lse, const float* g, float inv_temp, hipStream_t st) {
-  if (rows == 0) return;
-  const bool vec = (V % 8 == 0) && (ld % 8 == 0);
-  if (vec)
-    logprob_bwd_kernel<true, false, true><<<rows, 256, 0, st>>>(logits, ld, V, off, tgt, lse, g, nullptr,
-                                                                nullptr, inv_temp);
-  else
-    logprob_bwd_kernel<false, false, true><<<rows, 256, 0, st>>>(logits, ld, V, off, tgt, lse, g, nullptr,
-                                                                 nullptr, inv_temp);
-}
-
-void launch_logprob_entropy_fwd_temp(const bf16_t* logits, int64_t ld, int V, int64_t off, int64_t rows,
-                                     const int64_t* tgt, float* logp, float* lse, float* ent, float inv_temp,
-                                     hipStream_t st) {
-  if (rows == 0) return;
-  const bool vec = (V % 8 == 0) && (ld % 8 == 0);
-  if (vec)
-    logprob_fwd_kernel<true, true, true><<<rows, 256, 0, st>>>(logits, ld, V, off, tgt, logp, lse, ent,
-                                                               inv_temp);
-  else
-    logprob_fwd_kernel<false, true, true><<<rows, 256, 0, st>>>(logits, ld, V, off, tgt, logp, lse, ent,
-                                                                inv_temp);
-}
-
-void launch_logprob_entropy_bwd_temp(bf16_t* logits, int64_t ld, int V, int64_t off, int64_t rows,
-                                     const int64_t* tgt, const float* lse, const float* ent, const float* g,
-                                     const float* ge, float inv_temp, hipStream_t st) {
-  if (rows == 0) return;
-  const bool vec = (V % 8 == 0) && (ld % 8 == 0);
-  if (vec)
-    logprob_bwd_kernel<true, true, true><<<rows, 256, 0, st>>>(logits, ld, V, off, tgt, lse, g, ent, ge,
-                                                               inv_temp);
-  else
-    logprob_bwd_kernel<false, true, true><<<rows, 256, 0, st>>>(logits, ld, V, off, tgt, lse, g, ent, ge,
-                                                                inv_temp);
-}
-
-bool launch_logprob_entropy_bwd_t_temp(bf16_t* logits, int64_t ld, int V, int64_t rows, int64_t off,
-                                       const int64_t* tgt, const float* lse, const float* ent, const float* g,
-                                       const float* ge, bf16_t* outT, float inv_temp, hipStream_t st) {
-  if (rows % 8 != 0 || V % 8 != 0 || ld % 8 != 0) return false;
-  if (rows == 0) return true;
-  const dim3 grid((V + 255) / 256, static_cast<unsigned>((rows + 63) / 64));
-  logprob_bwd_t_kernel<true, true><<<grid, 256, 0, st>>>(logits, ld, V, off, tgt, lse, g, outT, rows, ent, ge,
-                                                         inv_temp);
-  return true;
-}
-
-bool launch_logprob_bwd_t_temp(bf16_t* logits, int64_t ld, int V, int64_t rows, int64_t off, const int64_t* tgt,
-                               const float* lse, const float* g, bf16_t* outT, float inv_temp, hipStream_t st) {
-  if (rows % 8 != 0 || V % 8 != 0 || ld % 8 != 0) return false;
-  if (rows == 0) return true;
-  const dim3 grid((V + 255) / 256, static_cast<unsigned>((rows + 63) / 64));
-  logprob_bwd_t_kernel<false, true><<<grid, 256, 0, st>>>(logits, ld, V, off, tgt, lse, g, outT, rows, nullptr,
-                                                          nullptr, inv_temp);
-  return true;
-}
-
-// The kept-set twins (MASK instantiations) of the tempered launches: keep uint8 [M, V / 8], keep_rows
-// int64 [rows] (< 0: no mask). V % 8 == 0 and ld % 8 == 0 are the caller's to check; no vocab shard.
-void launch_logprob_fwd_keep(const bf16_t* logits, int64_t ld, int V, int64_t rows, const int64_t* tgt,
-                             float* logp, float* lse, const uint8_t* keep, const int64_t* keep_rows,
-                             float inv_temp, hipStream_t st) {
-  if (rows == 0) return;
-  logprob_fwd_kernel<true, false, true, true><<<rows, 256, 0, st>>>(logits, ld, V, 0, tgt, logp, lse, nullptr,
-                                                                    inv_temp, keep, keep_rows);
-}
-
-void launch_logprob_bwd_keep(bf16_t* logits, int64_t ld, int V, int64_t rows, const int64_t* tgt,
-                             const float* lse, const float* g, const uint8_t* keep, const int64_t* keep_rows,
-                             float inv_temp, hipStream_t st) {
-  if (rows == 0) return;
-  logprob_bwd_kernel<true, false, true, true><<<rows, 256, 0, st>>>(logits, ld, V, 0, tgt, lse, g, nullptr,
-                                                                    nullptr, inv_temp, keep, keep_rows);
-}
-
-bool launch_logprob_bwd_t_keep(bf16_t* logits, int64_t ld, int V, int64_t rows, const int64_t* tgt,
-                               const float* lse, const float* g, bf16_t* outT, const uint8_t* keep,
-                               const int64_t* keep_rows, float inv_temp, hipStream_t st) {
-  if (rows % 8 != 0 || V % 8 != 0 || ld % 8 != 0) return false;
-  if (rows == 0) return true;
-  const dim3 grid((V + 255) / 256, static_cast<unsigned>((rows + 63) / 64));
-  logprob_bwd_t_kernel<false, true, true><<<grid, 256, 0, st>>>(logits, ld, V, 0, tgt, lse, g, outT, rows,
-                                                                nullptr, nullptr, inv_temp, keep, keep_rows);
+bool launch_logprob_bwd_t(const LogprobParams& p, hipStream_t st) {
+  const bool ent = p.ge != nullptr;
+  check_combo(p, ent);
+  if (p.rows % 8 != 0 || !vec_ok(p)) return false;
+  if (p.rows == 0) return true;
+  if (p.keep) {
+    bwd_t_tiles<false, true, true>(p, st);
+    return true;
+  }
+  with_flag(ent, [&](auto ENT) {
+    with_flag(p.temp, [&](auto TEMP) { bwd_t_tiles<ENT(), TEMP()>(p, st); });
+  });
   return true;
 }
 

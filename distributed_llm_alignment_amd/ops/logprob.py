@@ -116,25 +116,78 @@ def _ref_linear_logprob_keep(hidden, weight, targets, temperature, keep, keep_ro
     return torch.where(targets >= 0, lp, torch.zeros_like(lp))
 
 
+def _variant(inv_temp, off, keep, keep_rows, entropy):
+    """The op-name suffix and the trailing arguments of a row op: plain, `_temp` or `_keep`."""
+    if (keep is None) != (keep_rows is None):
+        raise ValueError("keep and keep_rows go together")
+    if keep is not None:
+        if inv_temp is None or entropy or off:
+            raise ValueError("the keep ops take an inv_temp and neither the entropy nor a vocab shard")
+        return "_keep", (keep, keep_rows, inv_temp)
+    tail = (int(off),) if off else ()  # (0 is the schemas' default)
+    return ("", tail) if inv_temp is None else ("_temp", (inv_temp,) + tail)
+
+
+def rows_fwd(logits, targets, *, inv_temp=None, off=0, keep=None, keep_rows=None, entropy=False):
+    """The forward row op on bf16 logits [N, V]: (logp, lse), with `entropy` (logp, lse, ent).
+    inv_temp None = the plain ops, a float = the tempered twins (see `inv_temperature`); keep /
+    keep_rows (with an inv_temp) = their kept-set twins; off = the first entry of a vocabulary shard."""
+    suffix, tail = _variant(inv_temp, off, keep, keep_rows, entropy)
+    op = getattr(_ext.require(), ("logprob_entropy_fwd" if entropy else "logprob_fwd") + suffix)
+    return op(logits, targets, *tail)
+
+
+def rows_bwd(logits, targets, lse, g, *, ent=None, ge=None, inv_temp=None, off=0, keep=None, keep_rows=None,
+             transposed=False):
+    """The backward row op: `logits` rewritten in place as dlogits. With no gradient `ge` for the
+    entropy the plain ops run (`ent` is not read). `transposed`: the op that also returns dlogits^T
+    [V, N] (empty, with nothing written, outside its shapes); otherwise None is returned."""
+    suffix, tail = _variant(inv_temp, off, keep, keep_rows, ge is not None)
+    name = ("logprob_bwd" if ge is None else "logprob_entropy_bwd") + ("_t" if transposed else "") + suffix
+    rows = (lse, g) if ge is None else (lse, ent, g, ge)
+    out = getattr(_ext.require(), name)(logits, targets, *rows, *tail)
+    return out if transposed else None
+
+
+def _head_backward(needs, hidden, weight, logits, targets, lse, g, **kw):
+    """The backward both Functions share: logits -> dlogits in place (`rows_bwd(..., **kw)`), then
+    (dH, dW); dW is None where it was accumulated into the weight's main_grad."""
+    from .linear import _tn_ok, accumulate_weight_grad
+
+    dlt = None
+    mg = getattr(weight, "main_grad", None)
+    if (LOGPROB_T and needs[1] and mg is not None and not getattr(weight, "_dla_shared", False)
+            and _tn_ok(mg, logits.shape[0])):
+        # the LM head's weight gradient runs as a TN GEMM on dlogits^T: write it from the
+        # same pass that turns the logits into dlogits (undefined when the shape is outside
+        # the kernel -> in-place kernel + transpose inside accumulate_weight_grad)
+        dlt = rows_bwd(logits, targets, lse, g, transposed=True, **kw)
+        if not dlt.numel():
+            dlt = None
+    if dlt is None:
+        rows_bwd(logits, targets, lse, g, **kw)
+    dlogits = logits  # rewritten in place
+    dh = input_grad(dlogits, weight) if needs[0] else None
+    dw = None
+    if needs[1]:
+        if not accumulate_weight_grad(weight, dlogits, hidden, dyt=dlt):
+            dw = dlogits.t() @ hidden
+    return dh, dw
+
+
 class _LinearLogprobFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, hidden, weight, targets, inv_temp=None, keep=None, keep_rows=None):
         # inv_temp: None = the plain ops; a float = the tempered twins (see `inv_temperature`)
         # keep / keep_rows (with a float inv_temp): the kept-set twins of the tempered ops
-        ops = _ext.require()
         need_grad = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
         N = hidden.shape[0]
         ctx.inv_temp = inv_temp
         ctx.keep, ctx.keep_rows = keep, keep_rows
 
-        def fwd(lg, tg, kr=None):
-            if keep is not None:
-                return ops.logprob_fwd_keep(lg, tg, keep, kr, inv_temp)
-            return ops.logprob_fwd(lg, tg) if inv_temp is None else ops.logprob_fwd_temp(lg, tg, inv_temp)
-
         if need_grad:
             logits = F.linear(hidden, weight)
-            logp, lse = fwd(logits, targets, keep_rows)
+            logp, lse = rows_fwd(logits, targets, inv_temp=inv_temp, keep=keep, keep_rows=keep_rows)
             ctx.save_for_backward(hidden, targets, lse, logits)
             ctx.weight = weight  # (on ctx: see ops.linear._LinearMainGradFn)
             return logp
@@ -142,47 +195,16 @@ class _LinearLogprobFn(torch.autograd.Function):
         for s in range(0, N, _NO_GRAD_CHUNK):
             e = min(N, s + _NO_GRAD_CHUNK)
             lg = F.linear(hidden[s:e], weight)
-            lp, _ = fwd(lg, targets[s:e], keep_rows[s:e] if keep is not None else None)
+            lp, _ = rows_fwd(lg, targets[s:e], inv_temp=inv_temp, keep=keep,
+                             keep_rows=keep_rows[s:e] if keep is not None else None)
             logp[s:e] = lp
         return logp
 
     @staticmethod
     def backward(ctx, g):
-        ops = _ext.require()
         hidden, targets, lse, logits = ctx.saved_tensors
-        weight = ctx.weight
-        it = ctx.inv_temp
-        keep, kr = ctx.keep, ctx.keep_rows
-        from .linear import _tn_ok, accumulate_weight_grad
-
-        g = g.float().contiguous()
-        dlt = None
-        mg = getattr(weight, "main_grad", None)
-        if (LOGPROB_T and ctx.needs_input_grad[1] and mg is not None and not getattr(weight, "_dla_shared", False)
-                and _tn_ok(mg, logits.shape[0])):
-            # the LM head's weight gradient runs as a TN GEMM on dlogits^T: write it from the
-            # same pass that turns the logits into dlogits (undefined when the shape is outside
-            # the kernel -> in-place kernel + transpose inside accumulate_weight_grad)
-            if keep is not None:
-                dlt = ops.logprob_bwd_t_keep(logits, targets, lse, g, keep, kr, it)
-            else:
-                dlt = (ops.logprob_bwd_t(logits, targets, lse, g) if it is None
-                       else ops.logprob_bwd_t_temp(logits, targets, lse, g, it))
-            if not dlt.numel():
-                dlt = None
-        if dlt is None:
-            if keep is not None:
-                ops.logprob_bwd_keep(logits, targets, lse, g, keep, kr, it)
-            elif it is None:
-                ops.logprob_bwd(logits, targets, lse, g)
-            else:
-                ops.logprob_bwd_temp(logits, targets, lse, g, it)
-        dlogits = logits  # rewritten in place
-        dh = input_grad(dlogits, weight) if ctx.needs_input_grad[0] else None
-        dw = None
-        if ctx.needs_input_grad[1]:
-            if not accumulate_weight_grad(weight, dlogits, hidden, dyt=dlt):
-                dw = dlogits.t() @ hidden
+        dh, dw = _head_backward(ctx.needs_input_grad, hidden, ctx.weight, logits, targets, lse, g.float().contiguous(),
+                                inv_temp=ctx.inv_temp, keep=ctx.keep, keep_rows=ctx.keep_rows)
         return dh, dw, None, None, None, None
 
 
@@ -234,19 +256,14 @@ class _LinearLogprobEntropyFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, hidden, weight, targets, inv_temp=None):
-        ops = _ext.require()
         ctx.set_materialize_grads(False)
         need_grad = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
         N = hidden.shape[0]
         ctx.inv_temp = inv_temp
 
-        def fwd(lg, tg):
-            return (ops.logprob_entropy_fwd(lg, tg) if inv_temp is None
-                    else ops.logprob_entropy_fwd_temp(lg, tg, inv_temp))
-
         if need_grad:
             logits = F.linear(hidden, weight)
-            logp, lse, ent = fwd(logits, targets)
+            logp, lse, ent = rows_fwd(logits, targets, inv_temp=inv_temp, entropy=True)
             ent = ent.masked_fill_(targets < 0, 0.0)
             ctx.save_for_backward(hidden, targets, lse, ent, logits)
             ctx.weight = weight  # (on ctx: see ops.linear._LinearMainGradFn)
@@ -256,52 +273,20 @@ class _LinearLogprobEntropyFn(torch.autograd.Function):
         for s in range(0, N, _NO_GRAD_CHUNK):
             e = min(N, s + _NO_GRAD_CHUNK)
             lg = F.linear(hidden[s:e], weight)
-            lp, _, en = fwd(lg, targets[s:e])
+            lp, _, en = rows_fwd(lg, targets[s:e], inv_temp=inv_temp, entropy=True)
             logp[s:e] = lp
             ent[s:e] = en
         return logp, ent.masked_fill_(targets < 0, 0.0)
 
     @staticmethod
     def backward(ctx, g, ge):
-        ops = _ext.require()
         hidden, targets, lse, ent, logits = ctx.saved_tensors
-        weight = ctx.weight
-        it = ctx.inv_temp
         if g is None and ge is None:
             return None, None, None, None
-        from .linear import _tn_ok, accumulate_weight_grad
-
         g = torch.zeros_like(lse) if g is None else g.float().contiguous()
         ge = None if ge is None else ge.float().contiguous()
-        dlt = None
-        mg = getattr(weight, "main_grad", None)
-        if (LOGPROB_T and ctx.needs_input_grad[1] and mg is not None and not getattr(weight, "_dla_shared", False)
-                and _tn_ok(mg, logits.shape[0])):
-            # as in _LinearLogprobFn: dlogits^T from the same pass (empty outside the kernel's shapes)
-            if it is None:
-                dlt = (ops.logprob_bwd_t(logits, targets, lse, g) if ge is None
-                       else ops.logprob_entropy_bwd_t(logits, targets, lse, ent, g, ge))
-            else:
-                dlt = (ops.logprob_bwd_t_temp(logits, targets, lse, g, it) if ge is None
-                       else ops.logprob_entropy_bwd_t_temp(logits, targets, lse, ent, g, ge, it))
-            if not dlt.numel():
-                dlt = None
-        if dlt is None:
-            if it is None:
-                if ge is None:
-                    ops.logprob_bwd(logits, targets, lse, g)
-                else:
-                    ops.logprob_entropy_bwd(logits, targets, lse, ent, g, ge)
-            elif ge is None:
-                ops.logprob_bwd_temp(logits, targets, lse, g, it)
-            else:
-                ops.logprob_entropy_bwd_temp(logits, targets, lse, ent, g, ge, it)
-        dlogits = logits  # rewritten in place
-        dh = input_grad(dlogits, weight) if ctx.needs_input_grad[0] else None
-        dw = None
-        if ctx.needs_input_grad[1]:
-            if not accumulate_weight_grad(weight, dlogits, hidden, dyt=dlt):
-                dw = dlogits.t() @ hidden
+        dh, dw = _head_backward(ctx.needs_input_grad, hidden, ctx.weight, logits, targets, lse, g, ent=ent, ge=ge,
+                                inv_temp=ctx.inv_temp)
         return dh, dw, None, None
 
 

@@ -33,6 +33,7 @@ import torch.distributed as dist
 import torch.nn.functional as F
 
 from ..ops import _ext
+from ..ops.logprob import rows_bwd, rows_fwd
 from . import collectives as coll
 
 
@@ -483,9 +484,7 @@ def vocab_parallel_embedding(ids: torch.Tensor, weight_l: torch.Tensor, off: int
 # (logp_l + lse_l is already the tempered target logit).
 def _local_fwd(logits_l, targets, off, it=None):
     if _ext.use_native(logits_l):
-        if it is not None:
-            return _ext.require().logprob_fwd_temp(logits_l, targets, it, int(off))
-        return _ext.require().logprob_fwd(logits_l, targets, int(off))
+        return rows_fwd(logits_l, targets, inv_temp=it, off=off)
     lf = logits_l.float()
     if it is not None:
         lf = lf * it
@@ -498,10 +497,7 @@ def _local_fwd(logits_l, targets, off, it=None):
 
 def _local_bwd(logits_l, targets, lse, g, off, it=None):
     if _ext.use_native(logits_l):
-        if it is not None:
-            _ext.require().logprob_bwd_temp(logits_l, targets, lse, g.float().contiguous(), it, int(off))
-        else:
-            _ext.require().logprob_bwd(logits_l, targets, lse, g.float().contiguous(), int(off))
+        rows_bwd(logits_l, targets, lse, g.float().contiguous(), inv_temp=it, off=off)
         return logits_l
     lf = logits_l.float()
     if it is not None:
@@ -582,9 +578,7 @@ def vocab_parallel_logprob(hidden, weight_l, targets, off: int, group, temperatu
 # and H, so no extra kernel: dz_j = g (1[j == t] - p_j) - e p_j (z_j - lse + H).
 def _local_fwd_entropy(logits_l, targets, off, it=None):
     if _ext.use_native(logits_l):
-        if it is not None:
-            return _ext.require().logprob_entropy_fwd_temp(logits_l, targets, it, int(off))
-        return _ext.require().logprob_entropy_fwd(logits_l, targets, int(off))
+        return rows_fwd(logits_l, targets, inv_temp=it, off=off, entropy=True)
     logp, lse = _local_fwd(logits_l, targets, off, it)
     lf = logits_l.float()
     if it is not None:
@@ -596,12 +590,8 @@ def _local_fwd_entropy(logits_l, targets, off, it=None):
 
 def _local_bwd_entropy(logits_l, targets, lse, ent, g, ge, off, it=None):
     if _ext.use_native(logits_l):
-        if it is not None:
-            _ext.require().logprob_entropy_bwd_temp(logits_l, targets, lse, ent, g.float().contiguous(),
-                                                    ge.float().contiguous(), it, int(off))
-        else:
-            _ext.require().logprob_entropy_bwd(logits_l, targets, lse, ent, g.float().contiguous(),
-                                               ge.float().contiguous(), int(off))
+        rows_bwd(logits_l, targets, lse, g.float().contiguous(), ent=ent, ge=ge.float().contiguous(), inv_temp=it,
+                 off=off)
         return logits_l
     lf = logits_l.float()
     if it is not None:

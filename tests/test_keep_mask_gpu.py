@@ -124,12 +124,12 @@ def test_keep_rows(kind, pattern, tau):
 
 @pytest.mark.parametrize("tau", [0.7, 1.0])
 @pytest.mark.parametrize("pattern", RK.PATTERNS)
-@pytest.mark.parametrize("N", [16, 72])
-def test_keep_bwd_t(N, pattern, tau):
-    """The transposing kernel gives `logprob_bwd_keep`'s bits in place and their exact transpose."""
+@pytest.mark.parametrize("N,V", [(16, 2048), (72, 2048), (72, 264)], ids=["16", "72", "72x264"])
+def test_keep_bwd_t(N, V, pattern, tau):
+    """The transposing kernel gives `logprob_bwd_keep`'s bits in place and their exact transpose
+    (72 x 264: a partial 64 x 256 tile in both grid dimensions)."""
     k = _ext.require()
     it = RT.inv32(tau)
-    V = 2048
     x = R.rows_case(V, N=N, seed=4)
     mask, kr, kept, tgt = RK.case(pattern, x)
     lse = RK.rows64(x, tgt, it, kept)["lse"].float().to(DEV)

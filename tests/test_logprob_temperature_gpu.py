@@ -111,8 +111,7 @@ def test_tempered_rows(kind, pattern, tau):
 
 
 # -------------------------------------------------------------------- transposing kernels
-def _t_case(pattern):
-    N, V = 16, 2048
+def _t_case(pattern, N=16, V=2048):
     x = R.rows_case(V, N=N, seed=4)
     tgt = R.rows_targets(N, V)
     dead = None
@@ -124,13 +123,14 @@ def _t_case(pattern):
 
 
 @pytest.mark.parametrize("tau", RT.TEMPS)
-@pytest.mark.parametrize("pattern", R.DEAD_PATTERNS)
-def test_tempered_bwd_t(pattern, tau):
+@pytest.mark.parametrize("pattern,N,V", [(p, 16, 2048) for p in R.DEAD_PATTERNS] + [(p, 72, 264) for p in R.DEAD_PATTERNS],
+                         ids=R.DEAD_PATTERNS + [p + "-72x264" for p in R.DEAD_PATTERNS])
+def test_tempered_bwd_t(pattern, N, V, tau):
     """The tempered transposing kernels write the tempered in-place kernel's bits and their exact
-    transpose."""
+    transpose (72 x 264: a partial 64 x 256 tile in both grid dimensions)."""
     k = _ext.require()
     it = RT.inv32(tau)
-    x, tgt, dead = _t_case(pattern)
+    x, tgt, dead = _t_case(pattern, N, V)
     N, V = x.shape
     ref = RT.rows64(x, tgt, it)
     lse, ent = ref["lse"].float().to(DEV), ref["ent"].float().to(DEV)
