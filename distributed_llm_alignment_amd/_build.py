@@ -1,10 +1,10 @@
 """In-tree build of the gfx950 HIP extension (`distributed_llm_alignment_amd/_C.so`).
 
 No hipify, no torch JIT cache: each `csrc/*.hip` is compiled by `hipcc --offload-arch=gfx950`
-into an object (device code + plain C++ launchers), `csrc/bindings.cpp` (the TORCH_LIBRARY op
-registry, host-only) by the host compiler against the installed torch headers, and everything is
-linked into one shared object loaded with `torch.ops.load_library`. The `.so` lives next to this
-file so it travels with the repository snapshot to the GPU box.
+into an object (device code + plain C++ launchers), each `csrc/bindings*.cpp` (the TORCH_LIBRARY op
+registry, one file per op family, host-only) by the host compiler against the installed torch
+headers, and everything is linked into one shared object loaded with `torch.ops.load_library`. The
+`.so` lives next to this file so it travels with the repository snapshot to the GPU box.
 
     python -m distributed_llm_alignment_amd._build [--force] [-j N] [--sanitize address,undefined]
 

@@ -1,4 +1,6 @@
-// Torch custom-op registry for the gfx950 kernels: `torch.ops.dla.*`.
+// Torch custom-op registry for the gfx950 kernels: `torch.ops.dla.*`. This file opens the library
+// (norms, activations, RoPE, attention, GJSD, optimizer); the other bindings_*.cpp add their family
+// as a fragment.
 //
 // Host side only (compiled by the host C++ compiler): every op validates operand shapes,
 // dtypes, strides and devices BEFORE launching (a mis-shaped launch of a hand-written kernel
@@ -41,35 +43,6 @@ void launch_rope_fwd(const bf16_t*, int64_t, bf16_t*, bf16_t*, const float*, con
                      const int*, int64_t, int, int, int, int, int, int, hipStream_t);
 void launch_rope_bwd(const bf16_t*, const bf16_t*, bf16_t*, int64_t, const float*, const float*,
                      const int*, int64_t, int, int, int, int, int, int, hipStream_t);
-void launch_seq_reduce(const float*, const float*, int, int, float*, float*, hipStream_t);
-void launch_seq_expand_grad(const float*, const float*, const float*, int, int, bool, float*,
-                            hipStream_t);
-void launch_dpo_loss(const float*, const float*, int, float, float, float*, float*, float*,
-                     float*, hipStream_t);
-void launch_pairwise_loss(const float*, const float*, int, float*, float*, float*, float*,
-                          hipStream_t);
-void launch_kl_penalty_pg(const float*, const float*, const float*, int, float, float*, float*,
-                          float*, float*, hipStream_t);
-void launch_gae(const float*, const float*, const float*, int, int, float, float, float*, float*,
-                hipStream_t);
-void launch_ppo_policy_loss(const float*, const float*, const float*, const float*, int64_t, float,
-                            float*, float*, float*, hipStream_t);
-void launch_ppo_value_loss(const float*, const float*, const float*, const float*, int64_t, float,
-                           float*, float*, hipStream_t);
-void launch_group_advantages(const float*, int, int, bool, float, float*, float*, hipStream_t);
-void launch_grpo_loss(const float*, const float*, const float*, const float*, const float*,
-                      const float*, int, int, float, float, float, int, float, float*, float*,
-                      float*, float*, hipStream_t);
-void launch_grpo_loss_w(const float*, const float*, const float*, const float*, const float*,
-                        const float*, const float*, int, int, float, float, float, int, float,
-                        float*, float*, float*, float*, hipStream_t);
-void launch_grpo_loss_seq(const float*, const float*, const float*, const float*, const float*,
-                          const float*, const float*, int, int, float, float, float, int, float,
-                          float*, float*, float*, float*, hipStream_t);
-void launch_ppo_policy_loss_w(const float*, const float*, const float*, const float*, const float*,
-                              int64_t, float, float*, float*, float*, hipStream_t);
-void launch_rollout_is_weights(const float*, const float*, const float*, int, int, float, float, int,
-                               int, float*, float*, float*, hipStream_t);
 void launch_adamw(bf16_t*, float*, const void*, bool, float*, float*, int64_t, float, float,
                   float, float, float, int, const float*, float, hipStream_t);
 void launch_grad_sumsq(const void*, bool, int64_t, float*, float*, bool, hipStream_t);
@@ -695,323 +668,6 @@ at::Tensor gjsd_bwd(const at::Tensor& s, const at::Tensor& t, const at::Tensor& 
   return ds;
 }
 
-// ================================= sequence objectives ========================================
-std::tuple<at::Tensor, at::Tensor> seq_reduce(const at::Tensor& lp, const at::Tensor& mask) {
-  check_f32(lp, "lp");
-  check_f32(mask, "mask");
-  TORCH_CHECK(lp.dim() == 2 && lp.is_contiguous() && mask.sizes() == lp.sizes() && mask.is_contiguous(),
-              "lp/mask [S, T]");
-  c10::hip::HIPGuardMasqueradingAsCUDA g(lp.device());
-  auto sum = at::empty({lp.size(0)}, lp.options());
-  auto cnt = at::empty({lp.size(0)}, lp.options());
-  launch_seq_reduce(lp.data_ptr<float>(), mask.data_ptr<float>(), static_cast<int>(lp.size(0)),
-                    static_cast<int>(lp.size(1)), sum.data_ptr<float>(), cnt.data_ptr<float>(),
-                    cur_stream(lp));
-  return {sum, cnt};
-}
-
-at::Tensor seq_expand_grad(const at::Tensor& coef, const at::Tensor& mask, const at::Tensor& cnt,
-                           bool mean) {
-  check_f32(coef, "coef");
-  check_f32(mask, "mask");
-  check_f32(cnt, "cnt");
-  TORCH_CHECK(mask.dim() == 2 && mask.is_contiguous() && coef.numel() == mask.size(0) &&
-                  cnt.numel() == mask.size(0) && coef.is_contiguous() && cnt.is_contiguous(),
-              "shapes");
-  c10::hip::HIPGuardMasqueradingAsCUDA g(mask.device());
-  auto out = at::empty_like(mask);
-  launch_seq_expand_grad(coef.data_ptr<float>(), mask.data_ptr<float>(), cnt.data_ptr<float>(),
-                         static_cast<int>(mask.size(0)), static_cast<int>(mask.size(1)), mean,
-                         out.data_ptr<float>(), cur_stream(mask));
-  return out;
-}
-
-std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> dpo_loss(const at::Tensor& pol,
-                                                                    const at::Tensor& ref,
-                                                                    double beta,
-                                                                    double label_smoothing) {
-  check_f32(pol, "pol");
-  check_f32(ref, "ref");
-  TORCH_CHECK(pol.is_contiguous() && ref.is_contiguous() && pol.numel() == ref.numel() &&
-                  pol.numel() % 2 == 0,
-              "pol/ref must be [2B] (chosen then rejected)");
-  const int B = static_cast<int>(pol.numel() / 2);
-  c10::hip::HIPGuardMasqueradingAsCUDA g(pol.device());
-  auto opt = pol.options();
-  auto loss = at::empty({}, opt);
-  auto dpol = at::empty({2 * B}, opt);
-  auto rewards = at::empty({2 * B}, opt);
-  auto metrics = at::empty({4}, opt);
-  launch_dpo_loss(pol.data_ptr<float>(), ref.data_ptr<float>(), B, static_cast<float>(beta),
-                  static_cast<float>(label_smoothing), loss.data_ptr<float>(),
-                  dpol.data_ptr<float>(), rewards.data_ptr<float>(), metrics.data_ptr<float>(),
-                  cur_stream(pol));
-  return {loss, dpol, rewards, metrics};
-}
-
-std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> pairwise_loss(const at::Tensor& sc,
-                                                                         const at::Tensor& sr) {
-  check_f32(sc, "sc");
-  check_f32(sr, "sr");
-  TORCH_CHECK(sc.is_contiguous() && sr.is_contiguous() && sc.numel() == sr.numel(), "shapes");
-  const int B = static_cast<int>(sc.numel());
-  c10::hip::HIPGuardMasqueradingAsCUDA g(sc.device());
-  auto opt = sc.options();
-  auto loss = at::empty({}, opt);
-  auto dsc = at::empty({B}, opt);
-  auto dsr = at::empty({B}, opt);
-  auto acc = at::empty({}, opt);
-  launch_pairwise_loss(sc.data_ptr<float>(), sr.data_ptr<float>(), B, loss.data_ptr<float>(),
-                       dsc.data_ptr<float>(), dsr.data_ptr<float>(), acc.data_ptr<float>(),
-                       cur_stream(sc));
-  return {loss, dsc, dsr, acc};
-}
-
-// ---- PPO (actor-critic) token objectives: [S, T] fp32 grids ----
-static void check_grid(const at::Tensor& t, const at::Tensor& like, const char* name) {
-  check_f32(t, name);
-  TORCH_CHECK(t.is_contiguous() && t.sizes() == like.sizes(), name, " must be a contiguous fp32 grid like the first operand");
-}
-
-std::tuple<at::Tensor, at::Tensor> gae(const at::Tensor& rewards, const at::Tensor& values,
-                                       const at::Tensor& mask, double gamma, double lam) {
-  check_f32(rewards, "rewards");
-  TORCH_CHECK(rewards.dim() == 2 && rewards.is_contiguous(), "rewards [S, T] contiguous");
-  check_grid(values, rewards, "values");
-  check_grid(mask, rewards, "mask");
-  c10::hip::HIPGuardMasqueradingAsCUDA g(rewards.device());
-  auto adv = at::empty_like(rewards);
-  auto ret = at::empty_like(rewards);
-  launch_gae(rewards.data_ptr<float>(), values.data_ptr<float>(), mask.data_ptr<float>(),
-             static_cast<int>(rewards.size(0)), static_cast<int>(rewards.size(1)),
-             static_cast<float>(gamma), static_cast<float>(lam), adv.data_ptr<float>(),
-             ret.data_ptr<float>(), cur_stream(rewards));
-  return {adv, ret};
-}
-
-// w: the importance weights of ppo_policy_loss_w (a grid like lp), or nullptr
-static std::tuple<at::Tensor, at::Tensor, at::Tensor> ppo_policy_loss_impl(
-    const at::Tensor& lp, const at::Tensor& old, const at::Tensor& adv, const at::Tensor& mask,
-    const at::Tensor* w, double eps) {
-  check_f32(lp, "lp");
-  TORCH_CHECK(lp.is_contiguous(), "lp contiguous");
-  check_grid(old, lp, "old");
-  check_grid(adv, lp, "adv");
-  check_grid(mask, lp, "mask");
-  if (w != nullptr) {
-    check_grid(*w, lp, "w");
-    same_device(lp, *w);
-  }
-  c10::hip::HIPGuardMasqueradingAsCUDA g(lp.device());
-  auto opt = lp.options();
-  auto loss = at::empty({}, opt);
-  auto dlp = at::empty_like(lp);
-  auto metrics = at::empty({3}, opt);
-  if (w != nullptr)
-    launch_ppo_policy_loss_w(lp.data_ptr<float>(), old.data_ptr<float>(), adv.data_ptr<float>(),
-                             mask.data_ptr<float>(), w->data_ptr<float>(), lp.numel(),
-                             static_cast<float>(eps), loss.data_ptr<float>(), dlp.data_ptr<float>(),
-                             metrics.data_ptr<float>(), cur_stream(lp));
-  else
-    launch_ppo_policy_loss(lp.data_ptr<float>(), old.data_ptr<float>(), adv.data_ptr<float>(),
-                           mask.data_ptr<float>(), lp.numel(), static_cast<float>(eps),
-                           loss.data_ptr<float>(), dlp.data_ptr<float>(), metrics.data_ptr<float>(),
-                           cur_stream(lp));
-  return {loss, dlp, metrics};
-}
-
-std::tuple<at::Tensor, at::Tensor, at::Tensor> ppo_policy_loss(const at::Tensor& lp,
-                                                               const at::Tensor& old,
-                                                               const at::Tensor& adv,
-                                                               const at::Tensor& mask,
-                                                               double eps) {
-  return ppo_policy_loss_impl(lp, old, adv, mask, nullptr, eps);
-}
-
-std::tuple<at::Tensor, at::Tensor, at::Tensor> ppo_policy_loss_w(
-    const at::Tensor& lp, const at::Tensor& old, const at::Tensor& adv, const at::Tensor& mask,
-    const at::Tensor& w, double eps) {
-  return ppo_policy_loss_impl(lp, old, adv, mask, &w, eps);
-}
-
-std::tuple<at::Tensor, at::Tensor> ppo_value_loss(const at::Tensor& values, const at::Tensor& old,
-                                                  const at::Tensor& returns,
-                                                  const at::Tensor& mask, double clip) {
-  check_f32(values, "values");
-  TORCH_CHECK(values.is_contiguous(), "values contiguous");
-  check_grid(old, values, "old");
-  check_grid(returns, values, "returns");
-  check_grid(mask, values, "mask");
-  c10::hip::HIPGuardMasqueradingAsCUDA g(values.device());
-  auto loss = at::empty({}, values.options());
-  auto dval = at::empty_like(values);
-  launch_ppo_value_loss(values.data_ptr<float>(), old.data_ptr<float>(), returns.data_ptr<float>(),
-                        mask.data_ptr<float>(), values.numel(), static_cast<float>(clip),
-                        loss.data_ptr<float>(), dval.data_ptr<float>(), cur_stream(values));
-  return {loss, dval};
-}
-
-// ---- GRPO: group advantages + clipped surrogate with a k3 reference-KL term ----
-std::tuple<at::Tensor, at::Tensor> group_advantages(const at::Tensor& scores, int64_t G,
-                                                    bool scale_std, double eps) {
-  check_f32(scores, "scores");
-  TORCH_CHECK(scores.dim() == 1 && scores.is_contiguous(), "scores [P*G] contiguous");
-  TORCH_CHECK(G >= 1 && scores.numel() % G == 0, "scores must hold whole groups of G");
-  const int64_t P = scores.numel() / G;
-  TORCH_CHECK(P < (1ll << 31) && G < (1ll << 31), "group_advantages: too many groups");
-  c10::hip::HIPGuardMasqueradingAsCUDA g(scores.device());
-  auto adv = at::empty_like(scores);
-  auto sd = at::empty({P}, scores.options());
-  launch_group_advantages(scores.data_ptr<float>(), static_cast<int>(P), static_cast<int>(G),
-                          scale_std, static_cast<float>(eps), adv.data_ptr<float>(),
-                          sd.data_ptr<float>(), cur_stream(scores));
-  return {adv, sd};
-}
-
-// lp / old / ref / mask: [S, T] fp32 grids, adv [S] (one value per rollout), denom: optional
-// device [1] replacing the final divisor. mode: 0 sequence, 1 token, 2 constant (S * max_len).
-// Returns (loss, dloss/dlp, metrics[4]); no host read of any device value.
-// w: the importance weights of grpo_loss_w (a grid like lp), or nullptr.
-// seq: the sequence-level ratio of grpo_loss_seq (two more rows of partials).
-static std::tuple<at::Tensor, at::Tensor, at::Tensor> grpo_loss_impl(
-    const at::Tensor& lp, const at::Tensor& old, const at::Tensor& ref, const at::Tensor& adv,
-    const at::Tensor& mask, const at::Tensor* w, const c10::optional<at::Tensor>& denom,
-    double clip_low, double clip_high, double beta, int64_t mode, double max_len, bool seq = false) {
-  check_f32(lp, "lp");
-  TORCH_CHECK(lp.dim() == 2 && lp.is_contiguous(), "lp [S, T] contiguous");
-  check_grid(old, lp, "old");
-  check_grid(ref, lp, "ref");
-  check_grid(mask, lp, "mask");
-  if (w != nullptr) {
-    check_grid(*w, lp, "w");
-    same_device(lp, *w);
-  }
-  check_f32(adv, "adv");
-  TORCH_CHECK(adv.is_contiguous() && adv.numel() == lp.size(0), "adv must be [S] contiguous");
-  TORCH_CHECK(mode >= 0 && mode <= 2, "grpo_loss mode must be 0 (sequence), 1 (token), 2 (constant)");
-  TORCH_CHECK(mode != 2 || max_len > 0 || denom.has_value(), "constant mode needs max_len > 0");
-  TORCH_CHECK(lp.size(0) > 0 && lp.size(0) < (1ll << 31) && lp.size(1) < (1ll << 31), "grpo_loss grid size");
-  same_device(lp, adv);
-  const float* dn = nullptr;
-  if (denom.has_value()) {
-    check_f32(*denom, "denom");
-    same_device(lp, *denom);
-    TORCH_CHECK(denom->numel() == 1, "denom must hold one value");
-    dn = denom->data_ptr<float>();
-  }
-  c10::hip::HIPGuardMasqueradingAsCUDA g(lp.device());
-  auto opt = lp.options();
-  const int S = static_cast<int>(lp.size(0)), T = static_cast<int>(lp.size(1));
-  auto loss = at::empty({}, opt);
-  auto dlp = at::empty_like(lp);
-  auto metrics = at::empty({4}, opt);
-  auto part = at::empty({seq ? 7 : 5, S}, opt);
-  const float lo = static_cast<float>(1.0 - clip_low), hi = static_cast<float>(1.0 + clip_high);
-  if (seq)
-    launch_grpo_loss_seq(lp.data_ptr<float>(), old.data_ptr<float>(), ref.data_ptr<float>(),
-                         adv.data_ptr<float>(), mask.data_ptr<float>(),
-                         w != nullptr ? w->data_ptr<float>() : nullptr, dn, S, T, lo, hi,
-                         static_cast<float>(beta), static_cast<int>(mode), static_cast<float>(max_len),
-                         part.data_ptr<float>(), loss.data_ptr<float>(), dlp.data_ptr<float>(),
-                         metrics.data_ptr<float>(), cur_stream(lp));
-  else if (w != nullptr)
-    launch_grpo_loss_w(lp.data_ptr<float>(), old.data_ptr<float>(), ref.data_ptr<float>(),
-                       adv.data_ptr<float>(), mask.data_ptr<float>(), w->data_ptr<float>(), dn, S, T,
-                       lo, hi, static_cast<float>(beta), static_cast<int>(mode),
-                       static_cast<float>(max_len), part.data_ptr<float>(), loss.data_ptr<float>(),
-                       dlp.data_ptr<float>(), metrics.data_ptr<float>(), cur_stream(lp));
-  else
-    launch_grpo_loss(lp.data_ptr<float>(), old.data_ptr<float>(), ref.data_ptr<float>(),
-                     adv.data_ptr<float>(), mask.data_ptr<float>(), dn, S, T, lo, hi,
-                     static_cast<float>(beta), static_cast<int>(mode), static_cast<float>(max_len),
-                     part.data_ptr<float>(), loss.data_ptr<float>(), dlp.data_ptr<float>(),
-                     metrics.data_ptr<float>(), cur_stream(lp));
-  return {loss, dlp, metrics};
-}
-
-std::tuple<at::Tensor, at::Tensor, at::Tensor> grpo_loss(
-    const at::Tensor& lp, const at::Tensor& old, const at::Tensor& ref, const at::Tensor& adv,
-    const at::Tensor& mask, const c10::optional<at::Tensor>& denom, double clip_low,
-    double clip_high, double beta, int64_t mode, double max_len) {
-  return grpo_loss_impl(lp, old, ref, adv, mask, nullptr, denom, clip_low, clip_high, beta, mode,
-                        max_len);
-}
-
-// grpo_loss with detached per-token importance weights w [S, T] on the policy-gradient term.
-std::tuple<at::Tensor, at::Tensor, at::Tensor> grpo_loss_w(
-    const at::Tensor& lp, const at::Tensor& old, const at::Tensor& ref, const at::Tensor& adv,
-    const at::Tensor& mask, const at::Tensor& w, const c10::optional<at::Tensor>& denom,
-    double clip_low, double clip_high, double beta, int64_t mode, double max_len) {
-  return grpo_loss_impl(lp, old, ref, adv, mask, &w, denom, clip_low, clip_high, beta, mode,
-                        max_len);
-}
-
-// grpo_loss with the length-normalised sequence-level ratio (GSPO); w as in grpo_loss_w, optional.
-std::tuple<at::Tensor, at::Tensor, at::Tensor> grpo_loss_seq(
-    const at::Tensor& lp, const at::Tensor& old, const at::Tensor& ref, const at::Tensor& adv,
-    const at::Tensor& mask, const c10::optional<at::Tensor>& w, const c10::optional<at::Tensor>& denom,
-    double clip_low, double clip_high, double beta, int64_t mode, double max_len) {
-  return grpo_loss_impl(lp, old, ref, adv, mask, w.has_value() ? &*w : nullptr, denom, clip_low,
-                        clip_high, beta, mode, max_len, true);
-}
-
-// trainer_lp / rollout_lp / mask: [S, T] fp32 grids. level: 0 token, 1 sequence (length-normalised);
-// mode: 0 truncate at cap, 1 mask outside [floor, cap]. Returns (w [S, T], metrics[5]); no host
-// read of any device value.
-std::tuple<at::Tensor, at::Tensor> rollout_is_weights(const at::Tensor& trainer_lp,
-                                                      const at::Tensor& rollout_lp,
-                                                      const at::Tensor& mask, double cap,
-                                                      double floor, int64_t level, int64_t mode) {
-  check_f32(trainer_lp, "trainer_lp");
-  TORCH_CHECK(trainer_lp.dim() == 2 && trainer_lp.is_contiguous(), "trainer_lp [S, T] contiguous");
-  check_grid(rollout_lp, trainer_lp, "rollout_lp");
-  check_grid(mask, trainer_lp, "mask");
-  same_device(trainer_lp, rollout_lp);
-  same_device(trainer_lp, mask);
-  TORCH_CHECK(std::isfinite(cap) && cap > 0, "rollout_is_weights: cap must be finite and > 0");
-  TORCH_CHECK(floor >= 0 && floor <= cap, "rollout_is_weights: floor must lie in [0, cap]");
-  TORCH_CHECK(level == 0 || level == 1, "rollout_is_weights level must be 0 (token) or 1 (sequence)");
-  TORCH_CHECK(mode == 0 || mode == 1, "rollout_is_weights mode must be 0 (truncate) or 1 (mask)");
-  TORCH_CHECK(trainer_lp.size(0) > 0 && trainer_lp.size(0) < (1ll << 31) &&
-                  trainer_lp.size(1) < (1ll << 31),
-              "rollout_is_weights grid size");
-  c10::hip::HIPGuardMasqueradingAsCUDA g(trainer_lp.device());
-  auto opt = trainer_lp.options();
-  const int S = static_cast<int>(trainer_lp.size(0)), T = static_cast<int>(trainer_lp.size(1));
-  auto w = at::empty_like(trainer_lp);
-  auto metrics = at::empty({5}, opt);
-  auto part = at::empty({5, S}, opt);
-  launch_rollout_is_weights(trainer_lp.data_ptr<float>(), rollout_lp.data_ptr<float>(),
-                            mask.data_ptr<float>(), S, T, static_cast<float>(cap),
-                            static_cast<float>(floor), static_cast<int>(level),
-                            static_cast<int>(mode), part.data_ptr<float>(), w.data_ptr<float>(),
-                            metrics.data_ptr<float>(), cur_stream(trainer_lp));
-  return {w, metrics};
-}
-
-std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> kl_penalty_pg(const at::Tensor& lp,
-                                                                         const at::Tensor& lr,
-                                                                         const at::Tensor& reward,
-                                                                         double kl_coef) {
-  check_f32(lp, "lp");
-  check_f32(lr, "lr");
-  check_f32(reward, "reward");
-  TORCH_CHECK(lp.is_contiguous() && lr.is_contiguous() && reward.is_contiguous() &&
-                  lp.numel() == lr.numel() && lp.numel() == reward.numel() && lp.numel() > 0,
-              "shapes");
-  const int n = static_cast<int>(lp.numel());
-  c10::hip::HIPGuardMasqueradingAsCUDA g(lp.device());
-  auto opt = lp.options();
-  auto loss = at::empty({}, opt);
-  auto klm = at::empty({}, opt);
-  auto dlp = at::empty({n}, opt);
-  auto adv = at::empty({n}, opt);
-  launch_kl_penalty_pg(lp.data_ptr<float>(), lr.data_ptr<float>(), reward.data_ptr<float>(), n,
-                       static_cast<float>(kl_coef), loss.data_ptr<float>(), klm.data_ptr<float>(),
-                       dlp.data_ptr<float>(), adv.data_ptr<float>(), cur_stream(lp));
-  return {loss, klm, dlp, adv};
-}
-
 // ================================= optimizer ==================================================
 void adamw_step(const c10::optional<at::Tensor>& param, const c10::optional<at::Tensor>& master,
                 const at::Tensor& grad, at::Tensor& m, at::Tensor& v, double lr, double b1,
@@ -1104,20 +760,6 @@ TORCH_LIBRARY(dla, m) {
   m.def("transpose_bf16(Tensor input, Tensor(a!) out) -> ()");
   m.def("gjsd_fwd(Tensor s, Tensor t, Tensor? row_mask, float beta, float inv_temp) -> (Tensor, Tensor, Tensor, Tensor)");
   m.def("gjsd_bwd(Tensor s, Tensor t, Tensor s_lse, Tensor t_lse, Tensor aux, Tensor? row_mask, Tensor grad, float beta, float inv_temp) -> Tensor");
-  m.def("seq_reduce(Tensor lp, Tensor mask) -> (Tensor, Tensor)");
-  m.def("seq_expand_grad(Tensor coef, Tensor mask, Tensor cnt, bool mean) -> Tensor");
-  m.def("dpo_loss(Tensor pol, Tensor ref, float beta, float label_smoothing) -> (Tensor, Tensor, Tensor, Tensor)");
-  m.def("pairwise_loss(Tensor sc, Tensor sr) -> (Tensor, Tensor, Tensor, Tensor)");
-  m.def("gae(Tensor rewards, Tensor values, Tensor mask, float gamma, float lam) -> (Tensor, Tensor)");
-  m.def("ppo_policy_loss(Tensor lp, Tensor old, Tensor adv, Tensor mask, float eps) -> (Tensor, Tensor, Tensor)");
-  m.def("ppo_value_loss(Tensor values, Tensor old, Tensor returns, Tensor mask, float clip) -> (Tensor, Tensor)");
-  m.def("group_advantages(Tensor scores, int G, bool scale_std, float eps) -> (Tensor, Tensor)");
-  m.def("grpo_loss(Tensor lp, Tensor old, Tensor ref, Tensor adv, Tensor mask, Tensor? denom, float clip_low, float clip_high, float beta, int mode, float max_len) -> (Tensor, Tensor, Tensor)");
-  m.def("grpo_loss_w(Tensor lp, Tensor old, Tensor ref, Tensor adv, Tensor mask, Tensor w, Tensor? denom, float clip_low, float clip_high, float beta, int mode, float max_len) -> (Tensor, Tensor, Tensor)");
-  m.def("grpo_loss_seq(Tensor lp, Tensor old, Tensor ref, Tensor adv, Tensor mask, Tensor? w, Tensor? denom, float clip_low, float clip_high, float beta, int mode, float max_len) -> (Tensor, Tensor, Tensor)");
-  m.def("ppo_policy_loss_w(Tensor lp, Tensor old, Tensor adv, Tensor mask, Tensor w, float eps) -> (Tensor, Tensor, Tensor)");
-  m.def("rollout_is_weights(Tensor trainer_lp, Tensor rollout_lp, Tensor mask, float cap, float floor, int level, int mode) -> (Tensor, Tensor)");
-  m.def("kl_penalty_pg(Tensor lp, Tensor lr, Tensor reward, float kl_coef) -> (Tensor, Tensor, Tensor, Tensor)");
   m.def("adamw_step(Tensor(a!)? param, Tensor(b!)? master, Tensor grad, Tensor(c!) m, Tensor(d!) v, float lr, float b1, float b2, float eps, float wd, int step, Tensor? clip, float grad_scale) -> ()");
   m.def("grad_sumsq(Tensor grad, Tensor(a!) out, bool accumulate) -> ()");
   m.def("clip_coef(Tensor sumsq, float max_norm) -> (Tensor, Tensor)");
@@ -1140,20 +782,6 @@ TORCH_LIBRARY_IMPL(dla, CUDA, m) {
   m.impl("transpose_bf16", &dla::transpose_bf16);
   m.impl("gjsd_fwd", &dla::gjsd_fwd);
   m.impl("gjsd_bwd", &dla::gjsd_bwd);
-  m.impl("seq_reduce", &dla::seq_reduce);
-  m.impl("seq_expand_grad", &dla::seq_expand_grad);
-  m.impl("dpo_loss", &dla::dpo_loss);
-  m.impl("pairwise_loss", &dla::pairwise_loss);
-  m.impl("kl_penalty_pg", &dla::kl_penalty_pg);
-  m.impl("gae", &dla::gae);
-  m.impl("ppo_policy_loss", &dla::ppo_policy_loss);
-  m.impl("ppo_value_loss", &dla::ppo_value_loss);
-  m.impl("group_advantages", &dla::group_advantages);
-  m.impl("grpo_loss", &dla::grpo_loss);
-  m.impl("grpo_loss_w", &dla::grpo_loss_w);
-  m.impl("grpo_loss_seq", &dla::grpo_loss_seq);
-  m.impl("ppo_policy_loss_w", &dla::ppo_policy_loss_w);
-  m.impl("rollout_is_weights", &dla::rollout_is_weights);
   m.impl("adamw_step", &dla::adamw_step);
   m.impl("grad_sumsq", &dla::grad_sumsq);
   m.impl("clip_coef", &dla::clip_coef);

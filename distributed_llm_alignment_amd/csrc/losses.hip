@@ -15,7 +15,9 @@
 //   grpo_loss_seq   : GSPO, the GRPO loss with the length-normalised sequence-level ratio (below)
 // Batch dimensions here are small (pairs per micro-batch), so each loss is a single
 // 256-thread block; the point is fusing fwd+bwd+metrics into one launch with no host sync.
+// The launchers at the end are declared in loss_params.h; the torch ops are in bindings_losses.cpp.
 #include "common.h"
+#include "loss_params.h"
 
 namespace dla {
 
@@ -639,41 +641,20 @@ void launch_group_advantages(const float* r, int P, int G, bool scale_std, float
   if (P == 0 || G == 0) return;
   group_advantages_kernel<<<P, 64, 0, st>>>(r, G, scale_std ? 1 : 0, eps, adv, sd);
 }
-void launch_grpo_loss(const float* lp, const float* old, const float* ref, const float* adv,
-                      const float* m, const float* denom, int S, int T, float lo, float hi,
-                      float beta, int mode, float max_len, float* part, float* loss, float* dlp,
-                      float* metrics, hipStream_t st) {
-  grpo_partials_kernel<false><<<S, kGrpoThreads, 0, st>>>(lp, old, ref, adv, m, S, T, lo, hi, beta,
-                                                           part, nullptr);
-  grpo_grad_kernel<false><<<S, kGrpoThreads, 0, st>>>(lp, old, ref, adv, m, part, denom, S, T, lo, hi,
-                                                      beta, mode, max_len, loss, dlp, metrics, nullptr);
+template <bool W, bool SEQ>
+static void grpo_loss_launch(const GrpoLossParams& p, hipStream_t st) {
+  grpo_partials_kernel<W, SEQ><<<p.S, kGrpoThreads, 0, st>>>(p.lp, p.old, p.ref, p.adv, p.m, p.S, p.T, p.lo, p.hi,
+                                                            p.beta, p.part, p.w);
+  grpo_grad_kernel<W, SEQ><<<p.S, kGrpoThreads, 0, st>>>(p.lp, p.old, p.ref, p.adv, p.m, p.part, p.denom, p.S, p.T,
+                                                        p.lo, p.hi, p.beta, p.mode, p.max_len, p.loss, p.dlp,
+                                                        p.metrics, p.w);
 }
-void launch_grpo_loss_w(const float* lp, const float* old, const float* ref, const float* adv,
-                        const float* m, const float* w, const float* denom, int S, int T, float lo,
-                        float hi, float beta, int mode, float max_len, float* part, float* loss,
-                        float* dlp, float* metrics, hipStream_t st) {
-  grpo_partials_kernel<true><<<S, kGrpoThreads, 0, st>>>(lp, old, ref, adv, m, S, T, lo, hi, beta,
-                                                          part, w);
-  grpo_grad_kernel<true><<<S, kGrpoThreads, 0, st>>>(lp, old, ref, adv, m, part, denom, S, T, lo, hi,
-                                                     beta, mode, max_len, loss, dlp, metrics, w);
-}
-// part holds 7 * S floats here (rows 5 and 6: see grpo_partials_kernel); w may be nullptr
-void launch_grpo_loss_seq(const float* lp, const float* old, const float* ref, const float* adv,
-                          const float* m, const float* w, const float* denom, int S, int T, float lo,
-                          float hi, float beta, int mode, float max_len, float* part, float* loss,
-                          float* dlp, float* metrics, hipStream_t st) {
-  if (w != nullptr) {
-    grpo_partials_kernel<true, true><<<S, kGrpoThreads, 0, st>>>(lp, old, ref, adv, m, S, T, lo, hi,
-                                                                  beta, part, w);
-    grpo_grad_kernel<true, true><<<S, kGrpoThreads, 0, st>>>(lp, old, ref, adv, m, part, denom, S, T, lo,
-                                                              hi, beta, mode, max_len, loss, dlp, metrics, w);
-  } else {
-    grpo_partials_kernel<false, true><<<S, kGrpoThreads, 0, st>>>(lp, old, ref, adv, m, S, T, lo, hi,
-                                                                   beta, part, nullptr);
-    grpo_grad_kernel<false, true><<<S, kGrpoThreads, 0, st>>>(lp, old, ref, adv, m, part, denom, S, T, lo,
-                                                               hi, beta, mode, max_len, loss, dlp, metrics,
-                                                               nullptr);
-  }
+void launch_grpo_loss(const GrpoLossParams& p, hipStream_t st) {
+  const bool weighted = p.w != nullptr;
+  if (p.seq)
+    weighted ? grpo_loss_launch<true, true>(p, st) : grpo_loss_launch<false, true>(p, st);
+  else
+    weighted ? grpo_loss_launch<true, false>(p, st) : grpo_loss_launch<false, false>(p, st);
 }
 void launch_rollout_is_weights(const float* tlp, const float* rlp, const float* m, int S, int T,
                                float cap, float floor_, int level, int mode, float* part, float* w,
@@ -686,15 +667,12 @@ void launch_gae(const float* r, const float* v, const float* m, int S, int T, fl
   if (S == 0 || T == 0) return;
   gae_kernel<<<S, 64, 0, st>>>(r, v, m, T, gamma, lam, adv, ret);
 }
-void launch_ppo_policy_loss(const float* lp, const float* old, const float* adv, const float* m,
-                            int64_t n, float eps, float* loss, float* dlp, float* metrics,
-                            hipStream_t st) {
-  ppo_policy_loss_kernel<false><<<1, 1024, 0, st>>>(lp, old, adv, m, n, eps, loss, dlp, metrics, nullptr);
-}
-void launch_ppo_policy_loss_w(const float* lp, const float* old, const float* adv, const float* m,
-                              const float* w, int64_t n, float eps, float* loss, float* dlp,
-                              float* metrics, hipStream_t st) {
-  ppo_policy_loss_kernel<true><<<1, 1024, 0, st>>>(lp, old, adv, m, n, eps, loss, dlp, metrics, w);
+void launch_ppo_policy_loss(const float* lp, const float* old, const float* adv, const float* m, const float* w,
+                            int64_t n, float eps, float* loss, float* dlp, float* metrics, hipStream_t st) {
+  if (w != nullptr)
+    ppo_policy_loss_kernel<true><<<1, 1024, 0, st>>>(lp, old, adv, m, n, eps, loss, dlp, metrics, w);
+  else
+    ppo_policy_loss_kernel<false><<<1, 1024, 0, st>>>(lp, old, adv, m, n, eps, loss, dlp, metrics, nullptr);
 }
 void launch_ppo_value_loss(const float* val, const float* old, const float* ret, const float* m,
                            int64_t n, float clip, float* loss, float* dval, hipStream_t st) {

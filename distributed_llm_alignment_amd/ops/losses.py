@@ -299,24 +299,20 @@ def gae(rewards: torch.Tensor, values: torch.Tensor, mask: torch.Tensor, gamma: 
     return adv, adv + v
 
 
+def _ppo_policy_op(lp, old, adv, mask, w, eps):
+    """The surrogate's op and its positional arguments: `ppo_policy_loss`, with weights `ppo_policy_loss_w`."""
+    if w is None:
+        return "ppo_policy_loss", (lp, old, adv, mask, eps)
+    return "ppo_policy_loss_w", (lp, old, adv, mask, w, eps)
+
+
 class _PPOPolicyFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, lp, old, adv, mask, eps):
-        loss, dlp, metrics = _ext.require().ppo_policy_loss(lp, old, adv, mask, eps)
-        ctx.save_for_backward(dlp)
-        ctx.mark_non_differentiable(metrics)
-        return loss, metrics
+    """`w` (the importance weights) may be None."""
 
-    @staticmethod
-    def backward(ctx, gloss, _gm):
-        (dlp,) = ctx.saved_tensors
-        return dlp * gloss, None, None, None, None
-
-
-class _PPOPolicyWFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, lp, old, adv, mask, w, eps):
-        loss, dlp, metrics = _ext.require().ppo_policy_loss_w(lp, old, adv, mask, w, eps)
+        name, args = _ppo_policy_op(lp, old, adv, mask, w, eps)
+        loss, dlp, metrics = getattr(_ext.require(), name)(*args)
         ctx.save_for_backward(dlp)
         ctx.mark_non_differentiable(metrics)
         return loss, metrics
@@ -324,7 +320,7 @@ class _PPOPolicyWFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gloss, _gm):
         (dlp,) = ctx.saved_tensors
-        return dlp * gloss, None, None, None, None, None
+        return (dlp * gloss,) + (None,) * 5
 
 
 def ppo_policy_loss(logp: torch.Tensor, old_logp: torch.Tensor, advantages: torch.Tensor,
@@ -343,10 +339,7 @@ def ppo_policy_loss(logp: torch.Tensor, old_logp: torch.Tensor, advantages: torc
         if w.shape != lp.shape:
             raise ValueError(f"ppo_policy_loss: is_weight {tuple(w.shape)} must have logp's shape {tuple(lp.shape)}")
     if _ext.use_native(lp):
-        if w is None:
-            loss, met = _PPOPolicyFn.apply(lp, old, a, m, float(clip_eps))
-        else:
-            loss, met = _PPOPolicyWFn.apply(lp, old, a, m, w, float(clip_eps))
+        loss, met = _PPOPolicyFn.apply(lp, old, a, m, w, float(clip_eps))
         return loss, {"clipfrac": met[0], "approx_kl": met[1]}
     n = m.sum().clamp(min=1)
     rho = torch.exp(lp - old)
@@ -512,11 +505,24 @@ def _ref_gspo_loss(lp, old, ref_logp, a, m, clip_low, clip_high, beta, loss_type
     return loss, metrics
 
 
+def _grpo_op(lp, old, ref, adv, mask, w, importance_level, *tail):
+    """The surrogate's op and its positional arguments: `grpo_loss`, with weights `grpo_loss_w`, at the
+    sequence level (GSPO) `grpo_loss_seq`, which takes `w` or None. `tail`: denom and the scalars."""
+    if importance_level == "sequence":
+        return "grpo_loss_seq", (lp, old, ref, adv, mask, w) + tail
+    if w is None:
+        return "grpo_loss", (lp, old, ref, adv, mask) + tail
+    return "grpo_loss_w", (lp, old, ref, adv, mask, w) + tail
+
+
 class _GRPOFn(torch.autograd.Function):
+    """`w` (the importance weights) may be None."""
+
     @staticmethod
-    def forward(ctx, lp, old, ref, adv, mask, denom, clip_low, clip_high, beta, mode, max_len):
-        loss, dlp, metrics = _ext.require().grpo_loss(lp, old, ref, adv, mask, denom, clip_low, clip_high,
-                                                      beta, mode, max_len)
+    def forward(ctx, lp, old, ref, adv, mask, w, importance_level, denom, clip_low, clip_high, beta, mode, max_len):
+        name, args = _grpo_op(lp, old, ref, adv, mask, w, importance_level, denom, clip_low, clip_high, beta, mode,
+                              max_len)
+        loss, dlp, metrics = getattr(_ext.require(), name)(*args)
         ctx.save_for_backward(dlp)
         ctx.mark_non_differentiable(metrics)
         return loss, metrics
@@ -524,39 +530,7 @@ class _GRPOFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gloss, _gm):
         (dlp,) = ctx.saved_tensors
-        return (dlp * gloss,) + (None,) * 10
-
-
-class _GRPOWFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, lp, old, ref, adv, mask, w, denom, clip_low, clip_high, beta, mode, max_len):
-        loss, dlp, metrics = _ext.require().grpo_loss_w(lp, old, ref, adv, mask, w, denom, clip_low,
-                                                        clip_high, beta, mode, max_len)
-        ctx.save_for_backward(dlp)
-        ctx.mark_non_differentiable(metrics)
-        return loss, metrics
-
-    @staticmethod
-    def backward(ctx, gloss, _gm):
-        (dlp,) = ctx.saved_tensors
-        return (dlp * gloss,) + (None,) * 11
-
-
-class _GRPOSeqFn(torch.autograd.Function):
-    """`grpo_loss_seq`: the sequence-level ratio (GSPO); `w` may be None."""
-
-    @staticmethod
-    def forward(ctx, lp, old, ref, adv, mask, w, denom, clip_low, clip_high, beta, mode, max_len):
-        loss, dlp, metrics = _ext.require().grpo_loss_seq(lp, old, ref, adv, mask, w, denom, clip_low,
-                                                          clip_high, beta, mode, max_len)
-        ctx.save_for_backward(dlp)
-        ctx.mark_non_differentiable(metrics)
-        return loss, metrics
-
-    @staticmethod
-    def backward(ctx, gloss, _gm):
-        (dlp,) = ctx.saved_tensors
-        return (dlp * gloss,) + (None,) * 11
+        return (dlp * gloss,) + (None,) * 12
 
 
 def grpo_loss(logp: torch.Tensor, old_logp: Optional[torch.Tensor], ref_logp: Optional[torch.Tensor],
@@ -617,14 +591,8 @@ def grpo_loss(logp: torch.Tensor, old_logp: Optional[torch.Tensor], ref_logp: Op
     a = adv.detach().float().contiguous().view(-1)
     m = mask.detach().float().contiguous()
     dn = denom.detach().float().reshape(1) if denom is not None else None
-    tail = (dn, float(clip_low), float(clip_high), float(beta), GRPO_LOSS_TYPES.index(loss_type),
-            float(max_len or 0))
-    if importance_level == "sequence":
-        loss, met = _GRPOSeqFn.apply(lp, old, ref, a, m, w, *tail)
-    elif w is None:
-        loss, met = _GRPOFn.apply(lp, old, ref, a, m, *tail)
-    else:
-        loss, met = _GRPOWFn.apply(lp, old, ref, a, m, w, *tail)
+    loss, met = _GRPOFn.apply(lp, old, ref, a, m, w, importance_level, dn, float(clip_low), float(clip_high),
+                              float(beta), GRPO_LOSS_TYPES.index(loss_type), float(max_len or 0))
     return loss, {"clipfrac": met[0], "approx_kl": met[1], "kl_ref": met[2], "tokens": met[3]}
 
 
