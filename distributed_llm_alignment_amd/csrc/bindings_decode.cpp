@@ -105,6 +105,32 @@ static void fill_w8(SkinnyParams& p, const at::Tensor& x, const at::Tensor& w8, 
   p.K = static_cast<int>(K);
 }
 
+// MXFP4 weight-only decode projections (ops/decode.py mxfp4_tiled_weight): w4 = e2m1 codes in the
+// tiled layout [N/16, K/128, 64, 16] (uint8 storage, two codes per byte), wblk = E8M0 block scales
+// [N/16, K/128, 16, 4] (SkinnyW::kTiledF4)
+static void fill_w4(SkinnyParams& p, const at::Tensor& x, const at::Tensor& w4, const at::Tensor& wblk) {
+  check_cuda(w4, "w4");
+  TORCH_CHECK(w4.scalar_type() == at::kByte && w4.dim() == 4 && w4.size(2) == 64 && w4.size(3) == 16 &&
+                  w4.is_contiguous(),
+              "w4 uint8 [N/16, K/128, 64, 16] contiguous");
+  check_cuda(wblk, "wblk");
+  TORCH_CHECK(wblk.scalar_type() == at::kByte && wblk.dim() == 4 && wblk.size(0) == w4.size(0) &&
+                  wblk.size(1) == w4.size(1) && wblk.size(2) == 16 && wblk.size(3) == 4 && wblk.is_contiguous(),
+              "wblk uint8 [N/16, K/128, 16, 4] contiguous");
+  const int64_t N = w4.size(0) * 16, K = w4.size(1) * 128;
+  TORCH_CHECK(N >= 16 && K >= 128 && N < (1ll << 30) && K < (1ll << 30), "shape too large");
+  check_aligned16(w4, "w4");
+  check_aligned16(wblk, "wblk");
+  same_device(x, w4);
+  same_device(x, wblk);
+  p.w = w4.data_ptr();
+  p.layout = SkinnyW::kTiledF4;
+  p.ldw = K;
+  p.wblk = wblk.data_ptr<uint8_t>();
+  p.N = static_cast<int>(N);
+  p.K = static_cast<int>(K);
+}
+
 // the producer's row-norm partials: fp32 [rows, nbp <= max_nbp], rows = 16 (skinny.hip) or M
 static void fill_ssq_in(SkinnyParams& p, const at::Tensor& x, const at::Tensor& sq, int64_t rows, int64_t max_nbp,
                         double eps) {
@@ -137,7 +163,7 @@ static at::Tensor alloc_y(SkinnyParams& p, const at::Tensor& x) {
   return y;
 }
 
-// skinny64 / skinny64_f8 (`p` arrives with the weight set): decode projection at 17..64 rows
+// skinny64 / skinny64_f8 / skinny64_f4 (`p` arrives with the weight set): decode projection at 17..64 rows
 // (skinny64.hip), the same fused-layer contract as skinny_fused below with row-norm partials per
 // (row, 1024 columns):
 //   * plain: y = x w^T;
@@ -184,6 +210,16 @@ std::tuple<at::Tensor, at::Tensor> skinny64_f8(const at::Tensor& x, const at::Te
                                                const c10::optional<at::Tensor>& ssq_in, double eps, bool glu) {
   SkinnyParams p{};
   fill_w8(p, x, w8, wscale);
+  return m64_step(p, x, res, ssq_in, eps, glu);
+}
+
+// MXFP4 form of skinny64: w4 / wblk the e2m1 tiled copy and its block scales (gate|up: the plain
+// [gate; up] row order, norm weight folded in)
+std::tuple<at::Tensor, at::Tensor> skinny64_f4(const at::Tensor& x, const at::Tensor& w4, const at::Tensor& wblk,
+                                               const c10::optional<at::Tensor>& res,
+                                               const c10::optional<at::Tensor>& ssq_in, double eps, bool glu) {
+  SkinnyParams p{};
+  fill_w4(p, x, w4, wblk);
   return m64_step(p, x, res, ssq_in, eps, glu);
 }
 
@@ -243,14 +279,49 @@ void quant_tile_f8(const at::Tensor& w, const c10::optional<at::Tensor>& nw, at:
                        glu_il, cur_stream(w));
 }
 
-// skinny_glu_il / skinny_glu_il_f8 (`p` arrives with the weight set): decode gate|up + SwiGLU at
+// w [N, K] bf16 (+ nw folded, glu_il interleave) -> codes uint8 [N/16, K/128, 64, 16] (e2m1, tiled)
+// and scales uint8 [N/16, K/128, 16, 4] (E8M0 per 32-block), in place (a captured decode graph
+// keeps reading them); one launch, no host sync
+void quant_tile_mxfp4(const at::Tensor& w, const c10::optional<at::Tensor>& nw, at::Tensor& codes,
+                      at::Tensor& scales, bool glu_il) {
+  check_bf16(w, "w");
+  TORCH_CHECK(w.dim() == 2 && w.stride(1) == 1 && w.stride(0) % 8 == 0, "w [N, K], unit inner stride");
+  const int64_t N = w.size(0), K = w.size(1);
+  TORCH_CHECK(N >= 16 && N % 16 == 0 && K >= 128 && K % 128 == 0 && N < (1ll << 30) && K < (1ll << 30),
+              "N % 16 == 0, K % 128 == 0");
+  TORCH_CHECK(!glu_il || N % 32 == 0, "glu_il: N = 2F, F % 16 == 0");
+  check_cuda(codes, "codes");
+  TORCH_CHECK(codes.scalar_type() == at::kByte && codes.is_contiguous() && codes.numel() == N * K / 2,
+              "codes uint8 contiguous, N * K / 2 bytes");
+  check_cuda(scales, "scales");
+  TORCH_CHECK(scales.scalar_type() == at::kByte && scales.is_contiguous() && scales.numel() == N * K / 32,
+              "scales uint8 contiguous, N * K / 32 bytes");
+  check_aligned16(w, "w");
+  check_aligned16(codes, "codes");
+  check_aligned16(scales, "scales");
+  same_device(w, codes);
+  same_device(w, scales);
+  const bf16_t* np = nullptr;
+  if (nw.has_value() && nw->defined()) {
+    check_bf16(*nw, "nw");
+    TORCH_CHECK(nw->dim() == 1 && nw->size(0) == K && nw->is_contiguous(), "nw [K] contiguous");
+    check_aligned16(*nw, "nw");
+    same_device(w, *nw);
+    np = cbp(*nw);
+  }
+  c10::hip::HIPGuardMasqueradingAsCUDA g(w.device());
+  launch_quant_tile_mxfp4(cbp(w), w.stride(0), np, codes.data_ptr<uint8_t>(), scales.data_ptr<uint8_t>(), (int)N,
+                          (int)K, glu_il, cur_stream(w));
+}
+
+// skinny_glu_il / skinny_glu_il_f8 / skinny_glu_il_f4 (`p` arrives with the weight set): decode gate|up + SwiGLU at
 // M <= 16 over the interleaved tiled weight (tile_weight / quant_tile_f8 glu_il, norm folded) from
 // the producer's row-norm partials: [M, F] = silu(rstd * g) * (rstd * u)
 static at::Tensor glu_il_step(SkinnyParams& p, const at::Tensor& x, const at::Tensor& ssq_in, double eps) {
   fill_x(p, x, 16, p.K);
-  TORCH_CHECK(p.K % 512 == 0 && (p.layout != SkinnyW::kTiledF8 || p.N % 32 == 0) &&
+  TORCH_CHECK(p.K % 512 == 0 && ((p.layout != SkinnyW::kTiledF8 && p.layout != SkinnyW::kTiledF4) || p.N % 32 == 0) &&
                   skinny_lds_bytes(p.M, p.K) <= kSkLdsNormX,
-              "skinny_glu_il: K % 512 == 0 (fp8: 2F % 32 == 0), x fits LDS");
+              "skinny_glu_il: K % 512 == 0 (fp8 / mxfp4: 2F % 32 == 0), x fits LDS");
   fill_ssq_in(p, x, ssq_in, 16, 512, eps);
   c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
   p.glu_out = true;
@@ -272,7 +343,14 @@ at::Tensor skinny_glu_il_f8(const at::Tensor& x, const at::Tensor& w8, const at:
   return glu_il_step(p, x, ssq_in, eps);
 }
 
-// skinny_fused / skinny_fused_f8 (`p` arrives with the weight set): fused decode-layer projection
+at::Tensor skinny_glu_il_f4(const at::Tensor& x, const at::Tensor& w4, const at::Tensor& wblk,
+                            const at::Tensor& ssq_in, double eps) {
+  SkinnyParams p{};
+  fill_w4(p, x, w4, wblk);
+  return glu_il_step(p, x, ssq_in, eps);
+}
+
+// skinny_fused / skinny_fused_f8 / skinny_fused_f4 (`p` arrives with the weight set): fused decode-layer projection
 // (M <= 16, skinny.hip KsFuse):
 //   * res given: returns (s = bf16(bf16(x w^T) + res) [M, N], ssq [16, N/16] fp32 partial sums of
 //     s^2 per (row, 16-column workgroup)) -- the o / down projection producing the residual;
@@ -294,10 +372,11 @@ static std::tuple<at::Tensor, at::Tensor> fused_step(SkinnyParams& p, const at::
     launch_skinny_gemm(p, cur_stream(x));
     return {m, at::Tensor()};
   }
-  // (a plain fp8 projection -- the LM head -- may be any width: one workgroup per 16 columns)
-  const bool wide_ok = p.layout == SkinnyW::kTiledF8 && !res.has_value() && !ssq_in.has_value();
+  // (a plain fp8 / mxfp4 projection -- the LM head -- may be any width: one workgroup per 16 columns)
+  const bool wide_ok = (p.layout == SkinnyW::kTiledF8 || p.layout == SkinnyW::kTiledF4) && !res.has_value() &&
+                       !ssq_in.has_value();
   TORCH_CHECK(wide_ok ? (p.N % 16 == 0 && p.K % 1024 == 0) : skinny_use_ksplit(p.N, p.K),
-              "fused skinny: N % 16 == 0, K % 1024 == 0, N < 16384 (but a plain fp8 projection)");
+              "fused skinny: N % 16 == 0, K % 1024 == 0, N < 16384 (but a plain fp8 / mxfp4 projection)");
   auto y = alloc_y(p, x);
   at::Tensor ssq;
   if (res.has_value()) ssq = fill_res(p, x, *res, 16, p.N / 16);
@@ -320,6 +399,15 @@ std::tuple<at::Tensor, at::Tensor> skinny_fused_f8(const at::Tensor& x, const at
                                                    const c10::optional<at::Tensor>& ssq_in, double eps) {
   SkinnyParams p{};
   fill_w8(p, x, w8, wscale);
+  return fused_step(p, x, res, ssq_in, eps, false);
+}
+
+std::tuple<at::Tensor, at::Tensor> skinny_fused_f4(const at::Tensor& x, const at::Tensor& w4,
+                                                   const at::Tensor& wblk,
+                                                   const c10::optional<at::Tensor>& res,
+                                                   const c10::optional<at::Tensor>& ssq_in, double eps) {
+  SkinnyParams p{};
+  fill_w4(p, x, w4, wblk);
   return fused_step(p, x, res, ssq_in, eps, false);
 }
 
@@ -782,6 +870,10 @@ TORCH_LIBRARY_FRAGMENT(dla, m) {
   m.def("skinny_glu_il(Tensor x, Tensor wt, Tensor ssq_in, float eps) -> Tensor");
   m.def("skinny_fused_f8(Tensor x, Tensor w8, Tensor wscale, Tensor? res, Tensor? ssq_in, float eps) -> (Tensor, Tensor)");
   m.def("skinny_glu_il_f8(Tensor x, Tensor w8, Tensor wscale, Tensor ssq_in, float eps) -> Tensor");
+  m.def("quant_tile_mxfp4(Tensor w, Tensor? norm_w, Tensor(a!) out_codes, Tensor(b!) out_scales, bool glu_il=False) -> ()");
+  m.def("skinny_fused_f4(Tensor x, Tensor w4, Tensor wblk, Tensor? res, Tensor? ssq_in, float eps) -> (Tensor, Tensor)");
+  m.def("skinny_glu_il_f4(Tensor x, Tensor w4, Tensor wblk, Tensor ssq_in, float eps) -> Tensor");
+  m.def("skinny64_f4(Tensor x, Tensor w4, Tensor wblk, Tensor? res, Tensor? ssq_in, float eps, bool glu) -> (Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(dla, CUDA, m) {
@@ -805,4 +897,8 @@ TORCH_LIBRARY_IMPL(dla, CUDA, m) {
   m.impl("skinny_glu_il", &dla::skinny_glu_il);
   m.impl("skinny_fused_f8", &dla::skinny_fused_f8);
   m.impl("skinny_glu_il_f8", &dla::skinny_glu_il_f8);
+  m.impl("quant_tile_mxfp4", &dla::quant_tile_mxfp4);
+  m.impl("skinny_fused_f4", &dla::skinny_fused_f4);
+  m.impl("skinny_glu_il_f4", &dla::skinny_glu_il_f4);
+  m.impl("skinny64_f4", &dla::skinny64_f4);
 }

@@ -140,5 +140,19 @@ __device__ __forceinline__ s16x8 f8x8_to_bf16(uint32_t w0, uint32_t w1) {
   return s16x8{a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1]};
 }
 
+// MXFP4 (OCP e2m1 codes, E8M0 block scale): one dword = 8 codes, byte j = elements 2j (low nibble)
+// and 2j + 1 (high nibble), the order v_cvt_scalef32_pk_bf16_fp4's byte select decodes. `sb` is the
+// block's E8M0 byte; the conversion's scale operand is the fp32 2^(sb - 127) = bits sb << 23, so
+// the 8 bf16 results are e2m1(code) * 2^(sb - 127), exact.
+__device__ __forceinline__ s16x8 f4x8_to_bf16(uint32_t w, uint32_t sb) {
+  typedef short s16x2v __attribute__((ext_vector_type(2)));
+  const float sc = __uint_as_float(sb << 23);
+  const s16x2v a = __builtin_bit_cast(s16x2v, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, sc, 0));
+  const s16x2v b = __builtin_bit_cast(s16x2v, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, sc, 1));
+  const s16x2v c = __builtin_bit_cast(s16x2v, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, sc, 2));
+  const s16x2v d = __builtin_bit_cast(s16x2v, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, sc, 3));
+  return s16x8{a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1]};
+}
+
 
 }  // namespace dla

@@ -250,6 +250,7 @@ template <class F>
 static void skinny_layout_dispatch(SkinnyW layout, F f) {
   switch (layout) {
     case SkinnyW::kTiledF8: f(sk_layout<SkinnyW::kTiledF8>{}); break;
+    case SkinnyW::kTiledF4: f(sk_layout<SkinnyW::kTiledF4>{}); break;
     case SkinnyW::kTiled: f(sk_layout<SkinnyW::kTiled>{}); break;
     default: f(sk_layout<SkinnyW::kRowMajor>{}); break;
   }
@@ -309,12 +310,12 @@ void launch_skinny_gemm(const SkinnyParams& p, hipStream_t st) {
 // per ring slot (4 at MT = 1; 2 above, which keeps the x fragments at ~110 VGPRs for MT = 4, four
 // waves per SIMD).
 template <int DEPTH, bool NT, bool GLU, int MT = 1, int UNR = kKsUnroll, bool RES = false, bool NIN = false,
-          bool TW = false, bool F8 = false>
+          bool TW = false, bool F8 = false, bool F4 = false>
 __global__ __launch_bounds__(512) void skinny_ksplit_kernel(
     const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __restrict__ W, int64_t ldw,
     bf16_t* __restrict__ y, int64_t ldy, int M, int N, int K, KsFuse fz = KsFuse{}) {
-  ks_body<DEPTH, NT, GLU, MT, UNR, RES, NIN, TW, F8>(blockIdx.x, gridDim.x, x, ldx, W, ldw, y, ldy, M,
-                                                             N, K, fz);
+  ks_body<DEPTH, NT, GLU, MT, UNR, RES, NIN, TW, F8, F4>(blockIdx.x, gridDim.x, x, ldx, W, ldw, y, ldy, M,
+                                                                 N, K, fz);
 }
 
 // `fused`: the decode-layer launches (KsFuse) -- the residual-producing projection (res) and the
@@ -322,17 +323,19 @@ __global__ __launch_bounds__(512) void skinny_ksplit_kernel(
 // ks_body's branch-free ring (KsFuse::straight) on every shape it covers; its A/B switch went in
 // round 6 (3.557 / 3.554 vs 3.581 / 3.569 ms/token at B = 8, profiles/r5_decode_fp8.md). Ring
 // depth: skinny_ks_depth; fp8 weights (e4m3 tiled copy + per-row scales, ks_body F8: the o / down /
-// qkv projections at half the weight bytes) skinny_ks_f8_depth.
+// qkv projections at half the weight bytes) skinny_ks_f8_depth; MXFP4 weights (e2m1 tiled copy +
+// E8M0 block scales, ks_body F4) kKsF4Depth.
 // Otherwise the plain projection, or with glu_out gate|up (N = 2F weight rows) -> m = silu(gate) *
 // up [M, F] on F / 16 workgroups, of a row-major weight at M <= 64, the ring as ks_body's default.
 void launch_skinny_ksplit(const SkinnyParams& p, bool fused, hipStream_t st) {
-  const KsFuse fz{p.res, p.ldr, p.ssq_out, p.ssq_in, p.nbp, p.eps, p.wscale, fused ? 1 : 0};
+  const KsFuse fz{p.res, p.ldr, p.ssq_out, p.ssq_in, p.nbp, p.eps, p.wscale, fused ? 1 : 0, p.wblk};
   const int nb = p.glu_out ? p.N / 32 : p.N / 16;
   auto launch = [&](auto depth, auto mt, auto glu, auto res, auto nin, auto lay) {
     constexpr int MT = decltype(mt)::value;
     constexpr bool TW = decltype(lay)::value != SkinnyW::kRowMajor, F8 = decltype(lay)::value == SkinnyW::kTiledF8;
+    constexpr bool F4 = decltype(lay)::value == SkinnyW::kTiledF4;
     skinny_ksplit_kernel<decltype(depth)::value, TW, decltype(glu)::value, MT, MT == 1 ? kKsUnroll : 2,
-                         decltype(res)::value, decltype(nin)::value, TW, F8><<<nb, 512, 0, st>>>(
+                         decltype(res)::value, decltype(nin)::value, TW, F8, F4><<<nb, 512, 0, st>>>(
         p.x, p.ldx, static_cast<const bf16_t*>(p.w), p.ldw, p.y, p.ldy, p.M, p.N, p.K, fz);
   };
   constexpr std::true_type yes{};
@@ -345,7 +348,9 @@ void launch_skinny_ksplit(const SkinnyParams& p, bool fused, hipStream_t st) {
         else if (p.ssq_in != nullptr) launch(depth, sk_int<1>{}, no, no, yes, lay);
         else launch(depth, sk_int<1>{}, no, no, no, lay);
       };
-      const int depth = p.layout == SkinnyW::kTiledF8 ? skinny_ks_f8_depth() : skinny_ks_depth(p.K);
+      const int depth = p.layout == SkinnyW::kTiledF8   ? skinny_ks_f8_depth()
+                        : p.layout == SkinnyW::kTiledF4 ? kKsF4Depth
+                                                        : skinny_ks_depth(p.K);
       if (depth == 4) epilogue(sk_int<4>{});
       else epilogue(sk_int<2>{});
     });
@@ -378,7 +383,11 @@ void launch_skinny_ksplit(const SkinnyParams& p, bool fused, hipStream_t st) {
 // F8: Wt is the e4m3 interleaved tiled copy [2F/16, K/64, 64, 16 B] (ks_body F8 layout) and
 // fz.wscale the per-row scales in the same interleaved row order; one 1-KB wave load feeds two
 // k-steps, so a ring slot of kSkUnroll k-steps is kSkUnroll / 2 loads.
-template <int DEPTH, bool F8 = false>
+// F4: Wt is the e2m1 interleaved tiled copy [2F/16, K/128, 64, 16 B] and fz.wblk its E8M0 block
+// scales [2F/16, K/128, 16, 4] (ks_body F4 layout, same interleaved row order): one 1-KB wave load
+// feeds four k-steps, so a ring slot is kSkUnroll / 4 code loads and as many 4-byte scale loads;
+// the scale is applied by the conversion and the epilogue has no weight scale.
+template <int DEPTH, bool F8 = false, bool F4 = false>
 __global__ __launch_bounds__(512) void skinny_glu_il_kernel(const bf16_t* __restrict__ x, int64_t ldx,
                                                            const bf16_t* __restrict__ Wt,
                                                            bf16_t* __restrict__ y, int64_t ldy, int M,
@@ -394,13 +403,24 @@ __global__ __launch_bounds__(512) void skinny_glu_il_kernel(const bf16_t* __rest
   const bf16_t* wrow = Wt + static_cast<int64_t>(active ? t : 0) * 16 * K + lane * 8;
   const uint8_t* wrow8 = reinterpret_cast<const uint8_t*>(Wt) + static_cast<int64_t>(active ? t : 0) * 16 * K +
                          lane * 16;
-  constexpr int UB = F8 ? kSkUnroll / 2 : kSkUnroll;  // wave loads per ring slot
+  static_assert(!(F8 && F4), "one weight format");
+  constexpr int UB = F4 ? kSkUnroll / 4 : F8 ? kSkUnroll / 2 : kSkUnroll;  // wave loads per ring slot
+  const uint8_t* wrow4 = reinterpret_cast<const uint8_t*>(Wt) + static_cast<int64_t>(active ? t : 0) * 8 * K +
+                         lane * 16;
+  const uint8_t* srow4 = F4 ? fz.wblk + static_cast<int64_t>(active ? t : 0) * (K >> 1) + r * 4 : nullptr;
   const int nchunks = K / kSkChunk;
   // DEPTH chunks of kSkUnroll k-steps in flight (a ring of register sets)
-  s16x8 b[DEPTH][F8 ? 1 : kSkUnroll];
-  ks_u32x4 b8[DEPTH][F8 ? UB : 1];
+  s16x8 b[DEPTH][(F8 || F4) ? 1 : kSkUnroll];
+  ks_u32x4 b8[DEPTH][(F8 || F4) ? UB : 1];
+  uint32_t bs4[DEPTH][F4 ? UB : 1];
   auto wload = [&](int j, int c) {
-    if constexpr (F8) {
+    if constexpr (F4) {
+#pragma unroll
+      for (int u = 0; u < UB; ++u) {
+        b8[j][u] = *reinterpret_cast<const ks_u32x4*>(wrow4 + (c * UB + u) * 1024);
+        bs4[j][u] = *reinterpret_cast<const uint32_t*>(srow4 + (c * UB + u) * 64);
+      }
+    } else if constexpr (F8) {
 #pragma unroll
       for (int u = 0; u < UB; ++u) b8[j][u] = *reinterpret_cast<const ks_u32x4*>(wrow8 + (c * UB + u) * 1024);
     } else {
@@ -458,7 +478,9 @@ __global__ __launch_bounds__(512) void skinny_glu_il_kernel(const bf16_t* __rest
         s16x8 a = {0, 0, 0, 0, 0, 0, 0, 0};
         if (arow) a = __builtin_bit_cast(s16x8, load_bf16x8(xrow + kk + u * 32));
         s16x8 bu;
-        if constexpr (F8) {
+        if constexpr (F4) {
+          bu = f4x8_to_bf16(b8[j][u >> 2][u & 3], (bs4[j][u >> 2] >> (8 * (u & 3))) & 0xffu);
+        } else if constexpr (F8) {
           const ks_u32x4 wv = b8[j][u >> 1];
           bu = (u & 1) ? f8x8_to_bf16(wv[2], wv[3]) : f8x8_to_bf16(wv[0], wv[1]);
         } else {
@@ -502,13 +524,14 @@ __global__ __launch_bounds__(512) void skinny_glu_il_kernel(const bf16_t* __rest
 }
 
 // gate|up over the interleaved tiled weight (2F rows -> [M, F]); waves per workgroup and ring depth
-// in skinny_geom.h (fp8: the interleaved e4m3 tiled copy, fz.wscale)
+// in skinny_geom.h (fp8: the interleaved e4m3 tiled copy, fz.wscale; mxfp4: the e2m1 one, fz.wblk)
 void launch_skinny_glu_il(const SkinnyParams& p, hipStream_t st) {
-  const bool f8 = p.layout == SkinnyW::kTiledF8;
-  const int ntiles = p.N / 16, w = glu_il_waves(ntiles, p.M, f8);
-  const KsFuse fz{nullptr, 0, nullptr, p.ssq_in, p.nbp, p.eps, p.wscale, 0};
-  auto launch = [&](auto depth, auto f8c) {
-    auto* kernel = &skinny_glu_il_kernel<decltype(depth)::value, decltype(f8c)::value>;
+  const bool f8 = p.layout == SkinnyW::kTiledF8, f4 = p.layout == SkinnyW::kTiledF4;
+  const int ntiles = p.N / 16, w = glu_il_waves(ntiles, p.M, f8 || f4);
+  const KsFuse fz{nullptr, 0, nullptr, p.ssq_in, p.nbp, p.eps, p.wscale, 0, p.wblk};
+  auto launch = [&](auto depth, auto fmt) {
+    constexpr int FMT = decltype(fmt)::value;  // 0 bf16, 1 e4m3, 2 mxfp4
+    auto* kernel = &skinny_glu_il_kernel<decltype(depth)::value, FMT == 1, FMT == 2>;
     static const bool attr_set = [kernel] {
       skinny_lds_limit(kernel, kSkLdsNormMax);
       return true;
@@ -517,15 +540,16 @@ void launch_skinny_glu_il(const SkinnyParams& p, hipStream_t st) {
     kernel<<<(ntiles + w - 1) / w, 64 * w, skinny_lds_bytes(p.M, p.K), st>>>(
         p.x, p.ldx, static_cast<const bf16_t*>(p.w), p.y, p.ldy, p.M, ntiles, p.K, fz);
   };
-  auto ring = [&](auto f8c) {
-    switch (glu_il_depth(f8)) {
-      case 2: launch(sk_int<2>{}, f8c); break;
-      case 3: launch(sk_int<3>{}, f8c); break;
-      default: launch(sk_int<4>{}, f8c); break;
+  auto ring = [&](auto fmt) {
+    switch (f4 ? kGluIlF4Depth : glu_il_depth(f8)) {
+      case 2: launch(sk_int<2>{}, fmt); break;
+      case 3: launch(sk_int<3>{}, fmt); break;
+      default: launch(sk_int<4>{}, fmt); break;
     }
   };
-  if (f8) ring(std::true_type{});
-  else ring(std::false_type{});
+  if (f4) ring(sk_int<2>{});
+  else if (f8) ring(sk_int<1>{});
+  else ring(sk_int<0>{});
 }
 
 }  // namespace dla

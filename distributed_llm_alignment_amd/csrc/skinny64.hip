@@ -43,6 +43,11 @@ __device__ __forceinline__ f32x4 mfma16(s16x8 a, s16x8 b, f32x4 c) {
 // fragments of two consecutive k-steps, so a 256-deep chunk is 4 loads per lane instead of 8 and
 // the stream is half the bytes; e4m3 -> bf16 in registers (exact), the bf16 MFMA unchanged, and
 // the per-row scale wsc[n] applied to the fp32 sum before any epilogue.
+// F4 (weight-only MXFP4 decode, TW + nt only): W is the e2m1 tiled copy [N/16, K/128, 64 lanes, 16 B]
+// and `wblk` its E8M0 block scales [N/16, K/128, 16, 4] (csrc/skinny_ks.h F4): one 16-byte load
+// per lane holds its B fragments of four consecutive k-steps, so a 256-deep chunk is 2 code loads
+// and 2 scale dwords per lane; v_cvt_scalef32_pk_bf16_fp4 applies the block scale while converting
+// (exact bf16 weights into the unchanged MFMA), and no epilogue carries a weight scale.
 // Weight layouts: row-major W [N, K], or TW (tiled, ops/decode.py `tiled_weight`):
 // Wt[N / 16][K / 32][4][16][8] with Wt[t][kk][q][r][e] = W[16 t + r][32 kk + 8 q + e], i.e. the
 // 16-byte pieces in the order lane (r = lane & 15, q = lane >> 4) of an MFMA B fragment reads them:
@@ -55,12 +60,15 @@ __device__ __forceinline__ f32x4 mfma16(s16x8 a, s16x8 b, f32x4 c) {
 // from ssq_in (the producer's row partial sums, [M][nbp]) when NIN, else 1; gate / up are
 // rounded to bf16 before SwiGLU exactly as the unfused GEMM + swiglu pair.
 // Otherwise S == 1 writes y = bf16(x W^T); S > 1 writes fp32 slab ws[s][m][n].
-template <int MT, bool GLU, bool NIN, bool TW, int DEPTH, int NW = kM64Waves, bool NTL = false, bool F8 = false>
+template <int MT, bool GLU, bool NIN, bool TW, int DEPTH, int NW = kM64Waves, bool NTL = false, bool F8 = false,
+          bool F4 = false>
 __global__ __launch_bounds__(64 * NW) void m64_gemm_kernel(
     const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __restrict__ W, int64_t ldw,
     bf16_t* __restrict__ y, int64_t ldy, float* __restrict__ ws, int M, int N, int K, int kc,
-    const float* __restrict__ ssq_in, int nbp, float eps, const float* __restrict__ wsc) {
+    const float* __restrict__ ssq_in, int nbp, float eps, const float* __restrict__ wsc,
+    const uint8_t* __restrict__ wblk = nullptr) {
   static_assert(!F8 || (TW && NTL), "fp8 weights: tiled layout, nt stream");
+  static_assert(!F4 || (TW && NTL && !F8), "mxfp4 weights: tiled layout, nt stream");
   extern __shared__ __attribute__((aligned(16))) bf16_t xs[];
   __shared__ float rstd_s[64];
   constexpr int RB = 16 * MT * kM64Ld;  // one ring slot
@@ -80,6 +88,10 @@ __global__ __launch_bounds__(64 * NW) void m64_gemm_kernel(
                          : W + static_cast<int64_t>(n0 + r) * ldw + k0 + q * 8;
   const uint8_t* wrow8 = reinterpret_cast<const uint8_t*>(W) + static_cast<int64_t>(n0 >> 4) * 16 * K +
                          (k0 >> 6) * 1024 + lane * 16;
+  // F4: 8 K code bytes and K / 2 scale bytes per 16-row tile; k-tile kt at + 1024 kt / + 64 kt
+  const uint8_t* wrow4 = reinterpret_cast<const uint8_t*>(W) + static_cast<int64_t>(n0 >> 4) * 8 * K +
+                         (k0 >> 7) * 1024 + lane * 16;
+  const uint8_t* srow4 = F4 ? wblk + static_cast<int64_t>(n0 >> 4) * (K >> 1) + (k0 >> 7) * 64 + r * 4 : nullptr;
 
   // NIN: this row's producer partials (thread m < M holds row m); up to kM64RegNbp are loaded
   // here, ahead of the first chunk, and summed once those loads land
@@ -100,8 +112,10 @@ __global__ __launch_bounds__(64 * NW) void m64_gemm_kernel(
   typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
   constexpr int KS8 = kM64Steps / 2;  // fp8: 16-byte weight loads per lane per chunk
   bf16x8 xr[DEPTH][XPASS];
-  s16x8 b[DEPTH][F8 ? 1 : kM64Steps];
-  u32x4v b8[DEPTH][F8 ? KS8 : 1];
+  constexpr int KS4 = kM64Steps / 4;  // mxfp4: 16-byte code loads (and scale dwords) per lane per chunk
+  s16x8 b[DEPTH][(F8 || F4) ? 1 : kM64Steps];
+  u32x4v b8[DEPTH][F8 ? KS8 : F4 ? KS4 : 1];
+  uint32_t bs4[DEPTH][F4 ? KS4 : 1];
   auto issue = [&](auto J, int c) {
     constexpr int j = decltype(J)::value;
 #pragma unroll
@@ -109,6 +123,14 @@ __global__ __launch_bounds__(64 * NW) void m64_gemm_kernel(
       const int m = xm + (NTH / 32) * t;
       xr[j][t] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
       if (m < M) xr[j][t] = load_bf16x8(x + static_cast<int64_t>(m) * ldx + k0 + c * kM64Ck + xc);
+    }
+    if constexpr (F4) {
+#pragma unroll
+      for (int u = 0; u < KS4; ++u) {
+        b8[j][u] = __builtin_nontemporal_load(reinterpret_cast<const u32x4v*>(wrow4 + (c * KS4 + u) * 1024));
+        bs4[j][u] = *reinterpret_cast<const uint32_t*>(srow4 + (c * KS4 + u) * 64);
+      }
+      return;
     }
     if constexpr (F8) {
 #pragma unroll
@@ -161,7 +183,9 @@ __global__ __launch_bounds__(64 * NW) void m64_gemm_kernel(
 #pragma unroll
     for (int u = 0; u < kM64Steps; ++u) {
       s16x8 bu;
-      if constexpr (F8) {
+      if constexpr (F4) {
+        bu = f4x8_to_bf16(b8[j][u >> 2][u & 3], (bs4[j][u >> 2] >> (8 * (u & 3))) & 0xffu);
+      } else if constexpr (F8) {
         const u32x4v wv = b8[j][u >> 1];
         bu = (u & 1) ? f8x8_to_bf16(wv[2], wv[3]) : f8x8_to_bf16(wv[0], wv[1]);
       } else {
@@ -324,13 +348,15 @@ int m64_num_splits(const SkinnyParams& p) {
 // Non-temporal loads on the tiled weight streams only (see skinny.hip), two weight chunks in flight
 // per wave on the bf16 ones (3 or 4 measured 5.10 / 5.27 vs 5.01 ms/token at B = 64: more bytes in
 // flight only lengthen the queues; removed), m64_f8_depth on the e4m3 tiled copy (p.wscale its
-// per-row scales).
+// per-row scales), kM64F4Depth on the e2m1 one (p.wblk its block scales).
+// `fmt`: the weight format as m64_int, 0 bf16, 1 e4m3, 2 mxfp4.
 void launch_m64(const SkinnyParams& p, hipStream_t st) {
   const int S = m64_num_splits(p);
-  auto gemm = [&](auto mt, auto glu, auto nin, auto tw, auto f8, auto depth) {
+  auto gemm = [&](auto mt, auto glu, auto nin, auto tw, auto fmt, auto depth) {
     constexpr int MT = decltype(mt)::value;
     constexpr bool GLU = decltype(glu)::value, NIN = decltype(nin)::value, TW = decltype(tw)::value;
-    auto* kernel = &m64_gemm_kernel<MT, GLU, NIN, TW, decltype(depth)::value, kM64Waves, TW, decltype(f8)::value>;
+    constexpr int FMT = decltype(fmt)::value;
+    auto* kernel = &m64_gemm_kernel<MT, GLU, NIN, TW, decltype(depth)::value, kM64Waves, TW, FMT == 1, FMT == 2>;
     static const bool attr = [kernel] {
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 static_cast<int>(kM64LdsMax));
@@ -342,22 +368,26 @@ void launch_m64(const SkinnyParams& p, hipStream_t st) {
     // the plain rows leave res / ssq_in to the reduce launch
     kernel<<<grid, 64 * kM64Waves, m64_lds_bytes(MT), st>>>(
         p.x, p.ldx, static_cast<const bf16_t*>(p.w), p.ldw, p.y, p.ldy, p.ws, p.M, p.N, p.K, p.K / S,
-        NIN ? p.ssq_in : nullptr, NIN ? p.nbp : 0, NIN ? p.eps : 0.f, p.wscale);
+        NIN ? p.ssq_in : nullptr, NIN ? p.nbp : 0, NIN ? p.eps : 0.f, p.wscale, p.wblk);
   };
   constexpr std::true_type yes{};
   constexpr std::false_type no{};
-  auto epilogue = [&](auto mt, auto tw, auto f8, auto depth) {
-    if (p.glu_out && p.ssq_in != nullptr) gemm(mt, yes, yes, tw, f8, depth);
-    else if (p.glu_out) gemm(mt, yes, no, tw, f8, depth);
-    else gemm(mt, no, no, tw, f8, depth);
+  auto epilogue = [&](auto mt, auto tw, auto fmt, auto depth) {
+    if (p.glu_out && p.ssq_in != nullptr) gemm(mt, yes, yes, tw, fmt, depth);
+    else if (p.glu_out) gemm(mt, yes, no, tw, fmt, depth);
+    else gemm(mt, no, no, tw, fmt, depth);
   };
+  constexpr m64_int<0> bf16w{};
+  constexpr m64_int<1> e4m3w{};
+  constexpr m64_int<2> mxfp4w{};
   auto weight = [&](auto mt) {
-    if (p.layout == SkinnyW::kRowMajor) return epilogue(mt, no, no, m64_int<2>{});
-    if (p.layout == SkinnyW::kTiled) return epilogue(mt, yes, no, m64_int<2>{});
+    if (p.layout == SkinnyW::kRowMajor) return epilogue(mt, no, bf16w, m64_int<2>{});
+    if (p.layout == SkinnyW::kTiled) return epilogue(mt, yes, bf16w, m64_int<2>{});
+    if (p.layout == SkinnyW::kTiledF4) return epilogue(mt, yes, mxfp4w, m64_int<kM64F4Depth>{});
     switch (m64_f8_depth()) {
-      case 2: epilogue(mt, yes, yes, m64_int<2>{}); break;
-      case 4: epilogue(mt, yes, yes, m64_int<4>{}); break;
-      default: epilogue(mt, yes, yes, m64_int<3>{}); break;
+      case 2: epilogue(mt, yes, e4m3w, m64_int<2>{}); break;
+      case 4: epilogue(mt, yes, e4m3w, m64_int<4>{}); break;
+      default: epilogue(mt, yes, e4m3w, m64_int<3>{}); break;
     }
   };
   if (m64_row_tiles(p.M) == 2) weight(m64_int<2>{});
@@ -498,6 +528,71 @@ __global__ __launch_bounds__(256) void quant_tile_f8_kernel(const bf16_t* __rest
 void launch_quant_tile_f8(const bf16_t* W, int64_t ldw, const bf16_t* nw, uint8_t* out, float* scale, int N,
                           int K, bool glu_il, hipStream_t st) {
   quant_tile_f8_kernel<<<N / 16, 256, 0, st>>>(W, ldw, nw, out, scale, K, glu_il ? N / 2 : 0);
+}
+
+// MXFP4 decode copy in one pass (ops/decode.py mxfp4_tiled_weight; refreshed every RLHF step):
+// W [N, K] (row stride ldw), nw folded as bf16(W * nw), glu_f > 0 = gate / up rows interleaved
+// 8 + 8 per tile -> e2m1 codes in the tiled layout [N/16, K/128, 64 lanes, 16 B] and E8M0 block
+// scales [N/16, K/128, 16, 4] (SkinnyW::kTiledF4). One thread per 16-byte lane piece: lane r + 16 q
+// reads row r's k = 128 kt + 32 s + 8 q + [0, 8) for s = 0..3 (the four q lanes of a row cover its
+// four 32-blocks, 256 B contiguous per row), the block amax meets by two lane swaps (lane ^ 16,
+// lane ^ 32: fmaxf, order free), and the q = 0 lane writes the row's four scale bytes as one dword.
+//   amax > 0: e = clamp(floor(log2 amax) - 2, -120, 120), scale byte e + 127 (floor(log2 .) is the
+//             fp32 exponent field; a denormal amax reads -127 and clamps like its true exponent);
+//   amax = 0: byte 127, codes 0.
+// The clamp keeps 2^e and 2^-e normal fp32 and every dequantised value 0.5 * 2^e .. 6 * 2^e a
+// normal bf16, so no denormal mode of any instruction can matter. v = |x| * 2^-e is exact in fp32
+// (a power-of-two product), so the rounding below is the formula's, bit for bit: e2m1 round to
+// nearest, ties to the even code, as integer compares against the midpoints (v >= 6 saturates).
+__device__ __forceinline__ uint32_t e2m1_rne(float x, float inv) {
+  const float v = fabsf(x) * inv;
+  const uint32_t c = (v > 0.25f) + (v >= 0.75f) + (v > 1.25f) + (v >= 1.75f) + (v > 2.5f) + (v >= 3.5f) + (v > 5.f);
+  return c | (x < 0.f ? 8u : 0u);
+}
+
+__global__ __launch_bounds__(256) void quant_tile_mxfp4_kernel(const bf16_t* __restrict__ W, int64_t ldw,
+                                                               const bf16_t* __restrict__ nw,
+                                                               uint8_t* __restrict__ codes,
+                                                               uint8_t* __restrict__ scales, int K,
+                                                               int64_t total, int glu_f) {
+  // (total = N K / 32 pieces is a multiple of 64: every wave is whole, the shuffles see live lanes)
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+  if (i >= total) return;
+  const int lane = static_cast<int>(i & 63), r = lane & 15, q = lane >> 4;
+  const int64_t blk = i >> 6;  // (tile, k-tile)
+  const int kb = K >> 7;
+  const int64_t t = blk / kb;
+  const int kt = static_cast<int>(blk - t * kb);
+  const int64_t row = tile_row_of(t, r, glu_f);
+  uint32_t wv[4], sb = 0;
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    const int col = 128 * kt + 32 * s + 8 * q;
+    const bf16x8 v = fold_norm8(load_bf16x8(W + row * ldw + col), nw != nullptr ? nw + col : nullptr);
+    float am = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) am = fmaxf(am, fabsf(bf2f(v[e])));
+    am = fmaxf(am, __shfl_xor(am, 16, 64));
+    am = fmaxf(am, __shfl_xor(am, 32, 64));
+    int ex = static_cast<int>((__float_as_uint(am) >> 23) & 0xffu) - 127 - 2;
+    ex = min(max(ex, -120), 120);
+    const uint32_t byte = am > 0.f ? static_cast<uint32_t>(ex + 127) : 127u;
+    const float inv = __uint_as_float((254u - byte) << 23);  // 2^-(byte - 127)
+    uint32_t w = 0;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) w |= e2m1_rne(bf2f(v[e]), inv) << (4 * e);
+    wv[s] = w;
+    sb |= byte << (8 * s);
+  }
+  *reinterpret_cast<uint4*>(codes + i * 16) = make_uint4(wv[0], wv[1], wv[2], wv[3]);
+  if (q == 0) *reinterpret_cast<uint32_t*>(scales + (blk * 16 + r) * 4) = sb;
+}
+
+void launch_quant_tile_mxfp4(const bf16_t* W, int64_t ldw, const bf16_t* nw, uint8_t* codes, uint8_t* scales,
+                             int N, int K, bool glu_il, hipStream_t st) {
+  const int64_t total = static_cast<int64_t>(N) * K / 32;
+  quant_tile_mxfp4_kernel<<<static_cast<unsigned>((total + 255) / 256), 256, 0, st>>>(W, ldw, nw, codes, scales, K,
+                                                                                      total, glu_il ? N / 2 : 0);
 }
 
 // ---- LoRA-merged forms: the same copies built from W + s B A in one pass (ops/decode.py `lora=`) ----

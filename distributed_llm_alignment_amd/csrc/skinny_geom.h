@@ -81,6 +81,13 @@ inline int skinny_ks_f8_depth() {
   return depth;
 }
 
+// MXFP4 weights (ks_body F4, skinny_glu_il_kernel F4, m64_gemm_kernel F4): ring depth 2 in all
+// three, the depth with the fewest VGPRs (92-110 / 96 / 70-118) and the one the e4m3 split-K ring
+// settled on. Not chosen by a per-kernel A/B: profiles/mxfp4_decode.md says what was run.
+constexpr int kKsF4Depth = 2;
+constexpr int kGluIlF4Depth = 2;
+constexpr int kM64F4Depth = 2;
+
 // skinny_glu_il_kernel ring depth: DLA_GLU_IL_DEPTH (2, 3 or 4) for A/B runs; fp8:
 // DLA_GLU_IL_F8_DEPTH (2, 3 or 4), same A/B: 2.712 / 2.710 / 2.729 ms/token
 inline int glu_il_depth(bool f8) {

@@ -75,8 +75,14 @@ __device__ __forceinline__ ks_u32x4 load_w8(const uint8_t* p) {
 // 64kt + 32 + 8q + [0, 8) in bytes 8-15, i.e. its B fragments of two consecutive MFMA k-steps, so
 // one 16-byte load feeds two MFMAs and the stream is half the bf16 bytes (ops/decode.py
 // fp8_tiled_weight); y[:, n] = wscale[n] * (x . w8[n]).
+// F4 (decode weight-only MXFP4, TW only): W points at the e2m1 tiled copy [N/16, K/128, 64 lanes,
+// 16 B] and fz.wblk at its E8M0 block scales [N/16, K/128, 16 rows, 4] (SkinnyW::kTiledF4). A ring
+// slot is one k-tile of 128: ONE 16-byte code load (dword s = the lane's B fragment of k-step s)
+// and ONE 4-byte scale load (byte s = row r's scale of k-step s; the four q lanes of a row read
+// the same dword) feed four MFMAs. v_cvt_scalef32_pk_bf16_fp4 applies the block scale while
+// converting, so the MFMA sees the exact bf16 weights and the epilogue has no weight scale.
 template <int DEPTH, bool NT, bool GLU, int MT = 1, int UNR = kKsUnroll, bool RES = false, bool NIN = false,
-          bool TW = false, bool F8 = false>
+          bool TW = false, bool F8 = false, bool F4 = false>
 __device__ __forceinline__ void ks_body(
     const int bx, const int nblk, const bf16_t* __restrict__ x, int64_t ldx,
     const bf16_t* __restrict__ W, int64_t ldw, bf16_t* __restrict__ y, int64_t ldy, int M, int N, int K,
@@ -84,6 +90,7 @@ __device__ __forceinline__ void ks_body(
   constexpr int CH = 32 * UNR;  // k per ring slot
   static_assert(!(RES || NIN) || (MT == 1 && !GLU), "fused residual / norm: M <= 16, plain output");
   static_assert(!F8 || (TW && !GLU && MT == 1 && UNR % 2 == 0), "fp8 weights: tiled, plain rows");
+  static_assert(!F4 || (TW && !F8 && !GLU && MT == 1 && UNR == 4), "mxfp4 weights: tiled, plain rows, 128 k per slot");
   constexpr int UB = F8 ? UNR / 2 : UNR;  // weight loads per ring slot
   __shared__ float red[8][4 * MT][64];
   __shared__ float rstd_s[16];
@@ -100,6 +107,10 @@ __device__ __forceinline__ void ks_body(
                           : W + static_cast<int64_t>(n0 + r) * ldw + k0 + q * 8;
   const uint8_t* wrow8 = reinterpret_cast<const uint8_t*>(W) + static_cast<int64_t>(n0 >> 4) * 16 * K +
                          (k0 >> 6) * 1024 + lane * 16;
+  // F4: 8 K code bytes and K / 2 scale bytes per 16-row tile; k-tile kt at + 1024 kt / + 64 kt
+  const uint8_t* wrow4 = reinterpret_cast<const uint8_t*>(W) + static_cast<int64_t>(n0 >> 4) * 8 * K +
+                         (k0 >> 7) * 1024 + lane * 16;
+  const uint8_t* srow4 = F4 ? fz.wblk + static_cast<int64_t>(n0 >> 4) * (K >> 1) + (k0 >> 7) * 64 + r * 4 : nullptr;
   bool arow[MT];
   const bf16_t* xrow[MT];
 #pragma unroll
@@ -108,10 +119,14 @@ __device__ __forceinline__ void ks_body(
     xrow[t] = x + static_cast<int64_t>(arow[t] ? 16 * t + r : 0) * ldx + k0 + q * 8;
   }
   // DEPTH chunks (W and x fragments) in flight: a ring of register sets, refilled as consumed
-  s16x8 b[DEPTH][F8 ? 1 : UNR], a[DEPTH][UNR][MT];
+  s16x8 b[DEPTH][(F8 || F4) ? 1 : UNR], a[DEPTH][UNR][MT];
   ks_u32x4 b8[DEPTH][F8 ? UB : 1];
+  uint32_t bs4[DEPTH];  // F4: the slot's four scale bytes (its codes ride in b8[j][0])
   auto load = [&](int j, int c) {
-    if constexpr (F8) {
+    if constexpr (F4) {
+      b8[j][0] = load_w8<NT>(wrow4 + c * 1024);
+      bs4[j] = *reinterpret_cast<const uint32_t*>(srow4 + c * 64);
+    } else if constexpr (F8) {
 #pragma unroll
       for (int u = 0; u < UB; ++u) b8[j][u] = load_w8<NT>(wrow8 + (c * UB + u) * 1024);
     } else {
@@ -132,7 +147,10 @@ __device__ __forceinline__ void ks_body(
   // masked to zero by AND, and the loop runs as a steady part whose refills are always in range
   // plus a tail without loads (nchunks a multiple of DEPTH; other shapes keep the form below).
   auto load_nb = [&](int j, int c) {
-    if constexpr (F8) {
+    if constexpr (F4) {
+      b8[j][0] = load_w8<NT>(wrow4 + c * 1024);
+      bs4[j] = *reinterpret_cast<const uint32_t*>(srow4 + c * 64);
+    } else if constexpr (F8) {
 #pragma unroll
       for (int u = 0; u < UB; ++u) b8[j][u] = load_w8<NT>(wrow8 + (c * UB + u) * 1024);
     } else {
@@ -155,7 +173,9 @@ __device__ __forceinline__ void ks_body(
 #pragma unroll
     for (int u = 0; u < UNR; ++u) {
       s16x8 bu;
-      if constexpr (F8) {
+      if constexpr (F4) {
+        bu = f4x8_to_bf16(b8[j][0][u], (bs4[j] >> (8 * u)) & 0xffu);
+      } else if constexpr (F8) {
         const ks_u32x4 wv = b8[j][u >> 1];
         bu = (u & 1) ? f8x8_to_bf16(wv[2], wv[3]) : f8x8_to_bf16(wv[0], wv[1]);
       } else {
@@ -194,7 +214,9 @@ __device__ __forceinline__ void ks_body(
 #pragma unroll
         for (int u = 0; u < UNR; ++u) {
           s16x8 bu;
-          if constexpr (F8) {
+          if constexpr (F4) {
+            bu = f4x8_to_bf16(b8[j][0][u], (bs4[j] >> (8 * u)) & 0xffu);
+          } else if constexpr (F8) {
             const ks_u32x4 wv = b8[j][u >> 1];
             bu = (u & 1) ? f8x8_to_bf16(wv[2], wv[3]) : f8x8_to_bf16(wv[0], wv[1]);
           } else {

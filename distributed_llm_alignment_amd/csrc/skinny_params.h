@@ -20,12 +20,18 @@ struct KsFuse {
   float eps;             // NIN: RMSNorm epsilon (the norm weight is folded into W by the caller)
   const float* wscale;   // F8 weights: per weight-row dequantisation scale (y[:, n] *= wscale[n])
   int straight;          // 1: branch-free ring (ks_body): every slot refill issued unconditionally
+  const uint8_t* wblk;   // F4 weights: E8M0 block scales [N/16, K/128, 16, 4] (wscale unused)
 };
 
 enum class SkinnyW {
   kRowMajor,  // bf16 [N, K], row stride ldw
   kTiled,     // bf16 [N/16, K/32, 4, 16, 8] (skinny64.hip TW; skinny_glu_il: gate / up interleaved)
   kTiledF8,   // e4m3 [N/16, K/64, 64, 16 B] (skinny_ks.h F8) with per-row scales `wscale`
+  // MXFP4: e2m1 codes [N/16, K/128, 64 lanes, 16 B]: lane r + 16 q of k-tile kt holds row r's
+  // k = 128 kt + 32 s + 8 q + [0, 8) in bytes 4s .. 4s+3 (its B fragments of four consecutive MFMA
+  // k-steps), and E8M0 block scales `wblk` [N/16, K/128, 16 rows, 4]: byte s of row r scales k-step
+  // s of that k-tile. No per-row fp32 scale.
+  kTiledF4,
 };
 
 // y = x w^T and its decode-layer epilogues. M <= 16 on skinny.hip (64 on the plain / GLU
@@ -39,6 +45,7 @@ struct SkinnyParams {
   SkinnyW layout;
   int64_t ldw;      // kRowMajor only
   const float* wscale;  // kTiledF8: [N] fp32, in the weight's (tiled) row order
+  const uint8_t* wblk;  // kTiledF4: E8M0 block scales, in the weight's (tiled) row order
   bf16_t* y;        // [M, N], row stride ldy ([M, N/2] with glu_out)
   int64_t ldy;
   const bf16_t* res;  // [M, N] row stride ldr: y = bf16(bf16(x w^T) + res), row partials of y^2 into ssq_out
@@ -59,7 +66,7 @@ void launch_skinny_gemm(const SkinnyParams& p, hipStream_t st);
 // in-workgroup split-K skinny_ksplit_kernel: plain or glu_out on a row-major weight (M <= 64); with
 // `fused` the decode-layer form (res / ssq_in, every layout, M <= 16)
 void launch_skinny_ksplit(const SkinnyParams& p, bool fused, hipStream_t st);
-// skinny_glu_il_kernel: gate|up over the interleaved tiled weight (kTiled / kTiledF8), ssq_in given
+// skinny_glu_il_kernel: gate|up over the interleaved tiled weight (kTiled / kTiledF8 / kTiledF4), ssq_in given
 void launch_skinny_glu_il(const SkinnyParams& p, hipStream_t st);
 // m64_gemm_kernel, then m64_reduce_kernel with the res / ssq_in epilogue when m64_num_splits > 1
 int m64_num_splits(const SkinnyParams& p);
@@ -71,5 +78,8 @@ void launch_tile_weight(const bf16_t* w, int64_t ldw, const bf16_t* nw, bf16_t* 
                         bool glu_il, hipStream_t st);
 void launch_quant_tile_f8(const bf16_t* w, int64_t ldw, const bf16_t* nw, uint8_t* out, float* scale,
                           int N, int K, bool glu_il, hipStream_t st);
+// the MXFP4 copy (kTiledF4): codes [N K / 2 bytes] and block scales [N K / 32 bytes], one pass
+void launch_quant_tile_mxfp4(const bf16_t* w, int64_t ldw, const bf16_t* nw, uint8_t* codes, uint8_t* scales,
+                             int N, int K, bool glu_il, hipStream_t st);
 
 }  // namespace dla

@@ -583,6 +583,15 @@ def generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional[
     fp8 inference GEMMs (ops.fp8_inference_scope: e4m3 weights and activations, row
     scales, hipBLASLt fp8). Attention, norms and the KV cache stay bf16.
 
+    `weight_dtype="mxfp4"`: the same decode projections and the LM head stream an OCP MXFP4 copy
+    (e2m1 codes, one E8M0 scale byte per 32 k: 4.25 bits per weight, ops.decode.mxfp4_weights)
+    at <= 64 rows; the block scale is applied by the fp4 -> bf16 conversion in front of the bf16
+    MFMA. Longer prompt prefills and MoE expert weights stay bf16 (the fp8 prefill scope belongs
+    to "fp8" only). Off the GPU, or at shapes the kernels do not take, those <= 64-row projections
+    run on dequantize_mxfp4(quantize_mxfp4(W)). It composes with `kv_dtype`, `adapters="merged"`
+    (copies built from `merged()` weights), `return_logprobs`, `return_keep_mask` and
+    `num_return_sequences`.
+
     `adapters`: None (default) refuses a model with live LoRA adapters (ValueError). "merged"
     runs them: the fused decode layer (decode rows <= 64 on the GPU, captured or eager) reads
     derived weight copies built from m = bf16(W + (alpha / r) B A) (one HIP pass per projection
@@ -604,8 +613,8 @@ def generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional[
     with `group_attention=True` or a layer-split model it raises ValueError. The cache changes
     which tokens are sampled (`ppo.rollout_logprobs` measures and corrects that gap). "bf16" is
     the default call, kernel for kernel; any other value raises ValueError."""
-    if weight_dtype not in ("bf16", "fp8"):
-        raise ValueError(f"weight_dtype must be 'bf16' or 'fp8', got {weight_dtype!r}")
+    if weight_dtype not in ("bf16", "fp8", "mxfp4"):
+        raise ValueError(f"weight_dtype must be 'bf16', 'fp8' or 'mxfp4', got {weight_dtype!r}")
     _check_kv_dtype(kv_dtype)
     if kv_dtype == "fp8" and group_attention:
         raise ValueError("kv_dtype='fp8' does not support group_attention=True")
@@ -631,8 +640,12 @@ def generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional[
         lp_mode = _keep_mode(model, bool(return_logprobs), logprob_temperature, do_sample, temperature)
     else:
         lp_mode = _logp_mode(bool(return_logprobs), logprob_temperature, do_sample, temperature)
-    f8 = weight_dtype == "fp8" or ops.decode.fp8_enabled()
-    with ops.decode.fp8_weights(f8), ops.fp8_inference_scope(model, f8 and PREFILL_FP8), \
+    f4 = weight_dtype == "mxfp4" or (weight_dtype == "bf16" and ops.decode.mxfp4_enabled())
+    f8 = not f4 and (weight_dtype == "fp8" or ops.decode.fp8_enabled())
+    # (the two scopes exclude each other: the leading mxfp4_weights(False) clears a process-wide
+    # DLA_DECODE_MXFP4=1 first, so that an explicit weight_dtype="fp8" can enter its scope)
+    with ops.decode.mxfp4_weights(False), ops.decode.fp8_weights(f8), ops.decode.mxfp4_weights(f4, model), \
+            ops.fp8_inference_scope(model, f8 and PREFILL_FP8), \
             ops.decode.lora_merged(live and adapters == "merged"):
         return _generate(model, input_ids, attention_mask, max_new_tokens, do_sample, temperature, top_p,
                          top_k, eos_token_id, pad_token_id, generator, return_mask, use_graph, seed, G,
@@ -695,7 +708,8 @@ def _generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional
     if GRAPH_REUSE and use_graph is not False and max_new_tokens > 2 and input_ids.is_cuda \
             and _graph_capable(model):
         reuse_key = (B, Tp, max_new_tokens, kv_start is None, greedy, float(temperature), int(top_k),
-                     float(top_p), eos, pad, input_ids.device, _weights_key(model), ops.decode.fp8_enabled(),
+                     float(top_p), eos, pad, input_ids.device, _weights_key(model),
+                     ops.decode.fp8_enabled() + 2 * ops.decode.mxfp4_enabled(),
                      G if group_attention else 0,  # the grouped ops capture G (and Tp) as host constants
                      return_logprobs,  # the captured step holds one sampler op or the other
                      # adapter mode: the captured step of a model with live adapters holds the first

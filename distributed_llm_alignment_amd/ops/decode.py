@@ -629,6 +629,8 @@ class fp8_weights:
         self.enabled = bool(enabled)
 
     def __enter__(self):
+        if self.enabled and _MXFP4[0]:
+            raise RuntimeError("fp8_weights inside mxfp4_weights: one decode weight format at a time")
         self.prev = _FP8[0]
         _FP8[0] = self.enabled
         return self
@@ -765,7 +767,196 @@ def head_f8(x: torch.Tensor, w: torch.Tensor) -> Optional[torch.Tensor]:
     return y.view(*x.shape[:-1], w.shape[0])
 
 
+# ---------------------------------------------------------------------------------------------
+# Weight-only MXFP4 decode (opt-in, OCP microscaling `mxfp4`): the same four weight streams and the
+# LM head read e2m1 codes with one E8M0 scale byte per 32 consecutive k of a weight row, 4.25 bits
+# per weight (csrc/skinny_ks.h F4, skinny_glu_il_kernel F4, csrc/skinny64.hip F4). There is no
+# per-row fp32 scale: v_cvt_scalef32_pk_bf16_fp4 applies the block scale while converting, so the
+# bf16 MFMA sees the exact dequantised weights. For RLHF rollouts (`generate(...,
+# weight_dtype="mxfp4")`, `ppo.rollout_weight_dtype`), as fp8: the copy only changes which tokens
+# are sampled. Mutually exclusive with fp8_weights. DLA_DECODE_MXFP4=1 turns it on process-wide.
+_MXFP4 = [os.environ.get("DLA_DECODE_MXFP4", "0") == "1"]
+if _MXFP4[0] and _FP8[0]:
+    raise RuntimeError("DLA_DECODE_MXFP4=1 and DLA_DECODE_FP8=1 are mutually exclusive")
+
+
+class mxfp4_weights:
+    """Context manager: decode projections on MXFP4 weight copies inside the block (not together
+    with `fp8_weights`). `model`: its qkv / o / gate|up / down and LM-head weights are marked for the
+    block, so that off the GPU their <= 64-row projections run the CPU formula (`mxfp4_ref_weight`;
+    MoE experts and routers are never marked)."""
+
+    def __init__(self, enabled: bool = True, model=None):
+        self.enabled, self.model, self.marked = bool(enabled), model, []
+
+    def __enter__(self):
+        if self.enabled and _FP8[0]:
+            raise RuntimeError("mxfp4_weights inside fp8_weights: one decode weight format at a time")
+        self.prev = _MXFP4[0]
+        _MXFP4[0] = self.enabled
+        if self.enabled and self.model is not None:
+            ws = [getattr(self.model, "head_weight", None)]
+            for layer in getattr(self.model, "layers", []):
+                at, mlp = getattr(layer, "attn", None), getattr(layer, "mlp", None)
+                ws += [getattr(at, "qkv_proj", None), getattr(at, "o_proj", None),
+                       getattr(mlp, "up_proj", None), getattr(mlp, "down_proj", None)]
+            for w in ws:
+                if isinstance(w, torch.Tensor) and w.dim() == 2 and not getattr(w, "_dla_mx", False):
+                    w._dla_mx = True
+                    self.marked.append(w)
+        return self
+
+    def __exit__(self, *exc):
+        _MXFP4[0] = self.prev
+        for w in self.marked:
+            w.__dict__.pop("_dla_mx", None)
+        self.marked = []
+        return False
+
+
+def mxfp4_enabled() -> bool:
+    return _MXFP4[0]
+
+
+E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)  # code & 7; code & 8 is the sign
+
+
+def quantize_mxfp4(src: torch.Tensor):
+    """src [N, K] (K % 32 == 0) -> (codes uint8 [N, K/2], scales uint8 [N, K/32]), the formula of
+    record of csrc/skinny64.hip quant_tile_mxfp4_kernel (bit-equal):
+
+        block = 32 consecutive k of one row, amax = max |x| over it
+        amax > 0:  e = clamp(floor(log2(amax)) - 2, -120, 120)   scale byte b = e + 127 (E8M0: 2^(b - 127))
+        amax == 0: b = 127, codes 0
+        code = e2m1_rne(clamp(x * 2^-e, -6, 6))                   ties to the even code, (6, 8) -> 6
+
+    floor(log2 .) comes from frexp, not a float log2. The clamp on e keeps 2^e and 2^-e normal fp32
+    and every dequantised value (0.5 .. 6) * 2^e a normal bf16, so no denormal mode of any
+    instruction can matter. x * 2^-e is a power-of-two product, exact in fp32, so there is no
+    rounding slack: GPU and CPU give equal bytes. A negative x that rounds to zero keeps its sign
+    bit (code 8 = -0). Nibble order: byte j of a row holds element 2j in its LOW nibble and 2j + 1
+    in its high nibble, the order the conversion instruction's byte select decodes."""
+    a = src.detach().float()
+    N, K = a.shape
+    blk = a.view(N, K // 32, 32)
+    amax = blk.abs().amax(dim=2)
+    _, ex = torch.frexp(amax)  # amax = m 2^ex, m in [0.5, 1): floor(log2 amax) = ex - 1
+    e = (ex.to(torch.int32) - 3).clamp_(-120, 120)
+    e = torch.where(amax > 0, e, torch.zeros_like(e))
+    v = blk.abs() * torch.ldexp(torch.ones_like(amax), -e).unsqueeze(-1)
+    code = ((v > 0.25).to(torch.uint8) + (v >= 0.75) + (v > 1.25) + (v >= 1.75) + (v > 2.5) + (v >= 3.5)
+            + (v > 5.0)).to(torch.uint8)
+    code = (code | ((blk < 0).to(torch.uint8) << 3)).view(N, K // 2, 2)
+    return (code[..., 0] | (code[..., 1] << 4)).contiguous(), (e + 127).to(torch.uint8).contiguous()
+
+
+def dequantize_mxfp4(codes: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+    """(codes uint8 [N, K/2], scales uint8 [N, K/32]) -> float32 [N, K]: e2m1(code) * 2^(b - 127),
+    exact in bf16."""
+    N = codes.shape[0]
+    c = torch.stack((codes & 15, codes >> 4), dim=-1).view(N, -1).long()
+    mag = torch.tensor(E2M1_VALUES, dtype=torch.float32, device=codes.device)[c & 7]
+    val = torch.where((c & 8) != 0, -mag, mag).view(N, -1, 32)
+    return torch.ldexp(val, (scales.to(torch.int32) - 127).unsqueeze(-1)).view(N, -1)
+
+
+def tile_mxfp4(codes: torch.Tensor, scales: torch.Tensor):
+    """(codes [N, K/2], scales [N, K/32]) -> the SkinnyW::kTiledF4 pair: codes [N/16, K/128, 64, 16],
+    lane r + 16 q of k-tile kt holding row r's k = 128 kt + 32 s + 8 q + [0, 8) in bytes 4s .. 4s+3,
+    and scales [N/16, K/128, 16, 4], byte s of row r the scale of that k-tile's block s."""
+    N, K = codes.shape[0], codes.shape[1] * 2
+    t = (codes.view(N // 16, 16, K // 128, 4, 4, 4).permute(0, 2, 4, 1, 3, 5)  # [t, kt, q, r, s, 4 B]
+         .reshape(N // 16, K // 128, 64, 16).contiguous())
+    sc = scales.view(N // 16, 16, K // 128, 4).permute(0, 2, 1, 3).contiguous()
+    return t, sc
+
+
+def mxfp4_tiled_weight(w: torch.Tensor, norm_w: Optional[torch.Tensor] = None, glu_il: bool = False, lora=None):
+    """Cached (e2m1 tiled codes, E8M0 block scales) of W (o norm_w folded in as the bf16 product
+    the e4m3 copy forms; glu_il: gate / up rows interleaved 8 + 8 per 16-row tile), refreshed in
+    place when W or norm_w moved (as fp8_tiled_weight). `lora`: of W + s B A instead -- `merged()`
+    into a temporary, then the quantiser (the composition path; there is no fused merge kernel)."""
+    N, K = w.shape
+    lora = lora_triple(lora)
+    w0 = w
+
+    def make(prev):
+        w = w0
+        if lora is not None:
+            MERGE_CALLS["composition"] += 1
+            w = merged(w, lora)
+        if _ext.use_native(w) and w.dtype == torch.bfloat16 and w.stride(-1) == 1 and w.stride(0) % 8 == 0:
+            # one HIP pass (csrc/skinny64.hip quant_tile_mxfp4_kernel), in place when refreshing: a
+            # captured decode graph keeps reading the same storage
+            t, sc = prev if prev is not None else (
+                torch.empty((N // 16, K // 128, 64, 16), dtype=torch.uint8, device=w.device),
+                torch.empty((N // 16, K // 128, 16, 4), dtype=torch.uint8, device=w.device))
+            _ext.require().quant_tile_mxfp4(w.detach(), norm_w.detach().contiguous() if norm_w is not None else None,
+                                            t, sc, bool(glu_il))
+            return (t, sc)
+        src = w.detach() if norm_w is None else w.detach() * norm_w.detach().view(1, -1)
+        if glu_il:
+            src = _glu_interleave(src)
+        t, sc = tile_mxfp4(*quantize_mxfp4(src))
+        if prev is not None:
+            prev[0].copy_(t)
+            prev[1].copy_(sc)
+            return prev
+        return (t, sc)
+
+    attr = "_dla_f4_g" if glu_il else ("_dla_f4_n" if norm_w is not None else "_dla_f4")
+    key = (_wkey(w), _wkey(norm_w) if norm_w is not None else None)
+    return _cached(w, attr, key if lora is None else key + (_lora_key(lora),), make)
+
+
+def _f4_ok(rows: int, w: torch.Tensor) -> bool:
+    """mxfp4 mode and a shape the MXFP4 kernels take: <= 16 rows csrc/skinny_ks.h F4 /
+    skinny_glu_il F4, 17..64 rows csrc/skinny64.hip F4."""
+    if not _MXFP4[0]:
+        return False
+    if rows <= 16:
+        return w.shape[0] % 32 == 0 and w.shape[1] % 1024 == 0
+    return DECODE_M64 and rows <= 64 and w.shape[0] % 128 == 0 and w.shape[1] % 256 == 0
+
+
+def head_f4(x: torch.Tensor, w: torch.Tensor) -> Optional[torch.Tensor]:
+    """LM-head logits x @ w^T on the MXFP4 copy of w (decode rows, mxfp4 mode), else None."""
+    if not (_MXFP4[0] and x.is_cuda and _ext.use_native(x)) or torch.is_grad_enabled() and x.requires_grad:
+        return None
+    rows = x.numel() // x.shape[-1]
+    if not (1 <= rows <= 64 and _f4_ok(rows, w) and x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16):
+        return None
+    w4, sb = mxfp4_tiled_weight(w)
+    if rows > 16:
+        y, _ = _ext.require().skinny64_f4(_rows(x), w4, sb, None, None, 0.0, False)
+    else:
+        y, _ = _ext.require().skinny_fused_f4(_rows(x), w4, sb, None, None, 0.0)
+    return y.view(*x.shape[:-1], w.shape[0])
+
+
+def mxfp4_ref_weight(x: torch.Tensor, w: torch.Tensor) -> Optional[torch.Tensor]:
+    """The CPU formula of the mxfp4 scope: dequantize_mxfp4(quantize_mxfp4(W)) in W's dtype, for a
+    no-grad projection of <= 64 rows off the GPU on a weight that `mxfp4_weights(model=...)` marked;
+    cached on W like the device copies. None when the call is not such a projection. It quantises
+    W itself, also for qkv and gate|up, where the device copies quantise bf16(W * norm_w): off the
+    GPU the norm stays a separate step, so the two agree exactly only while the norm weights are
+    powers of two (1.0 at initialisation) and to quantisation error otherwise."""
+    if (not _MXFP4[0] or not getattr(w, "_dla_mx", False) or torch.is_grad_enabled() or _ext.use_native(x)
+            or w.shape[1] % 32):
+        return None
+    rows = x.numel() // x.shape[-1] if x.dim() else 0
+    if not 1 <= rows <= 64:
+        return None
+
+    def make(prev):
+        d = dequantize_mxfp4(*quantize_mxfp4(w)).to(w.dtype)
+        return d if prev is None else prev.copy_(d)
+
+    return _cached(w, "_dla_f4_ref", _wkey(w), make)
+
+
 DERIVED_ATTRS = ("_dla_fold", "_dla_fold_t", "_dla_fold_g", "_dla_tile", "_dla_f8", "_dla_f8_n", "_dla_f8_g",
+                 "_dla_f4", "_dla_f4_n", "_dla_f4_g", "_dla_f4_ref",
                  "_dla_fp8")  # (the last: ops.moe.fp8_weight, the fp8 prefill GEMMs' weight copy)
 
 
@@ -796,6 +987,8 @@ def refresh_folded_weights(model) -> None:
     hw = getattr(model, "head_weight", None)
     if isinstance(hw, torch.Tensor) and getattr(hw, "_dla_f8", None) is not None:
         fp8_tiled_weight(hw)
+    if isinstance(hw, torch.Tensor) and getattr(hw, "_dla_f4", None) is not None:
+        mxfp4_tiled_weight(hw)
     def active(owner, name):  # the projection's adapter if attached and switched on
         ad = getattr(owner, name, None)
         return ad if (ad is not None and ad.enabled) else None
@@ -817,12 +1010,18 @@ def refresh_folded_weights(model) -> None:
                 fp8_tiled_weight(w, nw, lora=ad)
             if getattr(w, "_dla_f8_g", None) is not None:
                 fp8_tiled_weight(w, nw, glu_il=True, lora=ad)
+            if getattr(w, "_dla_f4_n", None) is not None:
+                mxfp4_tiled_weight(w, nw, lora=ad)
+            if getattr(w, "_dla_f4_g", None) is not None:
+                mxfp4_tiled_weight(w, nw, glu_il=True, lora=ad)
         for w, ad in ((getattr(layer.attn, "o_proj", None), active(layer.attn, "lora_o")),
                       (getattr(layer.mlp, "down_proj", None), active(layer.mlp, "lora_down"))):
             if w is not None and getattr(w, "_dla_tile", None) is not None:
                 tiled_weight(w, lora=ad)
             if w is not None and getattr(w, "_dla_f8", None) is not None:
                 fp8_tiled_weight(w, lora=ad)
+            if w is not None and getattr(w, "_dla_f4", None) is not None:
+                mxfp4_tiled_weight(w, lora=ad)
 
 
 def skinny_residual(x: torch.Tensor, w: torch.Tensor, res: torch.Tensor, lora=None):
@@ -837,6 +1036,13 @@ def skinny_residual(x: torch.Tensor, w: torch.Tensor, res: torch.Tensor, lora=No
             s, ssq = _ext.require().skinny64_f8(x2, w8, sc, _rows(res), None, 0.0, False)
         else:
             s, ssq = _ext.require().skinny_fused_f8(x2, w8, sc, _rows(res), None, 0.0)
+        return s.view(*res.shape[:-1], w.shape[0]), ssq
+    if _f4_ok(x2.shape[0], w):
+        w4, sb = mxfp4_tiled_weight(w, lora=lora)
+        if x2.shape[0] > 16:
+            s, ssq = _ext.require().skinny64_f4(x2, w4, sb, _rows(res), None, 0.0, False)
+        else:
+            s, ssq = _ext.require().skinny_fused_f4(x2, w4, sb, _rows(res), None, 0.0)
         return s.view(*res.shape[:-1], w.shape[0]), ssq
     wk = tiled_weight(w, lora=lora) if DECODE_TILED >= 2 else w
     if x2.shape[0] > 16:
@@ -865,6 +1071,19 @@ def skinny_normed(s: torch.Tensor, ssq: torch.Tensor, norm_w: torch.Tensor, eps:
             return m.view(*s.shape[:-1], m.shape[-1])
         w8, sc = fp8_tiled_weight(w, norm_w, lora=lora)
         y, _ = _ext.require().skinny_fused_f8(s2, w8, sc, None, ssq, float(eps))
+        return y.view(*s.shape[:-1], y.shape[-1])
+    if _f4_ok(s2.shape[0], w) and s2.shape[0] > 16:
+        # 17..64 rows: gate|up in the plain [gate; up] row order (the m64 GLU epilogue pairs them)
+        w4, sb = mxfp4_tiled_weight(w, norm_w, lora=lora)
+        y, _ = _ext.require().skinny64_f4(s2, w4, sb, None, ssq, float(eps), bool(glu))
+        return y.view(*s.shape[:-1], y.shape[-1])
+    if _f4_ok(s2.shape[0], w):
+        if glu:
+            w4, sb = mxfp4_tiled_weight(w, norm_w, glu_il=True, lora=lora)
+            m = _ext.require().skinny_glu_il_f4(s2, w4, sb, ssq, float(eps))
+            return m.view(*s.shape[:-1], m.shape[-1])
+        w4, sb = mxfp4_tiled_weight(w, norm_w, lora=lora)
+        y, _ = _ext.require().skinny_fused_f4(s2, w4, sb, None, ssq, float(eps))
         return y.view(*s.shape[:-1], y.shape[-1])
     if (glu and DECODE_GLU_IL and DECODE_TILED >= 1 and s2.shape[0] <= 16 and w.shape[0] % 32 == 0
             and w.shape[1] % 512 == 0):

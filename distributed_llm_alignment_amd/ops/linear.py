@@ -271,8 +271,21 @@ class _LinearAddFn(torch.autograd.Function):
         return dx, dw, (dy if ctx.needs_input_grad[2] else None)
 
 
+def _mxfp4_ref(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
+    """Inside `ops.decode.mxfp4_weights(model=...)` and off the GPU: the marked projection weights'
+    dequantised MXFP4 values for a no-grad call of <= 64 rows (the CPU formula of record)."""
+    if getattr(weight, "_dla_mx", False):
+        from . import decode
+
+        wq = decode.mxfp4_ref_weight(x, weight)
+        if wq is not None:
+            return wq
+    return weight
+
+
 def linear_add(x: torch.Tensor, weight: torch.Tensor, resid: torch.Tensor) -> torch.Tensor:
     """resid + linear(x, weight), the add inside the GEMM (bias-free projections)."""
+    weight = _mxfp4_ref(x, weight)
     if fp8_inference_ok(x, weight, None):
         return fp8_linear_frozen(x, weight).add_(resid)
     if torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad or resid.requires_grad):
@@ -282,6 +295,7 @@ def linear_add(x: torch.Tensor, weight: torch.Tensor, resid: torch.Tensor) -> to
 
 
 def linear(x: torch.Tensor, weight: torch.Tensor, bias=None) -> torch.Tensor:
+    weight = _mxfp4_ref(x, weight)
     # (fp8 inference first: it needs grad disabled, so a training forward never takes it; a
     # trainable policy's no-grad rollout prefill inside fp8_inference_scope does)
     if fp8_inference_ok(x, weight, bias):

@@ -270,6 +270,17 @@ def rollout_kv_dtype(ppo: Dict) -> str:
     return v
 
 
+def rollout_weight_dtype(ppo: Dict) -> str:
+    """`ppo.rollout_weight_dtype: bf16 | fp8 | mxfp4` (default bf16): the decode weight streams of the
+    rollout generation (`generate(weight_dtype=)`; fp8 = e4m3 with per-row scales, mxfp4 = OCP e2m1
+    codes with E8M0 block scales). A lossy copy changes the policy that samples:
+    `ppo.rollout_logprobs` measures and corrects that gap. An unknown value raises at start-up."""
+    v = ppo.get("rollout_weight_dtype", "bf16")
+    if v not in ("bf16", "fp8", "mxfp4"):
+        raise ValueError(f"ppo.rollout_weight_dtype must be bf16|fp8|mxfp4, got {v!r}")
+    return v
+
+
 def share_prefix_update(ppo: Dict, algo: str, hardware: Optional[Dict] = None, world: int = 1) -> bool:
     """`ppo.share_prefix_update` (default false): the GRPO update and stats forwards run on the
     prefix-shared layout, every group's prompt computed once (`shared_prefix_pack`). Every
@@ -428,6 +439,7 @@ def main(argv=None) -> int:
     keep_on = keep_sampling_mask(ppo, algo, ctx.hw, policy.model.cfg.vocab_size)  # likewise
     share_prefix_update(ppo, algo, ctx.hw, ctx.dp_size)  # likewise
     kv_dtype = rollout_kv_dtype(ppo)  # likewise
+    weight_dtype = rollout_weight_dtype(ppo)  # likewise
 
     # reward inputs built on the device when the reward tokenizer equals the policy's (no
     # decode / re-tokenise round trip through the host; training/handoff.py), else the
@@ -449,7 +461,7 @@ def main(argv=None) -> int:
                                     top_p=gen.get("top_p", 1.0), top_k=gen.get("top_k", 0),
                                     pad_token_id=tok.pad_token_id, eos_token_id=getattr(tok, "eos_token_id", None),
                                     generator=gen_g, return_mask=True,
-                                    weight_dtype=ppo.get("rollout_weight_dtype", "bf16"), kv_dtype=kv_dtype,
+                                    weight_dtype=weight_dtype, kv_dtype=kv_dtype,
                                     num_return_sequences=group, share_prefill=bool(ppo.get("share_prefill", True)),
                                     group_attention=bool(ppo.get("group_attention", False)),
                                     return_logprobs=want_logp,

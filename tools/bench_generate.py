@@ -23,7 +23,7 @@ def main() -> int:
     ap.add_argument("--prompt", type=int, default=1024)
     ap.add_argument("--new", type=int, default=256)
     ap.add_argument("--modes", default="eager,graph")
-    ap.add_argument("--weight-dtype", choices=("bf16", "fp8"), default="bf16",
+    ap.add_argument("--weight-dtype", choices=("bf16", "fp8", "mxfp4"), default="bf16",
                     help="decode weight streams (generate(weight_dtype=...))")
     ap.add_argument("--kv-dtype", choices=("bf16", "fp8"), default="bf16",
                     help="KV cache format (generate(kv_dtype=...); fp8 = e4m3 codes + row scales)")

@@ -77,7 +77,7 @@ def main() -> int:
                     help="ppo / grpo: entropy bonus (ppo.entropy_coef); the entropy comes out of the LM-head kernels")
     ap.add_argument("--log-entropy", action="store_true",
                     help="ppo / grpo: compute and report the policy entropy without a bonus (ppo.log_entropy)")
-    ap.add_argument("--rollout-dtype", choices=("bf16", "fp8"), default="bf16",
+    ap.add_argument("--rollout-dtype", choices=("bf16", "fp8", "mxfp4"), default="bf16",
                     help="decode weight streams of the rollout generation (ppo.rollout_weight_dtype)")
     ap.add_argument("--kv-dtype", choices=("bf16", "fp8"), default="bf16",
                     help="KV cache of the rollout generation (ppo.rollout_kv_dtype; fp8 = e4m3 codes + row scales)")
