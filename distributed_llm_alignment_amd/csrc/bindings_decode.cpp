@@ -223,29 +223,43 @@ std::tuple<at::Tensor, at::Tensor> skinny64_f4(const at::Tensor& x, const at::Te
   return m64_step(p, x, res, ssq_in, eps, glu);
 }
 
+// Source of the weight re-layout passes (tile_weight, quant_tile_f8, quant_tile_mxfp4): w bf16
+// [N, K] with unit inner stride and 16-byte aligned rows, and the optional RMSNorm weight nw bf16
+// [K] that the pass folds into w's input columns, contiguous, on w's device and 16-byte aligned
+// (skinny64.hip fold_norm8 reads it with the same 16-byte loads as w)
+struct TileSrc {
+  int64_t N, K;
+  const bf16_t* nw;
+};
+
+static TileSrc tile_src(const at::Tensor& w, const c10::optional<at::Tensor>& nw) {
+  check_bf16(w, "w");
+  TORCH_CHECK(w.dim() == 2 && w.stride(1) == 1 && w.stride(0) % 8 == 0, "w [N, K], unit inner stride");
+  TileSrc s{w.size(0), w.size(1), nullptr};
+  TORCH_CHECK(s.N < (1ll << 30) && s.K < (1ll << 30), "shape too large");
+  check_aligned16(w, "w");
+  if (nw.has_value() && nw->defined()) {
+    check_bf16(*nw, "nw");
+    TORCH_CHECK(nw->dim() == 1 && nw->size(0) == s.K && nw->is_contiguous(), "nw [K] contiguous");
+    check_aligned16(*nw, "nw");
+    same_device(w, *nw);
+    s.nw = cbp(*nw);
+  }
+  return s;
+}
+
 // out <- w [N, K] in the tiled decode layout [N/16, K/32, 4, 16, 8] (nw given: bf16(w * nw), the
 // RMSNorm weight folded into the input columns)
 void tile_weight(const at::Tensor& w, const c10::optional<at::Tensor>& nw, at::Tensor& out, bool glu_il) {
-  check_bf16(w, "w");
+  const auto [N, K, np] = tile_src(w, nw);
   check_bf16(out, "out");
-  TORCH_CHECK(w.dim() == 2 && w.stride(1) == 1 && w.stride(0) % 8 == 0, "w [N, K], unit inner stride");
-  const int64_t N = w.size(0), K = w.size(1);
-  TORCH_CHECK(N % 16 == 0 && K % 32 == 0 && N < (1ll << 30) && K < (1ll << 30), "N % 16 == 0, K % 32 == 0");
+  TORCH_CHECK(N % 16 == 0 && K % 32 == 0, "N % 16 == 0, K % 32 == 0");
   TORCH_CHECK(!glu_il || N % 32 == 0, "glu_il: N = 2F, F % 16 == 0");
   TORCH_CHECK(out.dim() == 5 && out.size(0) == N / 16 && out.size(1) == K / 32 && out.size(2) == 4 &&
                   out.size(3) == 16 && out.size(4) == 8 && out.is_contiguous(),
               "out [N/16, K/32, 4, 16, 8] contiguous");
-  check_aligned16(w, "w");
   check_aligned16(out, "out");
   same_device(w, out);
-  const bf16_t* np = nullptr;
-  if (nw.has_value()) {
-    check_bf16(*nw, "nw");
-    TORCH_CHECK(nw->dim() == 1 && nw->size(0) == K && nw->is_contiguous(), "nw [K]");
-    check_aligned16(*nw, "nw");
-    same_device(w, *nw);
-    np = cbp(*nw);
-  }
   c10::hip::HIPGuardMasqueradingAsCUDA g(w.device());
   launch_tile_weight(cbp(w), w.stride(0), np, bp(out), (int)N, (int)K, glu_il, cur_stream(w));
 }
@@ -254,26 +268,16 @@ void tile_weight(const at::Tensor& w, const c10::optional<at::Tensor>& nw, at::T
 // and scale fp32 [N] (per tiled row), in place (a captured decode graph keeps reading them)
 void quant_tile_f8(const at::Tensor& w, const c10::optional<at::Tensor>& nw, at::Tensor& out8, at::Tensor& scale,
                    bool glu_il) {
-  check_bf16(w, "w");
-  TORCH_CHECK(w.dim() == 2 && w.stride(1) == 1 && w.stride(0) % 8 == 0, "w [N, K], unit inner stride");
-  const int64_t N = w.size(0), K = w.size(1);
-  TORCH_CHECK(N % 32 == 0 && K % 64 == 0 && N < (1ll << 30) && K < (1ll << 30), "N % 32 == 0, K % 64 == 0");
+  const auto [N, K, np] = tile_src(w, nw);
+  TORCH_CHECK(N % 32 == 0 && K % 64 == 0, "N % 32 == 0, K % 64 == 0");
   check_cuda(out8, "out8");
   TORCH_CHECK(out8.scalar_type() == at::kByte && out8.is_contiguous() && out8.numel() == N * K,
               "out8 uint8 contiguous, N * K bytes");
   check_cuda(scale, "scale");
   TORCH_CHECK(scale.scalar_type() == at::kFloat && scale.is_contiguous() && scale.numel() == N, "scale fp32 [N]");
-  check_aligned16(w, "w");
   check_aligned16(out8, "out8");
   same_device(w, out8);
   same_device(w, scale);
-  const bf16_t* np = nullptr;
-  if (nw.has_value() && nw->defined()) {
-    check_bf16(*nw, "nw");
-    TORCH_CHECK(nw->dim() == 1 && nw->size(0) == K && nw->is_contiguous(), "nw [K] contiguous");
-    same_device(w, *nw);
-    np = cbp(*nw);
-  }
   c10::hip::HIPGuardMasqueradingAsCUDA g(w.device());
   launch_quant_tile_f8(cbp(w), w.stride(0), np, out8.data_ptr<uint8_t>(), scale.data_ptr<float>(), (int)N, (int)K,
                        glu_il, cur_stream(w));
@@ -284,11 +288,8 @@ void quant_tile_f8(const at::Tensor& w, const c10::optional<at::Tensor>& nw, at:
 // keeps reading them); one launch, no host sync
 void quant_tile_mxfp4(const at::Tensor& w, const c10::optional<at::Tensor>& nw, at::Tensor& codes,
                       at::Tensor& scales, bool glu_il) {
-  check_bf16(w, "w");
-  TORCH_CHECK(w.dim() == 2 && w.stride(1) == 1 && w.stride(0) % 8 == 0, "w [N, K], unit inner stride");
-  const int64_t N = w.size(0), K = w.size(1);
-  TORCH_CHECK(N >= 16 && N % 16 == 0 && K >= 128 && K % 128 == 0 && N < (1ll << 30) && K < (1ll << 30),
-              "N % 16 == 0, K % 128 == 0");
+  const auto [N, K, np] = tile_src(w, nw);
+  TORCH_CHECK(N >= 16 && N % 16 == 0 && K >= 128 && K % 128 == 0, "N % 16 == 0, K % 128 == 0");
   TORCH_CHECK(!glu_il || N % 32 == 0, "glu_il: N = 2F, F % 16 == 0");
   check_cuda(codes, "codes");
   TORCH_CHECK(codes.scalar_type() == at::kByte && codes.is_contiguous() && codes.numel() == N * K / 2,
@@ -296,19 +297,10 @@ void quant_tile_mxfp4(const at::Tensor& w, const c10::optional<at::Tensor>& nw, 
   check_cuda(scales, "scales");
   TORCH_CHECK(scales.scalar_type() == at::kByte && scales.is_contiguous() && scales.numel() == N * K / 32,
               "scales uint8 contiguous, N * K / 32 bytes");
-  check_aligned16(w, "w");
   check_aligned16(codes, "codes");
   check_aligned16(scales, "scales");
   same_device(w, codes);
   same_device(w, scales);
-  const bf16_t* np = nullptr;
-  if (nw.has_value() && nw->defined()) {
-    check_bf16(*nw, "nw");
-    TORCH_CHECK(nw->dim() == 1 && nw->size(0) == K && nw->is_contiguous(), "nw [K] contiguous");
-    check_aligned16(*nw, "nw");
-    same_device(w, *nw);
-    np = cbp(*nw);
-  }
   c10::hip::HIPGuardMasqueradingAsCUDA g(w.device());
   launch_quant_tile_mxfp4(cbp(w), w.stride(0), np, codes.data_ptr<uint8_t>(), scales.data_ptr<uint8_t>(), (int)N,
                           (int)K, glu_il, cur_stream(w));

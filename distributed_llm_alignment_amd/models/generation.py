@@ -642,9 +642,7 @@ def generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional[
         lp_mode = _logp_mode(bool(return_logprobs), logprob_temperature, do_sample, temperature)
     f4 = weight_dtype == "mxfp4" or (weight_dtype == "bf16" and ops.decode.mxfp4_enabled())
     f8 = not f4 and (weight_dtype == "fp8" or ops.decode.fp8_enabled())
-    # (the two scopes exclude each other: the leading mxfp4_weights(False) clears a process-wide
-    # DLA_DECODE_MXFP4=1 first, so that an explicit weight_dtype="fp8" can enter its scope)
-    with ops.decode.mxfp4_weights(False), ops.decode.fp8_weights(f8), ops.decode.mxfp4_weights(f4, model), \
+    with ops.decode.weight_format("mxfp4" if f4 else "fp8" if f8 else None, model), \
             ops.fp8_inference_scope(model, f8 and PREFILL_FP8), \
             ops.decode.lora_merged(live and adapters == "merged"):
         return _generate(model, input_ids, attention_mask, max_new_tokens, do_sample, temperature, top_p,

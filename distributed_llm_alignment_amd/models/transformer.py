@@ -693,9 +693,7 @@ class CausalLM(nn.Module):
     def logits(self, hidden: torch.Tensor) -> torch.Tensor:
         lg = None
         if self.lm_head_bias is None and self.vocab_parallel is None:
-            lg = ops.decode.head_f8(hidden, self.head_weight)  # fp8 decode mode only
-            if lg is None:
-                lg = ops.decode.head_f4(hidden, self.head_weight)  # mxfp4 decode mode only
+            lg = ops.decode.quant_head(hidden, self.head_weight)  # fp8 / mxfp4 decode mode only
             if lg is None:  # mxfp4 mode off the GPU: the CPU formula
                 wq = ops.decode.mxfp4_ref_weight(hidden, self.head_weight)
                 lg = F.linear(hidden, wq) if wq is not None else None

@@ -10,7 +10,8 @@ from __future__ import annotations
 
 import math
 import os
-from typing import Optional
+from dataclasses import dataclass
+from typing import Callable, Optional
 
 import torch
 
@@ -612,36 +613,22 @@ def tiled_weight(w: torch.Tensor, lora=None) -> torch.Tensor:
 
 
 # ---------------------------------------------------------------------------------------------
-# Weight-only fp8 decode (opt-in): the fused decode layer's four weight streams (qkv, o, gate|up,
-# down: 74 % of the bytes per token at Llama-3-8B B=8) read an e4m3 copy with one fp32 scale per
-# weight row (amax / 448), half the bf16 bytes; activations, the KV cache, the LM head and every
-# accumulation stay bf16 / fp32 (csrc/skinny_ks.h F8, csrc/skinny.hip skinny_glu_il_kernel F8). For
-# RLHF rollouts (`generate(..., weight_dtype="fp8")`, `ppo.rollout_weight_dtype`): the update's
-# old-policy log-probs are recomputed in bf16 on the sampled tokens (training/train_rlhf.py), so
-# the fp8 copy only changes which tokens are sampled. DLA_DECODE_FP8=1 turns it on process-wide.
-_FP8 = [os.environ.get("DLA_DECODE_FP8", "0") == "1"]
-
-
-class fp8_weights:
-    """Context manager: decode projections on fp8 weight copies inside the block."""
-
-    def __init__(self, enabled: bool = True):
-        self.enabled = bool(enabled)
-
-    def __enter__(self):
-        if self.enabled and _MXFP4[0]:
-            raise RuntimeError("fp8_weights inside mxfp4_weights: one decode weight format at a time")
-        self.prev = _FP8[0]
-        _FP8[0] = self.enabled
-        return self
-
-    def __exit__(self, *exc):
-        _FP8[0] = self.prev
-        return False
-
-
-def fp8_enabled() -> bool:
-    return _FP8[0]
+# Weight-only quantised decode (opt-in, one format at a time): the fused decode layer's four weight
+# streams (qkv, o, gate|up, down: 74 % of the bytes per token at Llama-3-8B B=8) and the LM head
+# read a quantised copy of the weight at <= 64 rows; activations, the KV cache and every
+# accumulation stay bf16 / fp32. For RLHF rollouts (`generate(..., weight_dtype=...)`,
+# `ppo.rollout_weight_dtype`): the update's old-policy log-probs are recomputed in bf16 on the
+# sampled tokens (training/train_rlhf.py), so the copy only changes which tokens are sampled. The
+# formats (`_WeightFormat` below states what the code needs of each):
+#
+#   fp8    e4m3 bytes tiled [N/16, K/64, 64, 16] and one fp32 scale per weight row (amax / 448), [N]:
+#          half the bf16 bytes; the kernels scale the row's accumulator (csrc/skinny_ks.h F8,
+#          csrc/skinny.hip skinny_glu_il_kernel F8, csrc/skinny64.hip F8). DLA_DECODE_FP8=1.
+#   mxfp4  OCP microscaling: e2m1 codes tiled [N/16, K/128, 64, 16], two per byte, and one E8M0
+#          scale byte per 32 consecutive k of a weight row, [N/16, K/128, 16, 4]: 4.25 bits per
+#          weight. There is no per-row scale: v_cvt_scalef32_pk_bf16_fp4 applies the block scale
+#          while converting, so the bf16 MFMA sees the exact dequantised weights (csrc/skinny_ks.h
+#          F4, skinny_glu_il_kernel F4, csrc/skinny64.hip F4). DLA_DECODE_MXFP4=1.
 
 
 # Merged-adapter decode (`generate(..., adapters="merged")`): only inside this scope does the fused
@@ -693,129 +680,6 @@ def tile_f8(q: torch.Tensor) -> torch.Tensor:
     N, K = q.shape
     return (q.view(N // 16, 16, K // 64, 2, 4, 8).permute(0, 2, 4, 1, 3, 5)
             .reshape(N // 16, K // 64, 64, 16).contiguous())
-
-
-def fp8_tiled_weight(w: torch.Tensor, norm_w: Optional[torch.Tensor] = None, glu_il: bool = False, lora=None):
-    """Cached (e4m3 tiled copy, per-row scales) of W (o norm_w folded in; glu_il: gate / up rows
-    interleaved 8 + 8 per 16-row tile), refreshed when W or norm_w moved (as folded_weight).
-    `lora`: of W + s B A instead, quantised after the merge (and the fold)."""
-    N, K = w.shape
-    lora = lora_triple(lora)
-    w0 = w
-
-    def make(prev):
-        w = w0
-        if lora is not None:
-            if merge_kernel_ok(w, lora, glu_il, f8=True):
-                MERGE_CALLS["kernel"] += 1
-                t, sc = prev if prev is not None else (
-                    torch.empty((N // 16, K // 64, 64, 16), dtype=torch.uint8, device=w.device),
-                    torch.empty(N, dtype=torch.float32, device=w.device))
-                _ext.require().lora_quant_tile_f8(w.detach(), lora[0].detach(), lora[1].detach(), lora[2],
-                                                  norm_w.detach().contiguous() if norm_w is not None else None,
-                                                  t, sc, bool(glu_il))
-                return (t, sc)
-            MERGE_CALLS["composition"] += 1
-            w = merged(w, lora)
-        if _ext.use_native(w) and w.stride(-1) == 1 and w.stride(0) % 8 == 0:
-            # one HIP pass (csrc/skinny64.hip quant_tile_f8_kernel), in place when refreshing: a
-            # captured decode graph keeps reading the same storage
-            t, sc = prev if prev is not None else (
-                torch.empty((N // 16, K // 64, 64, 16), dtype=torch.uint8, device=w.device),
-                torch.empty(N, dtype=torch.float32, device=w.device))
-            _ext.require().quant_tile_f8(w.detach(), norm_w.detach().contiguous() if norm_w is not None else None,
-                                         t, sc, bool(glu_il))
-            return (t, sc)
-        src = w.detach() if norm_w is None else w.detach() * norm_w.detach().view(1, -1)
-        if glu_il:
-            src = _glu_interleave(src)
-        q, sc = quantize_rows_f8(src)
-        t = tile_f8(q)
-        if prev is not None:
-            prev[0].copy_(t)
-            prev[1].copy_(sc)
-            return prev
-        return (t, sc)
-
-    attr = "_dla_f8_g" if glu_il else ("_dla_f8_n" if norm_w is not None else "_dla_f8")
-    key = (_wkey(w), _wkey(norm_w) if norm_w is not None else None)
-    return _cached(w, attr, key if lora is None else key + (_lora_key(lora),), make)
-
-
-def _f8_ok(rows: int, w: torch.Tensor) -> bool:
-    """fp8 mode and a shape the fp8 kernels take: <= 16 rows csrc/skinny_ks.h F8 / skinny_glu_il F8,
-    17..64 rows csrc/skinny64.hip F8."""
-    if not _FP8[0]:
-        return False
-    if rows <= 16:
-        return w.shape[0] % 32 == 0 and w.shape[1] % 1024 == 0
-    return DECODE_M64 and rows <= 64 and w.shape[0] % 128 == 0 and w.shape[1] % 256 == 0
-
-
-def head_f8(x: torch.Tensor, w: torch.Tensor) -> Optional[torch.Tensor]:
-    """LM-head logits x @ w^T on the fp8 copy of w (decode rows, fp8 mode), else None."""
-    if not (_FP8[0] and x.is_cuda and _ext.use_native(x)) or torch.is_grad_enabled() and x.requires_grad:
-        return None
-    rows = x.numel() // x.shape[-1]
-    if not (1 <= rows <= 64 and _f8_ok(rows, w) and x.dtype == torch.bfloat16):
-        return None
-    w8, sc = fp8_tiled_weight(w)
-    if rows > 16:
-        y, _ = _ext.require().skinny64_f8(_rows(x), w8, sc, None, None, 0.0, False)
-    else:
-        y, _ = _ext.require().skinny_fused_f8(_rows(x), w8, sc, None, None, 0.0)
-    return y.view(*x.shape[:-1], w.shape[0])
-
-
-# ---------------------------------------------------------------------------------------------
-# Weight-only MXFP4 decode (opt-in, OCP microscaling `mxfp4`): the same four weight streams and the
-# LM head read e2m1 codes with one E8M0 scale byte per 32 consecutive k of a weight row, 4.25 bits
-# per weight (csrc/skinny_ks.h F4, skinny_glu_il_kernel F4, csrc/skinny64.hip F4). There is no
-# per-row fp32 scale: v_cvt_scalef32_pk_bf16_fp4 applies the block scale while converting, so the
-# bf16 MFMA sees the exact dequantised weights. For RLHF rollouts (`generate(...,
-# weight_dtype="mxfp4")`, `ppo.rollout_weight_dtype`), as fp8: the copy only changes which tokens
-# are sampled. Mutually exclusive with fp8_weights. DLA_DECODE_MXFP4=1 turns it on process-wide.
-_MXFP4 = [os.environ.get("DLA_DECODE_MXFP4", "0") == "1"]
-if _MXFP4[0] and _FP8[0]:
-    raise RuntimeError("DLA_DECODE_MXFP4=1 and DLA_DECODE_FP8=1 are mutually exclusive")
-
-
-class mxfp4_weights:
-    """Context manager: decode projections on MXFP4 weight copies inside the block (not together
-    with `fp8_weights`). `model`: its qkv / o / gate|up / down and LM-head weights are marked for the
-    block, so that off the GPU their <= 64-row projections run the CPU formula (`mxfp4_ref_weight`;
-    MoE experts and routers are never marked)."""
-
-    def __init__(self, enabled: bool = True, model=None):
-        self.enabled, self.model, self.marked = bool(enabled), model, []
-
-    def __enter__(self):
-        if self.enabled and _FP8[0]:
-            raise RuntimeError("mxfp4_weights inside fp8_weights: one decode weight format at a time")
-        self.prev = _MXFP4[0]
-        _MXFP4[0] = self.enabled
-        if self.enabled and self.model is not None:
-            ws = [getattr(self.model, "head_weight", None)]
-            for layer in getattr(self.model, "layers", []):
-                at, mlp = getattr(layer, "attn", None), getattr(layer, "mlp", None)
-                ws += [getattr(at, "qkv_proj", None), getattr(at, "o_proj", None),
-                       getattr(mlp, "up_proj", None), getattr(mlp, "down_proj", None)]
-            for w in ws:
-                if isinstance(w, torch.Tensor) and w.dim() == 2 and not getattr(w, "_dla_mx", False):
-                    w._dla_mx = True
-                    self.marked.append(w)
-        return self
-
-    def __exit__(self, *exc):
-        _MXFP4[0] = self.prev
-        for w in self.marked:
-            w.__dict__.pop("_dla_mx", None)
-        self.marked = []
-        return False
-
-
-def mxfp4_enabled() -> bool:
-    return _MXFP4[0]
 
 
 E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)  # code & 7; code & 8 is the sign
@@ -871,66 +735,206 @@ def tile_mxfp4(codes: torch.Tensor, scales: torch.Tensor):
     return t, sc
 
 
-def mxfp4_tiled_weight(w: torch.Tensor, norm_w: Optional[torch.Tensor] = None, glu_il: bool = False, lora=None):
-    """Cached (e2m1 tiled codes, E8M0 block scales) of W (o norm_w folded in as the bf16 product
-    the e4m3 copy forms; glu_il: gate / up rows interleaved 8 + 8 per 16-row tile), refreshed in
-    place when W or norm_w moved (as fp8_tiled_weight). `lora`: of W + s B A instead -- `merged()`
-    into a temporary, then the quantiser (the composition path; there is no fused merge kernel)."""
+def _pair_f8(N: int, K: int, device):
+    return (torch.empty((N // 16, K // 64, 64, 16), dtype=torch.uint8, device=device),
+            torch.empty(N, dtype=torch.float32, device=device))
+
+
+def _pair_mxfp4(N: int, K: int, device):
+    return (torch.empty((N // 16, K // 128, 64, 16), dtype=torch.uint8, device=device),
+            torch.empty((N // 16, K // 128, 16, 4), dtype=torch.uint8, device=device))
+
+
+@dataclass(frozen=True, eq=False)
+class _WeightFormat:
+    """What differs between the quantised decode weight formats; everything below is written once
+    on top of it."""
+    name: str        # generate()'s weight_dtype
+    env: str         # "1" turns the format on process-wide
+    attrs: tuple     # cache attribute of the plain, the norm-folded, the folded + GLU-interleaved copy
+    alloc: Callable  # (N, K, device) -> the empty (codes, scales) pair
+    quant_op: str    # torch.ops.dla one-pass quantiser of a GPU w (+ norm fold, interleave) into the pair
+    formula: Callable  # src [N, K] -> the pair: the CPU formula of record
+    fused_op: str    # torch.ops.dla projections: <= 16 rows,
+    glu_il_op: str   # <= 16 rows gate|up + SwiGLU on the interleaved copy,
+    m64_op: str      # 17..64 rows
+    merge_op: Optional[str]  # fused LoRA merge + quantise kernel; None: every LoRA copy is the `merged()` composition
+    bf16_only: bool  # a W of another dtype: the copy is built by `formula`, and the LM head stays off the format
+    # (fp8 does not look at W's dtype: its quantiser op refuses a W that is not bf16)
+
+
+def _formula_f8(src: torch.Tensor):
+    q, sc = quantize_rows_f8(src)
+    return tile_f8(q), sc
+
+
+_F8 = _WeightFormat(name="fp8", env="DLA_DECODE_FP8", attrs=("_dla_f8", "_dla_f8_n", "_dla_f8_g"), alloc=_pair_f8,
+                    quant_op="quant_tile_f8", formula=_formula_f8, fused_op="skinny_fused_f8",
+                    glu_il_op="skinny_glu_il_f8", m64_op="skinny64_f8", merge_op="lora_quant_tile_f8", bf16_only=False)
+_F4 = _WeightFormat(name="mxfp4", env="DLA_DECODE_MXFP4", attrs=("_dla_f4", "_dla_f4_n", "_dla_f4_g"), alloc=_pair_mxfp4,
+                    quant_op="quant_tile_mxfp4", formula=lambda src: tile_mxfp4(*quantize_mxfp4(src)),
+                    fused_op="skinny_fused_f4", glu_il_op="skinny_glu_il_f4", m64_op="skinny64_f4", merge_op=None,
+                    bf16_only=True)
+_FORMATS = {f.name: f for f in (_F8, _F4)}
+
+_on = [f for f in _FORMATS.values() if os.environ.get(f.env, "0") == "1"]
+if len(_on) > 1:
+    raise RuntimeError("DLA_DECODE_MXFP4=1 and DLA_DECODE_FP8=1 are mutually exclusive")
+_ACTIVE = [_on[0] if _on else None]  # the active decode weight format (None: the bf16 weights)
+
+
+class weight_format:
+    """Context manager: inside the block the decode projections read `name`'s copies ("fp8",
+    "mxfp4"; None: the bf16 weights), whatever was active outside. `model`, under "mxfp4": its
+    qkv / o / gate|up / down and LM-head weights are marked for the block, so that off the GPU
+    their <= 64-row projections run the CPU formula (`mxfp4_ref_weight`; MoE experts and routers
+    are never marked)."""
+
+    def __init__(self, name: Optional[str], model=None):
+        self.fmt, self.model, self.marked = (_FORMATS[name] if name is not None else None), model, []
+
+    def _target(self, cur):
+        return self.fmt
+
+    def __enter__(self):
+        self.prev = _ACTIVE[0]
+        _ACTIVE[0] = self._target(self.prev)
+        if _ACTIVE[0] is _F4 and self.model is not None:
+            ws = [getattr(self.model, "head_weight", None)]
+            for layer in getattr(self.model, "layers", []):
+                at, mlp = getattr(layer, "attn", None), getattr(layer, "mlp", None)
+                ws += [getattr(at, "qkv_proj", None), getattr(at, "o_proj", None),
+                       getattr(mlp, "up_proj", None), getattr(mlp, "down_proj", None)]
+            for w in ws:
+                if isinstance(w, torch.Tensor) and w.dim() == 2 and not getattr(w, "_dla_mx", False):
+                    w._dla_mx = True
+                    self.marked.append(w)
+        return self
+
+    def __exit__(self, *exc):
+        _ACTIVE[0] = self.prev
+        for w in self.marked:
+            w.__dict__.pop("_dla_mx", None)
+        self.marked = []
+        return False
+
+
+class _one_format(weight_format):
+    """`X_weights(True)`: format X inside the block, RuntimeError if the other format is active;
+    `X_weights(False)`: X off inside the block (another active format stays)."""
+    name = None
+
+    def __init__(self, enabled: bool = True, model=None):
+        super().__init__(self.name, model)
+        self.enabled = bool(enabled)
+
+    def _target(self, cur):
+        if not self.enabled:
+            return None if cur is self.fmt else cur
+        if cur is not None and cur is not self.fmt:
+            raise RuntimeError(f"{self.name}_weights inside {cur.name}_weights: one decode weight format at a time")
+        return self.fmt
+
+
+class fp8_weights(_one_format):
+    """Context manager: decode projections on fp8 weight copies inside the block (not together
+    with `mxfp4_weights`)."""
+    name = "fp8"
+
+
+class mxfp4_weights(_one_format):
+    """Context manager: decode projections on MXFP4 weight copies inside the block (not together
+    with `fp8_weights`); `model` as in `weight_format`."""
+    name = "mxfp4"
+
+
+def fp8_enabled() -> bool:
+    return _ACTIVE[0] is _F8
+
+
+def mxfp4_enabled() -> bool:
+    return _ACTIVE[0] is _F4
+
+
+def _quant_tiled_weight(fmt: _WeightFormat, w: torch.Tensor, norm_w: Optional[torch.Tensor] = None,
+                        glu_il: bool = False, lora=None):
+    """Cached (tiled codes, scales) of W in `fmt` (norm_w: of bf16(W * norm_w), the RMSNorm weight
+    folded in; glu_il: gate / up rows interleaved 8 + 8 per 16-row tile), refreshed IN PLACE when W
+    or norm_w moved (as folded_weight): a captured decode graph keeps reading the same storage.
+    `lora`: of W + s B A instead, quantised after the merge (and the fold) -- one HIP pass where
+    the format has a merge kernel that takes the call, else `merged()` into a temporary."""
     N, K = w.shape
     lora = lora_triple(lora)
-    w0 = w
 
     def make(prev):
-        w = w0
+        src, nw = w.detach(), norm_w.detach() if norm_w is not None else None
+        out = prev if prev is not None else fmt.alloc(N, K, w.device)
         if lora is not None:
+            # (f8=True: the one quantising merge kernel is the e4m3 one, csrc/skinny64.hip lora_quant_tile_f8_kernel)
+            if fmt.merge_op is not None and merge_kernel_ok(src, lora, glu_il, f8=True):
+                MERGE_CALLS["kernel"] += 1
+                getattr(_ext.require(), fmt.merge_op)(src, lora[0].detach(), lora[1].detach(), lora[2],
+                                                      nw.contiguous() if nw is not None else None, *out, bool(glu_il))
+                return out
             MERGE_CALLS["composition"] += 1
-            w = merged(w, lora)
-        if _ext.use_native(w) and w.dtype == torch.bfloat16 and w.stride(-1) == 1 and w.stride(0) % 8 == 0:
-            # one HIP pass (csrc/skinny64.hip quant_tile_mxfp4_kernel), in place when refreshing: a
-            # captured decode graph keeps reading the same storage
-            t, sc = prev if prev is not None else (
-                torch.empty((N // 16, K // 128, 64, 16), dtype=torch.uint8, device=w.device),
-                torch.empty((N // 16, K // 128, 16, 4), dtype=torch.uint8, device=w.device))
-            _ext.require().quant_tile_mxfp4(w.detach(), norm_w.detach().contiguous() if norm_w is not None else None,
-                                            t, sc, bool(glu_il))
-            return (t, sc)
-        src = w.detach() if norm_w is None else w.detach() * norm_w.detach().view(1, -1)
-        if glu_il:
-            src = _glu_interleave(src)
-        t, sc = tile_mxfp4(*quantize_mxfp4(src))
-        if prev is not None:
-            prev[0].copy_(t)
-            prev[1].copy_(sc)
-            return prev
-        return (t, sc)
+            src = merged(src, lora)
+        if (_ext.use_native(src) and (not fmt.bf16_only or src.dtype == torch.bfloat16) and src.stride(-1) == 1
+                and src.stride(0) % 8 == 0):
+            # one HIP pass (csrc/skinny64.hip quant_tile_f8_kernel / quant_tile_mxfp4_kernel)
+            getattr(_ext.require(), fmt.quant_op)(src, nw.contiguous() if nw is not None else None, *out, bool(glu_il))
+            return out
+        if nw is not None:
+            src = src * nw.view(1, -1)
+        t, sc = fmt.formula(_glu_interleave(src) if glu_il else src)
+        out[0].copy_(t)
+        out[1].copy_(sc)
+        return out
 
-    attr = "_dla_f4_g" if glu_il else ("_dla_f4_n" if norm_w is not None else "_dla_f4")
+    attr = fmt.attrs[2 if glu_il else (1 if norm_w is not None else 0)]
     key = (_wkey(w), _wkey(norm_w) if norm_w is not None else None)
     return _cached(w, attr, key if lora is None else key + (_lora_key(lora),), make)
 
 
-def _f4_ok(rows: int, w: torch.Tensor) -> bool:
-    """mxfp4 mode and a shape the MXFP4 kernels take: <= 16 rows csrc/skinny_ks.h F4 /
-    skinny_glu_il F4, 17..64 rows csrc/skinny64.hip F4."""
-    if not _MXFP4[0]:
-        return False
+def fp8_tiled_weight(w: torch.Tensor, norm_w: Optional[torch.Tensor] = None, glu_il: bool = False, lora=None):
+    """`_quant_tiled_weight` in fp8: (e4m3 tiled copy, per-row fp32 scales)."""
+    return _quant_tiled_weight(_F8, w, norm_w, glu_il, lora)
+
+
+def mxfp4_tiled_weight(w: torch.Tensor, norm_w: Optional[torch.Tensor] = None, glu_il: bool = False, lora=None):
+    """`_quant_tiled_weight` in mxfp4: (e2m1 tiled codes, E8M0 block scales)."""
+    return _quant_tiled_weight(_F4, w, norm_w, glu_il, lora)
+
+
+def _quant_format(rows: int, w: torch.Tensor) -> Optional[_WeightFormat]:
+    """The active quantised format if its kernels take (rows, w), else None: <= 16 rows
+    csrc/skinny_ks.h / skinny_glu_il, 17..64 rows csrc/skinny64.hip."""
+    fmt = _ACTIVE[0]
+    if fmt is None:
+        return None
     if rows <= 16:
-        return w.shape[0] % 32 == 0 and w.shape[1] % 1024 == 0
-    return DECODE_M64 and rows <= 64 and w.shape[0] % 128 == 0 and w.shape[1] % 256 == 0
+        ok = w.shape[0] % 32 == 0 and w.shape[1] % 1024 == 0
+    else:
+        ok = DECODE_M64 and rows <= 64 and w.shape[0] % 128 == 0 and w.shape[1] % 256 == 0
+    return fmt if ok else None
 
 
-def head_f4(x: torch.Tensor, w: torch.Tensor) -> Optional[torch.Tensor]:
-    """LM-head logits x @ w^T on the MXFP4 copy of w (decode rows, mxfp4 mode), else None."""
-    if not (_MXFP4[0] and x.is_cuda and _ext.use_native(x)) or torch.is_grad_enabled() and x.requires_grad:
+def _quant_linear(fmt: _WeightFormat, x2: torch.Tensor, pair, res, ssq, eps: float, glu: bool = False):
+    """(y, ssq) of the format's projection op for x2's row count (`glu`: 17..64 rows only)."""
+    if x2.shape[0] > 16:
+        return getattr(_ext.require(), fmt.m64_op)(x2, *pair, res, ssq, eps, glu)
+    return getattr(_ext.require(), fmt.fused_op)(x2, *pair, res, ssq, eps)
+
+
+def quant_head(x: torch.Tensor, w: torch.Tensor) -> Optional[torch.Tensor]:
+    """LM-head logits x @ w^T on the active format's copy of w (decode rows on the GPU), else None."""
+    fmt = _ACTIVE[0]
+    if (fmt is None or not (x.is_cuda and _ext.use_native(x)) or torch.is_grad_enabled() and x.requires_grad
+            or fmt.bf16_only and w.dtype != torch.bfloat16):
         return None
     rows = x.numel() // x.shape[-1]
-    if not (1 <= rows <= 64 and _f4_ok(rows, w) and x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16):
+    if not (1 <= rows <= 64 and _quant_format(rows, w) is fmt and x.dtype == torch.bfloat16):
         return None
-    w4, sb = mxfp4_tiled_weight(w)
-    if rows > 16:
-        y, _ = _ext.require().skinny64_f4(_rows(x), w4, sb, None, None, 0.0, False)
-    else:
-        y, _ = _ext.require().skinny_fused_f4(_rows(x), w4, sb, None, None, 0.0)
+    y, _ = _quant_linear(fmt, _rows(x), _quant_tiled_weight(fmt, w), None, None, 0.0)
     return y.view(*x.shape[:-1], w.shape[0])
 
 
@@ -941,7 +945,7 @@ def mxfp4_ref_weight(x: torch.Tensor, w: torch.Tensor) -> Optional[torch.Tensor]
     W itself, also for qkv and gate|up, where the device copies quantise bf16(W * norm_w): off the
     GPU the norm stays a separate step, so the two agree exactly only while the norm weights are
     powers of two (1.0 at initialisation) and to quantisation error otherwise."""
-    if (not _MXFP4[0] or not getattr(w, "_dla_mx", False) or torch.is_grad_enabled() or _ext.use_native(x)
+    if (_ACTIVE[0] is not _F4 or not getattr(w, "_dla_mx", False) or torch.is_grad_enabled() or _ext.use_native(x)
             or w.shape[1] % 32):
         return None
     rows = x.numel() // x.shape[-1] if x.dim() else 0
@@ -955,9 +959,9 @@ def mxfp4_ref_weight(x: torch.Tensor, w: torch.Tensor) -> Optional[torch.Tensor]
     return _cached(w, "_dla_f4_ref", _wkey(w), make)
 
 
-DERIVED_ATTRS = ("_dla_fold", "_dla_fold_t", "_dla_fold_g", "_dla_tile", "_dla_f8", "_dla_f8_n", "_dla_f8_g",
-                 "_dla_f4", "_dla_f4_n", "_dla_f4_g", "_dla_f4_ref",
-                 "_dla_fp8")  # (the last: ops.moe.fp8_weight, the fp8 prefill GEMMs' weight copy)
+DERIVED_ATTRS = (("_dla_fold", "_dla_fold_t", "_dla_fold_g", "_dla_tile")
+                 + tuple(a for f in _FORMATS.values() for a in f.attrs)
+                 + ("_dla_f4_ref", "_dla_fp8"))  # (the last: ops.moe.fp8_weight, the fp8 prefill GEMMs' weight copy)
 
 
 def drop_derived_weights(model) -> int:
@@ -984,11 +988,16 @@ def refresh_folded_weights(model) -> None:
     ls = getattr(model, "layers_sharded", None)
     if ls is not None and ls():
         return
+    def requant(w, nw=None, ad=None):  # the quantised copies of w that exist: plain, or folded (+ interleaved)
+        for fmt in _FORMATS.values():
+            for i in ((0,) if nw is None else (1, 2)):
+                if getattr(w, fmt.attrs[i], None) is not None:
+                    _quant_tiled_weight(fmt, w, nw, glu_il=i == 2, lora=ad)
+
     hw = getattr(model, "head_weight", None)
-    if isinstance(hw, torch.Tensor) and getattr(hw, "_dla_f8", None) is not None:
-        fp8_tiled_weight(hw)
-    if isinstance(hw, torch.Tensor) and getattr(hw, "_dla_f4", None) is not None:
-        mxfp4_tiled_weight(hw)
+    if isinstance(hw, torch.Tensor):
+        requant(hw)
+
     def active(owner, name):  # the projection's adapter if attached and switched on
         ad = getattr(owner, name, None)
         return ad if (ad is not None and ad.enabled) else None
@@ -1006,22 +1015,14 @@ def refresh_folded_weights(model) -> None:
                 folded_weight(w, nw, tiled=True, lora=ad)
             if getattr(w, "_dla_fold_g", None) is not None:
                 folded_weight(w, nw, tiled=True, glu_il=True, lora=ad)
-            if getattr(w, "_dla_f8_n", None) is not None:
-                fp8_tiled_weight(w, nw, lora=ad)
-            if getattr(w, "_dla_f8_g", None) is not None:
-                fp8_tiled_weight(w, nw, glu_il=True, lora=ad)
-            if getattr(w, "_dla_f4_n", None) is not None:
-                mxfp4_tiled_weight(w, nw, lora=ad)
-            if getattr(w, "_dla_f4_g", None) is not None:
-                mxfp4_tiled_weight(w, nw, glu_il=True, lora=ad)
+            requant(w, nw, ad)
         for w, ad in ((getattr(layer.attn, "o_proj", None), active(layer.attn, "lora_o")),
                       (getattr(layer.mlp, "down_proj", None), active(layer.mlp, "lora_down"))):
-            if w is not None and getattr(w, "_dla_tile", None) is not None:
+            if w is None:
+                continue
+            if getattr(w, "_dla_tile", None) is not None:
                 tiled_weight(w, lora=ad)
-            if w is not None and getattr(w, "_dla_f8", None) is not None:
-                fp8_tiled_weight(w, lora=ad)
-            if w is not None and getattr(w, "_dla_f4", None) is not None:
-                mxfp4_tiled_weight(w, lora=ad)
+            requant(w, ad=ad)
 
 
 def skinny_residual(x: torch.Tensor, w: torch.Tensor, res: torch.Tensor, lora=None):
@@ -1030,19 +1031,9 @@ def skinny_residual(x: torch.Tensor, w: torch.Tensor, res: torch.Tensor, lora=No
     x2 = _rows(x)
     if lora is not None and DECODE_TILED < 2:
         raise RuntimeError("merged LoRA decode needs the tiled weight copies (DLA_DECODE_TILED=2)")
-    if _f8_ok(x2.shape[0], w):
-        w8, sc = fp8_tiled_weight(w, lora=lora)
-        if x2.shape[0] > 16:
-            s, ssq = _ext.require().skinny64_f8(x2, w8, sc, _rows(res), None, 0.0, False)
-        else:
-            s, ssq = _ext.require().skinny_fused_f8(x2, w8, sc, _rows(res), None, 0.0)
-        return s.view(*res.shape[:-1], w.shape[0]), ssq
-    if _f4_ok(x2.shape[0], w):
-        w4, sb = mxfp4_tiled_weight(w, lora=lora)
-        if x2.shape[0] > 16:
-            s, ssq = _ext.require().skinny64_f4(x2, w4, sb, _rows(res), None, 0.0, False)
-        else:
-            s, ssq = _ext.require().skinny_fused_f4(x2, w4, sb, _rows(res), None, 0.0)
+    fmt = _quant_format(x2.shape[0], w)
+    if fmt is not None:
+        s, ssq = _quant_linear(fmt, x2, _quant_tiled_weight(fmt, w, lora=lora), _rows(res), None, 0.0)
         return s.view(*res.shape[:-1], w.shape[0]), ssq
     wk = tiled_weight(w, lora=lora) if DECODE_TILED >= 2 else w
     if x2.shape[0] > 16:
@@ -1059,31 +1050,16 @@ def skinny_normed(s: torch.Tensor, ssq: torch.Tensor, norm_w: torch.Tensor, eps:
     s2 = _rows(s)
     if lora is not None and DECODE_TILED < 1:
         raise RuntimeError("merged LoRA decode needs the tiled weight copies (DLA_DECODE_TILED=2)")
-    if _f8_ok(s2.shape[0], w) and s2.shape[0] > 16:
-        # 17..64 rows: gate|up in the plain [gate; up] row order (the m64 GLU epilogue pairs them)
-        w8, sc = fp8_tiled_weight(w, norm_w, lora=lora)
-        y, _ = _ext.require().skinny64_f8(s2, w8, sc, None, ssq, float(eps), bool(glu))
-        return y.view(*s.shape[:-1], y.shape[-1])
-    if _f8_ok(s2.shape[0], w):
-        if glu:
-            w8, sc = fp8_tiled_weight(w, norm_w, glu_il=True, lora=lora)
-            m = _ext.require().skinny_glu_il_f8(s2, w8, sc, ssq, float(eps))
-            return m.view(*s.shape[:-1], m.shape[-1])
-        w8, sc = fp8_tiled_weight(w, norm_w, lora=lora)
-        y, _ = _ext.require().skinny_fused_f8(s2, w8, sc, None, ssq, float(eps))
-        return y.view(*s.shape[:-1], y.shape[-1])
-    if _f4_ok(s2.shape[0], w) and s2.shape[0] > 16:
-        # 17..64 rows: gate|up in the plain [gate; up] row order (the m64 GLU epilogue pairs them)
-        w4, sb = mxfp4_tiled_weight(w, norm_w, lora=lora)
-        y, _ = _ext.require().skinny64_f4(s2, w4, sb, None, ssq, float(eps), bool(glu))
-        return y.view(*s.shape[:-1], y.shape[-1])
-    if _f4_ok(s2.shape[0], w):
-        if glu:
-            w4, sb = mxfp4_tiled_weight(w, norm_w, glu_il=True, lora=lora)
-            m = _ext.require().skinny_glu_il_f4(s2, w4, sb, ssq, float(eps))
-            return m.view(*s.shape[:-1], m.shape[-1])
-        w4, sb = mxfp4_tiled_weight(w, norm_w, lora=lora)
-        y, _ = _ext.require().skinny_fused_f4(s2, w4, sb, None, ssq, float(eps))
+    fmt = _quant_format(s2.shape[0], w)
+    if fmt is not None:
+        # gate|up: interleaved for the <= 16-row GLU kernel; at 17..64 rows the plain [gate; up] row
+        # order (the m64 GLU epilogue pairs them)
+        il = bool(glu) and s2.shape[0] <= 16
+        pair = _quant_tiled_weight(fmt, w, norm_w, glu_il=il, lora=lora)
+        if il:
+            y = getattr(_ext.require(), fmt.glu_il_op)(s2, *pair, ssq, float(eps))
+        else:
+            y, _ = _quant_linear(fmt, s2, pair, None, ssq, float(eps), bool(glu))
         return y.view(*s.shape[:-1], y.shape[-1])
     if (glu and DECODE_GLU_IL and DECODE_TILED >= 1 and s2.shape[0] <= 16 and w.shape[0] % 32 == 0
             and w.shape[1] % 512 == 0):
