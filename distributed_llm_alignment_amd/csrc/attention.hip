@@ -22,17 +22,15 @@
 //   * query blocks are the slowest grid dimension, heaviest causal blocks first (LPT order).
 //   * HP query heads of one GQA group share a workgroup (and so every K/V tile in LDS): the
 //     per-head query block shrinks to 256 / HP rows, which narrows the causal diagonal band where
-//     part of the waves idle (see fwd_dispatch).
+//     part of the waves idle (see attn_fwd_plan, attn_geom.h).
 //   * widened store tail (T21): O leaves as 8 x 16 B per lane after a permlane32 swap instead
 //     of 16 x 8 B (the per-lane row stores are issue-bound): 141 -> 121 us causal T = 1024,
 //     190 -> 170 us non-causal (tools/attn_bench.py --ab, one box).
 // Backward: see attn_bwd_kernel.
-#include <cstdlib>
 #include <stdexcept>
 #include <type_traits>
 #include "common.h"
 
-#include <cstring>
 #include "attn_params.h"
 
 namespace dla {
@@ -2289,104 +2287,15 @@ __global__ __launch_bounds__(256) void attn_dkv_reduce_kernel(
 }
 
 // ----------------------------------------------------------------------------------------------
-// launchers
+// launchers: no decision and no environment here. The plan (attn_geom.h) names the kernel
+// instantiation and every grid; a zero grid means no launch.
 // ----------------------------------------------------------------------------------------------
-static inline unsigned stream_grid(int64_t work) {
-  // grid-stride cap of the reduce passes: 1024 / 8192 / 32768 measured as noise against 2048
-  constexpr int64_t cap = 2048;
-  int64_t g = (work + 255) / 256;
-  if (g > cap) g = cap;
-  return static_cast<unsigned>(g < 1 ? 1 : g);
-}
-
-// Forward: 8 waves (256 queries) per workgroup. A 4-wave / 128-query variant (two independent
-// workgroups per CU, unaligned barriers) measured 31-35 % slower at T = 1024 and 4096.
-// HP GQA heads per workgroup: 4 (64-query blocks, 2 waves per head) when the group size allows
-// it, else 2, else 1; DLA_ATTN_FWD_HP=1|2|4 caps it for A/B runs. Same-box A/B (B8 T1024 Hq32
-// Hkv8 D128, tools/gpu_attn_env_ab.sh): causal 140-148 / 131-133 / 124-129 us for HP 1 / 2 / 4,
-// non-causal 217 -> 205-209 us, T = 4096 unchanged (366-379 us).
-// Persistent forward (attn_fwd_persist_kernel): DLA_ATTN_FWD_PERSIST=1 always, =0 never, unset =
-// for key ranges of at most 512 (<= 8 tiles per block), where it measured faster: graph-timed,
-// B*T = 8192, Hq 32 / Hkv 8 / D 128 (profiles/r5_attention_fwd.md) causal 240 -> 290-318 TF/s
-// at T 256 and 413 -> 469-472 at T 512, equal at 1024, 5 % slower at 2048-4096. Read per call so
-// one process can A/B both (tools/attn_fwd_sweep.py --cfg, tests/test_kernels_gpu.py).
-static bool fwd_persist(int Tk) {
-  const char* e = std::getenv("DLA_ATTN_FWD_PERSIST");
-  if (e == nullptr || *e == '\0') return Tk <= 512;
-  return std::atoi(e) != 0;
-}
-
-static int device_cus() {
-  static int cached[64] = {0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  if (cached[dev] == 0) {
-    int n = 0;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    cached[dev] = n;
-  }
-  return cached[dev];
-}
-
-struct AttnFwdSwitches {
-  int prio, sgpr, pro, ostage, msub;
-};
-
-// Read from the environment once per process; tests flip a switch through attn_fwd_set_switch
-// (torch.ops.dla.attn_fwd_switch) instead of re-reading the environment on every launch.
-static AttnFwdSwitches& attn_fwd_switches() {
-  static AttnFwdSwitches sw = [] {
-    auto env = [](const char* name, int dflt) {
-      const char* e = std::getenv(name);
-      return e ? std::atoi(e) : dflt;
-    };
-    return AttnFwdSwitches{env("DLA_ATTN_FWD_PRIO", 1), env("DLA_ATTN_FWD_SGPR", 1), env("DLA_ATTN_FWD_PRO", 1),
-                           env("DLA_ATTN_FWD_OSTAGE", 1), env("DLA_ATTN_FWD_MSUB", 1)};
-  }();
-  return sw;
-}
-
-// Set one switch ("prio", "sgpr", "pro", "ostage", "msub"); returns its previous value, or
-// -1 for an unknown name (nothing changed).
-int attn_fwd_set_switch(const char* name, int value) {
-  AttnFwdSwitches& sw = attn_fwd_switches();
-  int* f = nullptr;
-  if (!std::strcmp(name, "prio")) f = &sw.prio;
-  else if (!std::strcmp(name, "sgpr")) f = &sw.sgpr;
-  else if (!std::strcmp(name, "pro")) f = &sw.pro;
-  else if (!std::strcmp(name, "ostage")) f = &sw.ostage;
-  else if (!std::strcmp(name, "msub")) f = &sw.msub;
-  if (f == nullptr) return -1;
-  const int prev = *f;
-  *f = value;
-  return prev;
-}
-
 template <int D, int HP>
-static void fwd_launch(const AttnParams& p0, bool causal, hipStream_t st) {
-  constexpr int NW = 8, BQ = 32 * NW / HP;
-  AttnParams p = p0;
-  {
-    // The forward's structure switches, read ONCE per process (attn_fwd_switches; every switch
-    // defaults to its measured winner, the others exist for same-binary A/B runs):
-    //   prio 1: s_setprio 1 around each MFMA chain, so the matrix chain of one wave issues ahead
-    //     of its SIMD partner's softmax VALU (cdna guide T5). Same box, graph-timed, B*T 8192:
-    //     causal T1024 654 vs 613 TF/s, T4096 937 vs 897; non-causal +4-6 %. 2 (static priority
-    //     for waves 4-7) measured +0-7 % and below 1 everywhere; 0 = off.
-    //   msub (D = 128): same box, graph-timed, interleaved: causal T1024 701 vs 668 TF/s, T2048
-    //     898 vs 865, non-causal +3-7 % (gpurun_out/r5/attn13); outputs within one bf16 ulp
-    const AttnFwdSwitches& sw = attn_fwd_switches();
-    p.fwd_prio = sw.prio;
-    p.fwd_sgpr = sw.sgpr;
-    p.fwd_pro = sw.pro;
-    p.fwd_ostage = sw.ostage;
-    p.fwd_msub = sw.msub;
-  }
-  const int nqb = (p.Tq + BQ - 1) / BQ;
-  const int64_t nblk = static_cast<int64_t>(nqb) * (p.Hq / HP) * p.B;
-  const dim3 grid(static_cast<unsigned>(nblk));
-  if (p.prefix != nullptr) {  // shared prefix: this kernel only (the persistent one has no second range)
-    if (!causal || p.seg_start == nullptr) throw std::invalid_argument("attn_fwd: prefix needs causal segs");
+static void fwd_launch(const AttnParams& p, const AttnFwdPlan& g, hipStream_t st) {
+  constexpr int NW = 8;
+  const unsigned grid = static_cast<unsigned>(g.grid);
+  if (g.prefix) {  // shared prefix: this kernel only (the persistent one has no second range)
+    if (!g.causal || p.seg_start == nullptr) throw std::invalid_argument("attn_fwd: prefix needs causal segs");
     if constexpr (D == 128) {
       if (p.fwd_msub) {
         attn_fwd_kernel<D, true, NW, HP, true, true><<<grid, 64 * NW, 0, st>>>(p);
@@ -2396,146 +2305,94 @@ static void fwd_launch(const AttnParams& p0, bool causal, hipStream_t st) {
     attn_fwd_kernel<D, true, NW, HP, false, true><<<grid, 64 * NW, 0, st>>>(p);
     return;
   }
-  if (fwd_persist(p.Tk) && nblk < (int64_t(1) << 30)) {
-    // one 8-wave workgroup per CU (230 VGPRs: two waves per SIMD), never more than the blocks
-    const int grid = static_cast<int>(std::min<int64_t>(nblk, device_cus()));
-    if (causal) attn_fwd_persist_kernel<D, true, NW, HP><<<grid, 64 * NW, 0, st>>>(p, static_cast<int>(nblk));
-    else attn_fwd_persist_kernel<D, false, NW, HP><<<grid, 64 * NW, 0, st>>>(p, static_cast<int>(nblk));
+  if (g.persist) {
+    const int nblk = static_cast<int>(g.nblk);
+    if (g.causal) attn_fwd_persist_kernel<D, true, NW, HP><<<grid, 64 * NW, 0, st>>>(p, nblk);
+    else attn_fwd_persist_kernel<D, false, NW, HP><<<grid, 64 * NW, 0, st>>>(p, nblk);
     return;
   }
   if constexpr (D == 128) {
     if (p.fwd_msub) {
-      if (causal) attn_fwd_kernel<D, true, NW, HP, true><<<grid, 64 * NW, 0, st>>>(p);
+      if (g.causal) attn_fwd_kernel<D, true, NW, HP, true><<<grid, 64 * NW, 0, st>>>(p);
       else attn_fwd_kernel<D, false, NW, HP, true><<<grid, 64 * NW, 0, st>>>(p);
       return;
     }
   }
-  if (causal) attn_fwd_kernel<D, true, NW, HP><<<grid, 64 * NW, 0, st>>>(p);
+  if (g.causal) attn_fwd_kernel<D, true, NW, HP><<<grid, 64 * NW, 0, st>>>(p);
   else attn_fwd_kernel<D, false, NW, HP><<<grid, 64 * NW, 0, st>>>(p);
 }
 
 template <int D>
-static void fwd_dispatch(const AttnParams& p, bool causal, hipStream_t st) {
-  static const int forced = [] {
-    const char* e = std::getenv("DLA_ATTN_FWD_HP");
-    return e ? std::atoi(e) : 0;
-  }();
-  const int group = p.Hq / p.Hkv;
-  const int want = forced > 0 ? forced : 4;
-  if (want >= 4 && group % 4 == 0) fwd_launch<D, 4>(p, causal, st);
-  else if (want >= 2 && group % 2 == 0) fwd_launch<D, 2>(p, causal, st);
-  else fwd_launch<D, 1>(p, causal, st);
+static void fwd_dispatch(const AttnParams& p, const AttnFwdPlan& g, hipStream_t st) {
+  switch (g.hp) {
+    case 4: fwd_launch<D, 4>(p, g, st); break;
+    case 2: fwd_launch<D, 2>(p, g, st); break;
+    case 1: fwd_launch<D, 1>(p, g, st); break;
+    default: throw std::invalid_argument("attn_fwd: heads per workgroup must be 4, 2 or 1");
+  }
 }
 
-void launch_attn_fwd(const AttnParams& p, int D, bool causal, hipStream_t st) {
-  if (p.B == 0 || p.Tq == 0) return;
-  switch (D) {
-    case 64: fwd_dispatch<64>(p, causal, st); break;
-    case 80: fwd_dispatch<80>(p, causal, st); break;
-    case 128: fwd_dispatch<128>(p, causal, st); break;
+void launch_attn_fwd(const AttnParams& p, const AttnFwdPlan& g, hipStream_t st) {
+  if (g.grid == 0) return;
+  switch (g.D) {
+    case 64: fwd_dispatch<64>(p, g, st); break;
+    case 80: fwd_dispatch<80>(p, g, st); break;
+    case 128: fwd_dispatch<128>(p, g, st); break;
     default: throw std::invalid_argument("attn_fwd: head_dim must be 64, 80 or 128");
   }
 }
 
-void launch_attn_bwd_delta(const bf16_t* o, const bf16_t* dout, int64_t o_sb, int64_t o_st,
-                           int64_t o_sh, int64_t do_sb, int64_t do_st, int64_t do_sh, int B,
-                           int H, int T, int D, float* delta, hipStream_t st) {
-  const int64_t rows = static_cast<int64_t>(B) * H * T;
-  if (rows == 0) return;
-  const int64_t rows_per_block = 4 * (64 / (D <= 64 ? 8 : 16));  // as attn_bwd_delta_kernel
-  const unsigned nb = static_cast<unsigned>((rows + rows_per_block - 1) / rows_per_block);
-  attn_bwd_delta_kernel<<<nb, 256, 0, st>>>(o, dout, o_sb, o_st, o_sh, do_sb, do_st, do_sh, B, H, T, D, delta);
-}
-
-// Backward main kernel: attn_bwd8_kernel (8 waves, default) or attn_bwd_kernel
-// (DLA_ATTN_BWD_WAVES=4). Same-box A/B, B8 T1024 Hq32 Hkv8 D128 causal, all backward passes:
-// 489 -> 410 us; non-causal 624 -> 549 us (profiles/r3_attention_bwd.md). Read per call (not
-// cached) so one process can A/B both.
-static int attn_bwd_waves() {
-  const char* e = std::getenv("DLA_ATTN_BWD_WAVES");
-  return (e && std::atoi(e) == 4) ? 4 : 8;
-}
-
-// bf16 dQ slabs (8-wave kernel; DLA_ATTN_DQ_BF16=0 keeps fp32). Read per call, like the wave count.
-bool attn_dq_slab_bf16() {
-  const char* e = std::getenv("DLA_ATTN_DQ_BF16");
-  return attn_bwd_waves() == 8 && !(e && std::atoi(e) == 0);
-}
-
-// bf16 dK / dV head-split partials (8-wave kernel; DLA_ATTN_DKV_BF16=0 keeps fp32), read per call
-bool attn_dkv_part_bf16() {
-  const char* e = std::getenv("DLA_ATTN_DKV_BF16");
-  return attn_bwd_waves() == 8 && !(e && std::atoi(e) == 0);
-}
-
+// Backward main kernel: attn_bwd8_kernel (8 waves) or attn_bwd_kernel (4)
 template <int D>
-static void bwd_dispatch(const AttnBwdParams& p_in, bool causal, hipStream_t st) {
-  const AttnBwdParams& p = p_in;
-  const int nkb = (p.Tk + kAttnBwdKeys - 1) / kAttnBwdKeys;
-  const dim3 grid(nkb * p.Hkv * p.B * p.hsplit);
-  if (attn_bwd_waves() == 8) {
-    if (causal) attn_bwd8_kernel<D, true><<<grid, 512, 0, st>>>(p);
+static void bwd_main(const AttnBwdParams& p, const AttnBwdPlan& g, hipStream_t st) {
+  const unsigned grid = static_cast<unsigned>(g.grid);
+  if (g.waves == 8) {
+    if (g.causal) attn_bwd8_kernel<D, true><<<grid, 512, 0, st>>>(p);
     else attn_bwd8_kernel<D, false><<<grid, 512, 0, st>>>(p);
     return;
   }
-  if (causal) attn_bwd_kernel<D, true><<<grid, 256, 0, st>>>(p);
+  if (g.causal) attn_bwd_kernel<D, true><<<grid, 256, 0, st>>>(p);
   else attn_bwd_kernel<D, false><<<grid, 256, 0, st>>>(p);
 }
 
-void launch_attn_bwd(const AttnBwdParams& p, int D, bool causal, hipStream_t st) {
-  if (p.B == 0 || p.Tq == 0 || p.Tk == 0) return;
-  switch (D) {
-    case 64: bwd_dispatch<64>(p, causal, st); break;
-    case 80: bwd_dispatch<80>(p, causal, st); break;
-    case 128: bwd_dispatch<128>(p, causal, st); break;
-    default: throw std::invalid_argument("attn_bwd: head_dim must be 64, 80 or 128");
-  }
+template <bool CAUSAL, typename ST>
+static void dq_reduce(const ST* slab, const AttnBwdParams& p, const AttnBwdHostArgs& h, const AttnBwdPlan& g,
+                      hipStream_t st) {
+  attn_dq_reduce_kernel<CAUSAL, ST><<<static_cast<unsigned>(g.dq_grid), 256, 0, st>>>(
+      slab, static_cast<int>(g.nkb), p.B, p.Tq, p.slab_rows, p.Hq, g.D, p.causal_off, p.window, p.kv_start,
+      p.kv_end, p.Tk, h.dq, h.dq_sb, h.dq_st, h.dq_sh, p.rope_cos, p.rope_sin, p.rope_pos, p.rope_rot);
 }
 
-void launch_attn_dq_reduce(const float* slab, int nkb, int B, int Tq, int slab_rows, int Hq, int D,
-                           bool causal, int causal_off, int window, const int* kv_start,
-                           const int* kv_end, int Tk, bf16_t* dst, int64_t d_sb, int64_t d_st,
-                           int64_t d_sh, const float* rcos, const float* rsin, const int* rpos,
-                           int rot, hipStream_t st, const bf16_t* slab16) {
-  const int64_t work = static_cast<int64_t>(B) * Tq * Hq * (rcos ? rot / 16 + (D - rot) / 8 : D / 8);
-  if (work == 0) return;
-  if (slab16 != nullptr) {
-    if (causal)
-      attn_dq_reduce_kernel<true, bf16_t><<<stream_grid(work), 256, 0, st>>>(
-          slab16, nkb, B, Tq, slab_rows, Hq, D, causal_off, window, kv_start, kv_end, Tk, dst, d_sb, d_st, d_sh,
-          rcos, rsin, rpos, rot);
-    else
-      attn_dq_reduce_kernel<false, bf16_t><<<stream_grid(work), 256, 0, st>>>(
-          slab16, nkb, B, Tq, slab_rows, Hq, D, causal_off, window, kv_start, kv_end, Tk, dst, d_sb, d_st, d_sh,
-          rcos, rsin, rpos, rot);
-    return;
-  }
-  if (causal)
-    attn_dq_reduce_kernel<true><<<stream_grid(work), 256, 0, st>>>(
-        slab, nkb, B, Tq, slab_rows, Hq, D, causal_off, window, kv_start, kv_end, Tk, dst, d_sb, d_st, d_sh,
-        rcos, rsin, rpos, rot);
-  else
-    attn_dq_reduce_kernel<false><<<stream_grid(work), 256, 0, st>>>(
-        slab, nkb, B, Tq, slab_rows, Hq, D, causal_off, window, kv_start, kv_end, Tk, dst, d_sb, d_st, d_sh,
-        rcos, rsin, rpos, rot);
+template <typename PT>
+static void dkv_reduce(const PT* dkp, const PT* dvp, const AttnBwdParams& p, const AttnBwdPlan& g, hipStream_t st) {
+  attn_dkv_reduce_kernel<PT><<<static_cast<unsigned>(g.dkv_grid), 256, 0, st>>>(
+      dkp, dvp, p.hsplit, p.B, p.Tk, p.Hkv, g.D, p.scale, p.dk, p.dk_sb, p.dk_st, p.dk_sh, p.dv, p.dv_sb, p.dv_st,
+      p.dv_sh, p.rope_cos, p.rope_sin, p.rope_pos, p.rope_rot);
 }
 
-void launch_attn_dkv_reduce(const float* dkp, const float* dvp, int hs, int B, int Tk, int Hkv,
-                            int D, float scale, bf16_t* dk, int64_t dk_sb, int64_t dk_st,
-                            int64_t dk_sh, bf16_t* dv, int64_t dv_sb, int64_t dv_st,
-                            int64_t dv_sh, const float* rcos, const float* rsin, const int* rpos,
-                            int rot, hipStream_t st, const bf16_t* dkp16, const bf16_t* dvp16) {
-  const int64_t work = static_cast<int64_t>(B) * Tk * Hkv * (rcos ? rot / 16 + (D - rot) / 8 : D / 8);
-  if (work == 0) return;
-  if (dkp16 != nullptr) {
-    attn_dkv_reduce_kernel<bf16_t><<<stream_grid(work), 256, 0, st>>>(
-        dkp16, dvp16, hs, B, Tk, Hkv, D, scale, dk, dk_sb, dk_st, dk_sh, dv, dv_sb, dv_st, dv_sh, rcos, rsin,
-        rpos, rot);
-    return;
+void launch_attn_bwd(const AttnBwdParams& p, const AttnBwdHostArgs& h, const AttnBwdPlan& g, hipStream_t st) {
+  if (g.D != 64 && g.D != 80 && g.D != 128) throw std::invalid_argument("attn_bwd: head_dim must be 64, 80 or 128");
+  if (g.delta_grid > 0) {  // p.delta is this pass's output and the main kernel's input
+    attn_bwd_delta_kernel<<<static_cast<unsigned>(g.delta_grid), 256, 0, st>>>(
+        h.o, p.dout, h.o_sb, h.o_st, h.o_sh, p.do_sb, p.do_st, p.do_sh, p.B, p.Hq, p.Tq, g.D,
+        const_cast<float*>(p.delta));
   }
-  attn_dkv_reduce_kernel<float><<<stream_grid(work), 256, 0, st>>>(dkp, dvp, hs, B, Tk, Hkv, D, scale, dk,
-                                                                   dk_sb, dk_st, dk_sh, dv, dv_sb, dv_st,
-                                                                   dv_sh, rcos, rsin, rpos, rot);
+  if (g.grid > 0) {
+    switch (g.D) {
+      case 64: bwd_main<64>(p, g, st); break;
+      case 80: bwd_main<80>(p, g, st); break;
+      default: bwd_main<128>(p, g, st); break;
+    }
+  }
+  if (g.dq_grid > 0) {
+    if (g.slab16) g.causal ? dq_reduce<true>(p.dq_slab16, p, h, g, st) : dq_reduce<false>(p.dq_slab16, p, h, g, st);
+    else g.causal ? dq_reduce<true>(p.dq_slab, p, h, g, st) : dq_reduce<false>(p.dq_slab, p, h, g, st);
+  }
+  if (g.dkv_grid > 0) {
+    if (g.part16) dkv_reduce(p.dk_part16, p.dv_part16, p, g, st);
+    else dkv_reduce(p.dk_part, p.dv_part, p, g, st);
+  }
 }
 
 }  // namespace dla
+

@@ -1,6 +1,11 @@
-// Kernel-argument structs shared by attention.hip (device side) and bindings.cpp (host side).
+// Training / prefill flash attention: the kernel-argument structs (AttnParams, AttnBwdParams), the
+// backward's host-only operands and the two launchers, shared by attention.hip (kernels and
+// launchers) and bindings_attention.cpp (argument checks, the launch plan of attn_geom.h, allocation).
 #pragma once
+#include <hip/hip_runtime_api.h>
 #include <stdint.h>
+
+#include "attn_geom.h"
 
 namespace dla {
 
@@ -34,20 +39,15 @@ struct AttnParams {
   int rope_k;             // 1: K rotated as it is staged too; 0: K arrives pre-rotated, Q only
   bf16_t* q_rot;          // optional [B, T, Hq, D] out: the rotated Q (what the backward reads)
   int64_t qr_sb, qr_st, qr_sh;
-  // forward structure switches (set once per process by the launcher, attn_fwd_switches)
+  // forward structure switches (read once per process by the binding, attn_fwd_switches)
   int fwd_prio;  // issue priority A/B (DLA_ATTN_FWD_PRIO): 1 = s_setprio 1 around each MFMA chain,
+                 // 2 = static s_setprio 1 for the second wave of each SIMD (waves 4-7)
   int fwd_sgpr;   // 1: whole K/V tiles load from an SGPR tile base + 32-bit lane offsets (A/B: DLA_ATTN_FWD_SGPR=0)
   int fwd_pro;    // 1: K/V tile-0 loads issued right after the Q loads (A/B: DLA_ATTN_FWD_PRO=0)
   int fwd_ostage; // 1: O staged through LDS and stored as whole rows (A/B: DLA_ATTN_FWD_OSTAGE=0)
   int fwd_msub;   // 1: running max subtracted inside the Q.K^T MFMA chain (A/B: DLA_ATTN_FWD_MSUB)
-                 // 2 = static s_setprio 1 for the second wave of each SIMD (waves 4-7)
   unsigned long long* stamps;  // debug (DLA_ATTN_STAMPS=1): persistent forward seam stamps
 };
-
-// Backward geometry: one workgroup per (256-key block, GQA head subset, kv head, batch);
-// queries are swept in 32-row tiles.
-constexpr int kAttnBwdKeys = 256;
-constexpr int kAttnBwdQRows = 32;
 
 struct AttnBwdParams {
   const bf16_t* q;
@@ -92,7 +92,20 @@ struct AttnBwdParams {
                           // forward's q_rot output)
   int rope_rot;           // rotary dims: D (full), or 32 at D = 80 (phi-2's partial rotary:
                           // only dims [0, 32) rotate, d < 16 pairing with d + 16)
-                          // 1 around every MFMA cluster, 2 both
 };
+
+// Operands of the backward's side passes that no AttnBwdParams kernel reads: O (the delta pass)
+// and the strided dQ the slab reduce writes.
+struct AttnBwdHostArgs {
+  const bf16_t* o;
+  int64_t o_sb, o_st, o_sh;
+  bf16_t* dq;
+  int64_t dq_sb, dq_st, dq_sh;
+};
+
+// The launchers decide nothing and read no environment: the plan names the kernel and every grid.
+void launch_attn_fwd(const AttnParams& p, const AttnFwdPlan& plan, hipStream_t stream);
+// delta, the main kernel, the dQ slab reduce and (hsplit > 1) the dK / dV reduce, in that order
+void launch_attn_bwd(const AttnBwdParams& p, const AttnBwdHostArgs& h, const AttnBwdPlan& plan, hipStream_t stream);
 
 }  // namespace dla

@@ -1,5 +1,5 @@
 // Torch custom-op registry for the gfx950 kernels: `torch.ops.dla.*`. This file opens the library
-// (norms, activations, RoPE, attention, GJSD, optimizer); the other bindings_*.cpp add their family
+// (norms, activations, RoPE, transpose, GJSD, optimizer); the other bindings_*.cpp add their family
 // as a fragment.
 //
 // Host side only (compiled by the host C++ compiler): every op validates operand shapes,
@@ -19,7 +19,6 @@
 #include <cstdlib>
 #include <tuple>
 
-#include "attn_params.h"
 #include "bind_util.h"
 #include "gjsd_params.h"
 
@@ -49,20 +48,6 @@ void launch_grad_sumsq(const void*, bool, int64_t, float*, float*, bool, hipStre
 int sumsq_grid(int64_t n);
 void launch_clip_coef(const float*, float, float*, float*, hipStream_t);
 
-void launch_attn_fwd(const AttnParams&, int, bool, hipStream_t);
-int attn_fwd_set_switch(const char* name, int value);
-void launch_attn_bwd_delta(const bf16_t*, const bf16_t*, int64_t, int64_t, int64_t, int64_t,
-                           int64_t, int64_t, int, int, int, int, float*, hipStream_t);
-void launch_attn_bwd(const AttnBwdParams&, int, bool, hipStream_t);
-bool attn_dkv_part_bf16();
-bool attn_dq_slab_bf16();
-void launch_attn_dq_reduce(const float*, int, int, int, int, int, int, bool, int, int,
-                           const int*, const int*, int, bf16_t*, int64_t, int64_t, int64_t,
-                           const float*, const float*, const int*, int, hipStream_t, const bf16_t*);
-void launch_attn_dkv_reduce(const float*, const float*, int, int, int, int, int, float, bf16_t*,
-                            int64_t, int64_t, int64_t, bf16_t*, int64_t, int64_t, int64_t,
-                            const float*, const float*, const int*, int, hipStream_t, const bf16_t*,
-                            const bf16_t*);
 void launch_transpose_bf16(const bf16_t*, int64_t, int64_t, int64_t, bf16_t*, int64_t, hipStream_t);
 
 // ================================= norms ======================================================
@@ -295,277 +280,6 @@ void rope_bwd(const at::Tensor& dq, const at::Tensor& dk, at::Tensor& dqkv,
                   cur_stream(dqkv));
 }
 
-// ================================= attention ==================================================
-static void check_bthd(const at::Tensor& t, const char* name) {
-  check_bf16(t, name);
-  TORCH_CHECK(t.dim() == 4 && t.stride(3) == 1, name, " must be [B, T, H, D] with unit d stride");
-  TORCH_CHECK(t.stride(0) % 8 == 0 && t.stride(1) % 8 == 0 && t.stride(2) % 8 == 0, name,
-              " strides must be multiples of 8 elements");
-  check_aligned16(t, name);
-}
-
-static void check_kv_range(const c10::optional<at::Tensor>& r, int64_t B, const char* name) {
-  if (r && r->defined()) {
-    TORCH_CHECK(r->scalar_type() == at::kInt && r->is_contiguous() && r->numel() == B && r->is_cuda(),
-                name, " must be int32 [B] on GPU");
-  }
-}
-
-// packed-sequence bounds [2, B, T] int32 (seg_start; seg_end), causal self-attention only
-static const int* seg_ptr(const c10::optional<at::Tensor>& segs, int64_t B, int64_t Tq, int64_t Tk,
-                          bool causal, int64_t causal_off, const at::Tensor& q, int row) {
-  if (!segs || !segs->defined()) return nullptr;
-  TORCH_CHECK(segs->scalar_type() == at::kInt && segs->is_contiguous() && segs->dim() == 3 &&
-                  segs->size(0) == 2 && segs->size(1) == B && segs->size(2) == Tq,
-              "segs must be contiguous int32 [2, B, T]");
-  TORCH_CHECK(causal && causal_off == 0 && Tq == Tk, "packed sequences need causal self-attention");
-  same_device(q, *segs);
-  return segs->data_ptr<int>() + row * B * Tq;
-}
-
-// rotary tables for the fused RoPE paths: contiguous fp32 [max_pos, D/2] cos / sin, optional
-// int32 [B*T] positions (else position = t); full rotary, self-attention only
-static void rope_args(const c10::optional<at::Tensor>& rope_cos, const c10::optional<at::Tensor>& rope_sin,
-                      const c10::optional<at::Tensor>& rope_pos, const at::Tensor& q, int64_t B,
-                      int64_t Tq, int64_t Tk, int64_t D, int64_t causal_off, const float** cos_p,
-                      const float** sin_p, const int** pos_p, int* rot_p = nullptr) {
-  *cos_p = *sin_p = nullptr;
-  *pos_p = nullptr;
-  if (rot_p) *rot_p = 0;
-  if (!rope_cos || !rope_cos->defined()) return;
-  TORCH_CHECK(rope_sin && rope_sin->defined(), "rope_sin missing");
-  // full rotary, or (backward only: rot_p given) phi-2's partial rotary, 32 of D = 80 dims
-  const int64_t half = rope_cos->dim() == 2 ? rope_cos->size(1) : -1;
-  const bool partial_ok = rot_p != nullptr && D == 80 && half == 16;
-  for (const at::Tensor* t : {&*rope_cos, &*rope_sin}) {
-    TORCH_CHECK(t->scalar_type() == at::kFloat && t->is_contiguous() && t->dim() == 2 &&
-                    (t->size(1) == D / 2 || (partial_ok && t->size(1) == 16)),
-                "rope cos/sin must be contiguous fp32 [max_pos, head_dim/2] (or [max_pos, 16] at "
-                "head_dim 80 in the backward)");
-    same_device(q, *t);
-  }
-  if (rot_p) *rot_p = static_cast<int>(2 * half);
-  TORCH_CHECK(Tq == Tk && causal_off == 0, "fused RoPE needs self-attention");
-  if (rope_pos && rope_pos->defined()) {
-    TORCH_CHECK(rope_pos->scalar_type() == at::kInt && rope_pos->is_contiguous() &&
-                    rope_pos->numel() == B * Tq, "rope_pos must be contiguous int32 [B*T]");
-    same_device(q, *rope_pos);
-    *pos_p = rope_pos->data_ptr<int>();
-  } else {
-    TORCH_CHECK(Tq <= rope_cos->size(0), "positions exceed the rotary table");
-  }
-  *cos_p = rope_cos->data_ptr<float>();
-  *sin_p = rope_sin->data_ptr<float>();
-}
-
-static at::Tensor& attn_stamp_buffer() {
-  static at::Tensor buf;
-  return buf;
-}
-
-at::Tensor attn_stamps(const at::Tensor& like) {
-  (void)like;
-  return attn_stamp_buffer().defined() ? attn_stamp_buffer().clone() : at::Tensor();
-}
-
-std::tuple<at::Tensor, at::Tensor> attn_fwd(const at::Tensor& q, const at::Tensor& k,
-                                            const at::Tensor& v, double scale, bool causal,
-                                            int64_t causal_off, int64_t window,
-                                            const c10::optional<at::Tensor>& kv_start,
-                                            const c10::optional<at::Tensor>& kv_end,
-                                            const c10::optional<at::Tensor>& segs,
-                                            const c10::optional<at::Tensor>& rope_cos,
-                                            const c10::optional<at::Tensor>& rope_sin,
-                                            const c10::optional<at::Tensor>& rope_pos,
-                                            const c10::optional<at::Tensor>& q_rot, bool rope_k,
-                                            const c10::optional<at::Tensor>& prefix) {
-  check_bthd(q, "q");
-  check_bthd(k, "k");
-  check_bthd(v, "v");
-  same_device(q, k);
-  same_device(q, v);
-  const int64_t B = q.size(0), Tq = q.size(1), Hq = q.size(2), D = q.size(3);
-  const int64_t Tk = k.size(1), Hkv = k.size(2);
-  TORCH_CHECK(D == 64 || D == 80 || D == 128, "head_dim must be 64, 80 or 128 (pad others)");
-  TORCH_CHECK(k.size(0) == B && v.size(0) == B && k.size(3) == D && v.size(3) == D &&
-                  v.size(1) == Tk && v.size(2) == Hkv,
-              "k/v shapes");
-  TORCH_CHECK(Hkv > 0 && Hq % Hkv == 0, "Hq must be a multiple of Hkv");
-  check_kv_range(kv_start, B, "kv_start");
-  check_kv_range(kv_end, B, "kv_end");
-  c10::hip::HIPGuardMasqueradingAsCUDA g(q.device());
-  auto o = at::empty({B, Tq, Hq, D}, q.options());
-  auto lse2 = at::empty({B, Hq, Tq}, q.options().dtype(at::kFloat));
-  AttnParams p{};
-  p.q = cbp(q);
-  p.k = cbp(k);
-  p.v = cbp(v);
-  p.o = bp(o);
-  p.lse2 = lse2.data_ptr<float>();
-  p.q_sb = q.stride(0); p.q_st = q.stride(1); p.q_sh = q.stride(2);
-  p.k_sb = k.stride(0); p.k_st = k.stride(1); p.k_sh = k.stride(2);
-  p.v_sb = v.stride(0); p.v_st = v.stride(1); p.v_sh = v.stride(2);
-  p.o_sb = o.stride(0); p.o_st = o.stride(1); p.o_sh = o.stride(2);
-  p.B = B; p.Hq = Hq; p.Hkv = Hkv; p.Tq = Tq; p.Tk = Tk;
-  p.scale2 = static_cast<float>(scale * 1.4426950408889634);
-  p.causal_off = static_cast<int>(causal_off);
-  p.window = static_cast<int>(window);
-  p.kv_start = (kv_start && kv_start->defined()) ? kv_start->data_ptr<int>() : nullptr;
-  p.kv_end = (kv_end && kv_end->defined()) ? kv_end->data_ptr<int>() : nullptr;
-  p.seg_start = seg_ptr(segs, B, Tq, Tk, causal, causal_off, q, 0);
-  if (prefix && prefix->defined()) {  // shared prefix (ps, pe, qe) per batch row
-    TORCH_CHECK(prefix->scalar_type() == at::kInt && prefix->is_contiguous() && prefix->dim() == 2 &&
-                    prefix->size(0) == B && prefix->size(1) == 3,
-                "prefix must be contiguous int32 [B, 3]");
-    TORCH_CHECK(p.seg_start != nullptr && causal && causal_off == 0 && Tq == Tk && window <= 0,
-                "prefix needs segs and causal self-attention without a window");
-    same_device(q, *prefix);
-    p.prefix = prefix->data_ptr<int>();
-  }
-  rope_args(rope_cos, rope_sin, rope_pos, q, B, Tq, Tk, D, causal_off, &p.rope_cos, &p.rope_sin,
-            &p.rope_pos);
-  TORCH_CHECK(p.rope_cos == nullptr || D != 80, "RoPE on load: full-rotary head dims 64 / 128 only");
-  p.rope_k = rope_k ? 1 : 0;
-  if (q_rot && q_rot->defined()) {
-    TORCH_CHECK(p.rope_cos != nullptr, "q_rot needs the rotary tables");
-    check_bthd(*q_rot, "q_rot");
-    TORCH_CHECK(q_rot->sizes() == q.sizes(), "q_rot shape");
-    same_device(q, *q_rot);
-    p.q_rot = bp(*q_rot);
-    p.qr_sb = q_rot->stride(0); p.qr_st = q_rot->stride(1); p.qr_sh = q_rot->stride(2);
-  }
-  static const bool stamps = [] {
-    const char* e = std::getenv("DLA_ATTN_STAMPS");
-    return e != nullptr && std::atoi(e) == 1;
-  }();
-  if (stamps) {  // debug: read back with attn_stamps()
-    auto& buf = attn_stamp_buffer();
-    if (!buf.defined() || buf.device() != q.device())
-      buf = at::zeros({1024 * 8 * 4}, q.options().dtype(at::kLong));
-    p.stamps = reinterpret_cast<unsigned long long*>(buf.data_ptr<int64_t>());
-  }
-  launch_attn_fwd(p, static_cast<int>(D), causal, cur_stream(q));
-  return {o, lse2};
-}
-
-static int device_cus(int dev) {
-  static int cache[64] = {0};
-  if (dev < 0 || dev >= 64) return 256;
-  if (cache[dev] == 0) {
-    int n = 0;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    cache[dev] = n;
-  }
-  return cache[dev];
-}
-
-// GQA heads of one kv head split across `hs` backward workgroups when the (key block x kv head x
-// batch) grid alone would under-fill the chip: causal key blocks carry unequal work (block 0
-// sees every query), so target two workgroups per CU there and let the heaviest-first dispatch
-// balance them. Partial dK/dV of the splits are summed by a reduce pass.
-static int attn_bwd_hsplit(int64_t nkb, int64_t Hkv, int64_t B, int64_t group, bool causal, int cus) {
-  const int64_t base = nkb * Hkv * B;
-  const int64_t target = causal ? 2 * static_cast<int64_t>(cus) : cus;
-  int hs = 1;
-  while (base * hs < target && group % (2 * hs) == 0) hs *= 2;
-  return hs;
-}
-
-// dq / dk / dv are written into the given (possibly strided, e.g. fused-dqkv) bf16 outputs
-void attn_bwd(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k,
-              const at::Tensor& v, const at::Tensor& o, const at::Tensor& lse2, at::Tensor& dq,
-              at::Tensor& dk, at::Tensor& dv, double scale, bool causal, int64_t causal_off,
-              int64_t window, const c10::optional<at::Tensor>& kv_start,
-              const c10::optional<at::Tensor>& kv_end, const c10::optional<at::Tensor>& segs,
-              const c10::optional<at::Tensor>& rope_cos, const c10::optional<at::Tensor>& rope_sin,
-              const c10::optional<at::Tensor>& rope_pos, bool rope_inputs) {
-  check_bthd(dout, "dout");
-  check_bthd(q, "q");
-  check_bthd(k, "k");
-  check_bthd(v, "v");
-  check_bthd(o, "o");
-  check_bthd(dq, "dq");
-  check_bthd(dk, "dk");
-  check_bthd(dv, "dv");
-  check_f32(lse2, "lse2");
-  const int64_t B = q.size(0), Tq = q.size(1), Hq = q.size(2), D = q.size(3);
-  const int64_t Tk = k.size(1), Hkv = k.size(2);
-  TORCH_CHECK(D == 64 || D == 80 || D == 128, "head_dim must be 64, 80 or 128");
-  TORCH_CHECK(dout.sizes() == q.sizes() && o.sizes() == q.sizes() && dq.sizes() == q.sizes(),
-              "dout/o/dq shape");
-  TORCH_CHECK(dk.sizes() == k.sizes() && dv.sizes() == v.sizes(), "dk/dv shape");
-  TORCH_CHECK(lse2.is_contiguous() && lse2.numel() == B * Hq * Tq, "lse2 shape");
-  TORCH_CHECK(Hkv > 0 && Hq % Hkv == 0, "GQA ratio");
-  check_kv_range(kv_start, B, "kv_start");
-  check_kv_range(kv_end, B, "kv_end");
-  c10::hip::HIPGuardMasqueradingAsCUDA g(q.device());
-  auto st = cur_stream(q);
-  auto fopt = q.options().dtype(at::kFloat);
-  auto delta = at::empty({B, Hq, Tq}, fopt);
-  launch_attn_bwd_delta(cbp(o), cbp(dout), o.stride(0), o.stride(1), o.stride(2),
-                        dout.stride(0), dout.stride(1), dout.stride(2), B, Hq, Tq, D,
-                        delta.data_ptr<float>(), st);
-  const int64_t nkb = (Tk + kAttnBwdKeys - 1) / kAttnBwdKeys;
-  // one fp32 dQ partial per key block (no zero fill: the reduce pass reads exactly the rows
-  // each key block's workgroups wrote)
-  const int64_t slab_rows = (Tq + kAttnBwdQRows - 1) / kAttnBwdQRows * kAttnBwdQRows;
-  const bool slab16 = attn_dq_slab_bf16();
-  auto slab = at::empty({std::max<int64_t>(nkb, 1), B, slab_rows, Hq, D}, slab16 ? q.options() : fopt);
-  const int hs = attn_bwd_hsplit(nkb, Hkv, B, Hq / Hkv, causal, device_cus(q.get_device()));
-  at::Tensor dkp, dvp;
-  const bool part16 = hs > 1 && attn_dkv_part_bf16();
-  if (hs > 1) {
-    dkp = at::empty({hs, B, Tk, Hkv, D}, part16 ? q.options() : fopt);
-    dvp = at::empty({hs, B, Tk, Hkv, D}, part16 ? q.options() : fopt);
-  }
-  AttnBwdParams p{};
-  p.q = cbp(q); p.k = cbp(k); p.v = cbp(v); p.dout = cbp(dout);
-  p.lse2 = lse2.data_ptr<float>(); p.delta = delta.data_ptr<float>();
-  p.dq_slab = slab16 ? nullptr : slab.data_ptr<float>();
-  p.dq_slab16 = slab16 ? bp(slab) : nullptr;
-  p.dk_part = hs > 1 && !part16 ? dkp.data_ptr<float>() : nullptr;
-  p.dv_part = hs > 1 && !part16 ? dvp.data_ptr<float>() : nullptr;
-  p.dk_part16 = part16 ? bp(dkp) : nullptr;
-  p.dv_part16 = part16 ? bp(dvp) : nullptr;
-  p.dk = bp(dk); p.dv = bp(dv);
-  p.hsplit = hs;
-  p.slab_rows = static_cast<int>(slab_rows);
-  p.q_sb = q.stride(0); p.q_st = q.stride(1); p.q_sh = q.stride(2);
-  p.k_sb = k.stride(0); p.k_st = k.stride(1); p.k_sh = k.stride(2);
-  p.v_sb = v.stride(0); p.v_st = v.stride(1); p.v_sh = v.stride(2);
-  p.do_sb = dout.stride(0); p.do_st = dout.stride(1); p.do_sh = dout.stride(2);
-  p.dk_sb = dk.stride(0); p.dk_st = dk.stride(1); p.dk_sh = dk.stride(2);
-  p.dv_sb = dv.stride(0); p.dv_st = dv.stride(1); p.dv_sh = dv.stride(2);
-  p.B = B; p.Hq = Hq; p.Hkv = Hkv; p.Tq = Tq; p.Tk = Tk;
-  p.scale = static_cast<float>(scale);
-  p.scale2 = static_cast<float>(scale * 1.4426950408889634);
-  p.causal_off = static_cast<int>(causal_off);
-  p.window = static_cast<int>(window);
-  p.kv_start = (kv_start && kv_start->defined()) ? kv_start->data_ptr<int>() : nullptr;
-  p.kv_end = (kv_end && kv_end->defined()) ? kv_end->data_ptr<int>() : nullptr;
-  p.seg_end = seg_ptr(segs, B, Tq, Tk, causal, causal_off, q, 1);
-  // fused RoPE backward: dq / dk receive the un-rotated gradients (full rotary only); with
-  // rope_inputs q / k are also un-rotated and get rotated as they are staged
-  rope_args(rope_cos, rope_sin, rope_pos, q, B, Tq, Tk, D, causal_off, &p.rope_cos, &p.rope_sin,
-            &p.rope_pos, &p.rope_rot);
-  TORCH_CHECK(!rope_inputs || p.rope_cos != nullptr, "rope_inputs needs the rotary tables");
-  TORCH_CHECK(!rope_inputs || p.rope_rot == D, "rope_inputs (RoPE on load): full rotary only");
-  p.rope_inputs = rope_inputs ? 1 : 0;
-  launch_attn_bwd(p, static_cast<int>(D), causal, st);
-  launch_attn_dq_reduce(p.dq_slab, static_cast<int>(nkb), static_cast<int>(B), static_cast<int>(Tq),
-                        p.slab_rows, static_cast<int>(Hq), static_cast<int>(D), causal, p.causal_off, p.window,
-                        p.kv_start, p.kv_end, static_cast<int>(Tk), bp(dq), dq.stride(0),
-                        dq.stride(1), dq.stride(2), p.rope_cos, p.rope_sin, p.rope_pos, p.rope_rot, st,
-                        p.dq_slab16);
-  if (hs > 1) {
-    launch_attn_dkv_reduce(p.dk_part, p.dv_part, hs, static_cast<int>(B), static_cast<int>(Tk),
-                           static_cast<int>(Hkv), static_cast<int>(D), p.scale, bp(dk),
-                           dk.stride(0), dk.stride(1), dk.stride(2), bp(dv), dv.stride(0),
-                           dv.stride(1), dv.stride(2), p.rope_cos, p.rope_sin, p.rope_pos, p.rope_rot, st,
-                           p.dk_part16, p.dv_part16);
-  }
-}
-
 // out [C, R] <- in [R, C]^T (both row-major with unit column stride, 16-byte aligned rows)
 void transpose_bf16(const at::Tensor& in, at::Tensor& out) {
   check_bf16(in, "in");
@@ -731,15 +445,6 @@ std::tuple<at::Tensor, at::Tensor> clip_coef(const at::Tensor& sumsq, double max
   return {norm, coef};
 }
 
-// Flip one attention-forward structure switch for this process (tests / same-binary A/B): the
-// launcher reads DLA_ATTN_FWD_{PRIO,SGPR,PRO,OSTAGE,MSUB} once; returns the previous value.
-int64_t attn_fwd_switch(c10::string_view name, int64_t value) {
-  const std::string n(name.data(), name.size());
-  const int prev = attn_fwd_set_switch(n.c_str(), static_cast<int>(value));
-  TORCH_CHECK(prev != -1, "attn_fwd_switch: unknown switch ", n);
-  return prev;
-}
-
 }  // namespace dla
 
 TORCH_LIBRARY(dla, m) {
@@ -753,10 +458,6 @@ TORCH_LIBRARY(dla, m) {
   m.def("gelu_bwd(Tensor x, Tensor dy) -> Tensor");
   m.def("rope_fwd(Tensor qkv, Tensor cos, Tensor sin, Tensor? pos, int Hq, int Hkv, int D, int rot, int T, int pos_offset) -> (Tensor, Tensor)");
   m.def("rope_bwd(Tensor dq, Tensor dk, Tensor(a!) dqkv, Tensor cos, Tensor sin, Tensor? pos, int Hq, int Hkv, int D, int rot, int T, int pos_offset) -> ()");
-  m.def("attn_fwd(Tensor q, Tensor k, Tensor v, float scale, bool causal, int causal_off, int window, Tensor? kv_start, Tensor? kv_end, Tensor? segs=None, Tensor? rope_cos=None, Tensor? rope_sin=None, Tensor? rope_pos=None, Tensor(a!)? q_rot=None, bool rope_k=True, Tensor? prefix=None) -> (Tensor, Tensor)");
-  m.def("attn_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse2, Tensor(a!) dq, Tensor(b!) dk, Tensor(c!) dv, float scale, bool causal, int causal_off, int window, Tensor? kv_start, Tensor? kv_end, Tensor? segs=None, Tensor? rope_cos=None, Tensor? rope_sin=None, Tensor? rope_pos=None, bool rope_inputs=False) -> ()");
-  m.def("attn_stamps(Tensor like) -> Tensor");
-  m.def("attn_fwd_switch(str name, int value) -> int", &dla::attn_fwd_switch);
   m.def("transpose_bf16(Tensor input, Tensor(a!) out) -> ()");
   m.def("gjsd_fwd(Tensor s, Tensor t, Tensor? row_mask, float beta, float inv_temp) -> (Tensor, Tensor, Tensor, Tensor)");
   m.def("gjsd_bwd(Tensor s, Tensor t, Tensor s_lse, Tensor t_lse, Tensor aux, Tensor? row_mask, Tensor grad, float beta, float inv_temp) -> Tensor");
@@ -776,9 +477,6 @@ TORCH_LIBRARY_IMPL(dla, CUDA, m) {
   m.impl("gelu_bwd", &dla::gelu_bwd);
   m.impl("rope_fwd", &dla::rope_fwd);
   m.impl("rope_bwd", &dla::rope_bwd);
-  m.impl("attn_fwd", &dla::attn_fwd);
-  m.impl("attn_bwd", &dla::attn_bwd);
-  m.impl("attn_stamps", &dla::attn_stamps);
   m.impl("transpose_bf16", &dla::transpose_bf16);
   m.impl("gjsd_fwd", &dla::gjsd_fwd);
   m.impl("gjsd_bwd", &dla::gjsd_bwd);

@@ -149,6 +149,15 @@ FUSED_ROPE_FWD = os.environ.get("DLA_FUSED_ROPE_FWD", "0") == "1"
 ROPE_Q_ON_LOAD = os.environ.get("DLA_ROPE_Q_ON_LOAD", "1") != "0"
 
 
+def _qkv_views(qkv, Hq, Hkv, D):
+    """The q [B, T, Hq, D], k and v [B, T, Hkv, D] column slices of a contiguous fused [B, T, C]
+    buffer as strided views (no copy)."""
+    B, T, C = qkv.shape
+    off = qkv.storage_offset()
+    view = lambda H, col: qkv.as_strided((B, T, H, D), (T * C, C, D, 1), off + col)  # noqa: E731
+    return view(Hq, 0), view(Hkv, Hq * D), view(Hkv, (Hq + Hkv) * D)
+
+
 class _FusedQKVAttnFn(torch.autograd.Function):
     """qkv [B, T, C] -> o [B, T, Hq*D]; RoPE (optional) fused in; returns one dqkv."""
 
@@ -158,14 +167,12 @@ class _FusedQKVAttnFn(torch.autograd.Function):
         ops = _ext.require()
         B, T, C = qkv.shape
         q2 = qkv.reshape(B * T, C)
-        off = qkv.storage_offset()
-        v4 = qkv.as_strided((B, T, Hkv, D), (T * C, C, D, 1), off + (Hq + Hkv) * D)
+        q4, k4, v4 = _qkv_views(qkv, Hq, Hkv, D)
         on_load = rot == D and D in (64, 128) and FUSED_ROPE_FWD
         q_load = rot == D and D in (64, 128) and ROPE_Q_ON_LOAD and not on_load
         if q_load:
             # K rotated by the rope kernel over the K columns only; Q rotated on load
             _, k_r = ops.rope_fwd(q2[:, Hq * D:], cos, sin, pos, 0, Hkv, D, rot, T, 0)
-            q4 = qkv.as_strided((B, T, Hq, D), (T * C, C, D, 1), off)
             k4 = k_r.view(B, T, Hkv, D)
             q_rot = torch.empty((B, T, Hq, D), dtype=qkv.dtype, device=qkv.device) \
                 if ctx.needs_input_grad[0] else None
@@ -175,8 +182,6 @@ class _FusedQKVAttnFn(torch.autograd.Function):
         elif on_load:
             # RoPE on load: the kernel rotates Q in registers and K as it stages it; the rotated
             # Q leaves as a side output only when a backward will read it
-            q4 = qkv.as_strided((B, T, Hq, D), (T * C, C, D, 1), off)
-            k4 = qkv.as_strided((B, T, Hkv, D), (T * C, C, D, 1), off + Hq * D)
             q_rot = torch.empty((B, T, Hq, D), dtype=qkv.dtype, device=qkv.device) \
                 if ctx.needs_input_grad[0] else None
             o, lse2 = ops.attn_fwd(q4, k4, v4, float(scale), bool(causal), 0, int(window), kv_start,
@@ -187,9 +192,6 @@ class _FusedQKVAttnFn(torch.autograd.Function):
                 q_r, k_r = ops.rope_fwd(q2, cos, sin, pos, Hq, Hkv, D, rot, T, 0)
                 q4 = q_r.view(B, T, Hq, D)
                 k4 = k_r.view(B, T, Hkv, D)
-            else:
-                q4 = qkv.as_strided((B, T, Hq, D), (T * C, C, D, 1), off)
-                k4 = qkv.as_strided((B, T, Hkv, D), (T * C, C, D, 1), off + Hq * D)
             o, lse2 = ops.attn_fwd(q4, k4, v4, float(scale), bool(causal), 0, int(window), kv_start,
                                    kv_end, segs, prefix=prefix)
             ctx.save_for_backward(qkv, q4 if rot > 0 else None, k4 if rot > 0 else None, o, lse2,
@@ -203,16 +205,14 @@ class _FusedQKVAttnFn(torch.autograd.Function):
         ops = _ext.require()
         qkv, q4, k4, o, lse2, cos, sin, pos, kv_start, kv_end, segs = ctx.saved_tensors
         B, T, C, Hq, Hkv, D, rot, scale, causal, window = ctx.cfg
-        off = qkv.storage_offset()
+        q_in, k_in, v4 = _qkv_views(qkv, Hq, Hkv, D)
         if ctx.on_load:  # q4 = the forward's rotated Q; K is rotated again as it is staged
-            k4 = qkv.as_strided((B, T, Hkv, D), (T * C, C, D, 1), off + Hq * D)
+            k4 = k_in
         elif rot == 0:
-            q4 = qkv.as_strided((B, T, Hq, D), (T * C, C, D, 1), off)
-            k4 = qkv.as_strided((B, T, Hkv, D), (T * C, C, D, 1), off + Hq * D)
-        v4 = qkv.as_strided((B, T, Hkv, D), (T * C, C, D, 1), off + (Hq + Hkv) * D)
+            q4, k4 = q_in, k_in
         do4 = do.contiguous().view(B, T, Hq, D)
         dqkv = torch.empty((B, T, C), dtype=qkv.dtype, device=qkv.device)
-        dv = dqkv.as_strided((B, T, Hkv, D), (T * C, C, D, 1), (Hq + Hkv) * D)
+        dq_out, dk_out, dv = _qkv_views(dqkv, Hq, Hkv, D)
         # full rotary at D 64 / 128, or phi-2's partial rotary (32 of D = 80 dims: the dK
         # epilogue un-rotates column tile 0, the reduce passes the rotary chunk pairs)
         fused_rope = (rot == D and D in (64, 128) or (D == 80 and rot == 32)) and \
@@ -221,8 +221,7 @@ class _FusedQKVAttnFn(torch.autograd.Function):
             dq = torch.empty((B, T, Hq, D), dtype=qkv.dtype, device=qkv.device)
             dk = torch.empty((B, T, Hkv, D), dtype=qkv.dtype, device=qkv.device)
         else:  # written straight into the fused dqkv buffer (un-rotated in the attention passes)
-            dq = dqkv.as_strided((B, T, Hq, D), (T * C, C, D, 1), 0)
-            dk = dqkv.as_strided((B, T, Hkv, D), (T * C, C, D, 1), Hq * D)
+            dq, dk = dq_out, dk_out
         if fused_rope:
             ops.attn_bwd(do4, q4, k4, v4, o, lse2, dq, dk, dv, float(scale), bool(causal), 0,
                          int(window), kv_start, kv_end, segs, cos, sin, pos, bool(ctx.on_load))

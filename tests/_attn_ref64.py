@@ -149,7 +149,7 @@ class Case:
         nkb = (self.Tk + BWD_KEYS - 1) // BWD_KEYS
         group = self.Hq // self.Hkv
         base, target, hs = nkb * self.Hkv * self.B, (2 * cus if self.causal else cus), 1
-        while base * hs < target and group % (2 * hs) == 0:  # bindings.cpp attn_bwd_hsplit
+        while base * hs < target and group % (2 * hs) == 0:  # attn_geom.h attn_bwd_hsplit
             hs *= 2
         return {"nf": nf, "nb": nb, "rope": rot > 0, "extra_round": rot > 0 and not fused,
                 "w8": waves == 8, "slab16": waves == 8 and bool(dq16),

@@ -62,7 +62,7 @@ int main(int argc, char** argv) {
   CK(hipMemcpy(delta, del.data(), del.size() * 4, hipMemcpyHostToDevice));
   const int nkb = (T + kAttnBwdKeys - 1) / kAttnBwdKeys;
   const int slab_rows = (T + kAttnBwdQRows - 1) / kAttnBwdQRows * kAttnBwdQRows;
-  int hs = 1;  // as bindings.cpp attn_bwd_hsplit with 256 CUs
+  int hs = 1;  // as attn_geom.h attn_bwd_hsplit with 256 CUs
   const int group = Hq / Hkv;
   while (static_cast<int64_t>(nkb) * Hkv * B * hs < (causal ? 512 : 256) && group % (2 * hs) == 0) hs *= 2;
   float *slab, *dkp = nullptr, *dvp = nullptr;
