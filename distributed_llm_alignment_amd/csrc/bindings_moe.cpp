@@ -6,6 +6,7 @@
 
 #include "bind_util.h"
 #include "gg_params.h"
+#include "moe_decode_params.h"
 #include "reward_head.h"
 
 namespace dla {
@@ -508,6 +509,83 @@ std::tuple<at::Tensor, at::Tensor> moe_combine_bwd(const at::Tensor& dout, const
   return {dys, dw};
 }
 
+// ---- decode-shaped expert block (moe_decode.hip): every refusal is raised here, before a launch
+static void check_md_rows(const at::Tensor& t, const char* name) {
+  check_bf16(t, name);
+  TORCH_CHECK(t.dim() == 2 && t.stride(1) == 1 && t.stride(0) % 8 == 0, name,
+              " must be [rows, cols] with unit column stride and 16-byte aligned rows");
+  check_aligned16(t, name);
+}
+
+static void check_md_topi(const at::Tensor& topi, int64_t E) {
+  check_i32(topi, "topi");
+  TORCH_CHECK(topi.dim() == 2 && topi.is_contiguous(), "topi must be contiguous int32 [M, k]");
+  const int64_t M = topi.size(0), k = topi.size(1);
+  TORCH_CHECK(M >= 1 && M <= kMdMaxRows, "moe_decode: 1 <= M <= 64 token rows, got ", M);
+  TORCH_CHECK(k >= 1 && k <= kMdMaxTopK && k <= E, "moe_decode: 1 <= k <= min(8, E), got k = ", k);
+}
+
+static void check_md_weight(const at::Tensor& w, const char* name) {
+  check_bf16(w, name);
+  TORCH_CHECK(w.dim() == 3 && w.is_contiguous(), name, " must be a contiguous 3-d expert stack");
+  check_aligned16(w, name);
+  TORCH_CHECK(w.size(0) >= 1 && w.size(0) <= 65535, name, ": 1 <= E <= 65535");
+}
+
+// a[t k + j] = bf16(silu(h2[t] W_g^T) * (h2[t] W_u^T)) of expert topi[t, j]; w_up [E, 2F, H] = [gate; up]
+at::Tensor moe_decode_glu(const at::Tensor& h2, const at::Tensor& topi, const at::Tensor& w_up) {
+  check_md_rows(h2, "h2");
+  check_md_weight(w_up, "w_up");
+  check_md_topi(topi, w_up.size(0));
+  same_device(h2, topi);
+  same_device(h2, w_up);
+  const int64_t M = h2.size(0), H = h2.size(1), k = topi.size(1);
+  TORCH_CHECK(topi.size(0) == M, "topi [M, k] against h2 [M, H]");
+  TORCH_CHECK(w_up.size(2) == H && w_up.size(1) % 2 == 0, "w_up [E, 2F, H] against h2 [M, H]");
+  const int64_t F = w_up.size(1) / 2;
+  TORCH_CHECK(H % 32 == 0 && F % 32 == 0 && F >= 32, "moe_decode: H % 32 == 0 and F % 32 == 0");
+  c10::hip::HIPGuardMasqueradingAsCUDA g(h2.device());
+  auto a = at::empty({M * k, F}, h2.options());
+  MoeDecodeParams p{};
+  p.h2 = cbp(h2);
+  p.ldh = h2.stride(0);
+  p.topi = topi.data_ptr<int>();
+  p.w_up = cbp(w_up);
+  p.a = bp(a);
+  p.M = (int)M; p.k = (int)k; p.E = (int)w_up.size(0); p.H = (int)H; p.F = (int)F;
+  launch_moe_decode_glu(p, cur_stream(h2));
+  return a;
+}
+
+// out[t] = bf16(sum_j topv[t, j] * (a[t k + j] W_d[topi[t, j]]^T)), experts in index order;
+// a [M k, F] from moe_decode_glu, w_down [E, H, F]
+at::Tensor moe_decode_down(const at::Tensor& a, const at::Tensor& topv, const at::Tensor& topi,
+                           const at::Tensor& w_down) {
+  check_md_rows(a, "a");
+  check_md_weight(w_down, "w_down");
+  check_md_topi(topi, w_down.size(0));
+  check_f32(topv, "topv");
+  same_device(a, topi);
+  same_device(a, topv);
+  same_device(a, w_down);
+  TORCH_CHECK(topv.sizes() == topi.sizes() && topv.is_contiguous(), "topv must be contiguous fp32 [M, k]");
+  const int64_t M = topi.size(0), k = topi.size(1), H = w_down.size(1), F = w_down.size(2);
+  TORCH_CHECK(a.size(0) == M * k && a.size(1) == F && a.stride(0) == F,
+              "a [M k, F] contiguous against w_down [E, H, F]");
+  TORCH_CHECK(H % 32 == 0 && F % 32 == 0 && H >= 32, "moe_decode: H % 32 == 0 and F % 32 == 0");
+  c10::hip::HIPGuardMasqueradingAsCUDA g(a.device());
+  auto out = at::empty({M, H}, a.options());
+  MoeDecodeParams p{};
+  p.a = bp(a);
+  p.topi = topi.data_ptr<int>();
+  p.topv = topv.data_ptr<float>();
+  p.w_down = cbp(w_down);
+  p.out = bp(out);
+  p.M = (int)M; p.k = (int)k; p.E = (int)w_down.size(0); p.H = (int)H; p.F = (int)F;
+  launch_moe_decode_down(p, cur_stream(a));
+  return out;
+}
+
 }  // namespace dla
 
 namespace dla {
@@ -539,6 +617,8 @@ TORCH_LIBRARY_FRAGMENT(dla, m) {
   m.def("gg_dgrad(Tensor dy, Tensor w, Tensor offs) -> Tensor");
   m.def("gg_dgrad_swiglu(Tensor dy, Tensor w_down, Tensor offs, Tensor gu) -> (Tensor, Tensor)");
   m.def("gg_wgrad(Tensor dy, Tensor x, Tensor offs, Tensor(a!) out, bool accumulate) -> ()");
+  m.def("moe_decode_glu(Tensor h2, Tensor topi, Tensor w_up) -> Tensor");
+  m.def("moe_decode_down(Tensor a, Tensor topv, Tensor topi, Tensor w_down) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(dla, CUDA, m) {
@@ -562,4 +642,6 @@ TORCH_LIBRARY_IMPL(dla, CUDA, m) {
   m.impl("gg_dgrad", &dla::gg_dgrad);
   m.impl("gg_dgrad_swiglu", &dla::gg_dgrad_swiglu);
   m.impl("gg_wgrad", &dla::gg_wgrad);
+  m.impl("moe_decode_glu", &dla::moe_decode_glu);
+  m.impl("moe_decode_down", &dla::moe_decode_down);
 }

@@ -10,6 +10,7 @@ to the cache through the same kernel with causal offset.
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import os
 import weakref
@@ -535,7 +536,7 @@ def generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional[
              weight_dtype: str = "bf16", num_return_sequences: int = 1, share_prefill: bool = True,
              group_attention: bool = False, return_logprobs: bool = False,
              logprob_temperature: Optional[float] = None, return_keep_mask: bool = False,
-             adapters: Optional[str] = None, kv_dtype: str = "bf16"):
+             adapters: Optional[str] = None, kv_dtype: str = "bf16", moe_decode: bool = False):
     """Left-padded prompts [B, Tp] -> sequences [B, Tp + n] (n <= max_new_tokens).
 
     `num_return_sequences=G` (group rollouts, GRPO): G samples per prompt, output [B*G, Tp + n]
@@ -612,7 +613,15 @@ def generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional[
     `return_logprobs`, `return_keep_mask`, `num_return_sequences` / `share_prefill` and MoE models;
     with `group_attention=True` or a layer-split model it raises ValueError. The cache changes
     which tokens are sampled (`ppo.rollout_logprobs` measures and corrects that gap). "bf16" is
-    the default call, kernel for kernel; any other value raises ValueError."""
+    the default call, kernel for kernel; any other value raises ValueError.
+
+    `moe_decode=True` (MoE models): the decode steps run every MoE block's experts on the two
+    decode kernels of csrc/moe_decode.hip (`ops.moe.skinny_decode`: <= 32 rows, bf16 experts, no
+    expert parallelism, no fp8 experts; a layer that is not eligible keeps the grouped path), still
+    without a host sync, so the step captures as before. The prompt prefill keeps the grouped
+    path. Same mathematics, different rounding (the per-expert output is never rounded to bf16),
+    so tokens can differ from the default arm's. False adds nothing to the call; DLA_MOE_DECODE=1
+    is the process-wide form."""
     if weight_dtype not in ("bf16", "fp8", "mxfp4"):
         raise ValueError(f"weight_dtype must be 'bf16', 'fp8' or 'mxfp4', got {weight_dtype!r}")
     _check_kv_dtype(kv_dtype)
@@ -644,11 +653,12 @@ def generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional[
     f8 = not f4 and (weight_dtype == "fp8" or ops.decode.fp8_enabled())
     with ops.decode.weight_format("mxfp4" if f4 else "fp8" if f8 else None, model), \
             ops.fp8_inference_scope(model, f8 and PREFILL_FP8), \
-            ops.decode.lora_merged(live and adapters == "merged"):
+            ops.decode.lora_merged(live and adapters == "merged"), \
+            (ops.moe.skinny_decode(True) if moe_decode else contextlib.nullcontext()):
         return _generate(model, input_ids, attention_mask, max_new_tokens, do_sample, temperature, top_p,
                          top_k, eos_token_id, pad_token_id, generator, return_mask, use_graph, seed, G,
                          bool(group_attention) and G > 1, lp_mode,
-                         bool(return_logprobs) if return_keep_mask else None, kv_dtype)
+                         bool(return_logprobs) if return_keep_mask else None, kv_dtype, bool(moe_decode))
 
 
 def _generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor],
@@ -656,21 +666,20 @@ def _generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional
               eos_token_id: Optional[int], pad_token_id: Optional[int],
               generator: Optional[torch.Generator], return_mask: bool, use_graph: Optional[bool],
               seed: Optional[int], G: int = 1, group_attention: bool = False,
-              return_logprobs: int = _LOGP_OFF, want_logp: Optional[bool] = None, kv_dtype: str = "bf16"):
+              return_logprobs: int = _LOGP_OFF, want_logp: Optional[bool] = None, kv_dtype: str = "bf16",
+              moe_decode: bool = False):
     # return_logprobs: the sampler mode (_LOGP_*); want_logp: whether logp is returned (None: whenever
     # the mode produces one; the keep mode produces it also for a call that wants the mask alone)
     if DECODE_GATHER and model.layers_sharded():
         # ZeRO-3 policy: gather it once for the whole rollout (fused decode kernels + captured
         # graph) instead of an all-gather per layer per token
-        import contextlib
-
         try:
             with contextlib.ExitStack() as stack:
                 for eng in model.sharding_engines():
                     stack.enter_context(eng.gathered_for_inference())
                 return _generate(model, input_ids, attention_mask, max_new_tokens, do_sample, temperature,
                                  top_p, top_k, eos_token_id, pad_token_id, generator, return_mask, use_graph,
-                                 seed, G, group_attention, return_logprobs, want_logp, kv_dtype)
+                                 seed, G, group_attention, return_logprobs, want_logp, kv_dtype, moe_decode)
         finally:
             # the gathered units are freed on exit: the captured graph (it reads their addresses),
             # its KV cache and the derived decode weight copies (a second full set of layer
@@ -713,7 +722,8 @@ def _generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional
                      # adapter mode: the captured step of a model with live adapters holds the first
                      # layer's adapter launches
                      (_live_adapters(model), ops.decode.lora_merged_enabled()),
-                     kv_dtype)  # the captured step holds the bf16 or the e4m3 cache ops and buffers
+                     kv_dtype,  # the captured step holds the bf16 or the e4m3 cache ops and buffers
+                     ops.moe.skinny_decode_enabled())  # ... and the grouped or the decode expert kernels
         hit = _GRAPH_SLOT.get(id(model))
         if hit is not None and hit[0]() is model and hit[1] == reuse_key:
             cache, dg = hit[2], hit[3]
@@ -725,14 +735,16 @@ def _generate(model: CausalLM, input_ids: torch.Tensor, attention_mask: Optional
     # folded RMSNorm weights of the fused decode layer are refreshed in place (never inside the
     # captured step): a cached graph replays the same buffers with the current weights
     ops.decode.refresh_folded_weights(model)
-    if G > 1:
-        # one prompt forward per group; its K/V and last hidden row replicated to the G rows
-        cache, last = prefill_shared(model, input_ids, attention_mask, G, Tp + max_new_tokens, cache,
-                                     group_attention=group_attention)
-        input_ids = input_ids.repeat_interleave(G, 0)
-        attention_mask = attention_mask.repeat_interleave(G, 0) if attention_mask is not None else None
-    else:
-        last = model(input_ids, cache=cache)[:, -1]
+    # `moe_decode=` is for the decode steps: the prompt keeps the grouped experts
+    with ops.moe.skinny_decode(False) if moe_decode else contextlib.nullcontext():
+        if G > 1:
+            # one prompt forward per group; its K/V and last hidden row replicated to the G rows
+            cache, last = prefill_shared(model, input_ids, attention_mask, G, Tp + max_new_tokens, cache,
+                                         group_attention=group_attention)
+            input_ids = input_ids.repeat_interleave(G, 0)
+            attention_mask = attention_mask.repeat_interleave(G, 0) if attention_mask is not None else None
+        else:
+            last = model(input_ids, cache=cache)[:, -1]
     if seed is None:
         seed = int(torch.randint(0, 2 ** 62, (1,), generator=generator).item()) if generator is not None \
             and generator.device.type == "cpu" else int(torch.randint(0, 2 ** 62, (1,)).item())

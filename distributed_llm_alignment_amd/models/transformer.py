@@ -351,6 +351,10 @@ class MoE(nn.Module):
         if self.ep is not None:
             out = self.ep.dispatch_combine(self, h2, topv, topi)
             return out.view(shp)
+        if (ops.moe.skinny_decode_enabled() and not torch.is_grad_enabled() and not self.fp8
+                and ops.moe.decode_experts_ok(h2, self.expert_up, self.expert_down)):
+            # decode rows: two launches on the stored expert weights (csrc/moe_decode.hip)
+            return ops.moe.decode_experts(h2, topv, topi, self.expert_up, self.expert_down).view(shp)
         pos, counts = ops.moe.expert_positions(topi, self.cfg.num_experts)
         xs = ops.moe.dispatch(h2, pos)
         ys = ops.moe.experts_swiglu(xs, self.expert_up, self.expert_down, counts, fp8=self.fp8)

@@ -603,6 +603,82 @@ def experts_swiglu_offsets(xs: torch.Tensor, w_up: torch.Tensor, w_down: torch.T
     return _ref_grouped_experts(xs, w_up, w_down, offs)
 
 
+# ------------------------------------------------------------------------------ decode
+# Decode-shaped expert block (csrc/moe_decode.hip): two launches from (topv, topi) to the MoE
+# block's output at <= 64 token rows, on the expert parameters as stored. Off by default;
+# DLA_MOE_DECODE=1 turns it on process-wide, `skinny_decode` for a block of code.
+# The ops take M <= 64; the gate stops at 32 rows, the last measured size at which the pair beats
+# the grouped chain at Mixtral's shape (block alone 674 vs 710 us at 32 rows, 736 vs 712 at 48, 792
+# vs 704 at 64: every 16-feature workgroup re-reads its rows' activations; profiles/moe_decode.md).
+MOE_DECODE_MAX_ROWS = 32
+_MOE_DECODE = [os.environ.get("DLA_MOE_DECODE", "0") == "1"]
+
+
+class skinny_decode:
+    """Context manager: inside the block `MoE.forward` runs eligible no-grad calls (see
+    `decode_experts_ok`) on the two decode kernels; `skinny_decode(False)` turns them off inside
+    the block, whatever was active outside."""
+
+    def __init__(self, enabled: bool = True):
+        self.enabled = bool(enabled)
+
+    def __enter__(self):
+        self.prev = _MOE_DECODE[0]
+        _MOE_DECODE[0] = self.enabled
+        return self
+
+    def __exit__(self, *exc):
+        _MOE_DECODE[0] = self.prev
+        return False
+
+
+def skinny_decode_enabled() -> bool:
+    return _MOE_DECODE[0]
+
+
+def decode_experts_ok(h2: torch.Tensor, w_up: torch.Tensor, w_down: torch.Tensor) -> bool:
+    """The decode kernels take this call and win it: bf16 on the GPU, 1 <= M <= MOE_DECODE_MAX_ROWS
+    rows (the ops themselves take 64), H and F multiples of 32, w_down [E, H, F] against w_up [E, 2F, H], contiguous expert stacks, 16-byte aligned rows.
+    (k is the op's own check: 1 <= k <= min(8, E).)"""
+    if not (_ext.use_native(h2) and h2.dim() == 2 and w_up.dim() == 3 and w_down.dim() == 3):
+        return False
+    M, H = h2.shape
+    E, F2, _ = w_up.shape
+    return (h2.dtype == w_up.dtype == w_down.dtype == torch.bfloat16
+            and h2.device == w_up.device == w_down.device
+            and 1 <= M <= MOE_DECODE_MAX_ROWS and H % 32 == 0 and F2 % 64 == 0 and F2 > 0
+            and tuple(w_up.shape) == (E, F2, H) and tuple(w_down.shape) == (E, H, F2 // 2)
+            and w_up.is_contiguous() and w_down.is_contiguous()
+            and h2.stride(1) == 1 and h2.stride(0) % 8 == 0
+            and h2.data_ptr() % 16 == 0 and w_up.data_ptr() % 16 == 0 and w_down.data_ptr() % 16 == 0)
+
+
+def decode_experts(h2: torch.Tensor, topv: torch.Tensor, topi: torch.Tensor, w_up: torch.Tensor,
+                   w_down: torch.Tensor) -> torch.Tensor:
+    """The routed SwiGLU experts of h2 [M, H] given route_topk's (topv, topi) [M, k] -> [M, H]:
+
+        out[t] = bf16( sum_j topv[t, j] * ( bf16(silu(x W_g^T) * (x W_u^T)) W_d^T ) )
+
+    fp32 math on the inputs as given, `a` rounded to the input dtype once, experts summed in index
+    order. An eligible GPU call (`decode_experts_ok`) is two HIP launches; everything else, the CPU
+    included, runs the formula here. Forward only."""
+    if decode_experts_ok(h2, w_up, w_down):
+        C = _ext.require()
+        ti = topi.to(torch.int32).contiguous()
+        a = C.moe_decode_glu(h2, ti, w_up)
+        return C.moe_decode_down(a, topv.float().contiguous(), ti, w_down)
+    Fd = w_up.shape[1] // 2
+    x = h2.float()
+    out = torch.zeros(h2.shape, dtype=torch.float32, device=h2.device)
+    for e in range(w_up.shape[0]):
+        hit = topi == e  # static shapes, no host read: every expert runs over all rows
+        wt = (topv.float() * hit).sum(-1, keepdim=True)
+        gu = x @ w_up[e].float().t()
+        a = (F.silu(gu[:, :Fd]) * gu[:, Fd:]).to(h2.dtype).float()
+        out += torch.where(hit.any(-1, keepdim=True), wt * (a @ w_down[e].float().t()), 0.0)
+    return out.to(h2.dtype)
+
+
 def ref_moe(h2, router, w_up, w_down, k):
     """Plain PyTorch fp32 Mixtral block (HF semantics: the router GEMM runs in the model dtype,
     softmax / top-k / expert math in fp32) for tests."""

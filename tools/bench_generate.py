@@ -35,6 +35,9 @@ def main() -> int:
                     help="also return the sampler's token log-probs (generate(return_logprobs=...)): 1 at "
                          "temperature 1, 2 at the draw temperature (logprob_temperature=0.7), 3 the kept-set "
                          "log-probs and the sampling mask (return_keep_mask=True)")
+    ap.add_argument("--moe-decode", action="store_true",
+                    help="MoE models: the decode steps' experts on the two decode kernels (generate(moe_decode=True))")
+    ap.add_argument("--layers", type=int, default=0, help="override the model's depth (0: as configured)")
     a = ap.parse_args()
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from distributed_llm_alignment_amd.models import build_model, generate, get_config
@@ -44,7 +47,7 @@ def main() -> int:
     dev = torch.device("cuda", 0)
     _ext.require()
     enable_gemm_tuning(0)
-    cfg = get_config(a.model)
+    cfg = get_config(a.model, num_layers=a.layers) if a.layers else get_config(a.model)
     m = build_model(cfg, device=dev, dtype=torch.bfloat16, seed=0)
     g = torch.Generator(device=dev).manual_seed(0)
     ids = torch.randint(3, cfg.vocab_size, (a.batch, a.prompt), device=dev, generator=g)
@@ -69,6 +72,8 @@ def main() -> int:
                   num_return_sequences=a.group, group_attention=bool(a.group_attention))
         if a.kv_dtype != "bf16":  # (left out otherwise: the call an older build of the package takes)
             kw["kv_dtype"] = a.kv_dtype
+        if a.moe_decode:  # (left out otherwise: the call an older build of the package takes)
+            kw["moe_decode"] = True
         if a.logprobs:  # (left out otherwise: the call an older build of the package takes)
             kw["return_logprobs"] = True
         if a.logprobs >= 2:
@@ -91,6 +96,7 @@ def main() -> int:
         tp = time.perf_counter() - t1
         print(json.dumps({"mode": mode, "model": cfg.name, "batch": a.batch, "prompt": a.prompt,
                           "weight_dtype": a.weight_dtype, "kv_dtype": a.kv_dtype, "group": a.group,
+                          "moe_decode": a.moe_decode, "layers": cfg.num_layers,
                           "group_attention": bool(a.group_attention), "logprobs": bool(a.logprobs),
                           "logprob_temperature": 0.7 if a.logprobs >= 2 else 1.0,
                           "keep_mask": a.logprobs == 3,
